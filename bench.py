@@ -19,6 +19,8 @@ executed rate beside it as `pipe_busy_frac`; every contraction launch together u
 The exact-fp32-MFMA path (`--precision fp32`) is measured beside the headline as `exact_fp32_mode`.
 The default N = 1 run also times a few steps of the other BASELINE configurations (`other_workloads`: config 2, the config-4
 clip shape, the config-5 recipe at 2160p) so that the driver's record carries them, not only builder-run files.
+--dump-outputs DIR: rank 0 also writes what the last timed step returned, DIR/clip_vectors.npy (float32 [N * clips per step, F];
+DIR/clip_matrix.npy in dataset mode), at most 64 MB; the inputs and weights are seeded, so two builds compare output for output.
 
   python bench.py --gpus N --workload config4 --dataset-clips 1200
 BASELINE config 4 as written (strong scaling): a KoNViD-1k-shaped list of 1200 clips sharded over the ranks
@@ -270,6 +272,9 @@ def main():
     ap.add_argument("--gemm-split-k", type=int, default=1, choices=[0, 1],
                     help="0: no tail split-K - bits independent of the batch composition, i.e. of the number of ranks")
     ap.add_argument("--dump-matrix", default=None, help="dataset mode: rank 0 saves the gathered [n, F] matrix as .npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in "
+                         "all: a seeded sample of rows beyond that); the inputs are seeded, so two builds can be compared file for file")
     ap.add_argument("--host-clips", action="store_true",
                     help="dataset mode: after the device-resident pass, the same pass with every clip living in (pageable) host memory - "
                          "loader threads stage it in pinned buffers, a side stream copies batch k+1 under the compute of batch k "
@@ -301,6 +306,8 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="only rehearse the N-rank launch + collectives (no engine, no GPU needed): tests/test_bench_launch.py")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.clips_per_step <= 0:
         # 2048 fragments per backbone pass for the backbone-only workloads, the dataset pass included (the partial last round of tiles
         # of a launch weighs less: config 3 +1 %, config 2 +9 %, config 4 +4 % over 16 clips per step); the full pipelines keep 16
@@ -442,6 +449,8 @@ def main():
     other_ms, other_flops, other_launches = prof["other"]   # contraction launches on the other kernel family
     assert eng.precision() == precision
     assert out.shape == (world * B, feat_dim) and bool(torch.isfinite(out).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"clip_vectors": out})     # [world * B, feat_dim], what step() hands its caller
 
     # metric (ii) of SURVEY §8(d): the same steps with every clip copied from pinned host memory on a side stream
     h2d = None
@@ -781,6 +790,26 @@ def host_feed_rehearsal(device, vit_dim, workload, n, B, rank, world, stub_ms, p
                 "pinned totals are host-side and carry over"}
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: {name: tensor} -> directory/<name>.npy, float32.  Above DUMP_LIMIT_BYTES in all, every array keeps the same
+    fraction of its rows: a seeded choice, in row order, so the same arguments give the same rows."""
+    os.makedirs(directory, exist_ok=True)
+    host = {name: a.detach().float().cpu().numpy() for name, a in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    keep = (DUMP_LIMIT_BYTES - 4096 * len(host)) / total if total else 1.0      # (4 KiB per file for the .npy header)
+    written = []
+    for name, a in host.items():
+        if keep < 1.0 and a.ndim:
+            rows = np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
+        written.append(f"{name}.npy {list(a.shape)}" + (f" (rows sampled from {host[name].shape[0]})" if a.shape != host[name].shape else ""))
+    print(f"bench.py: outputs of the last timed step written to {directory}: {', '.join(written)}", file=sys.stderr)
+
+
 def write_frame_files(directory, n_videos, T, H, W):
     """Sampled-frame PNGs of n_videos synthetic videos under `directory`, as the reference's ffmpeg step leaves them
     (src/video_frames_extract.py:51-69: {video}_{n}.png, {video}_{n}_next.png).  Content: low-pass noise + fine noise (compresses about
@@ -802,7 +831,7 @@ def write_frame_files(directory, n_videos, T, H, W):
 
 
 def dataset_pass(eng, workload, n, B, rank, world, split_k, host_clips=False, prefetch=2, workers=8, n_resident=4, warmup=1, dump=None,
-                 frame_files=None, workers_sweep=None, loader_pools=()):
+                 frame_files=None, workers_sweep=None, loader_pools=(), dump_dir=None):
     """BASELINE config 4 as written: n clips sharded over the ranks (relax-vqa_amd/dataset.py), ONE all-gather of the [n, F] matrix;
     strong scaling: value = n clips / the time of the whole pass (max over ranks), warm-up batches untimed.  `value` is the pass over
     device-resident clips (the metric's definition); host_clips adds the same pass fed from pageable host memory.
@@ -843,6 +872,8 @@ def dataset_pass(eng, workload, n, B, rank, world, split_k, host_clips=False, pr
     matrix, elapsed, gather_s, timings = one_pass(lambda i: resident[i % n_resident], B * world, False)
     if dump and rank == 0:
         np.save(dump, matrix.cpu().numpy())
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"clip_matrix": matrix})
     per_rank = -(-n // world)
     backend = dist.get_backend() if world > 1 else None
     rec = {
@@ -941,7 +972,7 @@ def dataset_pass(eng, workload, n, B, rank, world, split_k, host_clips=False, pr
 def dataset_mode(args, eng, rank, world, barrier, precision):
     rec = dataset_pass(eng, args.workload, args.dataset_clips, args.clips_per_step, rank, world, args.gemm_split_k,
                        host_clips=args.host_clips, prefetch=args.prefetch, workers=args.loader_workers,
-                       n_resident=args.resident_clips or 4, warmup=args.warmup, dump=args.dump_matrix,
+                       n_resident=args.resident_clips or 4, warmup=args.warmup, dump=args.dump_matrix, dump_dir=args.dump_outputs,
                        frame_files=args.from_frame_files, loader_pools=getattr(args, "loader_pools", ()),
                        workers_sweep=[int(x) for x in args.loader_workers_sweep.split(",")] if args.loader_workers_sweep else None)
     if rank == 0:

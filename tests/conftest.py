@@ -27,6 +27,9 @@ def _have_gpu():
 
 
 def pytest_collection_modifyitems(config, items):
+    # host-only tests first, each group in its own order: once a GPU test has initialised the device in this process, the loader
+    # process pools of tests/test_loaderpool_cpu.py may no longer start (relax-vqa_amd/loaderpool.py)
+    items.sort(key=lambda item: "gpu" in item.keywords)
     if _have_gpu():
         return
     skip = pytest.mark.skip(reason="no GPU in this environment")

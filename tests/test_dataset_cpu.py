@@ -13,6 +13,7 @@ import torch.multiprocessing as mp
 
 import relax_vqa_amd  # noqa: F401
 from relax_vqa_amd import dataset, sampling
+from tests.test_distributed_cpu import host_only_rank
 
 F = 11
 
@@ -67,12 +68,13 @@ def _want(n):
     return want
 
 
-def _patched(monkeypatch_dim=None):
-    dataset.feature_dim = lambda engine, resnet=True, vit=True, full=False: F   # the stand-in's width
+def _patched(monkeypatch):
+    """The stand-in's width, for this test only: the GPU tests of the dataset driver run in the same session."""
+    monkeypatch.setattr(dataset, "feature_dim", lambda engine, resnet=True, vit=True, full=False: F)
 
 
-def test_single_rank_ragged_clips_failures_files_and_resume(tmp_path):
-    _patched()
+def test_single_rank_ragged_clips_failures_files_and_resume(tmp_path, monkeypatch):
+    _patched(monkeypatch)
     eng = FakeEngine()
     n = 10
     out_dir = str(tmp_path / "feats")
@@ -106,7 +108,7 @@ def test_single_rank_ragged_clips_failures_files_and_resume(tmp_path):
 def test_a_per_frame_file_that_cannot_be_written_costs_only_its_clip(tmp_path, monkeypatch, prefetch):
     """A failing save_clip_features (disk full, permissions) becomes that clip's error entry - inline and from the writer pool - and the
     pass still returns every row and reaches the collective (a raise here would leave the other ranks waiting in the all-gather)."""
-    _patched()
+    _patched(monkeypatch)
     real = sampling.save_clip_features
 
     def flaky(out_dir, i, network_name, arr):
@@ -124,10 +126,10 @@ def test_a_per_frame_file_that_cannot_be_written_costs_only_its_clip(tmp_path, m
     assert os.path.exists(os.path.join(str(tmp_path / "f"), sampling.feature_file_name(3, "resnet50")))
 
 
-def test_a_loader_with_an_alloc_parameter_decodes_into_the_staging_pool(tmp_path):
+def test_a_loader_with_an_alloc_parameter_decodes_into_the_staging_pool(tmp_path, monkeypatch):
     """clips(i, alloc=f): the driver hands the loader its staging allocator, the loader fills f(shape) and returns it; nothing is copied
     on the host (staged_bytes stays 0) and the rows equal those of the plain loader.  sampling.load_clip_from_frames is such a loader."""
-    _patched()
+    _patched(monkeypatch)
     asked = []
 
     def loader(i, alloc):
@@ -159,18 +161,18 @@ def test_a_loader_with_an_alloc_parameter_decodes_into_the_staging_pool(tmp_path
     assert seen == [clip.shape] and np.array_equal(out, clip) and np.array_equal(sampling.load_clip_from_frames(str(tmp_path), "v"), clip)
 
 
-def test_sequence_input_and_empty_shards():
-    _patched()
+def test_sequence_input_and_empty_shards(monkeypatch):
+    _patched(monkeypatch)
     clips = [_clip(i) for i in (0, 1)]
     m, e = dataset.extract_dataset_clips(clips, 2, FakeEngine(), rank=0, world=1)
     assert m.shape == (2, F) and not e
 
 
 @pytest.mark.parametrize("prefetch,workers", [(0, 1), (1, 1), (2, 3), (5, 8)])
-def test_prefetch_depths_give_the_same_matrix_and_errors(prefetch, workers):
+def test_prefetch_depths_give_the_same_matrix_and_errors(prefetch, workers, monkeypatch):
     """The overlapped pass (loader threads, `prefetch` batches ahead) and the inline pass (prefetch = 0) return the same rows and
     the same error list; a loader that raises (clip 3) or returns a malformed clip (6) costs its own row only, and nothing hangs."""
-    _patched()
+    _patched(monkeypatch)
     eng = FakeEngine()
     matrix, errors = dataset.extract_dataset_clips(_clip, 10, eng, clips_per_step=3, rank=0, world=1, prefetch=prefetch, workers=workers)
     assert np.array_equal(matrix.numpy(), _want(10), equal_nan=True)
@@ -178,9 +180,9 @@ def test_prefetch_depths_give_the_same_matrix_and_errors(prefetch, workers):
     assert eng.batches[0] == 3                               # whole batches reach the engine
 
 
-def test_slow_and_failing_loaders_do_not_deadlock_the_pass():
+def test_slow_and_failing_loaders_do_not_deadlock_the_pass(monkeypatch):
     import time
-    _patched()
+    _patched(monkeypatch)
 
     def slow(i):
         time.sleep(0.02 * (i % 3))
@@ -197,10 +199,10 @@ def test_slow_and_failing_loaders_do_not_deadlock_the_pass():
     assert timings["loader_wait_s"] >= 0 and timings["h2d_bytes"] == 0
 
 
-def test_the_pass_opens_with_short_batches_and_returns_the_same_rows():
+def test_the_pass_opens_with_short_batches_and_returns_the_same_rows(monkeypatch):
     """ramp: B/8, 3B/8, B/2 (together one full batch), then full batches (the loading of the first batch has nothing to hide under); rows and error list as
     without it."""
-    _patched()
+    _patched(monkeypatch)
     src = lambda i: _clip(8 + (i % 3) * 4)                      # noqa: E731  (healthy clips only)
     e1, e2 = FakeEngine(), FakeEngine()
     a, ea = dataset.extract_dataset_clips(src, 70, e1, clips_per_step=16, rank=0, world=1)
@@ -209,18 +211,18 @@ def test_the_pass_opens_with_short_batches_and_returns_the_same_rows():
     assert np.array_equal(a.numpy(), b.numpy()) and not ea and not eb
 
 
-def test_clips_per_step_must_be_positive():
-    _patched()
+def test_clips_per_step_must_be_positive(monkeypatch):
+    _patched(monkeypatch)
     for bad in (0, -3):
         with pytest.raises(ValueError, match="clips_per_step"):
             dataset.extract_dataset_clips(_clip, 4, FakeEngine(), clips_per_step=bad, rank=0, world=1)
 
 
-def test_resume_recomputes_a_truncated_file_instead_of_failing_forever(tmp_path):
+def test_resume_recomputes_a_truncated_file_instead_of_failing_forever(tmp_path, monkeypatch):
     """A run killed mid-write used to leave a truncated .npy that every resume turned into a NaN row (round-3 advice).  Files are
     now written under a temporary name and renamed; a file that still cannot be read, or has the wrong width, is recomputed and
     overwritten."""
-    _patched()
+    _patched(monkeypatch)
     out_dir = str(tmp_path / "feats")
     first, _ = dataset.extract_dataset_clips(_clip, 3, FakeEngine(), clips_per_step=2, out_dir=out_dir, rank=0, world=1)
     assert not [f for f in os.listdir(out_dir) if f.endswith(".tmp")]
@@ -244,6 +246,7 @@ def _free_port():
 
 def _worker(rank, world, port, n, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    host_only_rank()          # (the stand-in engine and gloo need no GPU, and eight ranks must not hold one)
     import relax_vqa_amd  # noqa: F401
     from relax_vqa_amd import dataset as ds
     from relax_vqa_amd import distributed as rd
@@ -350,10 +353,10 @@ def _gated_engine(cap):
     return eng, st
 
 
-def test_alloc_buffers_of_clips_that_fail_after_loading_go_back_to_the_budget():
+def test_alloc_buffers_of_clips_that_fail_after_loading_go_back_to_the_budget(monkeypatch):
     """A loader that decodes into `alloc` memory and then returns something the driver refuses (a malformed clip, a copy, two
     allocations) must not keep its bytes: after the pass nothing is in use, and a second pass over the same stager runs."""
-    _patched()
+    _patched(monkeypatch)
     ids = [0, 1, 6, 2, 4, 6, 7, 8]                              # _clip(6) is malformed ([T,1,...]): _check_clip refuses it AFTER the decode
 
     def loader(i, alloc):
@@ -383,11 +386,11 @@ def test_alloc_buffers_of_clips_that_fail_after_loading_go_back_to_the_budget():
         gate.acquire(1, 80)
 
 
-def test_an_exception_in_the_driver_thread_does_not_hang_on_loaders_waiting_for_pinned_memory():
+def test_an_exception_in_the_driver_thread_does_not_hang_on_loaders_waiting_for_pinned_memory(monkeypatch):
     """Something escapes the driver loop (here: the engine's rows_mean is missing when a resumed clip comes up ... a HIP error would
     do the same) while loader threads wait at the gate for memory only the driver could hand back: the pass must raise, not hang,
     and the next pass over the same stager starts with a clean budget."""
-    _patched()
+    _patched(monkeypatch)
 
     class Boom(BaseException):
         pass

@@ -22,9 +22,18 @@ def _fake_clip_vector(i, F=37):
     return torch.randn(F, generator=g)
 
 
+def host_only_rank():
+    """Called first in a spawned rank of these CPU tests: the rank sees the host as a machine without a GPU shows it, on a GPU box
+    too.  Asking whether there is a device (distributed.init_from_env; dist.barrier() asks for the accelerator even under gloo)
+    opens it, and a GPU shared by several jobs admits only a few processes: eight ranks and the test runner are more than that."""
+    torch.cuda.is_available = lambda: False
+    torch._C._get_accelerator = lambda: torch.device("cpu")
+
+
 def _worker(rank, world, port, n_clips, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
+    host_only_rank()
     import relax_vqa_amd  # noqa: F401
     from relax_vqa_amd import distributed as rd2
     r, w, _ = rd2.init_from_env(backend="gloo")

@@ -78,3 +78,31 @@ def test_clip_vectors_of_one_bench_sized_clip_against_the_oracle_pipeline():
     edges = [0, 13120, 15171, 15171 + 2304, 19779]
     for a, b, nm in zip(edges[:-1], edges[1:], ["RN50 layer stack", "RN50 residual pool", "ViT original", "ViT residual"]):
         assert_close(got[a:b], want[a:b], f"clip vector block: {nm}")
+
+
+def test_bench_dump_outputs_hold_what_the_timed_path_returned(tmp_path):
+    """bench.py --dump-outputs: DIR/clip_vectors.npy is the output of the LAST timed step - config 4's clip shape, one clip per step,
+    two timed steps: step 1 takes resident clip 1 (synthetic_clip(16, 540, 960, clip_id=1, distinct=4)) - and the result line
+    carries the step count asked for and ms_per_step.  The same clip through clip_vectors here gives the same vector."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out_dir = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "config4", "--clips-per-step", "1",
+                          "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-fast-mode", "--no-h2d", "--no-measure-traffic",
+                          "--dump-outputs", str(out_dir)], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert os.listdir(out_dir) == ["clip_vectors.npy"]
+    dumped = np.load(out_dir / "clip_vectors.npy")
+    assert dumped.dtype == np.float32 and dumped.shape == (1, 19779)
+    rn50_weights(), vit_weights("vit_base")
+    clip = synth.synthetic_clip(16, 540, 960, clip_id=1, distinct=4)
+    want = engine().clip_vectors([torch.from_numpy(clip).cuda()]).cpu().numpy()
+    assert_close(dumped, want, "dumped clip vector vs clip_vectors", rtol=1e-5, atol_frac=1e-6)

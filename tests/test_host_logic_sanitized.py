@@ -33,7 +33,11 @@ def test_host_logic_under_asan_and_ubsan():
 
 
 def test_the_sanitizer_build_does_catch_an_overrun():
-    """The pass above means something only if the harness can fail: hand the packer an output buffer that is one row short."""
+    """The pass above means something only if the harness can fail: hand the packer an output buffer that is one row short.
+    60 output channels, not 64: 63 rows of 64 floats plus ASan's 256-byte left redzone fill a 16 KiB size class exactly, so nothing
+    poisoned follows the buffer in its own slot, and when that slot ends the mapped part of the heap the overrun is a SEGV instead of
+    a heap-buffer-overflow report (seen in about one allocator layout in four).  59 rows leave 1 KiB of poisoned slack behind the
+    buffer in every layout.  abort_on_error=0: the report ends the child with exit status 1, not SIGABRT."""
     asan = _gcc_file("libasan.so")
     if not asan:
         pytest.skip("no libasan in this toolchain")
@@ -41,12 +45,12 @@ def test_the_sanitizer_build_does_catch_an_overrun():
     code = (
         "import ctypes as C, numpy as np\n"
         f"lib = C.CDLL({os.path.join(CSRC, 'librelax_host_san.so')!r})\n"
-        "w = np.ones((64, 64, 1, 1), np.float32)\n"
+        "w = np.ones((60, 64, 1, 1), np.float32)\n"
         "ptrs = (C.c_void_p * 1)(w.ctypes.data); names = (C.c_char_p * 1)(b'c.weight'); numels = (C.c_int64 * 1)(w.size)\n"
-        "out = np.zeros((63, 64), np.float32)\n"
+        "out = np.zeros((59, 64), np.float32)\n"
         "err = C.create_string_buffer(64)\n"
-        "lib.relax_host_pack_conv(ptrs, names, numels, 1, b'c', b'', 64, 64, 64, 1, out.ctypes.data_as(C.c_void_p), None, err, 64)\n"
+        "lib.relax_host_pack_conv(ptrs, names, numels, 1, b'c', b'', 60, 64, 64, 1, out.ctypes.data_as(C.c_void_p), None, err, 64)\n"
         "print('survived')\n")
-    env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1")
+    env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0")
     res = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
     assert res.returncode != 0 and "heap-buffer-overflow" in res.stderr, (res.returncode, res.stderr[-1500:])

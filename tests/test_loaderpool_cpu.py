@@ -28,8 +28,8 @@ def _thread_path(n):
 
 
 @pytest.mark.parametrize("src", [loader_sources.source, loader_sources.plain_source], ids=["alloc", "plain"])
-def test_process_pool_gives_the_matrix_of_the_thread_path(src):
-    _patched()
+def test_process_pool_gives_the_matrix_of_the_thread_path(src, monkeypatch):
+    _patched(monkeypatch)
     n = 14
     before = _shm_names()
     with LoaderProcessPool(src, processes=3, segments_per_worker=2).start() as pool:
@@ -52,7 +52,7 @@ def test_process_pool_gives_the_matrix_of_the_thread_path(src):
 
 
 def test_a_dead_worker_costs_its_clips_only(monkeypatch):
-    _patched()
+    _patched(monkeypatch)
     monkeypatch.setenv("RELAX_TEST_KILL_WORKER", "1")          # (spawned workers inherit the environment)
     n = 16
     with LoaderProcessPool(loader_sources.source, processes=3).start() as pool:

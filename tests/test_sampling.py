@@ -69,14 +69,14 @@ def test_frame_files_are_paired_and_read_like_the_reference(tmp_path):
         sampling.load_clip_from_frames(str(d), "missing_video")
 
 
-def test_dataset_pass_from_frame_directories(tmp_path):
+def test_dataset_pass_from_frame_directories(tmp_path, monkeypatch):
     """The reference's data flow end to end on the host side: frame files on disk -> loader threads decode them -> batches (a stand-in
     engine here); an undecodable video costs its own row."""
     import torch
     from PIL import Image
     from relax_vqa_amd import dataset, sampling
     from tests.test_dataset_cpu import F, FakeEngine
-    dataset.feature_dim = lambda engine, resnet=True, vit=True, full=False: F
+    monkeypatch.setattr(dataset, "feature_dim", lambda engine, resnet=True, vit=True, full=False: F)
     g = np.random.default_rng(5)
     clips = []
     for v in range(4):
