@@ -41,6 +41,9 @@ extern "C" {
 #define RELAX_RN50_LAYER_STACK_DIM 13120 /* 64+3*256+4*512+4*1024+3*2048 */
 #define RELAX_RN50_POOL_DIM 2051         /* 2048 + mean,max,std */
 #define RELAX_RN50_NUM_TAPS 15
+#define RELAX_VGG16_LAYER_STACK_DIM 4224 /* 64+64+128+128+3*256+3*512+3*512 */
+#define RELAX_VGG16_POOL_DIM 4099        /* fc2 4096 + mean,max,std */
+#define RELAX_VGG16_NUM_TAPS 15          /* 13 convolutions, fc1, fc2 */
 
 typedef enum relax_status {
     RELAX_OK = 0,
@@ -125,6 +128,13 @@ int relax_load_resnet50(relax_handle* h, const float* const* tensors, const char
 int relax_load_vit(relax_handle* h, const float* const* tensors, const char* const* names,
                    const int64_t* numels, int n, int dim, int depth, int heads);
 
+/* Replaces models.vgg16(pretrained=True) (src/extractor/visualise_vgg.py:21, visualise_vgg_layer.py:19; torchvision
+ * configuration D, no BatchNorm).  torchvision keys: features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias} and
+ * classifier.{0,3}.{weight,bias}; "classifier.6.*" is ignored.  A missing key or a wrong size is refused with a message naming
+ * the key.  classifier.0's columns are permuted once here from the NCHW flatten of pool5 to the NHWC one. */
+int relax_load_vgg16(relax_handle* h, const float* const* tensors, const char* const* names,
+                     const int64_t* numels, int n);
+
 /* ---- stage A: residual -> patch score -> top-n -> fragments (bit-exact integer path) -------- */
 /* Replaces, per (frame, next) pair: cv2.absdiff (main_fragment_layerstack.py:302),
  * process_patches('frame_diff') = get_patch_diff + extract_important_patches (:232-240,
@@ -198,6 +208,19 @@ int relax_resnet50_features(relax_handle* h, const uint8_t* frags, int N, float*
  * as fp32, the pool statistics of the first group are not formed.  Either group may be empty (its pointer may then be NULL). */
 int relax_resnet50_clip_features(relax_handle* h, const uint8_t* frags, int N, int n_layer_stack, float* layer_stack, float* pool,
                                  relax_stream stream);
+
+/* VGG-16 on N fragments (uint8 [N,224,224,3] BGR; images are processed in chunks of at most 32).  Every tap is read POST-ReLU:
+ * torchvision's ReLU(inplace=True) behind each hooked module rectifies the hooked tensor before the reference copies it.
+ *   layer_stack : fp32 [N,4224] = get_deep_feature('vgg16',..,'layer_stack') + process_video_feature(..,'layer_stack'):
+ *                 spatial means of features[0,2,5,...,28] (main_fragment_layerstack.py:101-105,134-140;
+ *                 extractor/visualise_vgg.py:38-58)   (may be NULL)
+ *   pool        : fp32 [N,4099]  = get_deep_feature('vgg16',..,'pool') + process_video_feature(..,'pool'): fc2 =
+ *                 classifier[3] + mean,max,std (main_fragment_layerstack.py:106-108,141-149; extractor/visualise_vgg_layer.py:51-58)
+ *                 (may be NULL)
+ *   taps_nchw   : NULL, or RELAX_VGG16_NUM_TAPS device pointers (each NULL or fp32): 0..12 the convolutions [N,C,H,W],
+ *                 13 fc1 [N,4096], 14 fc2 [N,4096]. */
+int relax_vgg16_features(relax_handle* h, const uint8_t* frags, int N, float* layer_stack, float* pool,
+                         float* const* taps_nchw, relax_stream stream);
 
 /* ViT on N fragments.  tokens: fp32 [N,196,dim] final-norm patch tokens
  * (visualise_vit_layer.process_video_frame, :447-500) (may be NULL);

@@ -24,6 +24,7 @@ PROTOTYPES = {
     "relax_load_resnet50": (C.c_int, [c_vp, C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int]),
     "relax_load_vit": (C.c_int, [c_vp, C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
                                  C.c_int, C.c_int, C.c_int]),
+    "relax_load_vgg16": (C.c_int, [c_vp, C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int]),
     "relax_fragment_pairs": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "relax_fragment_image": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -35,6 +36,7 @@ PROTOTYPES = {
     "relax_resize_frames": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp]),
     "relax_resnet50_features": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, C.POINTER(c_vp), c_vp]),
     "relax_resnet50_clip_features": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_vp, c_vp, c_vp]),
+    "relax_vgg16_features": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, C.POINTER(c_vp), c_vp]),
     "relax_vit_features": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
     "relax_load_mlp_head": (C.c_int, [c_vp, C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
                                       c_vp, c_vp, c_vp, C.c_int]),

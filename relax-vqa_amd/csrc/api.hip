@@ -213,6 +213,7 @@ int relax_destroy(relax_handle* h) {
     (void)hipDeviceSynchronize();
     free_resnet(h);
     free_vit(h);
+    free_vgg(h);
     free_resize(h);
     free_head(h);
     if (h->head_ws.p) (void)hipFree(h->head_ws.p);
@@ -240,6 +241,10 @@ int relax_reserve(relax_handle* h, int max_images) {
     size_t need = resnet_arena_bytes(max_images);
     if (h->vit.loaded) {
         size_t v = vit_arena_bytes(h->vit, max_images);
+        if (v > need) need = v;
+    }
+    if (h->vgg.loaded) {   // (VGG-16 runs in chunks of images: its need stops growing past one chunk)
+        size_t v = vgg_arena_bytes(max_images);
         if (v > need) need = v;
     }
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));

@@ -145,6 +145,40 @@ double linear_of_layernorm_bound(const float* W, const float* b, const float* ga
 }  // namespace host
 }  // namespace relax
 
+namespace relax {
+namespace host {
+
+const int kVggFeatureIndex[kVggConvs] = {0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28};
+const int kVggConvCout[kVggConvs] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
+const int kVggConvCin[kVggConvs] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
+
+bool vgg16_check_keys(const StateDict& sd, std::string& err) {
+    const char* what = "vgg16 state dict";
+    for (int i = 0; i < kVggConvs; ++i) {
+        const std::string p = "features." + std::to_string(kVggFeatureIndex[i]);
+        if (!sd.get(p + ".weight", (int64_t)kVggConvCout[i] * kVggConvCin[i] * 9, err, what)) return false;
+        if (!sd.get(p + ".bias", kVggConvCout[i], err, what)) return false;
+    }
+    if (!sd.get("classifier.0.weight", (int64_t)4096 * 512 * 49, err, what)) return false;
+    if (!sd.get("classifier.0.bias", 4096, err, what)) return false;
+    if (!sd.get("classifier.3.weight", (int64_t)4096 * 4096, err, what)) return false;
+    if (!sd.get("classifier.3.bias", 4096, err, what)) return false;
+    return true;
+}
+
+void vgg16_fc1_to_nhwc(const float* w, int rows, int C, int HW, float* out) {
+    const size_t K = (size_t)C * HW;
+    for (int r = 0; r < rows; ++r) {
+        const float* src = w + (size_t)r * K;
+        float* dst = out + (size_t)r * K;
+        for (int c = 0; c < C; ++c)
+            for (int p = 0; p < HW; ++p) dst[(size_t)p * C + c] = src[(size_t)c * HW + p];
+    }
+}
+
+}  // namespace host
+}  // namespace relax
+
 #ifdef RELAX_HOST_TEST_API
 // ---- C entry points of the host half alone (librelax_host_san.so of tests/test_host_logic_sanitized.py; compiled only
 // with -DRELAX_HOST_TEST_API: the product library does not export them) ---------------------------------------------------------------------------------
@@ -229,6 +263,17 @@ double relax_host_layernorm_out_bound(const float* gamma, const float* beta, int
 double relax_host_linear_of_layernorm_bound(const float* w, const float* b, const float* gamma, const float* beta, int dim, int n0, int n1) {
     return relax::host::linear_of_layernorm_bound(w, b, gamma, beta, dim, n0, n1);
 }
+
+// VGG-16: 0 if every key is present with its size, -1 and the message otherwise; and the fc1 column permutation
+int relax_host_vgg16_check_keys(const float* const* tensors, const char* const* names, const int64_t* numels, int n, char* err, int err_len) {
+    relax::host::StateDict sd;
+    for (int i = 0; i < n; ++i) sd.add(names[i], tensors[i], numels[i]);
+    std::string e;
+    if (relax::host::vgg16_check_keys(sd, e)) return 0;
+    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+    return -1;
+}
+void relax_host_vgg16_fc1_to_nhwc(const float* w, int rows, int c, int hw, float* out) { relax::host::vgg16_fc1_to_nhwc(w, rows, c, hw, out); }
 
 }  // extern "C"
 #endif  // RELAX_HOST_TEST_API

@@ -47,6 +47,19 @@ struct TailSplit {
 };
 TailSplit choose_tail_split(int ntiles, int slots, int nk, int min_steps, bool can_split);
 
+// ---- VGG-16 (torchvision configuration D, no BatchNorm) -----------------------------------------------------------------------
+// The 13 convolutions features.{0,2,5,7,10,12,14,17,19,21,24,26,28} (3x3, pad 1) and the two classifier layers the features read
+// (classifier.0: 25088 -> 4096, classifier.3: 4096 -> 4096; classifier.6 is never run).
+constexpr int kVggConvs = 13;
+extern const int kVggFeatureIndex[kVggConvs];
+extern const int kVggConvCout[kVggConvs];
+extern const int kVggConvCin[kVggConvs];
+// Every weight / bias the VGG-16 loader reads is present with its torchvision size: true, or false and a message naming the key.
+bool vgg16_check_keys(const StateDict& sd, std::string& err);
+// classifier.0.weight [rows][C*HW] in torchvision's NCHW flatten order (column c*HW + p) -> the same rows in NHWC order
+// (column p*C + c), so fc1 is a plain GEMM over the pool5 rows as the NHWC driver stores them.  out must hold rows * C * HW floats.
+void vgg16_fc1_to_nhwc(const float* w, int rows, int C, int HW, float* out);
+
 // ---- scales of the two-plane fp16 format (csrc/h2.h): powers of two from RIGOROUS bounds, so no value can leave the fp16 range --------
 // The power of two that puts `amax` into [2^14, 2^15) (so twice the bound still fits below 65504); 1 for zero / non-finite.
 float h2_scale_for_bound(double amax);

@@ -455,6 +455,15 @@ int launch_gap_groups_finish(relax_handle* h, const float* groups, float* out, i
     return RELAX_OK;
 }
 
+int launch_gap_groups_finish_rows(relax_handle* h, const float* groups, float* out, int Nimg, int HW, int C, int64_t out_stride, int group,
+                                  hipStream_t s) {
+    RELAX_REQUIRE(h, group > 0 && HW % group == 0 && Nimg > 0 && C > 0, "gap_groups_finish: bad shape HW=%d C=%d group=%d", HW, C, group);
+    hipLaunchKernelGGL(gap_groups_finish, dim3((unsigned)(((int64_t)Nimg * C + 255) / 256)), dim3(256), 0, s, groups, out, Nimg,
+                       HW / group, HW, C, out_stride);
+    RELAX_HIP_CHECK(h, hipGetLastError());
+    return RELAX_OK;
+}
+
 constexpr int GAP_MAX_SPLIT = 16;
 
 int launch_gap_ws(relax_handle* h, const float* x, float* out, int Nimg, int HW, int C, int64_t out_stride,

@@ -209,6 +209,15 @@ struct VitW {
     std::vector<void*> allocs;
 };
 
+// ---- VGG-16 (csrc/vgg16.hip) -------------------------------------------------------------------------------------------------
+struct VggW {
+    bool loaded = false;
+    ConvW conv[13];         // conv[0]: [64][32] fp32 (k = (dy*3+dx)*3 + c, RGB, zero padded): vgg_conv1_1 reads it directly; the others as ResNet's
+    ConvW fc[2];            // classifier.0 (columns permuted to the NHWC flatten of pool5) and classifier.3 as 1x1 convolutions over 1x1 images
+    float conv1_scale = 1.f;   // static power of two of conv1_1's fp16-plane output (a bound from the normalised input range)
+    std::vector<void*> allocs;
+};
+
 // ---- quality head (imputer + scaler + MLP), BatchNorm folded into fc1 ----------------------------------------
 struct HeadW {
     bool loaded = false;
@@ -308,6 +317,7 @@ struct relax_handle {
     std::vector<relax::ResizeTable> resize_tables;
     relax::ResNet50W rn;
     relax::VitW vit;
+    relax::VggW vgg;
     relax::Profiler prof;
 };
 
@@ -382,8 +392,12 @@ int launch_bn_relu_maxpool_sp3(relax_handle* h, const float* x, const float* sca
                                int Nimg, int H, int W, int C, hipStream_t s, unsigned* amax_out = nullptr, unsigned* block_ws = nullptr);
 int launch_gap_groups_finish(relax_handle* h, const float* groups, float* out, int Nimg, int HW, int C, int64_t out_stride,
                              hipStream_t s);
+int launch_gap_groups_finish_rows(relax_handle* h, const float* groups, float* out, int Nimg, int HW, int C, int64_t out_stride, int group,
+                                  hipStream_t s);   // group sums of `group` rows each (gemm_h2.hip's epilogue: 4 at every map size)
 int launch_gap(relax_handle* h, const float* x, float* out, int Nimg, int HW, int C, int64_t out_stride,
                hipStream_t s);
+// (resnet50.hip) vector v[dim] -> out[0:dim] = v, out[dim .. dim+2] = mean, max, population std; dim = 2048 or 4096
+int launch_pool_stats(relax_handle* h, const float* v, int64_t v_stride, float* out, int64_t out_stride, int n, int dim, hipStream_t s);
 int launch_nhwc_to_nchw(relax_handle* h, const float* x, float* y, int Nimg, int HW, int C, hipStream_t s);
 
 // model drivers
@@ -391,6 +405,8 @@ void free_resnet(relax_handle* h);
 void free_vit(relax_handle* h);
 void free_resize(relax_handle* h);
 void free_head(relax_handle* h);
+void free_vgg(relax_handle* h);
+size_t vgg_arena_bytes(int n_images);
 size_t resnet_arena_bytes(int n_images);
 size_t vit_arena_bytes(const VitW& v, int n_images);
 

@@ -39,18 +39,19 @@ __global__ __launch_bounds__(256) void rn_preprocess(const uint8_t* __restrict__
     reinterpret_cast<float4*>(x)[i] = o;
 }
 
-// avgpool vector v[2048] -> out[0:2048] = v, out[2048..2050] = mean, max, population std
+// avgpool vector v[D] -> out[0:D] = v, out[D..D+2] = mean, max, population std  (D = 2048: ResNet-50's avgpool; 4096: VGG-16's fc2)
+template <int D>
 __global__ __launch_bounds__(256) void rn_pool_stats(const float* __restrict__ avg, int64_t avg_stride,
-                                                     float* __restrict__ out) {
+                                                     float* __restrict__ out, int64_t out_stride) {
     __shared__ float red[256];
     __shared__ float s_mean;
     const int n = blockIdx.x, t = threadIdx.x;
     const float* v = avg + (int64_t)n * avg_stride;
-    float* o = out + (int64_t)n * RELAX_RN50_POOL_DIM;
-    float vals[8];
+    float* o = out + (int64_t)n * out_stride;
+    float vals[D / 256];
     float s = 0.f, m = -INFINITY;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < D / 256; ++j) {
         vals[j] = v[t + 256 * j];
         o[t + 256 * j] = vals[j];
         s += vals[j];
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(256) void rn_pool_stats(const float* __restrict__ a
         if (t < w) red[t] += red[t + w];
         __syncthreads();
     }
-    if (t == 0) s_mean = red[0] / 2048.0f;
+    if (t == 0) s_mean = red[0] / (float)D;
     __syncthreads();
     const float mean = s_mean;
     __syncthreads();
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(256) void rn_pool_stats(const float* __restrict__ a
     __syncthreads();
     float q = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) q += (vals[j] - mean) * (vals[j] - mean);
+    for (int j = 0; j < D / 256; ++j) q += (vals[j] - mean) * (vals[j] - mean);
     red[t] = q;
     __syncthreads();
     for (int w = 128; w >= 1; w >>= 1) {
@@ -84,10 +85,18 @@ __global__ __launch_bounds__(256) void rn_pool_stats(const float* __restrict__ a
         __syncthreads();
     }
     if (t == 0) {
-        o[2048] = mean;
-        o[2049] = mx;
-        o[2050] = sqrtf(red[0] / 2048.0f);
+        o[D] = mean;
+        o[D + 1] = mx;
+        o[D + 2] = sqrtf(red[0] / (float)D);
     }
+}
+
+int launch_pool_stats(relax_handle* h, const float* v, int64_t v_stride, float* out, int64_t out_stride, int n, int dim, hipStream_t s) {
+    RELAX_REQUIRE(h, n > 0 && (dim == 2048 || dim == 4096), "pool_stats: n=%d dim=%d", n, dim);
+    if (dim == 2048) hipLaunchKernelGGL(rn_pool_stats<2048>, dim3(n), dim3(256), 0, s, v, v_stride, out, out_stride);
+    else hipLaunchKernelGGL(rn_pool_stats<4096>, dim3(n), dim3(256), 0, s, v, v_stride, out, out_stride);
+    RELAX_HIP_CHECK(h, hipGetLastError());
+    return RELAX_OK;
 }
 
 // ---- weights ---------------------------------------------------------------------------------------
@@ -448,9 +457,7 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
             avg_src = avg_ws;
             avg_stride = 2048;
         }
-        hipLaunchKernelGGL(rn_pool_stats, dim3(n_pool), dim3(256), 0, s, avg_src, avg_stride, pool);
-        RELAX_HIP_CHECK(h, hipGetLastError());
-        return RELAX_OK;
+        return launch_pool_stats(h, avg_src, avg_stride, pool, RELAX_RN50_POOL_DIM, n_pool, 2048, s);
     };
 
     if (h->gemm.precision >= 2) {   // (3 = f16x2: layer3 / layer4 and the 3x3 convolutions of layer1 / layer2 on fp16 planes - "rn_h2", "rn_h2_early" - the rest bf16x6)

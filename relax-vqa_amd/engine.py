@@ -27,6 +27,10 @@ LAYER_STACK_DIM = 13120
 RN50_POOL_DIM = 2051
 TOP_N = 196
 TARGET = 224
+VGG16_LAYER_STACK_DIM = 4224
+VGG16_POOL_DIM = 4099
+VGG16_FEATURE_INDEX = [0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28]   # features[i] of the 13 convolutions (tap order)
+VGG16_TAP_SHAPES = [(64, 224)] * 2 + [(128, 112)] * 2 + [(256, 56)] * 3 + [(512, 28)] * 3 + [(512, 14)] * 3
 RN50_TAP_SHAPES = [(64, 112)] + [(256, 56)] * 3 + [(512, 28)] * 4 + [(1024, 14)] * 4 + [(2048, 7)] * 3
 VIT_CONFIGS = {"vit_tiny": (192, 12, 3), "vit_small": (384, 12, 6), "vit_base": (768, 12, 12)}
 
@@ -92,6 +96,12 @@ class RelaxEngine:
         """state_dict: torchvision resnet50 key names -> fp32 arrays/tensors."""
         ptrs, names, numels, n, keep = self._marshal_state_dict(state_dict)
         self._check(self.lib.relax_load_resnet50(self.h, ptrs, names, numels, n), "relax_load_resnet50")
+        del keep
+
+    def load_vgg16(self, state_dict):
+        """state_dict: torchvision vgg16 key names -> fp32 arrays/tensors (classifier.6 is ignored)."""
+        ptrs, names, numels, n, keep = self._marshal_state_dict(state_dict)
+        self._check(self.lib.relax_load_vgg16(self.h, ptrs, names, numels, n), "relax_load_vgg16")
         del keep
 
     def load_vit(self, state_dict, name_model="vit_base"):
@@ -296,6 +306,30 @@ class RelaxEngine:
             tap_ptrs = arr
         rc = self.lib.relax_resnet50_features(self.h, _ptr(frags), N, _ptr(ls), _ptr(pl), tap_ptrs, _stream())
         self._check(rc, "relax_resnet50_features")
+        return (ls, pl, tap_out) if taps is not None else (ls, pl)
+
+    def vgg16_features(self, frags, layer_stack=True, pool=True, taps=None):
+        """frags uint8 [N,224,224,3] BGR -> (layer_stack fp32 [N,4224] | None, pool fp32 [N,4099] | None[, taps]).
+        taps: optional iterable of tap indices, 0..12 the convolutions (features[VGG16_FEATURE_INDEX[i]], [N,C,H,W]), 13 fc1 and
+        14 fc2 ([N,4096]); every tap is post-ReLU, as the reference's hooks read it."""
+        frags = self._frags(frags)
+        N = frags.shape[0]
+        dev = self.device
+        ls = torch.empty((N, VGG16_LAYER_STACK_DIM), dtype=torch.float32, device=dev) if layer_stack else None
+        pl = torch.empty((N, VGG16_POOL_DIM), dtype=torch.float32, device=dev) if pool else None
+        tap_out, tap_ptrs = {}, None
+        if taps is not None:
+            arr = (C.c_void_p * 15)()
+            for t in taps:
+                if t < 13:
+                    c, s = VGG16_TAP_SHAPES[t]
+                    tap_out[t] = torch.empty((N, c, s, s), dtype=torch.float32, device=dev)
+                else:
+                    tap_out[t] = torch.empty((N, 4096), dtype=torch.float32, device=dev)
+                arr[t] = tap_out[t].data_ptr()
+            tap_ptrs = arr
+        rc = self.lib.relax_vgg16_features(self.h, _ptr(frags), N, _ptr(ls), _ptr(pl), tap_ptrs, _stream())
+        self._check(rc, "relax_vgg16_features")
         return (ls, pl, tap_out) if taps is not None else (ls, pl)
 
     def resnet50_clip_features(self, frags, n_layer_stack):

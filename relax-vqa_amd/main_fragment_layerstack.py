@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import runtime
-from .extractor import visualise_resnet, visualise_resnet_layer, visualise_vit_layer
+from .extractor import visualise_resnet, visualise_resnet_layer, visualise_vgg, visualise_vgg_layer, visualise_vit_layer
 
 ALL_LAYERS = list(visualise_resnet.LAYER_INDEX)
 
@@ -109,11 +109,18 @@ def get_deep_feature(network_name, video_name, image, qp, layer_name):
             frame_npy = visualise_resnet_layer.process_fragment_array(image, "resnet50.avgpool")
         else:
             raise ValueError(f"unknown layer_name {layer_name!r}")
+    elif network_name == "vgg16":       # (reference :101-108; weights: runtime.ensure_vgg16 - NotImplementedError until loaded)
+        if layer_name == "layer_stack":
+            frame_npy = visualise_vgg.process_fragment_array(image, visualise_vgg.ALL_LAYERS)
+        elif layer_name == "pool":
+            frame_npy = visualise_vgg_layer.process_fragment_array(image, "fc2")
+        else:
+            raise ValueError(f"unknown layer_name {layer_name!r}")
     elif network_name == "vit":
         model = visualise_vit_layer.VitGenerator("vit_base", 16, None, evaluate=True, random=False, verbose=False)
         frame_npy = visualise_vit_layer.process_fragment_array(image, model)
     else:
-        raise NotImplementedError(f"network {network_name!r} is out of scope (VGG-16 is an ablation backbone)")
+        raise NotImplementedError(f"network {network_name!r} is out of scope")
     return png_path, npy_path, frame_npy
 
 

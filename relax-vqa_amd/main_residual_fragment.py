@@ -12,7 +12,7 @@ import numpy as np
 
 from . import main_fragment_layerstack as _ls
 from . import runtime
-from .extractor import visualise_resnet_layer, visualise_vit_layer
+from .extractor import visualise_resnet_layer, visualise_vgg_layer, visualise_vit_layer
 from .main_fragment_layerstack import flow_to_rgb, get_patch_diff  # noqa: F401  (same behaviour in both drivers)
 
 _fragments_by_path = {}     # path string -> uint8 [224,224,3]; bounded: the reference consumes each one right away
@@ -52,16 +52,23 @@ def get_deep_feature(network_name, video_name, image_path, qp, layer_name):
             frame_npy = visualise_resnet_layer.process_fragment_array(image, "resnet50.layer4[2]")
         else:
             raise ValueError(f"unknown layer_name {layer_name!r}")      # the reference hits an unbound local here
+    elif network_name == "vgg16":       # (reference :96-102)
+        if layer_name == "pool":
+            frame_npy = visualise_vgg_layer.process_fragment_array(image, "fc2")
+        elif layer_name == "last_layer":
+            frame_npy = visualise_vgg_layer.process_fragment_array(image, 28)
+        else:
+            raise ValueError(f"unknown layer_name {layer_name!r}")
     elif network_name == "vit":
         model = visualise_vit_layer.VitGenerator("vit_base", 16, None, evaluate=True, random=False, verbose=False)
         frame_npy = visualise_vit_layer.process_fragment_array(image, model)
     else:
-        raise NotImplementedError(f"network {network_name!r} is out of scope (VGG-16 is an ablation backbone)")
+        raise NotImplementedError(f"network {network_name!r} is out of scope")
     return png_path, npy_path, frame_npy
 
 
 def process_video_feature(video_feature, network_name):
-    """list of per-frame activations -> [T, 2304] (vit) or [T, 2051] (resnet50 pool) (reference :118-156)."""
+    """list of per-frame activations -> [T, 2304] (vit), [T, 2051] (resnet50 pool) or [T, 4099] (vgg16 fc2) (reference :118-156)."""
     if network_name != "vit":
         for frame in video_feature:
             if getattr(frame, "pooled", None) is None and np.squeeze(frame).ndim != 1:

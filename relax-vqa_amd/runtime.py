@@ -12,7 +12,7 @@ import numpy as np
 from . import synth
 
 log = logging.getLogger("relax_vqa_amd")
-_state = {"engine": None, "rn": False, "vit": None}
+_state = {"engine": None, "rn": False, "vit": None, "vgg": None}
 
 
 _WRAPPER_KEYS = ("state_dict", "model", "teacher", "student")   # torch.save({"state_dict": ...}), DINO full checkpoints
@@ -86,9 +86,27 @@ def ensure_vit(name_model="vit_base"):
     return eng
 
 
-def set_weights(resnet50=None, vit=None, vit_name="vit_base"):
+def ensure_vgg16():
+    """VGG-16 is an ablation backbone of the reference (its layer-stack ablation): its weights come from RELAX_VGG16_WEIGHTS or
+    set_weights(vgg16=...) only - there is no synthetic fallback.  Without them NotImplementedError says how to load them."""
+    eng = get_engine()
+    if not _state["vgg"]:
+        path = os.environ.get("RELAX_VGG16_WEIGHTS")
+        if not path:
+            raise NotImplementedError(
+                "VGG-16 weights are not loaded: point RELAX_VGG16_WEIGHTS at a torchvision vgg16 state dict, or call "
+                "runtime.set_weights(vgg16=state_dict)")
+        eng.load_vgg16(_load_file(path))
+        _state["vgg"] = True
+    return eng
+
+
+def set_weights(resnet50=None, vit=None, vit_name="vit_base", vgg16=None):
     """Explicit weight injection (tests, real checkpoints already in memory)."""
     eng = get_engine()
+    if vgg16 is not None:
+        eng.load_vgg16(vgg16)
+        _state["vgg"] = True
     if resnet50 is not None:
         eng.load_resnet50(resnet50)
         _state["rn"] = True
@@ -99,9 +117,10 @@ def set_weights(resnet50=None, vit=None, vit_name="vit_base"):
 
 
 def reset_weights():
-    """Forget which weights are loaded: the next ensure_resnet50() / ensure_vit() reads RELAX_*_WEIGHTS again."""
+    """Forget which weights are loaded: the next ensure_resnet50() / ensure_vit() / ensure_vgg16() reads RELAX_*_WEIGHTS again."""
     _state["rn"] = False
     _state["vit"] = None
+    _state["vgg"] = None
 
 
 def read_image_bgr(image_path):

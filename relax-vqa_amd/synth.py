@@ -16,6 +16,44 @@ def _rng(seed):
     return np.random.Generator(np.random.PCG64(seed))
 
 
+VGG16_FEATURE_INDEX = [0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28]
+VGG16_CONV_CHANNELS = [(64, 3), (64, 64), (128, 64), (128, 128), (256, 128), (256, 256), (256, 256),
+                       (512, 256), (512, 512), (512, 512), (512, 512), (512, 512), (512, 512)]
+
+
+def vgg16_state_dict(seed=11, adversarial=False):
+    """fp32 numpy state dict with torchvision vgg16 key names (features.* and classifier.{0,3}; classifier.6 omitted: the
+    reference never reads it).  He-scaled weights (std sqrt(2 / fan_in)) so activations stay O(1) through the 13 ReLU layers.
+    adversarial=True: mixed-sign biases of a visible size, and in every layer three output channels 50 - 100 x the others (their
+    weight rows and biases scaled up; the consumer's columns of those channels scaled down by the same factor, so the net stays
+    O(1) while every tap carries channels far above the rest)."""
+    g = _rng(seed + (1000 if adversarial else 0))
+    sd = {}
+    down = None    # per input channel: 1 / the factor its producer applied (adversarial)
+    for idx, (cout, cin) in zip(VGG16_FEATURE_INDEX, VGG16_CONV_CHANNELS):
+        w = g.standard_normal((cout, cin, 3, 3), dtype=np.float32) * np.float32(np.sqrt(2.0 / (cin * 9)))
+        b = (g.standard_normal(cout) * 0.05).astype(np.float32)
+        if adversarial:
+            b = (g.standard_normal(cout) * 0.5).astype(np.float32)
+            if down is not None:
+                w *= down[None, :, None, None]
+            f = np.ones(cout, np.float32)
+            f[g.choice(cout, 3, replace=False)] = g.uniform(50.0, 100.0, 3).astype(np.float32)
+            w *= f[:, None, None, None]
+            b *= f
+            down = (1.0 / f).astype(np.float32)
+        sd[f"features.{idx}.weight"] = w.astype(np.float32)
+        sd[f"features.{idx}.bias"] = b.astype(np.float32)
+    w1 = g.standard_normal((4096, 512 * 49), dtype=np.float32) * np.float32(np.sqrt(2.0 / (512 * 49)))
+    if adversarial:
+        w1 *= np.repeat(down, 49)[None, :]      # NCHW flatten: column c*49 + p
+    sd["classifier.0.weight"] = w1
+    sd["classifier.0.bias"] = (g.standard_normal(4096) * (0.5 if adversarial else 0.05)).astype(np.float32)
+    sd["classifier.3.weight"] = g.standard_normal((4096, 4096), dtype=np.float32) * np.float32(np.sqrt(2.0 / 4096))
+    sd["classifier.3.bias"] = (g.standard_normal(4096) * (0.5 if adversarial else 0.05)).astype(np.float32)
+    return sd
+
+
 def resnet50_state_dict(seed=7, adversarial=False):
     """fp32 numpy state dict with torchvision resnet50 key names (fc omitted:
     the reference computes fc but never reads it).
