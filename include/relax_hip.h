@@ -166,6 +166,22 @@ int relax_gather_patches(relax_handle* h, const uint8_t* image, int64_t item_str
 int relax_merge_fragments(relax_handle* h, const uint8_t* a, const uint8_t* b, uint8_t* out, int64_t n_bytes,
                           relax_stream stream);
 
+/* map_attention_to_original (src/demo_visual.py:12-25): per-patch values painted back onto the frames they were cut from,
+ * scaled to levels and blended with a colour table.
+ *   frames       : uint8 [H,W,3] BGR per frame; frame t at frames + t*frame_stride (bytes)
+ *   positions    : int32 [T,196,2], counts int32 [T]: relax_fragment_pairs' format (patch units, slot order).  Slot k < counts[t]
+ *                  paints the patch at positions[t,k] with patch_values[t,k]; a later slot on the same patch wins; out-of-range
+ *                  positions paint nothing (relax_gather_patches gives them a zero tile); every other pixel is 0.
+ *   patch_values : fp32 [T,196]
+ *   lut_bgr      : uint8 [256,3] BGR colour table (cv2.applyColorMap's role)
+ *   out          : uint8 [T,H,W,3] contiguous
+ * level = trunc((double)v / (double)max * 255) with max over the whole frame, zeros included (numpy on the reference's float64
+ * array); max <= 0 (undefined in the reference) gives level 0 everywhere, as do negative and NaN values.
+ * out = (6 frame + 4 lut[level] + 5) / 10 per byte = cv2.addWeighted(frame, 0.6, heat, 0.4, 0) on uint8. */
+int relax_attention_overlay(relax_handle* h, const uint8_t* frames, int64_t frame_stride, int T, int H, int W,
+                            const int32_t* positions, const int32_t* counts, const float* patch_values,
+                            const uint8_t* lut_bgr, uint8_t* out, relax_stream stream);
+
 /* ---- optical flow --------------------------------------------------------------- */
 /* Replaces cv2.calcOpticalFlowFarneback(gray(orig), gray(next), None, 0.5, 3, 15, 3, 5, 1.2, 0) and flow_to_rgb
  * (src/main_fragment_layerstack.py:313-316, 162-175; src/main_residual_fragment.py:283-287).  Parameters are the
@@ -227,6 +243,14 @@ int relax_vgg16_features(relax_handle* h, const uint8_t* frags, int N, float* la
  * pooled: fp32 [N,3*dim] mean|max|std over tokens (main_fragment_pool.py:124-133) (may be NULL). */
 int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled,
                        relax_stream stream);
+/* relax_vit_features plus the attention of the LAST block's CLS query (src/extractor/visualise_vit.py:241-250
+ * get_last_selfattention, :123-127 Block.forward(return_attention=True), :353-369 visualize_attention):
+ *   cls_attention : fp32 [N,heads,197] = softmax(q_0 . k_j / 8) over all 197 keys, per (image, head) (may be NULL).
+ *                   Column 0 is the CLS key; the reference keeps columns 1..196 (attn[0, :, 0, 1:]).
+ * Tokens and pooled are the same bits as relax_vit_features gives.  With cls_attention alone the forward stops after the
+ * last block's qkv GEMM (the last block's attention core, proj, MLP and the final norm are skipped).  All three NULL: refused. */
+int relax_vit_features_ex(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled, float* cls_attention,
+                          relax_stream stream);
 
 /* ---- quality head at inference --------------------------------------------------- */
 /* Replaces imputer.transform + scaler.transform + Mlp.forward (src/demo_test.py:177-208, src/model_regression.py:37-58).

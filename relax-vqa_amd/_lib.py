@@ -31,6 +31,7 @@ PROTOTYPES = {
                                        c_vp, c_vp, c_vp, c_vp, c_vp]),
     "relax_gather_patches": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp]),
     "relax_merge_fragments": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int64, c_vp]),
+    "relax_attention_overlay": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "relax_optical_flow": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp]),
     "relax_flow_to_rgb": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp, c_vp]),
     "relax_resize_frames": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp]),
@@ -38,6 +39,7 @@ PROTOTYPES = {
     "relax_resnet50_clip_features": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_vp, c_vp, c_vp]),
     "relax_vgg16_features": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, C.POINTER(c_vp), c_vp]),
     "relax_vit_features": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
+    "relax_vit_features_ex": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp]),
     "relax_load_mlp_head": (C.c_int, [c_vp, C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
                                       c_vp, c_vp, c_vp, C.c_int]),
     "relax_mlp_head": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp]),

@@ -384,6 +384,9 @@ int launch_attention_x6(relax_handle* h, const float* qkv, float* out, void* out
 // attention on the fp16 planes the qkv GEMM wrote (attention_h2.hip): qkv_planes [Nimg*197][3*dim*4 B] of qkv * s_qkv -> out_planes [..][dim*4 B] of out * out_scale
 int launch_attention_h2(relax_handle* h, const void* qkv_planes, float s_qkv, void* out_planes, float out_scale, int Nimg, int heads, hipStream_t s);
 int launch_attention_h2_op(relax_handle* h, const float* qkv, float* out, int Nimg, int heads, hipStream_t s);   // fp32 in / out (relax_op_attention)
+// the last block's CLS attention row (vit_attention_map.hip): qkv as fp32 rows [Nimg*197][3*dim] or, with planes, fp16 planes of
+// qkv * s_qkv (csrc/h2.h) -> out fp32 [Nimg, heads, 197] = softmax(q_0 k^T / 8) per (image, head)
+int launch_vit_cls_attention(relax_handle* h, const void* qkv, bool planes, float s_qkv, float* out, int Nimg, int heads, hipStream_t s);
 int launch_bn_relu_maxpool(relax_handle* h, const float* x, const float* scale, const float* shift, float* y,
                            int Nimg, int H, int W, int C, hipStream_t s);
 int launch_bn_relu_maxpool_f32(relax_handle* h, const float* x, const float* scale, const float* shift, float* y, int Nimg, int H, int W, int C,

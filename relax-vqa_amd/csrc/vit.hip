@@ -304,7 +304,9 @@ int relax_load_vit(relax_handle* h, const float* const* tensors, const char* con
     return RELAX_OK;
 }
 
-int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled,
+}  // extern "C"
+
+static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled, float* cls_attention,
                        relax_stream stream) {
     if (!h) return RELAX_ERR_INVALID;
     RELAX_REQUIRE(h, h->vit.loaded, "relax_vit_features: call relax_load_vit first");
@@ -322,6 +324,10 @@ int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* toke
     float* QKV = Y + n * NTOK * dim;
     float* Hid = QKV + n * NTOK * dim * 3;
     const int rows = N * NTOK;
+    // cls_attention: block `last`'s CLS row, launched right after its qkv GEMM (before its attention core, so nothing later in the
+    // forward can overwrite the qkv buffer first).  Without tokens / pooled the forward stops there (get_last_selfattention).
+    const int last = v.depth - 1;
+    const bool attention_only = cls_attention && !tokens && !pooled;
 
     if (h->gemm.precision == 3 && dim % 256 == 0) {
         // f16x2: GEMM inputs travel as two fp16 planes of (value x a static power of two), written by the kernel that produces them;
@@ -347,13 +353,18 @@ int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* toke
         const int64_t at = (int64_t)rows * (dim / 4);
         hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, v.pos, Xx, dim / 4, at);
         RELAX_HIP_CHECK(h, hipGetLastError());
-        for (const VitBlockW& b : v.blocks) {
+        for (int i = 0; i < v.depth; ++i) {
+            const VitBlockW& b = v.blocks[i];
             RELAX_TRY(launch_layernorm_h2(h, Xx, b.ln1_g, b.ln1_b, Ys, b.s_ln1, rows, dim, kLnEps, s));
             if (h->gemm.att_h2) {   // q, k, v leave the GEMM as fp16 planes (the same 4 bytes per value) and attention reads them as they are
                 RELAX_TRY(gemm(Ys, b.qkv, nullptr, nullptr, QKVx, b.s_qkv, rows, 0));
+                if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, true, b.s_qkv, cls_attention, N, v.heads, s));
+                if (attention_only && i == last) return RELAX_OK;
                 RELAX_TRY(launch_attention_h2(h, QKVx, b.s_qkv, Ys, b.s_att, N, v.heads, s));
             } else {
                 RELAX_TRY(gemm(Ys, b.qkv, nullptr, QKVx, nullptr, 0.f, rows, 0));
+                if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, false, 0.f, cls_attention, N, v.heads, s));
+                if (attention_only && i == last) return RELAX_OK;
                 RELAX_TRY(launch_attention_x6(h, QKVx, nullptr, Ys, N, v.heads, s, b.s_att));   // output straight into fp16 planes
             }
             RELAX_TRY(gemm(Ys, b.proj, Xx, Xx, nullptr, 0.f, rows, 0));                     // x += proj(attn)
@@ -388,9 +399,12 @@ int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* toke
         const int64_t at = (int64_t)rows * (dim / 4);
         hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, v.pos, Xx, dim / 4, at);
         RELAX_HIP_CHECK(h, hipGetLastError());
-        for (const VitBlockW& b : v.blocks) {
+        for (int i = 0; i < v.depth; ++i) {
+            const VitBlockW& b = v.blocks[i];
             RELAX_TRY(launch_layernorm_sp3(h, Xx, b.ln1_g, b.ln1_b, Ys, rows, dim, kLnEps, s));
             RELAX_TRY(launch_gemm_x6(h, Ys, b.qkv.w_sp3, b.qkv.b, nullptr, QKVx, nullptr, rows, 3 * dim, dim, 0, s));
+            if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, false, 0.f, cls_attention, N, v.heads, s));
+            if (attention_only && i == last) return RELAX_OK;
             RELAX_TRY(launch_attention_x6(h, QKVx, nullptr, Ys, N, v.heads, s));   // output straight into split planes
             RELAX_TRY(launch_gemm_x6(h, Ys, b.proj.w_sp3, b.proj.b, Xx, Xx, nullptr, rows, dim, dim, 0, s));      // x += proj(attn)
             RELAX_TRY(launch_layernorm_sp3(h, Xx, b.ln2_g, b.ln2_b, Ys, rows, dim, kLnEps, s));
@@ -414,9 +428,12 @@ int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* toke
     hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((atotal + 255) / 256)), dim3(256), 0, s, PE, v.cls, v.pos, X,
                        dim / 4, atotal);
     RELAX_HIP_CHECK(h, hipGetLastError());
-    for (const VitBlockW& b : v.blocks) {
+    for (int i = 0; i < v.depth; ++i) {
+        const VitBlockW& b = v.blocks[i];
         RELAX_TRY(launch_layernorm(h, X, b.ln1_g, b.ln1_b, Y, rows, dim, kLnEps, s));
         RELAX_TRY(launch_gemm(h, Y, b.qkv.w, b.qkv.b, nullptr, QKV, rows, 3 * dim, dim, 0, s));
+        if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKV, false, 0.f, cls_attention, N, v.heads, s));
+        if (attention_only && i == last) return RELAX_OK;
         RELAX_TRY(launch_attention(h, QKV, Y, N, v.heads, s));
         RELAX_TRY(launch_gemm(h, Y, b.proj.w, b.proj.b, X, X, rows, dim, dim, 0, s));       // x += proj(attn)
         RELAX_TRY(launch_layernorm(h, X, b.ln2_g, b.ln2_b, Y, rows, dim, kLnEps, s));
@@ -433,6 +450,19 @@ int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* toke
     return RELAX_OK;
 }
 
+extern "C" {
+
+int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled,
+                       relax_stream stream) {
+    return vit_forward(h, frags, N, tokens, pooled, nullptr, stream);
+}
+
+int relax_vit_features_ex(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled, float* cls_attention,
+                          relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, tokens || pooled || cls_attention, "relax_vit_features_ex: no output requested");
+    return vit_forward(h, frags, N, tokens, pooled, cls_attention, stream);
+}
 
 int relax_op_token_stats(relax_handle* h, const float* x, float* out, int Nimg, int tokens, int dim,
                          relax_stream stream) {

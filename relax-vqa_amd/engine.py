@@ -13,6 +13,9 @@ Array-in / array-out counterparts of the reference's path-based functions:
   resnet50_features   <- get_deep_feature('resnet50', .., 'layer_stack'|'pool') + process_video_feature
                          (src/main_fragment_layerstack.py:83-99,124-160)
   vit_features        <- get_deep_feature('vit', ..) + process_video_feature (src/main_fragment_pool.py:114-143)
+  vit_attention       <- get_last_selfattention + visualize_attention (src/extractor/visualise_vit.py:241-250,353-369)
+  attention_overlay   <- map_attention_to_original (src/demo_visual.py:12-25)
+  attention_overlays  <- the __main__ of src/demo_visual.py (:86-128) for a whole clip
   extract_clip        <- the per-video loop body of src/main_fragment_layerstack.py:293-344 plus the ViT
                          branch of src/demo_test.py:137-161 (config 3 of BASELINE.json)
 """
@@ -21,7 +24,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, colormap
 
 LAYER_STACK_DIM = 13120
 RN50_POOL_DIM = 2051
@@ -348,8 +351,10 @@ class RelaxEngine:
         self._check(rc, "relax_resnet50_clip_features")
         return ls, pl
 
-    def vit_features(self, frags, tokens=False, pooled=True):
-        """frags uint8 [N,224,224,3] BGR -> (tokens fp32 [N,196,dim] | None, pooled fp32 [N,3*dim] | None)"""
+    def vit_features(self, frags, tokens=False, pooled=True, attention=False):
+        """frags uint8 [N,224,224,3] BGR -> (tokens fp32 [N,196,dim] | None, pooled fp32 [N,3*dim] | None).
+        attention=True adds a third element: the last block's CLS attention to the 196 patches, fp32 [N,heads,196]
+        (src/extractor/visualise_vit.py:241-250,353-369: attn[:, :, 0, 1:]); tokens and pooled are unchanged by it."""
         if self.vit_dim is None:
             raise RuntimeError("load_vit first")
         frags = self._frags(frags)
@@ -357,9 +362,94 @@ class RelaxEngine:
         dev = self.device
         tk = torch.empty((N, 196, self.vit_dim), dtype=torch.float32, device=dev) if tokens else None
         pl = torch.empty((N, 3 * self.vit_dim), dtype=torch.float32, device=dev) if pooled else None
-        self._check(self.lib.relax_vit_features(self.h, _ptr(frags), N, _ptr(tk), _ptr(pl), _stream()),
-                    "relax_vit_features")
-        return tk, pl
+        if not attention:
+            self._check(self.lib.relax_vit_features(self.h, _ptr(frags), N, _ptr(tk), _ptr(pl), _stream()),
+                        "relax_vit_features")
+            return tk, pl
+        at = torch.empty((N, self.vit_dim // 64, 197), dtype=torch.float32, device=dev)
+        self._check(self.lib.relax_vit_features_ex(self.h, _ptr(frags), N, _ptr(tk), _ptr(pl), _ptr(at), _stream()),
+                    "relax_vit_features_ex")
+        return tk, pl, at[:, :, 1:]
+
+    def vit_attention(self, frags, with_cls=False):
+        """frags uint8 [N,224,224,3] BGR -> fp32 [N,heads,196]: get_last_selfattention's CLS row without the CLS column
+        (src/extractor/visualise_vit.py:241-250,353-369).  The forward stops after the last block's qkv GEMM.
+        with_cls=True returns the whole row [N,heads,197] (column 0 = the CLS key; each row sums to 1)."""
+        if self.vit_dim is None:
+            raise RuntimeError("load_vit first")
+        frags = self._frags(frags)
+        N = frags.shape[0]
+        at = torch.empty((N, self.vit_dim // 64, 197), dtype=torch.float32, device=self.device)
+        self._check(self.lib.relax_vit_features_ex(self.h, _ptr(frags), N, None, None, _ptr(at), _stream()),
+                    "relax_vit_features_ex")
+        return at if with_cls else at[:, :, 1:]
+
+    def attention_overlay(self, frames, positions, counts, patch_values, lut=None):
+        """map_attention_to_original (src/demo_visual.py:12-25) on the GPU.
+        frames uint8 [T,H,W,3] BGR (items may be strided, pixels packed); positions int32 [T,196,2] / counts int32 [T] as
+        fragment_pairs returns them; patch_values fp32 [T,196] in slot order; lut uint8 [256,3] BGR (None: colormap.jet_lut_bgr(),
+        see there for passing cv2's own table) -> uint8 [T,H,W,3] = 0.6 frame + 0.4 lut[level] (csrc/vit_attention_map.hip)."""
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        frames = frames.to(self.device, non_blocking=True)
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError(f"frames must be uint8 [T,H,W,3], got {frames.dtype} {tuple(frames.shape)}")
+        T, H, W, _ = frames.shape
+        if frames.stride()[1:] != (W * 3, 3, 1):
+            frames = frames.contiguous()
+        positions = torch.as_tensor(positions).to(self.device, torch.int32).contiguous()
+        counts = torch.as_tensor(counts).to(self.device, torch.int32).contiguous()
+        values = torch.as_tensor(patch_values).to(self.device, torch.float32).contiguous()
+        if tuple(positions.shape) != (T, TOP_N, 2) or tuple(counts.shape) != (T,) or tuple(values.shape) != (T, TOP_N):
+            raise ValueError(f"attention_overlay: positions [T,196,2], counts [T], patch_values [T,196] expected for T={T}, got "
+                             f"{tuple(positions.shape)}, {tuple(counts.shape)}, {tuple(values.shape)}")
+        if lut is None:
+            if getattr(self, "_jet_lut", None) is None:
+                self._jet_lut = torch.from_numpy(colormap.jet_lut_bgr()).to(self.device)
+            lut = self._jet_lut
+        else:
+            lut = torch.as_tensor(np.asarray(lut) if not torch.is_tensor(lut) else lut).to(self.device).contiguous()
+            if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+                raise ValueError(f"lut must be uint8 [256,3] BGR, got {lut.dtype} {tuple(lut.shape)}")
+        out = torch.empty((T, H, W, 3), dtype=torch.uint8, device=self.device)
+        stride = frames.stride(0) if T > 1 else H * W * 3
+        rc = self.lib.relax_attention_overlay(self.h, _ptr(frames), stride, T, H, W, _ptr(positions), _ptr(counts), _ptr(values),
+                                              _ptr(lut), _ptr(out), _stream())
+        self._check(rc, "relax_attention_overlay")
+        return out
+
+    OVERLAY_FRAGMENTS = ("residual_imp", "residual_of_imp", "ori_frag", "residual_merged_frag")
+
+    def attention_overlays(self, frames, fragment="ori_frag", flow_images=None, lut=None):
+        """The __main__ of src/demo_visual.py (:86-128) for a whole clip: frames uint8 [T,2,H,W,3] as fragment_pairs takes them;
+        fragment one of OVERLAY_FRAGMENTS:
+          residual_imp          the frame-difference fragment, frame-difference positions
+          ori_frag              the original fragment, frame-difference positions
+          residual_merged_frag  merge_fragments(difference fragment, flow fragment), frame-difference positions
+          residual_of_imp       the flow fragment, flow positions (flow_images, or Farneback on the GPU when None)
+        -> dict(overlay uint8 [T,H,W,3] over frames[:, 0], patch_means fp32 [T,196] (head mean, slot order),
+                attention fp32 [T,heads,196], positions, counts)."""
+        if fragment not in self.OVERLAY_FRAGMENTS:
+            raise ValueError(f"fragment must be one of {self.OVERLAY_FRAGMENTS}, got {fragment!r}")
+        frames = self._dev_u8(frames)
+        fr = self.fragment_pairs(frames)
+        positions, counts = fr["positions"], fr["counts"]
+        if fragment in ("residual_of_imp", "residual_merged_frag"):
+            if flow_images is None:
+                _, flow_images = self.optical_flow(frames)
+            fl = self.fragment_image(flow_images)
+        if fragment == "residual_imp":
+            image = fr["diff_frag"]
+        elif fragment == "ori_frag":
+            image = fr["ori_frag"]
+        elif fragment == "residual_merged_frag":
+            image = self.merge_fragments(fr["diff_frag"], fl["frag"])
+        else:
+            image, positions, counts = fl["frag"], fl["positions"], fl["counts"]
+        attention = self.vit_attention(image)
+        patch_means = attention.mean(dim=1)
+        overlay = self.attention_overlay(frames[:, 0], positions, counts, patch_means, lut=lut)
+        return dict(overlay=overlay, patch_means=patch_means, attention=attention, positions=positions, counts=counts)
 
     # ---- whole clip ---------------------------------------------------------------------------
     def extract_clip(self, frames, resnet=True, vit=True, flow_images=None, flow=False):
