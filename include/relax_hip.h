@@ -73,7 +73,10 @@ int relax_reserve(relax_handle* h, int max_images);
  * accumulation (al*bl, 2^-22 of the product, is added for K < 256 only); every scale comes from a bound, never from the data of a
  * batch - weights per output row, ViT activations one static power of two per tensor, ResNet-50 activations one per image from
  * Hoelder's inequality on the measured per-image maxima of the producer's inputs - so nothing can overflow and no row depends on its
- * batch (csrc/gemm_h2.hip, csrc/h2.h, tests/test_gpu_h2.py).  It covers the plain GEMMs with N % 256 == 0 (the whole ViT-B/16;
+ * batch (csrc/gemm_h2.hip, csrc/h2.h, tests/test_gpu_h2.py).  Accuracy: against fp64, each output's error measured against its sum of
+ * magnitudes is no larger than the exact-fp32 path's, within two bounds of the format (tests/fp32_grade.py): at short K it may
+ * exceed the chain's by 2^-23 / sqrt(K) (22-bit operands against one fp32 rounding per product), and a value below 2^-17 of its row's maximum keeps an absolute error of 2^-39 of that
+ * maximum instead of 22 bits of itself.  It covers the plain GEMMs with N % 256 == 0 (the whole ViT-B/16;
  * relax_op_gemm), the convolutions of ResNet-50's layer3 / layer4 (relax_op_conv2d_nhwc with Cin % 32 == 0, Cout % 256 == 0) and the
  * 3x3 convolutions of its layer1 / layer2 (K x K filters onto 64 / 128 channels, K >= 256: v_mfma_f32_32x32x16_f16 on the four-wave
  * tiles of csrc/gemm_x6.hip, the two small products in an accumulator of their own), its stem (csrc/conv1_x6.hip) and the ViT's attention (csrc/attention_h2.hip;

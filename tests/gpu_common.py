@@ -105,3 +105,34 @@ def run_ranks(make_cmd, cwd, env, timeout=600, attempts=2):
                       f"first attempt:\n{res.stderr[-1500:]}")
     res.first_attempt = first
     return res
+
+
+# ---- the exact-fp32 path beside a kernel under test, and which kernel ran ------------------------------------------------------
+def exact_fp32_gemm(eng, A, W, bias=None, residual=None, act=0):
+    """op_gemm on the exact-fp32 kernel, on the same inputs: K is padded with zero columns to the multiple of 32 that kernel takes
+    (0 x 0 added to an fp32 partial sum leaves it as it is, so the padded chain IS the chain of the unpadded problem)."""
+    pad = -A.shape[1] % 32
+    if pad:
+        A = torch.nn.functional.pad(A, (0, pad)).contiguous()
+        W = torch.nn.functional.pad(W, (0, pad)).contiguous()
+    prev = eng.precision()
+    eng.set_precision("fp32")
+    try:
+        return eng.op_gemm(A, W, bias, residual, act=act)
+    finally:
+        eng.set_precision(prev)
+
+
+# read kinds of relax_profile_read (csrc/api.hip): 0 the exact-fp32 / bf16x3 kernel, 3 bf16x6, 7 every f16x2 launch, 9 the plain f16x2 GEMMs
+ROUTE_KINDS = (0, 3, 7, 9)
+
+
+def launches(eng, fn):
+    """Runs fn() with the profiler on and returns (fn's result, {read kind: launches}): which contraction kernels actually ran."""
+    eng.profile_enable(True)
+    try:
+        out = fn()
+        counts = {k: eng.profile_read(k)[2] for k in ROUTE_KINDS}
+    finally:
+        eng.profile_enable(False)
+    return out, counts

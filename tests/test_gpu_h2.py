@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import fragment_ref, pooling_ref, vit_ref
-from tests.gpu_common import WEIGHT_SET_IDS, WEIGHT_SETS, assert_close, engine, golden_tag, synth, vit_weights
+from tests.gpu_common import WEIGHT_SET_IDS, WEIGHT_SETS, assert_close, engine, golden_tag, launches, synth, vit_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -168,7 +168,7 @@ CONVS = [  # Nimg, H, Cin, Cout, k, stride, pad
     (33, 9, 64, 256, 1, 1, 0), (50, 5, 64, 256, 3, 1, 1), (70, 4, 64, 256, 1, 1, 0),
     # the four-wave f16x2 form of gemm_x6.hip (64 / 128 output columns, K x K, K >= 256): the 3x3 convolutions of layer1 / layer2
     (2, 56, 64, 64, 3, 1, 1), (3, 28, 128, 128, 3, 1, 1), (2, 56, 128, 128, 3, 2, 1), (5, 9, 64, 64, 3, 1, 1), (2, 14, 32, 64, 3, 1, 1),
-    (37, 7, 64, 128, 3, 1, 1), (2, 12, 16, 64, 5, 2, 2),
+    (37, 7, 64, 128, 3, 1, 1), (2, 12, 16, 64, 4, 2, 1),
 ]
 
 
@@ -187,7 +187,8 @@ def test_conv2d_nhwc_under_f16x2(Nimg, H, Cin, Cout, k, stride, pad):
     eng.set_precision("fp32")
     e32 = (eng.op_conv2d_nhwc(x_nhwc, wp, b.cuda(), None, Cout, k, k, stride, pad, act=1).permute(0, 3, 1, 2).cpu().double() - ref).abs()
     eng.set_precision("f16x2")
-    got = eng.op_conv2d_nhwc(x_nhwc, wp, b.cuda(), None, Cout, k, k, stride, pad, act=1).permute(0, 3, 1, 2)
+    got, n_launch = launches(eng, lambda: eng.op_conv2d_nhwc(x_nhwc, wp, b.cuda(), None, Cout, k, k, stride, pad, act=1).permute(0, 3, 1, 2))
+    assert n_launch[7] - n_launch[9] >= 1 and n_launch[3] == 0 and n_launch[0] == 0, f"not an f16x2 convolution: {n_launch}"
     assert torch.equal(got, eng.op_conv2d_nhwc(x_nhwc, wp, b.cuda(), None, Cout, k, k, stride, pad, act=1).permute(0, 3, 1, 2))
     e2 = (got.cpu().double() - ref).abs()
     per_img = ref.abs().mean(dim=(1, 2, 3)).clamp_min(1e-300)

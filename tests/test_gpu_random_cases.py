@@ -101,7 +101,8 @@ def test_flow_on_small_and_odd_frames(h, w, pairs, seed):
 import torch.nn.functional as F  # noqa: E402
 
 from relax_vqa_amd.engine import pack_conv_weight  # noqa: E402
-from tests.gpu_common import assert_close  # noqa: E402
+from tests import fp32_grade  # noqa: E402
+from tests.gpu_common import assert_close, exact_fp32_gemm  # noqa: E402
 
 
 def _randn(g, *shape, scale=1.0):
@@ -111,11 +112,12 @@ def _randn(g, *shape, scale=1.0):
 @settings(max_examples=60, **COMMON)
 @given(nimg=st.integers(1, 4), h=st.integers(3, 30), w=st.integers(3, 30), cin=st.sampled_from([32, 64, 96, 128, 256]),
        cout=st.sampled_from([64, 128, 192, 256, 512]), k=st.sampled_from([1, 3]), stride=st.sampled_from([1, 2]),
-       act=st.sampled_from([0, 1]), with_res=st.booleans(), precision=st.sampled_from(["bf16x6", "fp32"]), seed=st.integers(0, 2 ** 31 - 1))
+       act=st.sampled_from([0, 1]), with_res=st.booleans(), precision=st.sampled_from(["bf16x6", "fp32", "f16x2"]), seed=st.integers(0, 2 ** 31 - 1))
 def test_conv2d_on_random_geometries(nimg, h, w, cin, cout, k, stride, act, with_res, precision, seed):
     """Implicit-GEMM convolution on random image sizes (rows of a tile straddle images, every tap mask pattern at the borders,
     non-square maps, row counts far from a multiple of the tile), channel counts of every tile variant, stride 1 / 2, 1x1 and 3x3,
-    with and without residual: against an fp64 convolution."""
+    with and without residual: against an fp64 convolution.  Under bf16x6 and f16x2 (and its documented bf16x6 / fp32 fall-backs) also
+    the fp32-grade gate of tests/fp32_grade.py beside the exact-fp32 path, where that path takes the geometry."""
     pad = 1 if k == 3 else 0
     if precision == "fp32" and k == 3 and cin & (cin - 1):
         return      # the exact-fp32 kernel takes power-of-two channel counts for KHxKW > 1 (it says so: tests/test_gpu_errors_and_dist.py)
@@ -134,15 +136,25 @@ def test_conv2d_on_random_geometries(nimg, h, w, cin, cout, k, stride, act, with
     got = eng.op_conv2d_nhwc(x.permute(0, 2, 3, 1).contiguous().cuda(), torch.from_numpy(pack_conv_weight(wt.numpy())).cuda(), b.cuda(),
                              res.permute(0, 2, 3, 1).contiguous().cuda() if with_res else None, cout, k, k, stride, pad, act=act)
     assert_close(got.permute(0, 3, 1, 2), ref.float().numpy(), f"{precision} conv {nimg}x{h}x{w}x{cin}->{cout} k{k}s{stride} act{act} res{with_res}")
+    if precision != "fp32" and not (k == 3 and cin & (cin - 1)):
+        mag = F.conv2d(x.double().abs(), wt.double().abs(), b.double().abs(), stride=stride, padding=pad)
+        if with_res:
+            mag = mag + res.double().abs()
+        eng.set_precision("fp32")
+        got32 = eng.op_conv2d_nhwc(x.permute(0, 2, 3, 1).contiguous().cuda(), torch.from_numpy(pack_conv_weight(wt.numpy())).cuda(), b.cuda(),
+                                   res.permute(0, 2, 3, 1).contiguous().cuda() if with_res else None, cout, k, k, stride, pad, act=act)
+        fp32_grade.check(got.permute(0, 3, 1, 2).cpu().numpy(), got32.permute(0, 3, 1, 2).cpu().numpy(), ref.numpy(), mag.numpy(),
+                         slack=fp32_grade.SLACK + (fp32_grade.h2_slack(cin * k * k) if precision == "f16x2" else 0.0), what=f"{precision} conv {nimg}x{h}x{w}x{cin}->{cout} k{k}s{stride} act{act} res{with_res} (fp32-grade gate)")
 
 
 @settings(max_examples=60, **COMMON)
 @given(m=st.integers(1, 1500), n=st.sampled_from([64, 128, 192, 256, 320, 768]), k=st.sampled_from([16, 32, 48, 64, 160, 768, 1024]),
-       act=st.sampled_from([0, 1, 2]), with_bias=st.booleans(), with_res=st.booleans(), precision=st.sampled_from(["bf16x6", "fp32"]),
+       act=st.sampled_from([0, 1, 2]), with_bias=st.booleans(), with_res=st.booleans(), precision=st.sampled_from(["bf16x6", "fp32", "f16x2"]),
        seed=st.integers(0, 2 ** 31 - 1))
 def test_gemm_on_random_shapes(m, n, k, act, with_bias, with_res, precision, seed):
     """out = act(A W^T + bias + residual) on random row counts (partial tiles, fewer rows than a tile, tail split-K) and every
-    tile variant, against an fp64 product."""
+    tile variant, against an fp64 product; under bf16x6 and f16x2 (N % 256 != 0: its bf16x6 fall-back) also the fp32-grade gate of
+    tests/fp32_grade.py beside the exact-fp32 path."""
     if precision == "fp32" and k % 32:
         return
     g = np.random.default_rng(seed)
@@ -159,11 +171,16 @@ def test_gemm_on_random_shapes(m, n, k, act, with_bias, with_res, precision, see
     eng.set_precision(precision)
     got = eng.op_gemm(A.cuda(), W.cuda(), b.cuda() if with_bias else None, r.cuda() if with_res else None, act=act)
     assert_close(got, want, f"{precision} gemm {m}x{n}x{k} act{act} bias{with_bias} res{with_res}")
+    if precision != "fp32":
+        mag = fp32_grade.gemm_mag(A.numpy(), W.numpy(), b.numpy() if with_bias else None, r.numpy() if with_res else None)
+        got32 = exact_fp32_gemm(eng, A.cuda(), W.cuda(), b.cuda() if with_bias else None, r.cuda() if with_res else None, act)
+        fp32_grade.check(got.cpu().numpy(), got32.cpu().numpy(), [y, F.relu(y), F.gelu(y)][act].numpy(), mag,
+                         slack=fp32_grade.SLACK + (fp32_grade.h2_slack(k) if precision == "f16x2" else 0.0), what=f"{precision} gemm {m}x{n}x{k} act{act} bias{with_bias} res{with_res} (fp32-grade gate)")
 
 
 @settings(max_examples=30, **COMMON)
 @given(n_img=st.integers(1, 5), heads=st.sampled_from([1, 3, 6, 12]), scale=st.floats(0.05, 5.0), outlier=st.booleans(),
-       precision=st.sampled_from(["bf16x6", "fp32"]), seed=st.integers(0, 2 ** 31 - 1))
+       precision=st.sampled_from(["bf16x6", "fp32", "f16x2"]), seed=st.integers(0, 2 ** 31 - 1))
 def test_attention_on_random_inputs(n_img, heads, scale, outlier, precision, seed):
     """softmax(q k^T / 8) v for random image / head counts and logit magnitudes from near-uniform to near one-hot rows; with
     `outlier` one query and one key carry 6x larger entries (dominant logits of a few hundred: the max-subtraction path; much larger
@@ -180,6 +197,11 @@ def test_attention_on_random_inputs(n_img, heads, scale, outlier, precision, see
     eng.set_precision(precision)
     got = eng.op_attention(qkv.cuda(), n_img, heads)
     assert_close(got, ref.float().numpy(), f"{precision} attention n={n_img} heads={heads} scale={scale:.2f} outlier={outlier}")
+    if precision != "fp32":     # the fp32-grade gate, normalised by the max |v| of each (image, head), beside the exact-fp32 path
+        eng.set_precision("fp32")
+        got32 = eng.op_attention(qkv.cuda(), n_img, heads)
+        fp32_grade.check(got.cpu().numpy(), got32.cpu().numpy(), ref.numpy(), fp32_grade.attention_mag(t[2].abs().amax(dim=(2, 3)).numpy(), 197),
+                         max_abs=None, slack=fp32_grade.SLACK + (fp32_grade.h2_slack(64) if precision == "f16x2" else 0.0), what=f"{precision} attention n={n_img} heads={heads} scale={scale:.2f} outlier={outlier} (fp32-grade gate)")
 
 
 @settings(max_examples=40, **COMMON)

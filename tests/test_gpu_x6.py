@@ -6,7 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.gpu_common import assert_close, engine
+from tests.gpu_common import assert_close, engine, launches
 
 pytestmark = pytest.mark.gpu
 
@@ -276,6 +276,7 @@ def test_conv2d_nhwc_under_x6(Nimg, H, Cin, Cout, k, stride, pad):
 
 @pytest.mark.parametrize("Nimg,H,Cin,Cout,k,stride,pad", [(2, 28, 32, 64, 7, 2, 3),      # 49 taps: beyond the kernel's 32-tap mask
                                                           (2, 20, 8, 64, 3, 1, 1),       # Cin = 8: no 16-channel chunk
+                                                          (2, 12, 16, 64, 5, 2, 2),      # K = 400, packed to 416: neither split form
                                                           (2, 14, 64, 64, 1, 1, 0)])     # (control: this one IS a bf16x6 shape)
 def test_conv_geometries_outside_the_x6_kernel_fall_back_to_the_fp32_kernel(Nimg, H, Cin, Cout, k, stride, pad):
     """Round-2 advice: under the default arithmetic relax_op_conv2d_nhwc must keep accepting what the fp32 kernel accepted
@@ -285,9 +286,11 @@ def test_conv_geometries_outside_the_x6_kernel_fall_back_to_the_fp32_kernel(Nimg
     x = _rand(Nimg, Cin, H, H, seed=17)
     w = _rand(Cout, Cin, k, k, seed=18, scale=(Cin * k * k) ** -0.5)
     ref = F.conv2d(x.double(), w.double(), None, stride=stride, padding=pad).float().numpy()
-    got = eng.op_conv2d_nhwc(x.permute(0, 2, 3, 1).contiguous().cuda(), torch.from_numpy(pack_conv_weight(w.numpy())).cuda(), None, None,
-                             Cout, k, k, stride, pad, act=0).permute(0, 3, 1, 2)
+    got, n_launch = launches(eng, lambda: eng.op_conv2d_nhwc(x.permute(0, 2, 3, 1).contiguous().cuda(), torch.from_numpy(pack_conv_weight(w.numpy())).cuda(),
+                                                             None, None, Cout, k, k, stride, pad, act=0).permute(0, 3, 1, 2))
     assert_close(got, ref, f"conv {Cin}->{Cout} k{k} under the default precision")
+    want = {0: 0, 3: 1, 7: 0} if k == 1 else {0: 1, 3: 0, 7: 0}     # the control runs bf16x6, the others the exact-fp32 kernel
+    assert {kind: n_launch[kind] for kind in want} == want, n_launch
 
 
 def test_misaligned_operands_are_refused_not_faulted():
