@@ -310,6 +310,41 @@ int relax_copy_bytes(relax_handle* h, const void* src, void* dst, int64_t n_byte
 int relax_segment_mean(relax_handle* h, const float* src, int64_t src_stride, int ncols, int row0, const int32_t* seg_offsets,
                        int nseg, float* dst, int64_t dst_stride, int dst_col0, relax_stream stream);
 
+/* ---- PNG decode ------------------------------------------------------------------------------- */
+/* Per-image status words of relax_png_decode (0 = decoded). */
+#define RELAX_PNG_OK 0
+#define RELAX_PNG_BAD_ARGS 1             /* geometry refused, or a buffer range of the item out of bounds */
+#define RELAX_PNG_BAD_ZLIB_HEADER 2      /* CMF/FLG: not deflate, window > 32 KiB or check bits wrong */
+#define RELAX_PNG_PRESET_DICT 3          /* FDICT set: a preset dictionary is refused */
+#define RELAX_PNG_TRUNCATED 4            /* the stream ends before its last block or its Adler-32 */
+#define RELAX_PNG_BAD_BLOCK_TYPE 5       /* reserved block type 3 */
+#define RELAX_PNG_BAD_STORED_LEN 6       /* stored block: LEN != ~NLEN */
+#define RELAX_PNG_BAD_CODE_LENGTHS 7     /* over-subscribed or incomplete code, bad repeat, too many lengths, no end-of-block */
+#define RELAX_PNG_BAD_SYMBOL 8           /* a literal/length or distance code that the block's code does not define */
+#define RELAX_PNG_DIST_TOO_FAR 9         /* a distance reaching before the first byte */
+#define RELAX_PNG_OUTPUT_TOO_LONG 10     /* more than H * (1 + W*C) bytes */
+#define RELAX_PNG_OUTPUT_TOO_SHORT 11    /* fewer than H * (1 + W*C) bytes */
+#define RELAX_PNG_BAD_FILTER 12          /* a row filter byte above 4 */
+#define RELAX_PNG_BAD_ADLER 13           /* the Adler-32 of the inflated bytes differs from the stream's */
+
+/* The image data of N PNG files -> uint8 BGR, as cv2.imread (src/main_fragment_layerstack.py:295-296) returns it: RGB
+ * swapped, alpha dropped, gray replicated.  The caller parses the container (signature, IHDR, chunk CRCs) and concatenates
+ * each file's IDAT payloads into one zlib stream; only 8-bit, non-interlaced gray (C = 1), RGB (3) and RGBA (4) images with
+ * W*C <= 16384 come here, every other file is decoded on the host.
+ *   src     DEVICE bytes [src_bytes]: the zlib streams
+ *   items   DEVICE int64 [N][8]: src offset, src length, raw offset, out offset, H, W, C, 0
+ *   out     DEVICE uint8 [out_bytes]: image n is written as [H][W][3] at out + out offset (n * item_stride for a batch tensor;
+ *           any slot of a clip tensor [T,2,H,W,3])
+ *   raw     DEVICE uint8 [raw_bytes]: scratch, H * (1 + W*C) bytes per image at its raw offset (the inflated rows)
+ *   status  DEVICE int32 [N]: RELAX_PNG_* per image
+ * One 64-lane workgroup per image, on `stream`.  Every read of image n stays inside its stream and every write inside its raw
+ * range and its output slot (ranges outside the buffers give RELAX_PNG_BAD_ARGS); a corrupt stream stops only its own image.
+ * No handle and no library state: the caller owns all memory, so loader threads may call this at the same time, each with its
+ * own scratch and its own stream (the Python layer keeps one decoder, stream and scratch per thread).  Returns
+ * RELAX_ERR_INVALID for bad arguments, RELAX_ERR_HIP if the launch fails; the per-image outcome is in `status`. */
+int relax_png_decode(const uint8_t* src, int64_t src_bytes, const int64_t* items, int N, uint8_t* out, int64_t out_bytes,
+                     uint8_t* raw, int64_t raw_bytes, int32_t* status, relax_stream stream);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* While enabled, every launch of the contraction kernel (GEMM / implicit-GEMM conv) and of the patch-score
  * kernel is bracketed by HIP events on the caller's stream.  relax_profile_read synchronises those events and

@@ -78,6 +78,18 @@ class RelaxEngine:
         if rc != 0:
             raise RuntimeError(f"{what} failed ({rc}): {self.lib.relax_last_error(self.h).decode()}")
 
+    # ---- frame decode ---------------------------------------------------------------------------
+    def decode_png(self, sources, out=None, statuses=None, stats=None):
+        """PNG files (paths or bytes) -> uint8 BGR [N,H,W,3] on this engine's device, as sampling.read_frame_bgr /
+        cv2.imread (src/main_fragment_layerstack.py:295-296) give them, decoded by relax_png_decode (one workgroup per
+        image); a list of [H,W,3] tensors if the sizes differ.  out: a uint8 [N,H,W,3] view to fill (strided slots allowed,
+        e.g. clip.view(-1,H,W,3) of a [T,2,H,W,3] clip).  statuses / stats: see pngdecode.PngDecoder.decode.  The decode runs
+        on this thread's own stream (pngdecode.decoder_for) and has finished when this returns; the result is recorded on
+        the current stream.  16-bit, palette, gray + alpha and interlaced files are decoded on the host (counted in
+        stats['fallback'])."""
+        from . import pngdecode
+        return pngdecode.decoder_for(self.device).decode(sources, out=out, statuses=statuses, stats=stats)
+
     # ---- weights ------------------------------------------------------------------------------
     def _marshal_state_dict(self, sd):
         names, arrays = [], []

@@ -78,6 +78,58 @@ def load_clip_from_frames(sampled_frame_path, video_name, alloc=None):
     return out
 
 
+class GpuFrameLoader:
+    """load_clip_from_frames on the GPU: clip i -> the uint8 BGR device tensor [T,2,H,W,3] that
+    load_clip_from_frames(sampled_frame_path, names[i]) returns on the host, byte for byte (same pairing, same errors).  The
+    files are read and their containers parsed on the calling thread; the image data is decoded by relax_png_decode on that
+    thread's own stream (pngdecode.decoder_for), so loader threads decode at the same time.  Pass it as the `clips` of
+    dataset.extract_dataset_clips, which uses device tensors as they are.  The clip is complete when __call__ returns and is
+    recorded on `consumer_stream` (default: the current stream of `device` when the loader is made - the stream the dataset
+    pass computes on).  A file the decoder refuses raises (in a dataset pass: that clip's NaN row and error entry).
+    fallbacks: how many files so far were decoded on the host (16-bit, palette, gray + alpha, interlaced)."""
+
+    def __init__(self, sampled_frame_path, names, device=None, consumer_stream=None):
+        import torch
+        self.path = sampled_frame_path
+        self.names = list(names)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.consumer = consumer_stream if consumer_stream is not None else torch.cuda.current_stream(self.device)
+        self.fallbacks = 0
+        self._lock = threading.Lock()
+
+    def __len__(self):
+        return len(self.names)
+
+    def __call__(self, i):
+        import torch
+
+        from . import png, pngdecode
+        name = self.names[i]
+        pairs = frame_pair_paths(self.path, name)
+        if not pairs:
+            raise FileNotFoundError(f"no `{name}_<n>.png` / `{name}_<n>_next.png` pair under {self.path}")
+        parsed = []
+        for pa, pb in pairs:
+            for path in (pa, pb):
+                src, data = png.read_source(path)
+                parsed.append((src, png.parse(data, src)))
+        shape = parsed[0][1].shape
+        for t, (pa, pb) in enumerate(pairs):
+            for j in (0, 1):
+                s = parsed[2 * t + j][1].shape
+                if s != shape:
+                    raise ValueError(f"{pa} / {pb}: frame sizes differ inside one video ({s} vs {shape})")
+        dec = pngdecode.decoder_for(self.device)
+        with torch.cuda.stream(dec.stream):
+            clip = torch.empty((len(pairs), 2) + shape, dtype=torch.uint8, device=self.device)
+        stats = {}
+        dec.decode(None, out=clip.view((-1,) + shape), parsed=parsed, stats=stats)
+        clip.record_stream(self.consumer)
+        with self._lock:
+            self.fallbacks += stats.get("fallback", 0)
+        return clip
+
+
 def feature_file_name(video_index, network_name, resolution=None):
     """video_index is 0-based like the reference's loop variable i."""
     name = f"{network_name}_feature_map_original" + (f"_{resolution}" if resolution else "")
