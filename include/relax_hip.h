@@ -266,6 +266,73 @@ int relax_load_mlp_head(relax_handle* h, const float* const* tensors, const char
 /* features: device fp32 [n, input_features] (the all-gathered per-clip vectors) -> scores: device fp32 [n]. */
 int relax_mlp_head(relax_handle* h, const float* features, int n, float* scores, relax_stream stream);
 
+/* ---- quality head, training ----------------------------------------------------------- */
+/* Replaces preprocess_data's fit (src/model_regression.py:122-135): NaN and +-inf of x (device fp32 [n,F]) count as 0;
+ * imputer_statistics = column means (SimpleImputer.statistics_), scaler_scale = 1 / (max - min) (1 where the range is below
+ * 10 eps(float64), sklearn's _handle_zeros_in_scale), scaler_min = -data_min * scale (MinMaxScaler.scale_ / .min_): DEVICE
+ * float64 [F] each, the vectors relax_load_mlp_head takes from the host.  data_min / data_max: DEVICE float64 [F], may be NULL.
+ * One pass over the matrix.  Enqueued on `stream`. */
+int relax_head_fit_scaler(relax_handle* h, const float* x, int n, int F, double* imputer_statistics, double* scaler_scale,
+                          double* scaler_min, double* data_min, double* data_max, relax_stream stream);
+/* Replaces X[isnan] = 0; X[isinf] = 0; scaler.transform(X); torch.FloatTensor(X) (model_regression.py:123-130, :392):
+ * x device fp32 [n,F] -> xp device fp32 [n, Fpad], Fpad = F rounded up to a multiple of 32, padding columns zero.
+ * (The reference scores with NaN -> column mean, demo_test.py:177-181, but trains on NaN -> 0: relax_mlp_head keeps the former.) */
+int relax_head_train_transform(relax_handle* h, const float* x, int n, int F, const double* scaler_scale, const double* scaler_min,
+                               float* xp, relax_stream stream);
+/* Allocates the training state of an Mlp(input_features, hidden_features) (model_regression.py:37-58; hidden_features a multiple of
+ * 128): three parameter sets with their BatchNorm buffers - 0 the live model with its SGD momentum buffers, 1 the SWA average
+ * (AveragedModel, :388), 2 a snapshot (copy.deepcopy(model), :445) - all zero until relax_head_train_import, and the workspace
+ * of batches of up to max_batch rows (2..1024).  Waits for the device. */
+int relax_head_train_init(relax_handle* h, int input_features, int hidden_features, int max_batch);
+/* Loads a state dict (the keys relax_load_mlp_head takes; HOST pointers) into a set: the initial model, or the checkpoint
+ * fine_tune.py:130-136 starts from.  Into set 0 it also zeroes the momentum buffers (a new optimizer).  Waits for the device. */
+int relax_head_train_import(relax_handle* h, int set, const float* const* tensors, const char* const* names, const int64_t* numels, int n,
+                            int64_t num_batches_tracked, int64_t n_averaged);
+/* Floats of a set as relax_head_train_export writes them (-1 without a state). */
+int64_t relax_head_train_export_numel(relax_handle* h);
+/* model.state_dict() (or, with momentum != 0, the momentum_buffer of each parameter; set 0 only): HOST fp32, in the order
+ * fc1.weight [H1,F], fc1.bias, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, fc2.weight [H2,H1], fc2.bias,
+ * fc3.weight [1,H2], fc3.bias; counters[2] = bn1.num_batches_tracked, n_averaged.  Waits for `stream`. */
+int relax_head_train_export(relax_handle* h, int set, int momentum, float* out, int64_t* counters, relax_stream stream);
+/* dst_set <- src_set, parameters, buffers and counters (copy.deepcopy(model); AveragedModel(model) at its creation). */
+int relax_head_train_copy(relax_handle* h, int dst_set, int src_set, relax_stream stream);
+/* MAEAndRankLoss.forward (model_regression.py:69-89, use_margin off) and its gradient: pred / target device fp32 [B];
+ * loss device fp32 [1]; grad device fp32 [B] (may be NULL).  One B x B kernel. */
+int relax_head_criterion(relax_handle* h, const float* pred, const float* target, int B, float l1_w, float rank_w, float* loss,
+                         float* grad, relax_stream stream);
+/* One iteration of train_one_epoch (model_regression.py:296-304) on the live set: zero_grad, forward in train mode, criterion,
+ * backward, optim.SGD(momentum, weight_decay).step().  xp: device [n, Fpad] from relax_head_train_transform; target: device
+ * fp32 [n]; index: device int32 [B], the batch's rows; 2 <= B <= max_batch.  Dropout masks come from a counter-based generator
+ * keyed by (seed, step, layer, element) - not torch's stream; mask1 [B,H1] / mask2 [B,H2] (device uint8, may be NULL) receive
+ * the masks used.  The batch loss is added into a device accumulator (relax_head_train_loss_read).  Enqueued on `stream`;
+ * never waits for the device (relax_head_train_init sizes the contraction's split-K workspace).  fc1 / fc2 run on the exact-fp32
+ * contraction whatever "gemm_precision" is set.  `index` is not validated: a row outside [0, n) is clamped into the matrix. */
+int relax_head_train_step(relax_handle* h, const float* xp, const float* target, int n, const int32_t* index, int B, float lr,
+                          float momentum, float weight_decay, float l1_w, float rank_w, float drop_rate, uint64_t seed, uint64_t step,
+                          uint8_t* mask1, uint8_t* mask2, relax_stream stream);
+/* One iteration of evaluate (model_regression.py:308-322): eval-mode forward of a set over the rows `index`, predictions to
+ * pred (device fp32 [B]); with target != NULL the batch's criterion goes into the evaluation accumulator.  1 <= B <= max_batch. */
+int relax_head_train_eval(relax_handle* h, int set, const float* xp, const float* target, int n, const int32_t* index, int B, float l1_w,
+                          float rank_w, float* pred, relax_stream stream);
+/* torch.optim.swa_utils.update_bn (model_regression.py:459), one batch per call: with reset != 0 first running_mean = 0,
+ * running_var = 1, num_batches_tracked = 0; then (B > 0) a train-mode forward through bn1 whose momentum is
+ * 1 / num_batches_tracked.  B = 0 only resets. */
+int relax_head_train_bn_pass(relax_handle* h, int set, int reset, const float* xp, int n, const int32_t* index, int B, relax_stream stream);
+/* swa_model.update_parameters(model) (model_regression.py:410): set 1 <- running average of set 0's parameters (buffers are
+ * not averaged: AveragedModel's use_buffers=False), n_averaged += 1.  One launch over all parameters. */
+int relax_head_train_swa_update(relax_handle* h, relax_stream stream);
+/* The loss accumulators (which: 0 training steps, 1 evaluation): out[3] HOST = sum of batch losses, sum of batch loss x batch
+ * rows (the loss.item() * inputs.size(0) of :304 / :320), batches; reset != 0 zeroes them.  Waits for `stream`: the one read of
+ * an epoch. */
+int relax_head_train_loss_read(relax_handle* h, int which, int reset, double* out, relax_stream stream);
+/* out[2] HOST = sum |fc1.weight[:, F:Fpad]|, sum |its momentum buffer[:, F:Fpad]| of the live set: the zero padding of K, which a step
+ * must leave exactly zero.  Waits for `stream`. */
+int relax_head_train_pad_abs_sum(relax_handle* h, double* out, relax_stream stream);
+/* The last stage of a step alone, on the batch and dz1 the last relax_head_train_step left (a measurement, tools/head_train_bench.py):
+ * fused != 0 the step's own kernel (dW1 = dz1^T X_b with the SGD update in its epilogue); fused == 0 the same tiles writing dW1 to
+ * memory, then a separate update pass.  Both change fc1.weight and its momentum. */
+int relax_head_train_dw1(relax_handle* h, int fused, int B, float lr, float momentum, float weight_decay, relax_stream stream);
+
 /* ---- operator level (what the backbones are built from; parity-tested one by one) ------------ */
 /* out[M,N] = act(A[M,K] * W[N,K]^T + bias[N] + residual[M,N]);  act: 0 none, 1 relu, 2 gelu(erf).
  * fp32 in, fp32 MFMA accumulate.  K % 32 == 0 (bf16x6: K % 16 == 0), N % 64 == 0.  bias/residual may be NULL; every pointer

@@ -43,6 +43,23 @@ PROTOTYPES = {
     "relax_load_mlp_head": (C.c_int, [c_vp, C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
                                       c_vp, c_vp, c_vp, C.c_int]),
     "relax_mlp_head": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp]),
+    "relax_head_fit_scaler": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "relax_head_train_transform": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "relax_head_train_init": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_int]),
+    "relax_head_train_import": (C.c_int, [c_vp, C.c_int, C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
+                                          C.c_int64, C.c_int64]),
+    "relax_head_train_export_numel": (C.c_int64, [c_vp]),
+    "relax_head_train_export": (C.c_int, [c_vp, C.c_int, C.c_int, c_vp, c_vp, c_vp]),
+    "relax_head_train_copy": (C.c_int, [c_vp, C.c_int, C.c_int, c_vp]),
+    "relax_head_criterion": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.c_float, C.c_float, c_vp, c_vp, c_vp]),
+    "relax_head_train_step": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_vp, C.c_int] + [C.c_float] * 6 + [C.c_uint64, C.c_uint64,
+                                        c_vp, c_vp, c_vp]),
+    "relax_head_train_eval": (C.c_int, [c_vp, C.c_int, c_vp, c_vp, C.c_int, c_vp, C.c_int, C.c_float, C.c_float, c_vp, c_vp]),
+    "relax_head_train_bn_pass": (C.c_int, [c_vp, C.c_int, C.c_int, c_vp, C.c_int, c_vp, C.c_int, c_vp]),
+    "relax_head_train_swa_update": (C.c_int, [c_vp, c_vp]),
+    "relax_head_train_loss_read": (C.c_int, [c_vp, C.c_int, C.c_int, c_vp, c_vp]),
+    "relax_head_train_pad_abs_sum": (C.c_int, [c_vp, c_vp, c_vp]),
+    "relax_head_train_dw1": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, c_vp]),
     "relax_op_gemm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_op_conv2d_nhwc": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp] + [C.c_int] * 10 + [c_vp]),
     "relax_op_layernorm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_float, c_vp]),

@@ -52,4 +52,27 @@ __device__ inline float gelu_erf(float v) {
     return v * (z >= 0.f ? 1.0f - h : h);
 }
 
+// Phi(v), the factor gelu_erf multiplies v with (the same operations), for the backward pass of the head's training step:
+// GELU'(v) = Phi(v) + v * exp(-v^2 / 2) / sqrt(2 pi)
+__device__ inline float gelu_erf_cdf(float v) {
+    const float z = v * 0.70710678118654752440f;
+    const float t = fminf(fabsf(z), 5.0f);
+    float q = -5.936020443186862e-06f;
+    q = fmaf(q, t, 9.409502672497183e-05f);
+    q = fmaf(q, t, -0.0005975606618449092f);
+    q = fmaf(q, t, 0.0017074682982638478f);
+    q = fmaf(q, t, 0.0006545027135871351f);
+    q = fmaf(q, t, -0.028285665437579155f);
+    q = fmaf(q, t, 0.14854633808135986f);
+    q = fmaf(q, t, 0.9183921813964844f);
+    q = fmaf(q, t, 1.6279112100601196f);
+    const float h = 0.5f * __builtin_amdgcn_exp2f(-(t * q));
+    return z >= 0.f ? 1.0f - h : h;
+}
+
+__device__ inline float gelu_erf_grad(float v) {
+    // exp(-v^2 / 2) as exp2(-v^2 * log2(e) / 2); below 2^-126 for |v| > 13.2, where it flushes to 0 as the true value does in fp32
+    return gelu_erf_cdf(v) + v * 0.3989422804014327f * __builtin_amdgcn_exp2f(-0.72134752044448170368f * v * v);
+}
+
 }  // namespace relax

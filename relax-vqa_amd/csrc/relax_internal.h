@@ -228,6 +228,27 @@ struct HeadW {
     std::vector<void*> allocs;
 };
 
+// ---- quality head, training state (head_train.hip) -----------------------------------------------------------
+// One parameter set is ONE device block of floats: the parameters first (what SGD and the SWA average touch), then the BatchNorm
+// buffers:  W1 [H1][Fpad] | b1 | gamma | beta | W2 [H2][H1] | b2 | w3 [H2] | b3 | running_mean [H1] | running_var [H1]
+// and two int64 counters (num_batches_tracked, n_averaged).  Sets: 0 live (with one momentum block), 1 SWA average, 2 snapshot.
+struct HeadTrain {
+    static constexpr int kSets = 3;
+    static constexpr int kMaxBatch = 1024;
+    bool ready = false;
+    int F = 0, Fpad = 0, H1 = 0, H2 = 0, max_batch = 0;
+    size_t n_params = 0, n_all = 0;   // floats of the parameter part / of the whole set
+    float* set[kSets] = {};
+    float* mom = nullptr;             // SGD momentum buffers, parameter part's layout
+    int64_t* counters = nullptr;      // [kSets][2]
+    double* loss = nullptr;           // [2][3]: train / eval: sum of batch losses, sum of batch loss * batch size, batches
+    float* act = nullptr;             // activations of one batch (head_train.hip lays them out)
+    float* xb = nullptr;              // the gathered batch rows [max_batch][Fpad]
+    float* grad_w1 = nullptr;         // dW1 of the UNFUSED form (relax_head_train_dw1 with fused = 0, a measurement): allocated on its first use
+    DevBuf scaler_ws;                 // partial column sums / minima / maxima of the scaler fit
+    std::vector<void*> allocs;
+};
+
 // ---- resize coefficient tables (Pillow-exact), cached per (input size, filter) ------------------------------
 struct ResizeTable {
     int in_size = 0, filt = 0, ksize = 0;
@@ -314,6 +335,7 @@ struct relax_handle {
     relax::DevBuf flow_ws;      // optical-flow pyramid workspace
     relax::DevBuf head_ws;      // scaled features + hidden activations of the quality head
     relax::HeadW head;
+    relax::HeadTrain head_train;
     std::vector<relax::ResizeTable> resize_tables;
     relax::ResNet50W rn;
     relax::VitW vit;
@@ -408,6 +430,7 @@ void free_resnet(relax_handle* h);
 void free_vit(relax_handle* h);
 void free_resize(relax_handle* h);
 void free_head(relax_handle* h);
+void free_head_train(relax_handle* h);
 void free_vgg(relax_handle* h);
 size_t vgg_arena_bytes(int n_images);
 size_t resnet_arena_bytes(int n_images);

@@ -146,6 +146,49 @@ class RelaxEngine:
         self._check(self.lib.relax_mlp_head(self.h, _ptr(features), features.shape[0], _ptr(out), _stream()), "relax_mlp_head")
         return out
 
+    # ---- training the quality head (head_train.py, csrc/head_train.hip) -------------------------------------------
+    def fit_scaler(self, features, want_range=False):
+        """preprocess_data's fit (src/model_regression.py:122-135) on a device fp32 [n, F] matrix, NaN / +-inf counted as 0:
+        {'imputer_statistics', 'scale', 'min'} as host float64 [F] - what load_mlp_head takes (+ 'data_min' / 'data_max')."""
+        features = features.to(self.device, torch.float32).contiguous()
+        n, F = features.shape
+        out = torch.empty((5, F), dtype=torch.float64, device=self.device)
+        rc = self.lib.relax_head_fit_scaler(self.h, _ptr(features), n, F, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                            _ptr(out[3]) if want_range else None, _ptr(out[4]) if want_range else None, _stream())
+        self._check(rc, "relax_head_fit_scaler")
+        host = out.cpu().numpy()
+        res = {"imputer_statistics": host[0].copy(), "scale": host[1].copy(), "min": host[2].copy()}
+        if want_range:
+            res.update(data_min=host[3].copy(), data_max=host[4].copy())
+        return res
+
+    def head_train_transform(self, features, scale, min_):
+        """The training transform: NaN / +-inf -> 0, x * scale + min_ in float64, to fp32 [n, Fpad] (columns padded to a
+        multiple of 32 with zeros) - the matrix the training steps read."""
+        features = features.to(self.device, torch.float32).contiguous()
+        n, F = features.shape
+        sc = torch.as_tensor(np.ascontiguousarray(scale, dtype=np.float64)).to(self.device)
+        mn = torch.as_tensor(np.ascontiguousarray(min_, dtype=np.float64)).to(self.device)
+        xp = torch.empty((n, (F + 31) // 32 * 32), dtype=torch.float32, device=self.device)
+        rc = self.lib.relax_head_train_transform(self.h, _ptr(features), n, F, _ptr(sc), _ptr(mn), _ptr(xp), _stream())
+        self._check(rc, "relax_head_train_transform")
+        return xp
+
+    def fit_head(self, features, mos, config=None):
+        """Trains the quality head as the reference's train_and_evaluate does; see head_train.fit_head."""
+        from . import head_train
+        return head_train.fit_head(self, features, mos, config)
+
+    def fine_tune_head(self, state_dict, features, mos, config=None):
+        """Fine-tunes a trained head as the reference's fine_tune_model does; see head_train.fine_tune_head."""
+        from . import head_train
+        return head_train.fine_tune_head(self, state_dict, features, mos, config)
+
+    def load_fitted_head(self, result):
+        """load_mlp_head on what fit_head / fine_tune_head returned."""
+        state_dict, scaler = result[0], result[1]
+        self.load_mlp_head(state_dict, scaler["scale"], scaler["min"], scaler["imputer_statistics"])
+
     PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16x6": 2, "f16x2": 3}
 
     def set_precision(self, mode):
