@@ -2,6 +2,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 namespace relax {
@@ -176,6 +177,128 @@ void vgg16_fc1_to_nhwc(const float* w, int rows, int C, int HW, float* out) {
     }
 }
 
+// ---- ResNet-50 schedule ------------------------------------------------------------------------------------------------------------------
+const RnBlockGeom* rn_geometry() {
+    struct Table { RnBlockGeom g[kRnBlocks]; };
+    static const Table t = [] {
+        Table r{};
+        const int stage_blocks[4] = {3, 4, 6, 3}, stage_width[4] = {64, 128, 256, 512};
+        const int stage_taps[4] = {3, 4, 4, 3};  // layer3 blocks 4, 5 are not tapped
+        int cin = 64, tap = 1, b = 0;            // (tap 0 is the stem's raw conv1 output)
+        for (int st = 0; st < 4; ++st)
+            for (int i = 0; i < stage_blocks[st]; ++i, ++b) {
+                const int w = stage_width[st];
+                r.g[b] = {b, st + 1, i, cin, w, w * 4, (i == 0 && st > 0) ? 2 : 1, i == 0, i < stage_taps[st] ? tap++ : -1};
+                cin = w * 4;
+            }
+        return r;
+    }();
+    return t.g;
+}
+
+bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* plan, std::string& err) {
+    const RnBlockGeom* g = rn_geometry();
+    RnPlan p{};
+    // f16x2 for layer3 / layer4 ("gemm_precision" 3 with "rn_h2"): per-image tables {maximum, scale, 1 / scale}, one slot per tensor
+    const bool use_h2 = o.precision == 3 && o.rn_h2;
+    // "rn_h2_early": the 3x3 convolutions of layer1 / layer2 on f16x2 as well (gemm_x6.hip, H2 form).  Their input (conv1's output)
+    // is written as fp16 planes with the image's Hoelder scale  l1max(conv1) max|block input| + max|bias|; the block input's maximum
+    // is measured by its producer: the max-pool (block maxima, reduced per image) or the previous block's conv3 epilogue.
+    bool use_early = use_h2 && o.rn_h2_early;
+    for (int b = 0; b < kRnFirstH2Block && use_early; ++b) use_early = rn_early_h2(g[b].width, g[b].width);
+    // "rn_fuse": layer1[0] back to back too, with the downsample convolution folded into its conv3 - the block input then travels as fp32 rows
+    // (4 B per value instead of 6: conv1 splits them in its K loop, the fused launch reads each pixel's row as conv3's second source)
+    const bool fuse0 = use_early && o.rn_fuse && o.fp32_rows && rn_can_b2b_x2(g[0]);
+    // layer2[0] (stride 2, 256 -> 512 downsample: too many channels for a second source in registers): the downsample convolution as a
+    // launch of its own (f16x2, on the compact fp16 planes of the input's stride-2 sample) whose fp32 output is the residual of the
+    // block's back-to-back launch (3x3 with the stride -> conv3) - instead of the 3x3 + the two-source bf16x6 conv3
+    auto down_launch = [&](const RnBlockGeom& k) {
+        return use_early && o.rn_fuse && o.rn_c1_h2 && o.fp32_rows && rn_can_down_launch(k) && rn_can_b2b(k) && rn_can_c1_h2(k);
+    };
+    int next_slot = 0;
+    p.conv1_h2 = use_h2 && o.rn_h2_early;
+    p.pool_f32 = fuse0;
+    p.s_stem = use_early ? next_slot++ : -1;
+    // A block output exists as split planes (next convolutions, next residual: hi + mid + lo is the fp32 value, exactly) and as
+    // fp32 only where something needs it, and only for the images that need it: the tap export, the spatial mean of the 7x7
+    // taps of the layer-stack images (49 rows per image do not divide into the 16- or 4-row groups of the mean fused into
+    // the epilogue), the last block's map of the pool images.
+    // The block outputs inside layer1 and layer2 (56x56x256 and 28x28x512: the widest tensors, their consumers HBM-bound) travel
+    // as plain fp32 instead, 4 bytes per value where the planes take 6: the next block's conv1 (64 / 128 output columns, one
+    // column tile, so every value is split exactly once, as the producer's epilogue would have) splits them inside its K loop
+    // and its conv3 adds them as an fp32 residual - the same values bit for bit.  A layer's last block writes planes: the next
+    // layer's first conv3 reads them as its second activation source.
+    int in_form = fuse0 ? kRnF32 : kRnSp3, in_sample = kRnNoSample, s_x = -1, s_xin = p.s_stem, s_dr = -1, H = 56;
+    for (int b = 0; b < kRnBlocks; ++b) {
+        const RnBlockGeom& k = g[b];
+        RnBlockPlan& q = p.blk[b];
+        const int Ho = H / k.stride, HWo = Ho * Ho;
+        const bool is_last = b + 1 == kRnBlocks, tapped = k.tap >= 0;
+        const bool pool_needs32 = is_last && rq.want_pool && !rn_pool_from_stack(rq);
+        q.want_mean = tapped && rq.n_ls > 0;
+        q.want_export = tapped && ((rq.taps >> k.tap) & 1u);
+        q.in_form = in_form; q.in_sample = in_sample;
+        q.s_in_max = s_xin; q.s_in = s_x; q.s_dr_in = s_dr;
+        q.s_c1 = q.s_t1 = q.s_t1m = q.s_t2 = q.s_out = q.s_dr_out = -1;
+        bool out_f32 = false;
+        if (use_h2 && !rn_early(k)) {
+            // Every tensor that feeds a convolution travels as two fp16 planes with one scale per image; the scale of a tensor is fixed
+            // BEFORE it is written, from Hoelder's bound on its producer (measured maxima of the producer's inputs, l1max / bmax of its
+            // weights).  fp32 copies as above; the residual of a block without a downsample branch is read from the block input's PLANES.
+            q.form = kRnFormH2;
+            q.s_t1 = next_slot++; q.s_t2 = next_slot++; q.s_out = next_slot++;
+            q.fuse_mean = q.want_mean && HWo % 4 == 0 && HWo % 16 != 0;   // 14x14 maps: 4-row groups (gemm_h3's fused mean)
+            q.no_split = tapped && HWo % 4 == 0 && HWo % 16 != 0;
+            q.out_form = is_last ? kRnNone : kRnH2;
+        } else {
+            const bool cur_f32 = in_form == kRnF32;
+            // "rn_fuse": conv2 and conv3 back to back in one launch - the 3x3's tile never leaves the CU; conv3 on f16x2 with one scale per pixel row
+            const bool fuse_x2 = b == 0 && fuse0;
+            const bool fuse_dr = b > 0 && cur_f32 && down_launch(k) && HWo >= 256 && in_sample == kRnSampleH2;
+            const bool fuse = fuse_x2 || fuse_dr || (use_early && o.rn_fuse && !k.has_down && rn_can_b2b(k) && cur_f32 && k.stride == 1 && H * H >= 256);
+            // a layer's last block in front of a downsample block: its output travelled as three bf16 planes (6 B per value: the next block's conv1 and
+            // the second source of its conv3 read planes).  Back to back it leaves as fp32 rows like the others (conv1 splits in its K loop) PLUS the
+            // planes of the stride-2 sample only - all the downsample branch reads -, compacted: 4 + 1.5 bytes per value instead of 6, and conv1 reads 4
+            // (fp16 planes with a per-image scale where the next block runs its downsample convolution as a launch of its own)
+            const bool next_down = !is_last && g[b + 1].has_down;
+            const bool next_dr = next_down && fuse && down_launch(g[b + 1]);
+            const bool compact = fuse && next_down && !next_dr && rn_early(g[b + 1]) && o.fp32_rows && k.cout <= 512 && Ho % 2 == 0 && g[b + 1].stride == 2;
+            out_f32 = o.fp32_rows && k.cout <= 512 && !is_last && (!next_down || compact || next_dr);
+            q.handover = use_h2 && b + 1 == kRnFirstH2Block;
+            q.pre_handover = use_h2 && b + 2 == kRnFirstH2Block;
+            q.form = fuse_x2 ? kRnFormB2BX2 : fuse_dr ? kRnFormB2BDown : fuse ? kRnFormB2B : use_early ? kRnFormEarly : kRnFormX6;
+            if ((q.handover || next_dr) && fuse) q.s_t1m = next_slot++;
+            if (q.handover) { q.s_t2 = next_slot++; q.s_out = next_slot++; }
+            if (use_early) q.s_t1 = next_slot++;
+            // the maximum of this block's output: the next block's conv1 scale (early), the residual term of the hand-over block
+            if (!q.handover && (use_early || q.pre_handover)) q.s_out = next_slot++;
+            q.c1_h2 = use_early && cur_f32 && o.rn_c1_h2 && rn_can_c1_h2(k);
+            if (q.c1_h2) q.s_c1 = next_slot++;
+            if (next_dr) q.s_dr_out = next_slot++;
+            q.fuse_mean = q.want_mean && HWo % 4 == 0;
+            q.no_split = !fuse && tapped && HWo % 4 == 0;
+            q.out_form = q.handover ? kRnH2 : out_f32 ? kRnF32 : kRnSp3;
+            q.out_sample = compact ? kRnSampleSp3 : next_dr ? kRnSampleH2 : kRnNoSample;
+        }
+        // (a launch that fuses the mean when the layer stack is asked for runs unsplit either way - no_split does not look at the request: the
+        // pool vector's bits do not depend on whether the layer stack is requested)
+        q.need32 = out_f32 || q.want_export || (q.want_mean && !q.fuse_mean) || pool_needs32;
+        // fp32 rows: every image for the next block, an export or the pool images behind the layer-stack ones, else the layer-stack images only
+        q.rows32 = ((out_f32 || q.want_export || pool_needs32) ? rq.N : rq.n_ls) * HWo;
+        in_form = q.out_form; in_sample = q.out_sample;
+        s_x = q.out_form == kRnH2 ? q.s_out : -1;
+        s_xin = q.s_out; s_dr = q.s_dr_out;
+        H = Ho;
+    }
+    p.n_slots = next_slot;
+    if (next_slot > max_slots) {
+        err = "resnet50: " + std::to_string(next_slot) + " per-image scale slots used, " + std::to_string(max_slots) + " reserved";
+        return false;
+    }
+    *plan = p;
+    return true;
+}
+
 }  // namespace host
 }  // namespace relax
 
@@ -274,6 +397,27 @@ int relax_host_vgg16_check_keys(const float* const* tensors, const char* const* 
     return -1;
 }
 void relax_host_vgg16_fc1_to_nhwc(const float* w, int rows, int c, int hw, float* out) { relax::host::vgg16_fc1_to_nhwc(w, rows, c, hw, out); }
+
+// ResNet-50 schedule as plain integers.  opts: the six RnOptions in order; req: N, n_ls, pool_from, want_pool, tap mask.
+// out: [conv1_h2, pool_f32, s_stem, n_slots] + per block the 23 RnBlockPlan fields in declaration order (4 + 16 * 23 ints).
+// 0, or -1 with a message and `out` untouched when the plan needs more than max_slots slots.
+int relax_host_rn_plan(const int* opts, const int* req, int max_slots, int* out, char* err, int err_len) {
+    using namespace relax::host;
+    static_assert(sizeof(RnBlockPlan) == 23 * sizeof(int), "RnBlockPlan is 23 ints");
+    const RnOptions o{opts[0], opts[1], opts[2], opts[3], opts[4], opts[5]};
+    const RnRequest rq{req[0], req[1], req[2], req[3], (unsigned)req[4]};
+    RnPlan p;
+    std::string e;
+    if (!rn_plan(o, rq, max_slots, &p, e)) {
+        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return -1;
+    }
+    static_assert(sizeof(RnPlan) == (4 + kRnBlocks * 23) * sizeof(int), "RnPlan is a flat array of ints");
+    std::memcpy(out, &p, sizeof(p));
+    return 0;
+}
+// the 16 bottlenecks: block, layer, index, cin, width, cout, stride, has_down, tap (16 * 9 ints)
+void relax_host_rn_geometry(int* out) { std::memcpy(out, relax::host::rn_geometry(), sizeof(relax::host::RnBlockGeom) * relax::host::kRnBlocks); }
 
 }  // extern "C"
 #endif  // RELAX_HOST_TEST_API

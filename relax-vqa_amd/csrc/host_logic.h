@@ -74,5 +74,79 @@ double layernorm_out_bound(const float* gamma, const float* beta, int dim);
 // inherits the bound.  W [N][dim] row-major, b may be null.
 double linear_of_layernorm_bound(const float* W, const float* b, const float* gamma, const float* beta, int dim, int n0, int n1);
 
+// ---- ResNet-50 under bf16x6 / f16x2: which launches a forward issues and in which form every tensor travels (resnet50.hip executes it) --------
+constexpr int kRnBlocks = 16;
+constexpr int kRnFirstH2Block = 7;   // layer3[0]: from here on the blocks run f16x2 under "gemm_precision" 3 (with "rn_h2")
+struct RnBlockGeom {
+    int block, layer, index;          // 0 .. 15 = layer<layer>.<index> of the state dict
+    int cin, width, cout, stride;     // conv1 cin -> width, conv2 3x3 (stride) width -> width, conv3 width -> cout; downsample cin -> cout (stride)
+    int has_down, tap;                // tap: layer-stack tap index, -1 if not tapped (layer3 blocks 4, 5)
+};
+const RnBlockGeom* rn_geometry();     // the kRnBlocks bottlenecks of torchvision's ResNet-50
+
+// "This block can run form X": the loader builds the derived weights of a form where its predicate holds, the planner launches the form
+// only there.  A convolution of layer1 / layer2 on the four-wave f16x2 tiles of gemm_x6.hip (64 / 128 columns: "rn_h2_early") ...
+inline bool rn_early(const RnBlockGeom& k) { return k.block < kRnFirstH2Block; }
+inline bool rn_early_h2(int cin, int cout) { return cin % 16 == 0 && cout % 64 == 0 && cout % 256 != 0; }
+// ... its conv1 on fp32 rows split into fp16 planes in the K loop ("rn_c1_h2"; layer2: MFMA-bound on six products)
+inline bool rn_can_c1_h2(const RnBlockGeom& k) { return rn_early(k) && rn_early_h2(k.cin, k.width) && k.cin >= 256 && k.width % 128 == 0; }
+// ... the downsample convolution of a stride-2 first block (layer2[0]) as an f16x2 launch of its own, whose output is the fused conv3's fp32 residual
+inline bool rn_can_down_launch(const RnBlockGeom& k) {
+    return rn_early(k) && k.has_down && k.stride == 2 && k.cin % 16 == 0 && k.cout % 128 == 0 && k.cin >= 256;
+}
+// ... conv2 -> conv3 back to back ("rn_fuse": 64-wide blocks on four waves, 128-wide on eight; a 128-wide FIRST block too - layer2[0]: its
+// downsample branch arrives as a residual)
+inline bool rn_can_b2b(const RnBlockGeom& k) {
+    return rn_early(k) && (k.width == 64 || k.width == 128) && (!k.has_down || (k.width == 128 && k.stride == 2));
+}
+// ... back to back with the downsample convolution in conv3's accumulator (layer1[0]: 64-wide, 64 input channels, no stride)
+inline bool rn_can_b2b_x2(const RnBlockGeom& k) { return rn_early(k) && k.has_down && k.width == 64 && k.cin == 64 && k.stride == 1; }
+
+struct RnOptions { int precision, rn_h2, rn_h2_early, rn_fuse, rn_c1_h2, fp32_rows; };   // "gemm_precision" (2 or 3), ..., "x6_fp32_rows"
+// Images [0, n_ls) get layer-stack rows, images [pool_from, N) pool rows if want_pool; bit t of taps: tap t is exported
+struct RnRequest { int N, n_ls, pool_from, want_pool; unsigned taps; };
+// the pool vector of an image that is also in the layer stack is the last 2048 columns of its layer-stack row
+inline bool rn_pool_from_stack(const RnRequest& r) { return r.want_pool && r.n_ls > 0 && r.pool_from == 0 && r.n_ls == r.N; }
+
+enum RnForm {
+    kRnFormX6 = 0,     // three bf16x6 launches (conv3 + downsample in one contraction where the block has the branch)
+    kRnFormEarly,      // the same with the 3x3 on f16x2 (conv1 writes fp16 planes with the image's Hoelder scale)
+    kRnFormB2B,        // conv2 -> conv3 back to back in one launch
+    kRnFormB2BX2,      // ... with the downsample convolution folded into its conv3 (layer1[0])
+    kRnFormB2BDown,    // ... behind a downsample launch of its own (layer2[0])
+    kRnFormH2          // f16x2 with per-image scales (gemm_h2.hip: layer3 / layer4)
+};
+enum RnTensor { kRnNone = 0, kRnF32, kRnSp3, kRnH2 };   // fp32 rows / three bf16 planes / two fp16 planes with one scale per image
+enum RnSample { kRnNoSample = 0, kRnSampleSp3, kRnSampleH2 };   // + the stride-2 sample's planes, compacted (for the next block's downsample branch)
+
+// One bottleneck of the schedule.  s_*: slots of the per-image tables {maximum, scale, 1 / scale}, -1 = unused; a slot is written (its maximum by a
+// launch's epilogue, its scale from maxima written earlier) before anything reads it.
+struct RnBlockPlan {
+    int form, c1_h2;
+    int in_form, in_sample, out_form, out_sample;
+    int need32, rows32;          // the output also as fp32 rows [0, rows32): every image, or the layer-stack images only
+    int want_mean, fuse_mean;    // the tap's spatial mean of the layer-stack images; formed in conv3's epilogue (else from the fp32 copy)
+    int want_export, no_split;
+    int handover, pre_handover;  // the two blocks in front of the f16x2 ones: block 5 measures its output maximum (the residual term of block 6's
+                                 // bound), block 6 its conv2 maximum, and its output leaves as fp16 planes with its Hoelder scale + its maximum
+    int s_in_max;                // measured maximum of the block input (its producer's epilogue)
+    int s_in;                    // scale of the block input's fp16 planes (kRnH2)
+    int s_dr_in;                 // scale of the input's compact fp16 planes (kRnSampleH2)
+    int s_c1;                    // conv1 on f16x2: scale of the fp32 input rows, from their measured maximum
+    int s_t1, s_t1m;             // conv1's output: its scale from Hoelder's bound; its MEASURED maximum (what a back-to-back launch bounds planes it writes from)
+    int s_t2;                    // conv2's output: scale (kRnFormH2) / measured maximum (hand-over block)
+    int s_out;                   // the block output: scale (fp16 planes) and measured maximum
+    int s_dr_out;                // scale of the compact fp16 planes this block leaves
+};
+struct RnPlan {
+    int conv1_h2;                // the stem on f16x2
+    int pool_f32;                // the max-pool writes fp32 rows (block 0 folds its downsample convolution in), else bf16 planes
+    int s_stem;                  // the max-pool measures the maximum of its output here
+    int n_slots;
+    RnBlockPlan blk[kRnBlocks];
+};
+// The schedule of one forward: host arithmetic only.  false and a message if it needs more than max_slots per-image tables.
+bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* plan, std::string& err);
+
 }  // namespace host
 }  // namespace relax

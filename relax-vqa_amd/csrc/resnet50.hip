@@ -160,7 +160,6 @@ static constexpr size_t kT1 = 56 * 56 * 128;        // largest conv1-of-block ou
 static constexpr size_t kT2 = 56 * 56 * 64;         // largest conv2 output
 static constexpr size_t kGapWs = 196 * 256;         // GAP partial sums (16 x 2048 two-stage kernel; 3136/16 x 256 fused group sums)
 static constexpr size_t kAvg = 2048;
-static constexpr size_t kFirstH2Block = 7;          // layer3[0]: from here on the blocks run f16x2 under "gemm_precision" 3 (with "rn_h2")
 static constexpr size_t kImgSlots = 64;             // per-image tables of the f16x2 blocks: slot t = {maximum, scale, 1 / scale} x images
 static constexpr size_t kRnFloatsPerImage = kX0 + 3 * kBig + kT1 + kT2 + kGapWs + kAvg;
 // bf16x6 path: block inputs / outputs exist twice (fp32 for the residual add and the taps, split planes = 1.5 floats per
@@ -172,18 +171,26 @@ size_t resnet_arena_bytes(int n) {
     return sizeof(float) * (kRnFloatsPerImage > kRnFloatsPerImageX6 ? kRnFloatsPerImage : kRnFloatsPerImageX6) * (size_t)n;
 }
 
-static int run_conv_x6(relax_handle* h, const ConvW& c, const void* in_sp3, int Nimg, int H, int W, const float* residual,
-                       float* out, void* out_sp3, int act, hipStream_t s, const void* residual_sp3 = nullptr,
-                       float* gap_groups = nullptr) {
+// geometry, bf16x6 weights and bias of one folded convolution over N square maps of H x H
+static ConvDescX6 conv_x6(const ConvW& c, const void* in_sp3, int Nimg, int H, int act = 1) {
     ConvDescX6 d{};
-    d.in = in_sp3; d.Nimg = Nimg; d.H = H; d.W = W; d.Cin = c.Cin;
-    d.Ho = (H + 2 * c.pad - c.KH) / c.stride + 1;
-    d.Wo = (W + 2 * c.pad - c.KW) / c.stride + 1;
+    d.in = in_sp3; d.Nimg = Nimg; d.H = H; d.W = H; d.Cin = c.Cin;
+    d.Ho = d.Wo = (H + 2 * c.pad - c.KH) / c.stride + 1;
     d.KH = c.KH; d.KW = c.KW; d.stride = c.stride; d.pad = c.pad;
-    d.w = c.w_sp3; d.Cout = c.Cout;
-    d.bias = c.bias; d.residual = residual; d.out = out; d.out_sp3 = out_sp3; d.act = act;
-    d.residual_sp3 = residual_sp3; d.gap_groups = gap_groups;
-    return launch_conv_x6(h, d, s);
+    d.w = c.w_sp3; d.Cout = c.Cout; d.bias = c.bias; d.act = act;
+    return d;
+}
+
+// the loader built what the plan's form of this block reads (both go by the predicates of host_logic.h)
+static bool has_weights(const Bottleneck& k, const host::RnBlockPlan& q) {
+    if (q.c1_h2 && !k.c1.w_h2) return false;
+    switch (q.form) {
+        case host::kRnFormH2: return k.c1.w_h2 && k.c2.w_h2 && k.c3.w_h2 && (!k.has_down || k.down.w_h2);
+        case host::kRnFormB2BX2: return k.c2.w_h2 && k.c3d_w_h2p;
+        case host::kRnFormB2BDown: return k.c2.w_h2 && k.c3.w_h2p && k.down.w_h2;
+        case host::kRnFormB2B: return k.c2.w_h2 && k.c3.w_h2p;
+        default: return (q.form == host::kRnFormX6 || k.c2.w_h2) && (!k.has_down || k.c3d_w_sp3);
+    }
 }
 
 static int run_conv(relax_handle* h, const ConvW& c, const float* in, int Nimg, int H, int W, const float* residual,
@@ -196,6 +203,158 @@ static int run_conv(relax_handle* h, const ConvW& c, const float* in, int Nimg, 
     d.w = c.w; d.Cout = c.Cout; d.Kpad = c.Kpad;
     d.bias = c.bias; d.residual = residual; d.out = out; d.act = act; d.flops = flops;
     return launch_conv(h, d, s);
+}
+
+// ---- derived weights: device memory, conversions ------------------------------------------------------
+// fp32 staging rows of a weight conversion: device memory freed at the end of the scope
+struct ScopedDev {
+    float* p = nullptr;
+    bool alloc(size_t floats) { return hipMalloc(reinterpret_cast<void**>(&p), sizeof(float) * floats) == hipSuccess; }
+    ~ScopedDev() { if (p) (void)hipFree(p); }
+};
+
+// device memory that lives with the model (free_resnet), or nullptr
+static void* keep_alloc(ResNet50W& rn, size_t bytes) {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    rn.allocs.push_back(p);
+    return p;
+}
+
+// room for [rows][K] as two fp16 planes and their inverse row scales
+static bool alloc_h2(ResNet50W& rn, int rows, int K, void** q, float** inv) {
+    *q = keep_alloc(rn, (size_t)rows * K * 4);
+    *inv = *q ? static_cast<float*>(keep_alloc(rn, sizeof(float) * (size_t)rows)) : nullptr;
+    return *inv != nullptr;
+}
+
+// dst [rows][Ka + Kb] = [a | b] rows side by side
+static hipError_t concat_rows(float* dst, const float* a, int Ka, const float* b, int Kb, int rows) {
+    const size_t ld = sizeof(float) * (Ka + Kb);
+    hipError_t e = hipMemcpy2D(dst, ld, a, sizeof(float) * Ka, sizeof(float) * Ka, rows, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy2D(dst + Ka, ld, b, sizeof(float) * Kb, sizeof(float) * Kb, rows, hipMemcpyDeviceToDevice);
+    return e;
+}
+
+// the end of a conversion through staging rows: it is through before they are freed, and a failure carries the step's name
+static int built(relax_handle* h, int rc, const char* what) {
+    if (rc == RELAX_OK && hipDeviceSynchronize() != hipSuccess) rc = RELAX_ERR_HIP;
+    if (rc != RELAX_OK) set_error(h, "resnet50: building %s failed", what);
+    return rc;
+}
+
+// everything relax_load_resnet50 puts on the device; the caller frees it all if this fails
+static int load_resnet(relax_handle* h, const HostSD& sd) {
+    ResNet50W& rn = h->rn;
+    RELAX_TRY(make_conv(h, sd, "conv1", "", 64, 3, 4, 7, 2, 3, &rn.conv1, rn.allocs));
+    {
+        const float* g = sd_get(h, sd, "bn1.weight", 64);
+        const float* b = g ? sd_get(h, sd, "bn1.bias", 64) : nullptr;
+        const float* mu = b ? sd_get(h, sd, "bn1.running_mean", 64) : nullptr;
+        const float* var = mu ? sd_get(h, sd, "bn1.running_var", 64) : nullptr;
+        if (!var) return RELAX_ERR_INVALID;
+        std::vector<float> sc(64), sh(64);
+        host::fold_bn(g, b, mu, var, kBnEps, 64, sc.data(), sh.data());
+        RELAX_TRY(upload(h, sc.data(), 64, &rn.bn1_scale, rn.allocs));
+        RELAX_TRY(upload(h, sh.data(), 64, &rn.bn1_shift, rn.allocs));
+    }
+    const host::RnBlockGeom* geom = host::rn_geometry();
+    for (int b = 0; b < host::kRnBlocks; ++b) {
+        const host::RnBlockGeom& k = geom[b];
+        Bottleneck blk;
+        const std::string p = "layer" + std::to_string(k.layer) + "." + std::to_string(k.index);
+        std::vector<float> shift3, shiftd;
+        RELAX_TRY(make_conv(h, sd, p + ".conv1", p + ".bn1", k.width, k.cin, k.cin, 1, 1, 0, &blk.c1, rn.allocs));
+        RELAX_TRY(make_conv(h, sd, p + ".conv2", p + ".bn2", k.width, k.width, k.width, 3, k.stride, 1, &blk.c2, rn.allocs));
+        RELAX_TRY(make_conv(h, sd, p + ".conv3", p + ".bn3", k.cout, k.width, k.width, 1, 1, 0, &blk.c3, rn.allocs, &shift3));
+        blk.has_down = k.has_down;
+        if (blk.has_down) {
+            RELAX_TRY(make_conv(h, sd, p + ".downsample.0", p + ".downsample.1", k.cout, k.cin, k.cin, 1, k.stride, 0, &blk.down, rn.allocs, &shiftd));
+            for (size_t o = 0; o < shift3.size(); ++o) shift3[o] += shiftd[o];   // bias of the fused conv3 + downsample contraction
+            RELAX_TRY(upload(h, shift3.data(), shift3.size(), &blk.c3d_bias, rn.allocs));
+        }
+        blk.tap = k.tap;
+        rn.blocks.push_back(blk);
+    }
+    // split planes for the bf16x6 kernels (made on the device from the packed fp32 copies): conv1 in its own K layout ...
+    RELAX_TRY(make_conv1_x6_weights(h, rn.conv1.w, rn.conv1.Kpad, &rn.conv1.w_sp3, rn.allocs));
+    RELAX_TRY(make_conv1_h2_weights(h, rn.conv1.w, rn.conv1.Kpad, &rn.conv1.w_h2, &rn.conv1.w_inv, rn.allocs));
+    for (int b = 0; b < host::kRnBlocks; ++b) {
+        Bottleneck& blk = rn.blocks[b];
+        const host::RnBlockGeom& k = geom[b];
+        const bool late = !host::rn_early(k);
+        // ... every other convolution as [Cout][K] rows
+        // ... the convolutions of layer3 / layer4 (256 / 512-wide, every Cout a multiple of 256, every Cin of 32) also as two fp16 planes with one
+        // power-of-two scale per output row (gemm_h2.hip; w_inv = the inverse scales, the epilogue's colscale), and of layer1 / layer2 the
+        // convolutions whose f16x2 form the schedule can ask for (host_logic.h: the 3x3, conv1, the downsample launch of layer2[0])
+        const std::pair<ConvW*, bool> convs[] = {{&blk.c1, late || host::rn_early_h2(k.cin, k.width)}, {&blk.c2, late || host::rn_early_h2(k.width, k.width)},
+                                                 {&blk.c3, late}, {&blk.down, k.has_down && (late || host::rn_can_down_launch(k))}};
+        for (const auto& [c, as_h2] : convs) {
+            if (!c->w) continue;
+            const int K = c->KH * c->KW * c->Cin;
+            if (K != c->Kpad || c->Cin % 16 != 0) {
+                set_error(h, "resnet50: conv K=%d (padded %d) does not fit the split-plane layout", K, c->Kpad);
+                return RELAX_ERR_INVALID;
+            }
+            c->w_sp3 = keep_alloc(rn, (size_t)c->Cout * K * 6);
+            if (!c->w_sp3) {
+                set_error(h, "resnet50: hipMalloc of split-plane weights failed");
+                return RELAX_ERR_NOMEM;
+            }
+            RELAX_TRY(launch_to_sp3(h, c->w, K, c->w_sp3, c->Cout, K, nullptr));
+            if (!as_h2) continue;
+            if ((late && (c->Cin % 32 != 0 || c->Cout % 256 != 0)) || !alloc_h2(rn, c->Cout, K, &c->w_h2, &c->w_inv)) {
+                set_error(h, "resnet50: fp16-plane weights of block %d (Cin %d, Cout %d) could not be made", b, c->Cin, c->Cout);
+                return RELAX_ERR_NOMEM;
+            }
+            RELAX_TRY(launch_to_h2_rows(h, c->w, K, c->w_h2, c->Cout, K, c->w_inv, nullptr));
+        }
+        const int Co = blk.c3.Cout;
+        // ... conv3 of a block that can run back to back once more as fp16 planes with the K axis in the order of that form ("rn_fuse":
+        // gemm_x6.hip, B2B - the 3x3's transposed accumulator tile is the A operand)
+        if (host::rn_can_b2b(k)) {
+            const int K = blk.c3.Cin;
+            ScopedDev perm;
+            if (!perm.alloc((size_t)Co * K) || !alloc_h2(rn, Co, K, &blk.c3.w_h2p, &blk.c3.w_invp)) {
+                set_error(h, "resnet50: hipMalloc of the back-to-back conv3 weights failed");
+                return RELAX_ERR_NOMEM;
+            }
+            int rc = launch_b2b_permute_k(h, blk.c3.w, perm.p, Co, K, nullptr);
+            if (rc == RELAX_OK) rc = launch_to_h2_rows(h, perm.p, K, blk.c3.w_h2p, Co, K, blk.c3.w_invp, nullptr);
+            RELAX_TRY(built(h, rc, "the back-to-back conv3 weights"));
+        }
+        // ... for layer1[0] [conv3 (K permuted) | downsample (natural K)] rows of 128 as fp16 planes: its back-to-back form contracts conv3 and
+        // the downsample convolution in one accumulator (gemm_x6.hip, B2B == 2)
+        if (host::rn_can_b2b_x2(k)) {
+            ScopedDev perm, cat;
+            if (!perm.alloc((size_t)Co * 64) || !cat.alloc((size_t)Co * 128) || !alloc_h2(rn, Co, 128, &blk.c3d_w_h2p, &blk.c3d_w_invp)) {
+                set_error(h, "resnet50: hipMalloc of the two-source back-to-back weights failed");
+                return RELAX_ERR_NOMEM;
+            }
+            hipError_t e = launch_b2b_permute_k(h, blk.c3.w, perm.p, Co, 64, nullptr) == RELAX_OK ? hipDeviceSynchronize() : hipErrorUnknown;
+            if (e == hipSuccess) e = concat_rows(cat.p, perm.p, 64, blk.down.w, 64, Co);
+            RELAX_TRY(built(h, e == hipSuccess ? launch_to_h2_rows(h, cat.p, 128, blk.c3d_w_h2p, Co, 128, blk.c3d_w_invp, nullptr) : RELAX_ERR_HIP,
+                            "the two-source back-to-back weights"));
+        }
+        // ... and, for the four blocks with a downsample branch, [conv3 | downsample] rows side by side as split planes
+        if (blk.has_down) {
+            const int K1 = blk.c3.Cin, K2 = blk.down.Cin;
+            ScopedDev cat;
+            blk.c3d_w_sp3 = cat.alloc((size_t)Co * (K1 + K2)) ? keep_alloc(rn, (size_t)Co * (K1 + K2) * 6) : nullptr;
+            if (!blk.c3d_w_sp3) {
+                set_error(h, "resnet50: hipMalloc of the fused conv3 + downsample weights failed");
+                return RELAX_ERR_NOMEM;
+            }
+            const hipError_t e = concat_rows(cat.p, blk.c3.w, K1, blk.down.w, K2, Co);
+            RELAX_TRY(built(h, e == hipSuccess ? launch_to_sp3(h, cat.p, K1 + K2, blk.c3d_w_sp3, Co, K1 + K2, nullptr) : RELAX_ERR_HIP,
+                            "the fused conv3 + downsample weights"));
+        }
+    }
+    if (hipDeviceSynchronize() != hipSuccess) {
+        set_error(h, "resnet50: weight conversion failed");
+        return RELAX_ERR_HIP;
+    }
+    return RELAX_OK;
 }
 
 }  // namespace relax
@@ -212,211 +371,10 @@ int relax_load_resnet50(relax_handle* h, const float* const* tensors, const char
     free_resnet(h);
     HostSD sd;
     for (int i = 0; i < n; ++i) sd.add(names[i], tensors[i], numels[i]);
-    ResNet50W& rn = h->rn;
-    int rc = make_conv(h, sd, "conv1", "", 64, 3, 4, 7, 2, 3, &rn.conv1, rn.allocs);
-    if (rc != RELAX_OK) { free_resnet(h); return rc; }
-    {
-        const float* g = sd_get(h, sd, "bn1.weight", 64);
-        const float* b = g ? sd_get(h, sd, "bn1.bias", 64) : nullptr;
-        const float* mu = b ? sd_get(h, sd, "bn1.running_mean", 64) : nullptr;
-        const float* var = mu ? sd_get(h, sd, "bn1.running_var", 64) : nullptr;
-        if (!var) { free_resnet(h); return RELAX_ERR_INVALID; }
-        std::vector<float> sc(64), sh(64);
-        host::fold_bn(g, b, mu, var, kBnEps, 64, sc.data(), sh.data());
-        rc = upload(h, sc.data(), 64, &rn.bn1_scale, rn.allocs);
-        if (rc == RELAX_OK) rc = upload(h, sh.data(), 64, &rn.bn1_shift, rn.allocs);
-        if (rc != RELAX_OK) { free_resnet(h); return rc; }
-    }
-    const int stage_blocks[4] = {3, 4, 6, 3};
-    const int stage_width[4] = {64, 128, 256, 512};
-    const int stage_taps[4] = {3, 4, 4, 3};  // layer3 blocks 4,5 are not tapped
-    int cin = 64, tap = 1;
-    for (int st = 0; st < 4; ++st) {
-        for (int b = 0; b < stage_blocks[st]; ++b) {
-            Bottleneck blk;
-            const int width = stage_width[st];
-            const int stride = (b == 0 && st > 0) ? 2 : 1;
-            char pfx[64];
-            snprintf(pfx, sizeof(pfx), "layer%d.%d", st + 1, b);
-            const std::string p(pfx);
-            rc = make_conv(h, sd, p + ".conv1", p + ".bn1", width, cin, cin, 1, 1, 0, &blk.c1, rn.allocs);
-            if (rc == RELAX_OK)
-                rc = make_conv(h, sd, p + ".conv2", p + ".bn2", width, width, width, 3, stride, 1, &blk.c2, rn.allocs);
-            std::vector<float> shift3, shiftd;
-            if (rc == RELAX_OK)
-                rc = make_conv(h, sd, p + ".conv3", p + ".bn3", width * 4, width, width, 1, 1, 0, &blk.c3, rn.allocs, &shift3);
-            blk.has_down = (b == 0);
-            if (rc == RELAX_OK && blk.has_down)
-                rc = make_conv(h, sd, p + ".downsample.0", p + ".downsample.1", width * 4, cin, cin, 1, stride, 0,
-                               &blk.down, rn.allocs, &shiftd);
-            if (rc == RELAX_OK && blk.has_down) {   // bias of the fused conv3 + downsample contraction
-                for (size_t o = 0; o < shift3.size(); ++o) shift3[o] += shiftd[o];
-                rc = upload(h, shift3.data(), shift3.size(), &blk.c3d_bias, rn.allocs);
-            }
-            if (rc != RELAX_OK) { free_resnet(h); return rc; }
-            blk.tap = b < stage_taps[st] ? tap++ : -1;
-            rn.blocks.push_back(blk);
-            cin = width * 4;
-        }
-    }
-    // split planes for the bf16x6 kernels (made on the device from the packed fp32 copies): conv1 in its own K layout ...
-    rc = make_conv1_x6_weights(h, rn.conv1.w, rn.conv1.Kpad, &rn.conv1.w_sp3, rn.allocs);
-    if (rc == RELAX_OK) rc = make_conv1_h2_weights(h, rn.conv1.w, rn.conv1.Kpad, &rn.conv1.w_h2, &rn.conv1.w_inv, rn.allocs);
-    if (rc != RELAX_OK) { free_resnet(h); return rc; }
-    // ... every other convolution as [Cout][K] rows
-    for (Bottleneck& blk : rn.blocks) {
-        for (ConvW* c : {&blk.c1, &blk.c2, &blk.c3, &blk.down}) {
-            if (!c->w) continue;
-            const int K = c->KH * c->KW * c->Cin;
-            if (K != c->Kpad || c->Cin % 16 != 0) {
-                set_error(h, "resnet50: conv K=%d (padded %d) does not fit the split-plane layout", K, c->Kpad);
-                free_resnet(h);
-                return RELAX_ERR_INVALID;
-            }
-            void* q = nullptr;
-            if (hipMalloc(&q, (size_t)c->Cout * K * 6) != hipSuccess) {
-                set_error(h, "resnet50: hipMalloc of split-plane weights failed");
-                free_resnet(h);
-                return RELAX_ERR_NOMEM;
-            }
-            rn.allocs.push_back(q);
-            c->w_sp3 = q;
-            rc = launch_to_sp3(h, c->w, K, q, c->Cout, K, nullptr);
-            if (rc != RELAX_OK) { free_resnet(h); return rc; }
-        }
-    }
-    // ... the convolutions of layer3 / layer4 (blocks 7 .. 15: 256 / 512-wide, every Cout a multiple of 256, every Cin of 32) also as two
-    // fp16 planes with one power-of-two scale per output row (gemm_h2.hip; w_inv = the inverse scales, the epilogue's colscale)
-    // ... and the 3x3 convolutions of layer1 / layer2 (64 / 128 columns: the four-wave f16x2 form of gemm_x6.hip, "rn_h2_early")
-    for (size_t b = 0; b < rn.blocks.size(); ++b) {
-        Bottleneck& blk = rn.blocks[b];
-        const bool early = b < kFirstH2Block;
-        for (ConvW* c : {&blk.c1, &blk.c2, &blk.c3, &blk.down}) {
-            // (early blocks: the 3x3 - and conv1, whose fp32 input rows are split in the K loop under "rn_c1_h2")
-            // ... and the downsample convolution of a stride-2 first block (layer2[0]), which runs as a launch of its own in front of that block's
-            // back-to-back launch: its output is the fused conv3's fp32 residual)
-            const bool early_down = early && c == &blk.down && blk.has_down && c->stride == 2 && c->Cin % 16 == 0 && c->Cout % 128 == 0 && c->Cin >= 256;
-            if (!c->w || (early && !early_down && ((c != &blk.c2 && c != &blk.c1) || c->Cin % 16 != 0 || c->Cout % 64 != 0 || c->Cout % 256 == 0))) continue;
-            const int K = c->KH * c->KW * c->Cin;
-            void* q = nullptr;
-            float* inv = nullptr;
-            if ((!early && (c->Cin % 32 != 0 || c->Cout % 256 != 0)) || hipMalloc(&q, (size_t)c->Cout * K * 4) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void**>(&inv), sizeof(float) * (size_t)c->Cout) != hipSuccess) {
-                if (q) (void)hipFree(q);
-                set_error(h, "resnet50: fp16-plane weights of block %zu (Cin %d, Cout %d) could not be made", b, c->Cin, c->Cout);
-                free_resnet(h);
-                return RELAX_ERR_NOMEM;
-            }
-            rn.allocs.push_back(q);
-            rn.allocs.push_back(inv);
-            c->w_h2 = q;
-            c->w_inv = inv;
-            rc = launch_to_h2_rows(h, c->w, K, q, c->Cout, K, inv, nullptr);
-            if (rc != RELAX_OK) { free_resnet(h); return rc; }
-        }
-    }
-    // ... the conv3 of the layer1 / layer2 blocks without a downsample branch once more as fp16 planes with the K axis in the order of the
-    // back-to-back form ("rn_fuse": gemm_x6.hip, B2B - the 3x3's transposed accumulator tile is the A operand)
-    for (size_t b = 0; b < kFirstH2Block && b < rn.blocks.size(); ++b) {
-        Bottleneck& blk = rn.blocks[b];
-        // (64-wide blocks: the four-wave form; 128-wide: eight waves; a 128-wide FIRST block too - layer2[0]: its downsample branch arrives as a residual)
-        if ((blk.has_down && !(blk.c3.Cin == 128 && blk.down.stride == 2)) || (blk.c3.Cin != 64 && blk.c3.Cin != 128)) continue;
-        const int K = blk.c3.Cin, Co = blk.c3.Cout;
-        float* perm = nullptr;
-        void* q = nullptr;
-        float* inv = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&perm), sizeof(float) * (size_t)Co * K) != hipSuccess ||
-            hipMalloc(&q, (size_t)Co * K * 4) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&inv), sizeof(float) * (size_t)Co) != hipSuccess) {
-            if (perm) (void)hipFree(perm);
-            if (q) (void)hipFree(q);
-            set_error(h, "resnet50: hipMalloc of the back-to-back conv3 weights failed");
-            free_resnet(h);
-            return RELAX_ERR_NOMEM;
-        }
-        rn.allocs.push_back(q);
-        rn.allocs.push_back(inv);
-        rc = launch_b2b_permute_k(h, blk.c3.w, perm, Co, K, nullptr);
-        if (rc == RELAX_OK) rc = launch_to_h2_rows(h, perm, K, q, Co, K, inv, nullptr);
-        if (rc == RELAX_OK && hipDeviceSynchronize() != hipSuccess) rc = RELAX_ERR_HIP;
-        (void)hipFree(perm);
-        if (rc != RELAX_OK) {
-            set_error(h, "resnet50: building the back-to-back conv3 weights failed");
-            free_resnet(h);
-            return rc;
-        }
-        blk.c3.w_h2p = q;
-        blk.c3.w_invp = inv;
-    }
-    // ... and for a 64-wide FIRST block (layer1[0]: downsample without a stride, 64 input channels) [conv3 (K permuted) | downsample (natural K)] rows of
-    // 128 as fp16 planes: its back-to-back form contracts conv3 and the downsample convolution in one accumulator (gemm_x6.hip, B2B == 2)
-    for (size_t b = 0; b < kFirstH2Block && b < rn.blocks.size(); ++b) {
-        Bottleneck& blk = rn.blocks[b];
-        if (!blk.has_down || blk.c3.Cin != 64 || blk.down.Cin != 64 || blk.down.stride != 1 || blk.c2.stride != 1) continue;
-        const int Co = blk.c3.Cout;
-        float *perm = nullptr, *cat = nullptr, *inv = nullptr;
-        void* q = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&perm), sizeof(float) * (size_t)Co * 64) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&cat), sizeof(float) * (size_t)Co * 128) != hipSuccess ||
-            hipMalloc(&q, (size_t)Co * 128 * 4) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&inv), sizeof(float) * (size_t)Co) != hipSuccess) {
-            if (perm) (void)hipFree(perm);
-            if (cat) (void)hipFree(cat);
-            if (q) (void)hipFree(q);
-            set_error(h, "resnet50: hipMalloc of the two-source back-to-back weights failed");
-            free_resnet(h);
-            return RELAX_ERR_NOMEM;
-        }
-        rn.allocs.push_back(q);
-        rn.allocs.push_back(inv);
-        rc = launch_b2b_permute_k(h, blk.c3.w, perm, Co, 64, nullptr);
-        hipError_t e = rc == RELAX_OK ? hipDeviceSynchronize() : hipErrorUnknown;
-        if (e == hipSuccess) e = hipMemcpy2D(cat, sizeof(float) * 128, perm, sizeof(float) * 64, sizeof(float) * 64, Co, hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipMemcpy2D(cat + 64, sizeof(float) * 128, blk.down.w, sizeof(float) * 64, sizeof(float) * 64, Co, hipMemcpyDeviceToDevice);
-        rc = e == hipSuccess ? launch_to_h2_rows(h, cat, 128, q, Co, 128, inv, nullptr) : RELAX_ERR_HIP;
-        if (rc == RELAX_OK && hipDeviceSynchronize() != hipSuccess) rc = RELAX_ERR_HIP;
-        (void)hipFree(perm);
-        (void)hipFree(cat);
-        if (rc != RELAX_OK) {
-            set_error(h, "resnet50: building the two-source back-to-back weights failed");
-            free_resnet(h);
-            return rc;
-        }
-        blk.c3d_w_h2p = q;
-        blk.c3d_w_invp = inv;
-    }
-    // ... and, for the four blocks with a downsample branch, [conv3 | downsample] rows side by side
-    for (Bottleneck& blk : rn.blocks) {
-        if (!blk.has_down) continue;
-        const int K1 = blk.c3.Cin, K2 = blk.down.Cin, Co = blk.c3.Cout;
-        float* cat = nullptr;
-        void* q = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&cat), sizeof(float) * (size_t)Co * (K1 + K2)) != hipSuccess ||
-            hipMalloc(&q, (size_t)Co * (K1 + K2) * 6) != hipSuccess) {
-            if (cat) (void)hipFree(cat);
-            set_error(h, "resnet50: hipMalloc of the fused conv3 + downsample weights failed");
-            free_resnet(h);
-            return RELAX_ERR_NOMEM;
-        }
-        rn.allocs.push_back(q);
-        blk.c3d_w_sp3 = q;
-        hipError_t e = hipMemcpy2D(cat, sizeof(float) * (K1 + K2), blk.c3.w, sizeof(float) * K1, sizeof(float) * K1, Co, hipMemcpyDeviceToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy2D(cat + K1, sizeof(float) * (K1 + K2), blk.down.w, sizeof(float) * K2, sizeof(float) * K2, Co, hipMemcpyDeviceToDevice);
-        rc = e == hipSuccess ? launch_to_sp3(h, cat, K1 + K2, q, Co, K1 + K2, nullptr) : RELAX_ERR_HIP;
-        if (rc == RELAX_OK && hipDeviceSynchronize() != hipSuccess) rc = RELAX_ERR_HIP;
-        (void)hipFree(cat);
-        if (rc != RELAX_OK) {
-            set_error(h, "resnet50: building the fused conv3 + downsample weights failed");
-            free_resnet(h);
-            return rc;
-        }
-    }
-    if (hipDeviceSynchronize() != hipSuccess) {
-        set_error(h, "resnet50: weight conversion failed");
-        free_resnet(h);
-        return RELAX_ERR_HIP;
-    }
-    rn.loaded = true;
-    return RELAX_OK;
+    const int rc = load_resnet(h, sd);
+    if (rc == RELAX_OK) h->rn.loaded = true;
+    else free_resnet(h);   // a failed load leaves nothing behind
+    return rc;
 }
 
 // One forward over N images.  Images [0, n_ls) get layer-stack rows (n_ls = 0: none), images [pool_from, N) get pool rows
@@ -461,13 +419,21 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
     };
 
     if (h->gemm.precision >= 2) {   // (3 = f16x2: layer3 / layer4 and the 3x3 convolutions of layer1 / layer2 on fp16 planes - "rn_h2", "rn_h2_early" - the rest bf16x6)
+        // which launches run and in which form every tensor travels is host_logic.cpp's rn_plan (CPU-tested); here are the buffers and the launches
+        const host::RnOptions opt{h->gemm.precision, h->gemm.rn_h2, h->gemm.rn_h2_early, h->gemm.rn_fuse, h->gemm.rn_c1_h2, h->gemm.fp32_rows};
+        host::RnRequest rq{N, n_ls, pool_from, pool != nullptr, 0u};
+        for (int t = 0; taps_nchw && t < RELAX_RN50_NUM_TAPS; ++t) rq.taps |= taps_nchw[t] ? 1u << t : 0u;
+        host::RnPlan plan;
+        std::string plan_err;
+        RELAX_REQUIRE(h, rn.blocks.size() == (size_t)host::kRnBlocks && host::rn_plan(opt, rq, (int)kImgSlots, &plan, plan_err), "%s",
+                      plan_err.empty() ? "resnet50: not the 16 bottlenecks of the schedule" : plan_err.c_str());
         // bf16x6.  conv1 7x7/2 (raw) straight from the uint8 fragments (conv1_x6.hip: preprocess, im2col, split and contraction in one
         // kernel, the 16-pixel sums of the tap's spatial mean formed in its epilogue); from the max-pool on, every convolution input
         // travels as split planes written by its producer
         float* gap0 = T2 + kT2 * n;   // = the fp32 carving's gapws: free until the blocks carve the arena anew below
-        const bool conv1_h2 = h->gemm.precision == 3 && h->gemm.rn_h2 && h->gemm.rn_h2_early && rn.conv1.w_h2;   // the stem on f16x2 as well
-        RELAX_TRY(launch_conv1_x6(h, frags, conv1_h2 ? rn.conv1.w_h2 : rn.conv1.w_sp3, bufA, layer_stack ? gap0 : nullptr, N, s,
-                                  conv1_h2 ? rn.conv1.w_inv : nullptr));
+        RELAX_REQUIRE(h, !plan.conv1_h2 || rn.conv1.w_h2, "resnet50: the stem's fp16-plane weights are missing");
+        RELAX_TRY(launch_conv1_x6(h, frags, plan.conv1_h2 ? rn.conv1.w_h2 : rn.conv1.w_sp3, bufA, layer_stack ? gap0 : nullptr, N, s,
+                                  plan.conv1_h2 ? rn.conv1.w_inv : nullptr));
         if (layer_stack) RELAX_TRY(launch_gap_groups_finish(h, gap0, layer_stack, n_ls, 112 * 112, 64, RELAX_RN50_LAYER_STACK_DIM, s));
         if (taps_nchw && taps_nchw[0]) RELAX_TRY(launch_nhwc_to_nchw(h, bufA, taps_nchw[0], N, 112 * 112, 64, s));
         float* f32a = bufB;                                   // block outputs as fp32, where something needs them (ping-pong with f32b)
@@ -476,309 +442,161 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
         char* spb = spa + sizeof(float) * (kBig * 3 / 2) * n;
         char* T1s = spb + sizeof(float) * (kBig * 3 / 2) * n;
         char* T2s = T1s + sizeof(float) * (kT1 * 3 / 2) * n;
-        float* gapws6 = reinterpret_cast<float*>(T2s + sizeof(float) * (kT2 * 3 / 2) * n);
-        float* avg6 = gapws6 + kGapWs * n;
-        gapws = gapws6;
-        // f16x2 for layer3 / layer4 ("gemm_precision" 3 with "rn_h2"): per-image tables {maximum, scale, 1 / scale}, one slot per tensor
-        const bool use_h2 = h->gemm.precision == 3 && h->gemm.rn_h2 && rn.blocks.size() == 16;
+        gapws = reinterpret_cast<float*>(T2s + sizeof(float) * (kT2 * 3 / 2) * n);
+        float* avg6 = gapws + kGapWs * n;
+        // per-image tables {maximum, scale, 1 / scale} of the f16x2 launches, one slot per tensor (the plan's s_* fields)
         float* imgtab = avg6 + kAvg * n;
-        int next_slot = 0;
         auto slot_amax = [&](int t) { return reinterpret_cast<unsigned*>(imgtab + (size_t)(3 * t) * n); };
         auto slot_scale = [&](int t) { return imgtab + (size_t)(3 * t + 1) * n; };
         auto slot_inv = [&](int t) { return imgtab + (size_t)(3 * t + 2) * n; };
-        if (use_h2) RELAX_HIP_CHECK(h, hipMemsetAsync(imgtab, 0, sizeof(float) * 3 * kImgSlots * n, s));
-        int slot_x = -1;          // the current block input's slot, once it exists as fp16 planes
-        int slot_prev_out = -1;   // maximum of the previous block's output (the residual of the hand-over block)
-        // "rn_h2_early": the 3x3 convolutions of layer1 / layer2 on f16x2 as well (gemm_x6.hip, H2 form).  Their input (conv1's output)
-        // is written as fp16 planes with the image's Hoelder scale  l1max(conv1) max|block input| + max|bias|; the block input's maximum
-        // is measured by its producer: the max-pool (block maxima, reduced per image) or the previous block's conv3 epilogue.
-        bool use_early = use_h2 && h->gemm.rn_h2_early;
-        for (size_t b = 0; b < kFirstH2Block && use_early; ++b) use_early = rn.blocks[b].c2.w_h2 != nullptr;
-        int slot_xin = -1;        // (early) the slot that holds the maximum of the current block input
-        if (use_early) slot_xin = next_slot++;
-        // "rn_fuse": layer1[0] back to back too, with the downsample convolution folded into its conv3 - the block input then travels as fp32 rows
-        // (4 B per value instead of 6: conv1 splits them in its K loop, the fused launch reads each pixel's row as conv3's second source)
-        const bool fuse0 = use_early && h->gemm.rn_fuse && h->gemm.fp32_rows && rn.blocks[0].c3d_w_h2p != nullptr;
-        if (fuse0)
-            RELAX_TRY(launch_bn_relu_maxpool_f32(h, bufA, rn.bn1_scale, rn.bn1_shift, bufD, N, 112, 112, 64, s, slot_amax(slot_xin),
-                                                 reinterpret_cast<unsigned*>(imgtab + 3 * kImgSlots * n)));
+        // slot t's scale and inverse from Hoelder's bound  la max(a) + lb max(b) + max(r) + c  over measured maxima (-1: no such term)
+        auto scales = [&](int t, int a, float la, int b, float lb, int r, float c) {
+            return launch_h2_image_scales(h, slot_amax(a), la, b >= 0 ? slot_amax(b) : nullptr, lb, r >= 0 ? slot_amax(r) : nullptr, c, slot_scale(t),
+                                          slot_inv(t), N, s);
+        };
+        auto conv_h2 = [&](const ConvW& c, const void* in, int Hin, int slot_in, GemmDescH2 g, int slot_out, int act) {
+            g.a = in; g.w = c.w_h2; g.colscale = c.w_inv; g.bias = c.bias; g.act = act;
+            g.pixels = 1; g.Nimg = N; g.H = Hin; g.W = Hin; g.Cin = c.Cin;
+            g.Ho = (Hin + 2 * c.pad - c.KH) / c.stride + 1; g.Wo = g.Ho;
+            g.KH = c.KH; g.KW = c.KW; g.stride = c.stride; g.pad = c.pad;
+            g.M = N * g.Ho * g.Wo; g.N = c.Cout; g.K = c.KH * c.KW * c.Cin;
+            g.rows_per_img = g.Ho * g.Wo; g.img_in_inv = slot_inv(slot_in);
+            if (g.out_h2) { g.img_out_scale = slot_scale(slot_out); g.amax_out = slot_amax(slot_out); }
+            return launch_gemm_h2(h, g, s);
+        };
+        if (plan.n_slots) RELAX_HIP_CHECK(h, hipMemsetAsync(imgtab, 0, sizeof(float) * 3 * kImgSlots * n, s));
+        unsigned* blockmax = reinterpret_cast<unsigned*>(imgtab + 3 * kImgSlots * n);
+        if (plan.pool_f32)
+            RELAX_TRY(launch_bn_relu_maxpool_f32(h, bufA, rn.bn1_scale, rn.bn1_shift, bufD, N, 112, 112, 64, s, slot_amax(plan.s_stem), blockmax));
         else
-        RELAX_TRY(launch_bn_relu_maxpool_sp3(h, bufA, rn.bn1_scale, rn.bn1_shift, spa, N, 112, 112, 64, s,
-                                             use_early ? slot_amax(slot_xin) : nullptr,
-                                             reinterpret_cast<unsigned*>(imgtab + 3 * kImgSlots * n)));
-        // A block output exists as split planes (next convolutions, next residual: hi + mid + lo is the fp32 value, exactly) and as
-        // fp32 only where something needs it, and only for the images that need it: the tap export, the spatial mean of the 7x7
-        // taps of the layer-stack images (49 rows per image do not divide into the 16- or 4-row groups of the mean fused into
-        // the epilogue), the last block's map of the pool images.
-        // The block outputs inside layer1 and layer2 (56x56x256 and 28x28x512: the widest tensors, their consumers HBM-bound) travel
-        // as plain fp32 instead, 4 bytes per value where the planes take 6: the next block's conv1 (64 / 128 output columns, one
-        // column tile, so every value is split exactly once, as the producer's epilogue would have) splits them inside its K loop
-        // and its conv3 adds them as an fp32 residual - the same values bit for bit.  A layer's last block writes planes: the next
-        // layer's first conv3 reads them as its second activation source.
-        const float* cur32 = fuse0 ? bufD : nullptr;   // (f32b: block 0 writes f32a, block 1 - which overwrites f32b - runs when block 0 is through)
-        char* cursp = spa;
+            RELAX_TRY(launch_bn_relu_maxpool_sp3(h, bufA, rn.bn1_scale, rn.bn1_shift, spa, N, 112, 112, 64, s,
+                                                 plan.s_stem >= 0 ? slot_amax(plan.s_stem) : nullptr, blockmax));
+        const float* cur32 = plan.pool_f32 ? bufD : nullptr;   // (f32b: block 0 writes f32a, block 1 - which overwrites f32b - runs when block 0 is through)
+        char* cursp = spa;       // the block input's planes; a stride-2 sample the previous block left (in_sample) lies in othersp
         char* othersp = spb;
         float* out32 = f32a;
-        bool cur_is_f32 = fuse0;   // the current block input exists as fp32 rows only
-        const char* dr_planes = nullptr;    // ... or as fp16 planes with the per-image scale of slot dr_slot (for a downsample launch of its own)
-        int dr_slot = -1, dr_slot_next = -1;
-        const char* compact_in = nullptr;   // ... plus the planes of its stride-2 sample, compacted (what the previous block left for a downsample branch)
         int H = 56;
         for (size_t b = 0; b < rn.blocks.size(); ++b) {
             const Bottleneck& blk = rn.blocks[b];
+            const host::RnBlockPlan& q = plan.blk[b];
             const int Ho = H / blk.c2.stride;
             const int HWo = Ho * Ho, Cout = blk.c3.Cout;
-            const bool tapped = blk.tap >= 0;
-            const bool want_mean = tapped && layer_stack;
-            const bool want_export = tapped && taps_nchw && taps_nchw[blk.tap];
-            const bool is_last = b + 1 == rn.blocks.size();
-            const bool fuse_mean = want_mean && HWo % 4 == 0;
-            const bool pool_needs32 = is_last && pool && !pool_from_stack;
-            // "rn_fuse" (below): conv2 and conv3 back to back in one launch
-            const bool fuse_x2 = b == 0 && fuse0;      // the first block: conv3 + downsample in the fused launch's one contraction
-            // layer2[0] (stride 2, 256 -> 512 downsample: too many channels for a second source in registers): the downsample convolution as a
-            // launch of its own (f16x2, the fp32 rows sampled with the stride and split in the K loop) whose fp32 output is the residual of the
-            // block's back-to-back launch (3x3 with the stride -> conv3) - instead of the 3x3 + the two-source bf16x6 conv3
-            auto down_as_residual = [&](const Bottleneck& k) {
-                return use_early && h->gemm.rn_fuse && h->gemm.rn_c1_h2 && h->gemm.fp32_rows && k.has_down && k.c2.stride == 2 && k.c3.w_h2p && k.down.w_h2 &&
-                       k.c1.w_h2 && k.c1.Cout % 128 == 0 && k.c1.Cin >= 256;
-            };
-            const bool fuse_dr = b > 0 && b < kFirstH2Block && cur_is_f32 && down_as_residual(blk) && Ho * Ho >= 256 && dr_planes != nullptr;
-            const bool fuse = fuse_x2 || fuse_dr || (use_early && b < kFirstH2Block && h->gemm.rn_fuse && !blk.has_down && blk.c3.w_h2p && cur_is_f32 && blk.c2.stride == 1 && H * H >= 256);
-            // a layer's last block in front of a downsample block: its output travelled as three bf16 planes (6 B per value: the next block's conv1 and
-            // the second source of its conv3 read planes).  Back to back it leaves as fp32 rows like the others (conv1 splits in its K loop) PLUS the
-            // planes of the stride-2 sample only - all the downsample branch reads -, compacted: 4 + 1.5 bytes per value instead of 6, and conv1 reads 4
-            const bool next_down = !is_last && rn.blocks[b + 1].has_down;
-            const bool next_dr = next_down && b + 1 < kFirstH2Block && fuse && down_as_residual(rn.blocks[b + 1]);   // the next block reads fp32 rows only
-            const bool compact = fuse && next_down && !next_dr && b + 1 < kFirstH2Block && h->gemm.fp32_rows && Cout <= 512 && Ho % 2 == 0 && rn.blocks[b + 1].c2.stride == 2;
-            const bool out_is_f32 = h->gemm.fp32_rows && Cout <= 512 && !is_last && (!next_down || compact || next_dr);
-            const bool need32 = out_is_f32 || want_export || (want_mean && !fuse_mean) || pool_needs32;
-            // fp32 rows: every image for the next block, an export or the pool images behind the layer-stack ones, else the
-            // layer-stack images only
-            const int rows32 = (out_is_f32 || want_export || pool_needs32) ? N * HWo : n_ls * HWo;
-            if (use_h2 && b >= kFirstH2Block) {
-                // ---- an f16x2 block (gemm_h2.hip).  Every tensor that feeds a convolution travels as two fp16 planes with one scale per
-                // image; the scale of a tensor is fixed BEFORE it is written, from Hoelder's bound on its producer (measured maxima of
-                // the producer's inputs, l1max / bmax of its weights).  cursp = the block input's planes (slot_x).
-                const int s1 = next_slot++, s2 = next_slot++, sy = next_slot++;
-                // fp32 copies only where something reads them: an export, the spatial mean of the 7x7 taps (49 rows do not divide into the
-                // 4-row groups of the fused mean), the last block's map of the pool images - and only for the images that need them.  The
-                // residual of a block without a downsample branch is read from the block input's PLANES (hi + lo, the stored 22-bit value).
-                const bool fuse_h2 = want_mean && HWo % 4 == 0 && HWo % 16 != 0;   // 14x14 maps: 4-row groups (gemm_h3's fused mean)
-                const bool need32_h2 = want_export || (want_mean && !fuse_h2) || pool_needs32;
-                const int rows32_h2 = (want_export || pool_needs32) ? N * HWo : n_ls * HWo;
-                auto conv_h2 = [&](const ConvW& c, const void* in, int Hin, int slot_in, GemmDescH2 g, int slot_out, int act) {
-                    g.a = in; g.w = c.w_h2; g.colscale = c.w_inv; g.bias = c.bias; g.act = act;
-                    g.pixels = 1; g.Nimg = N; g.H = Hin; g.W = Hin; g.Cin = c.Cin;
-                    g.Ho = (Hin + 2 * c.pad - c.KH) / c.stride + 1; g.Wo = g.Ho;
-                    g.KH = c.KH; g.KW = c.KW; g.stride = c.stride; g.pad = c.pad;
-                    g.M = N * g.Ho * g.Wo; g.N = c.Cout; g.K = c.KH * c.KW * c.Cin;
-                    g.rows_per_img = g.Ho * g.Wo; g.img_in_inv = slot_inv(slot_in);
-                    if (g.out_h2) { g.img_out_scale = slot_scale(slot_out); g.amax_out = slot_amax(slot_out); }
-                    return launch_gemm_h2(h, g, s);
-                };
+            const bool b2b = q.form == host::kRnFormB2B || q.form == host::kRnFormB2BX2 || q.form == host::kRnFormB2BDown;
+            float* y32 = q.need32 ? out32 : nullptr;
+            float* gap = q.fuse_mean ? gapws : nullptr;
+            RELAX_REQUIRE(h, has_weights(blk, q), "resnet50: block %zu lacks the derived weights of launch form %d", b, q.form);
+            if (q.form == host::kRnFormH2) {
+                // ---- an f16x2 block (gemm_h2.hip): cursp = the block input's planes (slot s_in)
                 // conv1 1x1 + ReLU
-                RELAX_TRY(launch_h2_image_scales(h, slot_amax(slot_x), blk.c1.l1max, nullptr, 0.f, nullptr, blk.c1.bmax, slot_scale(s1), slot_inv(s1), N, s));
-                { GemmDescH2 g{}; g.out_h2 = T1s; RELAX_TRY(conv_h2(blk.c1, cursp, H, slot_x, g, s1, 1)); }
+                RELAX_TRY(scales(q.s_t1, q.s_in, blk.c1.l1max, -1, 0.f, -1, blk.c1.bmax));
+                { GemmDescH2 g{}; g.out_h2 = T1s; RELAX_TRY(conv_h2(blk.c1, cursp, H, q.s_in, g, q.s_t1, 1)); }
                 // conv2 3x3 (stride) + ReLU
-                RELAX_TRY(launch_h2_image_scales(h, slot_amax(s1), blk.c2.l1max, nullptr, 0.f, nullptr, blk.c2.bmax, slot_scale(s2), slot_inv(s2), N, s));
-                { GemmDescH2 g{}; g.out_h2 = T2s; RELAX_TRY(conv_h2(blk.c2, T1s, H, s1, g, s2, 1)); }
+                RELAX_TRY(scales(q.s_t2, q.s_t1, blk.c2.l1max, -1, 0.f, -1, blk.c2.bmax));
+                { GemmDescH2 g{}; g.out_h2 = T2s; RELAX_TRY(conv_h2(blk.c2, T1s, H, q.s_t1, g, q.s_t2, 1)); }
                 // conv3 1x1 + identity + ReLU: the identity is the block input (its planes) or the downsample convolution of it (fp32, no
                 // activation; bounded by its own Hoelder term)
                 GemmDescH2 g3{};
                 if (blk.has_down) {
                     GemmDescH2 gd{};
                     gd.out = bufA;
-                    RELAX_TRY(conv_h2(blk.down, cursp, H, slot_x, gd, -1, 0));
+                    RELAX_TRY(conv_h2(blk.down, cursp, H, q.s_in, gd, -1, 0));
                     g3.residual = bufA;
-                    RELAX_TRY(launch_h2_image_scales(h, slot_amax(s2), blk.c3.l1max, slot_amax(slot_x), blk.down.l1max, nullptr,
-                                                     blk.c3.bmax + blk.down.bmax, slot_scale(sy), slot_inv(sy), N, s));
+                    RELAX_TRY(scales(q.s_out, q.s_t2, blk.c3.l1max, q.s_in, blk.down.l1max, -1, blk.c3.bmax + blk.down.bmax));
                 } else {
-                    g3.residual_h2 = cursp; g3.img_res_inv = slot_inv(slot_x);
-                    RELAX_TRY(launch_h2_image_scales(h, slot_amax(s2), blk.c3.l1max, nullptr, 0.f, slot_amax(slot_x), blk.c3.bmax, slot_scale(sy),
-                                                     slot_inv(sy), N, s));
+                    g3.residual_h2 = cursp; g3.img_res_inv = slot_inv(q.s_in);
+                    RELAX_TRY(scales(q.s_out, q.s_t2, blk.c3.l1max, -1, 0.f, q.s_in, blk.c3.bmax));
                 }
-                g3.out = need32_h2 ? out32 : nullptr; g3.out_rows = rows32_h2;
-                g3.out_h2 = is_last ? nullptr : othersp;
-                g3.gap_groups = fuse_h2 ? gapws : nullptr; g3.gap_rows = n_ls * HWo;
-                g3.no_split = tapped && HWo % 4 == 0 && HWo % 16 != 0;   // a launch that fuses the mean when the layer stack is asked for runs
-                                                                         // unsplit either way: the pool vector's bits do not depend on the request
-                RELAX_TRY(conv_h2(blk.c3, T2s, Ho, s2, g3, sy, 1));
-                cur32 = need32_h2 ? out32 : nullptr;
-                if (need32_h2) out32 = out32 == f32a ? f32b : f32a;
-                { char* t = cursp; cursp = othersp; othersp = t; }
-                cur_is_f32 = false;
-                slot_x = sy;
-                H = Ho;
-                if (tapped) {
-                    const int off = tap_offset(blk.tap);
-                    if (fuse_h2)
-                        RELAX_TRY(launch_gap_groups_finish(h, gapws, layer_stack + off, n_ls, HWo, Cout, RELAX_RN50_LAYER_STACK_DIM, s));
-                    else if (want_mean)
-                        RELAX_TRY(launch_gap_ws(h, cur32, layer_stack + off, n_ls, HWo, Cout, RELAX_RN50_LAYER_STACK_DIM, gapws, s));
-                    if (want_export) RELAX_TRY(launch_nhwc_to_nchw(h, cur32, taps_nchw[blk.tap], N, HWo, Cout, s));
-                }
-                continue;
-            }
-            // the two blocks in front of the f16x2 ones hand over: block 5's output maximum (the residual of block 6), block 6's conv2
-            // maximum, and block 6's output as fp32 + fp16 planes with its Hoelder scale + its maximum
-            const bool handover = use_h2 && b + 1 == kFirstH2Block;
-            const bool pre_handover = use_h2 && b + 2 == kFirstH2Block;
-            int slot_c2 = -1, slot_y = -1, slot_t1 = -1, slot_o = -1, slot_t1m = -1;
-            // ("rn_fuse", `fuse` above: the 3x3's tile never leaves the CU; conv3 on f16x2 with one scale per pixel row)
-            if ((handover || next_dr) && fuse) slot_t1m = next_slot++;   // the MEASURED maximum of conv1's output: what the scale of an output that leaves as fp16 planes is bounded from (below)
-            if (handover) { slot_c2 = next_slot++; slot_y = next_slot++; }
-            if (use_early) slot_t1 = next_slot++;
-            // the maximum of this block's output: the next block's conv1 scale (early), the residual term of the hand-over block
-            if (handover) slot_o = slot_y;
-            else if (use_early || pre_handover) slot_o = next_slot++;
-            if (pre_handover) slot_prev_out = slot_o;
-            {
-                ConvDescX6 d{};
-                d.in = cur_is_f32 ? static_cast<const void*>(cur32) : cursp; d.in_f32 = cur_is_f32;
-                d.Nimg = N; d.H = H; d.W = H; d.Cin = blk.c1.Cin; d.Ho = H; d.Wo = H;
-                d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0;
-                d.w = blk.c1.w_sp3; d.Cout = blk.c1.Cout; d.bias = blk.c1.bias; d.act = 1;
-                if (use_early && cur_is_f32 && h->gemm.rn_c1_h2 && blk.c1.w_h2 && blk.c1.Cin >= 256 && blk.c1.Cout % 128 == 0) {   // (layer2: MFMA-bound on six products)
+                g3.out = y32; g3.out_rows = q.rows32;
+                g3.out_h2 = q.out_form == host::kRnH2 ? othersp : nullptr;
+                g3.gap_groups = gap; g3.gap_rows = n_ls * HWo;
+                g3.no_split = q.no_split;
+                RELAX_TRY(conv_h2(blk.c3, T2s, Ho, q.s_t2, g3, q.s_out, 1));
+            } else {
+                // ---- conv1 1x1 + ReLU, from fp32 rows (split in the K loop) or planes
+                const bool in_f32 = q.in_form == host::kRnF32;
+                ConvDescX6 d = conv_x6(blk.c1, in_f32 ? static_cast<const void*>(cur32) : cursp, N, H);
+                d.in_f32 = in_f32;
+                if (q.c1_h2) {
                     // f16x2: the rows are split into fp16 planes in the K loop, with the image's scale from the MEASURED maximum of the block input
-                    const int sx = next_slot++;
-                    RELAX_TRY(launch_h2_image_scales(h, slot_amax(slot_xin), 1.f, nullptr, 0.f, nullptr, 0.f, slot_scale(sx), slot_inv(sx), N, s));
-                    d.w = blk.c1.w_h2; d.colscale = blk.c1.w_inv; d.img_in_scale = slot_scale(sx); d.img_in_inv = slot_inv(sx);
+                    RELAX_TRY(scales(q.s_c1, q.s_in_max, 1.f, -1, 0.f, -1, 0.f));
+                    d.w = blk.c1.w_h2; d.colscale = blk.c1.w_inv; d.img_in_scale = slot_scale(q.s_c1); d.img_in_inv = slot_inv(q.s_c1);
                 }
-                if (use_early) {   // fp16 planes for the f16x2 conv2, scaled by the image's bound
-                    RELAX_TRY(launch_h2_image_scales(h, slot_amax(slot_xin), blk.c1.l1max, nullptr, 0.f, nullptr, blk.c1.bmax, slot_scale(slot_t1),
-                                                     slot_inv(slot_t1), N, s));
-                    d.out_h2 = T1s; d.img_out_scale = slot_scale(slot_t1);
-                    if (slot_t1m >= 0) d.amax_out = slot_amax(slot_t1m);
+                if (q.s_t1 >= 0) {   // fp16 planes for the f16x2 conv2, scaled by the image's bound
+                    RELAX_TRY(scales(q.s_t1, q.s_in_max, blk.c1.l1max, -1, 0.f, -1, blk.c1.bmax));
+                    d.out_h2 = T1s; d.img_out_scale = slot_scale(q.s_t1);
+                    if (q.s_t1m >= 0) d.amax_out = slot_amax(q.s_t1m);
                 } else {
                     d.out_sp3 = T1s;
                 }
                 RELAX_TRY(launch_conv_x6(h, d, s));
-            }
-            if (handover || use_early) {
-                ConvDescX6 d2{};
-                d2.in = T1s; d2.Nimg = N; d2.H = H; d2.W = H; d2.Cin = blk.c2.Cin;
-                d2.Ho = (H + 2 * blk.c2.pad - blk.c2.KH) / blk.c2.stride + 1; d2.Wo = d2.Ho;
-                d2.KH = blk.c2.KH; d2.KW = blk.c2.KW; d2.stride = blk.c2.stride; d2.pad = blk.c2.pad;
-                d2.w = blk.c2.w_sp3; d2.Cout = blk.c2.Cout; d2.bias = blk.c2.bias; d2.out_sp3 = T2s; d2.act = 1;
-                if (use_early) { d2.in_h2 = 1; d2.w = blk.c2.w_h2; d2.colscale = blk.c2.w_inv; d2.img_in_inv = slot_inv(slot_t1); }
-                if (handover && !fuse) d2.amax_out = slot_amax(slot_c2);
-                if (fuse) {
-                    d2.out_sp3 = nullptr;
+                // ---- conv2 3x3 (stride) + ReLU; back to back, conv3 in the same launch
+                ConvDescX6 d2 = conv_x6(blk.c2, T1s, N, H);
+                if (q.s_t1 >= 0) { d2.in_h2 = 1; d2.w = blk.c2.w_h2; d2.colscale = blk.c2.w_inv; d2.img_in_inv = slot_inv(q.s_t1); }
+                // ---- conv3 1x1 + identity + ReLU.  Its output: fp32 rows where the plan wants them, and bf16 planes, or - the hand-over block - fp16
+                // planes with a per-image scale, or fp32 rows only plus the planes of the stride-2 sample the next block's downsample branch reads
+                ConvDescX6 d3 = conv_x6(blk.c3, T2s, N, Ho);
+                ConvDescX6& y = b2b ? d2 : d3;      // the launch that writes the block output
+                int s_planes = q.handover ? q.s_out : q.s_dr_out;   // scale of the fp16 planes the block output leaves as, if any
+                if (b2b) {
                     d2.w3 = blk.c3.w_h2p; d2.colscale3 = blk.c3.w_invp; d2.bias3 = blk.c3.bias; d2.Cout3 = Cout;
                     d2.residual = cur32;
-                    if (fuse_dr) {
+                    if (q.form == host::kRnFormB2BDown) {
                         // the downsample branch first: fp32 [N*Ho*Ho][Cout] into bufA (the stem's raw output: dead since the max-pool), on gemm_h3's
-                        // 1x1 form from the compact fp16 planes of the input's stride-2 sample the previous block left (its per-image scale: dr_slot)
+                        // 1x1 form from the compact fp16 planes of the input's stride-2 sample the previous block left (its per-image scale: s_dr_in)
+                        ConvW down1 = blk.down;
+                        down1.stride = 1;
                         GemmDescH2 g{};
-                        g.a = dr_planes; g.w = blk.down.w_h2; g.colscale = blk.down.w_inv; g.bias = blk.down.bias; g.act = 0;
-                        g.pixels = 1; g.Nimg = N; g.H = Ho; g.W = Ho; g.Cin = blk.down.Cin; g.Ho = Ho; g.Wo = Ho;
-                        g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0;
-                        g.M = N * Ho * Ho; g.N = blk.down.Cout; g.K = blk.down.Cin;
-                        g.rows_per_img = Ho * Ho; g.img_in_inv = slot_inv(dr_slot);
                         g.out = bufA;
-                        RELAX_TRY(launch_gemm_h2(h, g, s));
+                        RELAX_TRY(conv_h2(down1, othersp, Ho, q.s_dr_in, g, -1, 0));
                         d2.residual = bufA;
                     }
-                    if (next_dr) {
-                        // this block's output leaves as fp32 rows AND as the fp16 planes of its stride-2 sample (compacted): what the next block's
-                        // downsample launch reads.  Their per-image scale: Hoelder from the measured maxima of conv1's output and of the block input
-                        // (as the hand-over block below)
-                        const int sy = next_slot++;
-                        RELAX_TRY(launch_h2_image_scales(h, slot_amax(slot_t1m), blk.c3.l1max * blk.c2.l1max, nullptr, 0.f, slot_amax(slot_xin),
-                                                         blk.c3.l1max * blk.c2.bmax + blk.c3.bmax, slot_scale(sy), slot_inv(sy), N, s));
-                        d2.out_h2 = othersp; d2.img_out_scale = slot_scale(sy); d2.sp3_sub = 2;
-                        dr_slot_next = sy;
+                    if (q.form == host::kRnFormB2BX2) { d2.w3 = blk.c3d_w_h2p; d2.colscale3 = blk.c3d_w_invp; d2.bias3 = blk.c3d_bias; d2.residual = nullptr; d2.x2 = cur32; }
+                    // fp16 planes with a per-image scale from a bound.  Two launches: Hoelder on conv3 with the MEASURED maximum of conv2's
+                    // output; back to back that tensor never exists, so it is bounded in turn from the measured maximum of conv1's output:
+                    // |y| <= l1(c3) (l1(c2) max|t1| + b2) + b3 + max|x|  - one more L1-to-max ratio of looseness (2^5 - 2^7 of fp16's 19
+                    // binades), still never compounding beyond this block
+                    if (s_planes >= 0)
+                        RELAX_TRY(scales(s_planes, q.s_t1m, blk.c3.l1max * blk.c2.l1max, -1, 0.f, q.s_in_max, blk.c3.l1max * blk.c2.bmax + blk.c3.bmax));
+                    d2.sp3_sub = q.out_sample != host::kRnNoSample ? 2 : 1;
+                } else {
+                    if (q.handover) d2.amax_out = slot_amax(q.s_t2);
+                    d2.out_sp3 = T2s;
+                    RELAX_TRY(launch_conv_x6(h, d2, s));
+                    d3.no_split = q.no_split;
+                    if (blk.has_down) {
+                        // conv3 and the downsample convolution in ONE contraction over K = [conv2 output | block input sampled with the
+                        // block's stride]: no fp32 copy of the branch is written and read back (layer1.0: 6.6 GB per 1024 images)
+                        d3.w = blk.c3d_w_sp3; d3.bias = blk.c3d_bias;
+                        d3.in2 = cursp; d3.H2 = H; d3.W2 = H; d3.Cin2 = blk.down.Cin; d3.stride2 = blk.down.stride;
+                        if (q.in_sample == host::kRnSampleSp3) { d3.in2 = othersp; d3.H2 = Ho; d3.W2 = Ho; d3.stride2 = 1; }   // (the previous block left the stride-2 sample only)
+                    } else if (in_f32) {
+                        d3.residual = cur32;
+                    } else {
+                        d3.residual_sp3 = cursp;
                     }
-                    if (fuse_x2) { d2.w3 = blk.c3d_w_h2p; d2.colscale3 = blk.c3d_w_invp; d2.bias3 = blk.c3d_bias; d2.residual = nullptr; d2.x2 = cur32; }
-                    d2.out = need32 ? out32 : nullptr; d2.out_rows = rows32;
-                    d2.out_sp3 = (compact || !out_is_f32) ? othersp : nullptr;
-                    d2.sp3_sub = (compact || next_dr) ? 2 : 1;
-                    d2.gap_groups = fuse_mean ? gapws : nullptr; d2.gap_rows = n_ls * HWo;
-                    d2.amax_out = slot_o >= 0 ? slot_amax(slot_o) : nullptr;
-                    if (handover) {
-                        // the block's output leaves as fp16 planes with a per-image scale from a bound.  Two launches: Hoelder on conv3 with the
-                        // MEASURED maximum of conv2's output; back to back that tensor never exists, so it is bounded in turn from the measured
-                        // maximum of conv1's output:  |y| <= l1(c3) (l1(c2) max|t1| + b2) + b3 + max|x|  - one more L1-to-max ratio of looseness
-                        // (2^5 - 2^7 of fp16's 19 binades), still never compounding beyond this block
-                        RELAX_TRY(launch_h2_image_scales(h, slot_amax(slot_t1m), blk.c3.l1max * blk.c2.l1max, nullptr, 0.f, slot_amax(slot_prev_out),
-                                                         blk.c3.l1max * blk.c2.bmax + blk.c3.bmax, slot_scale(slot_y), slot_inv(slot_y), N, s));
-                        d2.out_sp3 = nullptr;
-                        d2.out_h2 = othersp; d2.img_out_scale = slot_scale(slot_y); d2.amax_out = slot_amax(slot_y);
-                    }
+                    // (block 6 has no downsample branch and its input is fp32 rows; its output leaves as fp16 planes with the Hoelder scale of
+                    // conv3 + identity; block 7 takes its identity from its downsample branch)
+                    if (q.handover) RELAX_TRY(scales(s_planes, q.s_t2, blk.c3.l1max, -1, 0.f, q.s_in_max, blk.c3.bmax));
                 }
-                RELAX_TRY(launch_conv_x6(h, d2, s));
-            } else {
-                RELAX_TRY(run_conv_x6(h, blk.c2, T1s, N, H, H, nullptr, nullptr, T2s, 1, s));
+                y.out = y32; y.out_rows = q.rows32;
+                y.gap_groups = gap; y.gap_rows = n_ls * HWo;
+                y.out_sp3 = (q.out_form == host::kRnSp3 || q.out_sample == host::kRnSampleSp3) ? othersp : nullptr;
+                if (s_planes >= 0) { y.out_h2 = othersp; y.img_out_scale = slot_scale(s_planes); }
+                y.amax_out = q.s_out >= 0 ? slot_amax(q.s_out) : nullptr;
+                RELAX_TRY(launch_conv_x6(h, y, s));
             }
-            if (!fuse) {
-            ConvDescX6 d{};
-            d.in = T2s; d.Nimg = N; d.H = Ho; d.W = Ho; d.Cin = blk.c3.Cin; d.Ho = Ho; d.Wo = Ho;
-            d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0;
-            d.Cout = Cout; d.act = 1;
-            d.out = need32 ? out32 : nullptr; d.out_rows = rows32;
-            d.out_sp3 = out_is_f32 ? nullptr : othersp;
-            d.gap_groups = fuse_mean ? gapws : nullptr; d.gap_rows = n_ls * HWo;
-            d.no_split = tapped && HWo % 4 == 0;   // a launch that fuses the mean when the layer stack is asked for runs unsplit either
-                                                    // way: the pool vector's bits do not depend on whether the layer stack is requested
-            if (blk.has_down) {
-                // conv3 and the downsample convolution in ONE contraction over K = [conv2 output | block input sampled with the
-                // block's stride]: no fp32 copy of the branch is written and read back (layer1.0: 6.6 GB per 1024 images)
-                d.w = blk.c3d_w_sp3; d.bias = blk.c3d_bias;
-                d.in2 = cursp; d.H2 = H; d.W2 = H; d.Cin2 = blk.down.Cin; d.stride2 = blk.down.stride;
-                if (compact_in) { d.in2 = compact_in; d.H2 = Ho; d.W2 = Ho; d.stride2 = 1; }   // (the previous block left the stride-2 sample only)
-            } else {
-                d.w = blk.c3.w_sp3; d.bias = blk.c3.bias;
-                if (cur_is_f32) d.residual = cur32; else d.residual_sp3 = cursp;
-            }
-            if (slot_o >= 0 && !handover) d.amax_out = slot_amax(slot_o);
-            if (handover) {
-                // (block 6 has no downsample branch and its input is fp32 rows: residual = cur32; its output leaves as fp16 planes with the
-                // Hoelder scale of conv3 + identity)
-                RELAX_TRY(launch_h2_image_scales(h, slot_amax(slot_c2), blk.c3.l1max, nullptr, 0.f, slot_amax(slot_prev_out), blk.c3.bmax,
-                                                 slot_scale(slot_y), slot_inv(slot_y), N, s));
-                d.out_sp3 = nullptr;       // (fp32 rows as the tap logic above decided; block 7 takes its identity from its downsample branch)
-                d.out_h2 = othersp; d.img_out_scale = slot_scale(slot_y); d.amax_out = slot_amax(slot_y);
-            }
-            RELAX_TRY(launch_conv_x6(h, d, s));
-            }
-            if (handover) {
-                cur32 = need32 ? out32 : nullptr;
-                if (need32) out32 = out32 == f32a ? f32b : f32a;
-                { char* t = cursp; cursp = othersp; othersp = t; }
-                cur_is_f32 = false;
-                slot_x = slot_y;
-                H = Ho;
-                if (tapped) {
-                    const int off = tap_offset(blk.tap);
-                    if (fuse_mean)
-                        RELAX_TRY(launch_gap_groups_finish(h, gapws, layer_stack + off, n_ls, HWo, Cout, RELAX_RN50_LAYER_STACK_DIM, s));
-                    else if (want_mean)
-                        RELAX_TRY(launch_gap_ws(h, cur32, layer_stack + off, n_ls, HWo, Cout, RELAX_RN50_LAYER_STACK_DIM, gapws, s));
-                    if (want_export) RELAX_TRY(launch_nhwc_to_nchw(h, cur32, taps_nchw[blk.tap], N, HWo, Cout, s));
-                }
-                continue;
-            }
-            cur32 = need32 ? out32 : nullptr;
-            if (need32) out32 = out32 == f32a ? f32b : f32a;
-            if (!out_is_f32) { char* t = cursp; cursp = othersp; othersp = t; }
-            compact_in = compact ? othersp : nullptr;
-            dr_planes = (fuse && next_dr) ? othersp : nullptr;
-            dr_slot = dr_slot_next;
-            dr_slot_next = -1;
-            cur_is_f32 = out_is_f32;
-            slot_xin = slot_o;
+            // ---- the block is through: its output becomes the next block's input; the tap
+            cur32 = y32;
+            if (y32) out32 = out32 == f32a ? f32b : f32a;
+            if (q.out_form != host::kRnF32) { char* t = cursp; cursp = othersp; othersp = t; }   // (fp32 rows: a stride-2 sample, if any, stays in othersp)
             H = Ho;
-            if (tapped) {
-                const int off = tap_offset(blk.tap);
-                if (fuse_mean)
-                    RELAX_TRY(launch_gap_groups_finish(h, gapws, layer_stack + off, n_ls, HWo, Cout, RELAX_RN50_LAYER_STACK_DIM, s));
-                else if (want_mean)
-                    RELAX_TRY(launch_gap_ws(h, cur32, layer_stack + off, n_ls, HWo, Cout, RELAX_RN50_LAYER_STACK_DIM, gapws, s));
-                if (want_export) RELAX_TRY(launch_nhwc_to_nchw(h, cur32, taps_nchw[blk.tap], N, HWo, Cout, s));
-            }
+            const int off = q.want_mean ? tap_offset(blk.tap) : 0;
+            if (q.fuse_mean)
+                RELAX_TRY(launch_gap_groups_finish(h, gapws, layer_stack + off, n_ls, HWo, Cout, RELAX_RN50_LAYER_STACK_DIM, s));
+            else if (q.want_mean)
+                RELAX_TRY(launch_gap_ws(h, cur32, layer_stack + off, n_ls, HWo, Cout, RELAX_RN50_LAYER_STACK_DIM, gapws, s));
+            if (q.want_export) RELAX_TRY(launch_nhwc_to_nchw(h, cur32, taps_nchw[blk.tap], N, HWo, Cout, s));
         }
-        RELAX_REQUIRE(h, next_slot <= (int)kImgSlots, "resnet50: %d per-image scale slots used, %d reserved", next_slot, (int)kImgSlots);
         return pool_tail(cur32, avg6, gapws);
     }
     auto emit_tap = [&](int tap, const float* act) -> int {

@@ -187,3 +187,8 @@ for x in rows:
 assert worst_ln <= ln_bound and worst_lin <= lin_bound, (worst_ln, ln_bound, worst_lin, lin_bound)
 assert worst_ln > 0.5 * ln_bound          # (the one-hot row nearly attains the LayerNorm bound: it is tight, not merely safe)
 print("f16x2 bound helpers ok: LayerNorm", worst_ln, "<=", ln_bound, " Linear", worst_lin, "<=", lin_bound)
+
+
+# ---- the ResNet-50 schedule: all 320 option x request cases (slot budget, dataflow, request-independence, the default schedules) --------
+from tests import rn_schedule_checks  # noqa: E402
+print("resnet50 schedule ok:", rn_schedule_checks.check_all(lib), "cases")

@@ -2,7 +2,8 @@
 """Do two builds of the library give the same bits?  (GPU box only.)
   python tools/ab_bits.py tools/abl/librelax_prev.so relax-vqa_amd/csrc/librelax_hip.so [N] [resnet|vit|both|flow]
 Each build runs in its own process (RELAX_HIP_LIB) on the same seeded fragments, for gemm_split_k 0 and 1, with and without the
-tap export; prints per output whether the tensors are equal and the largest relative difference."""
+tap export; prints per output whether the tensors are equal and the largest relative difference.  RELAX_OPTS=name=value,... sets
+options in both builds first (as tools/resnet_step.py: e.g. RELAX_OPTS=rn_h2_early=0,rn_h2=0 compares a non-default schedule)."""
 import os
 import subprocess
 import sys
@@ -18,6 +19,9 @@ def child(out, n, what):
     from relax_vqa_amd import synth
     from relax_vqa_amd.engine import RelaxEngine
     eng = RelaxEngine(0)
+    for kv in os.environ.get("RELAX_OPTS", "").split(","):
+        if "=" in kv:
+            eng.set_option(kv.split("=")[0], int(kv.split("=")[1]))
     g = torch.Generator().manual_seed(5)
     frags = torch.randint(0, 256, (n, 224, 224, 3), dtype=torch.uint8, generator=g).cuda()
     res = {}
