@@ -333,6 +333,34 @@ int relax_head_train_pad_abs_sum(relax_handle* h, double* out, relax_stream stre
  * memory, then a separate update pass.  Both change fc1.weight and its momentum. */
 int relax_head_train_dw1(relax_handle* h, int fused, int B, float lr, float momentum, float weight_decay, relax_stream stream);
 
+/* ---- correlation metrics of a head's predictions (csrc/metrics.hip, csrc/metrics_core.h) ----- */
+/* compute_correlation_metrics (src/model_regression.py:149-161) with fit_logistic_regression / logistic_func (:138-147) on the
+ * device: y_true / y_pred DEVICE fp64 [n], 2 <= n <= 131072 (beyond that n^3 leaves the exact range of the rank sums;
+ * RELAX_ERR_INVALID).  out: 17 doubles, DEVICE or HOST memory -
+ *   [0] plcc   pearson(y_true, fitted)            [1] rmse   sqrt(mean((y_true - fitted)^2))
+ *   [2] srcc   Spearman's rho of the average ranks [3] krcc   Kendall's tau-b
+ *   [4..7] popt = b1..b4 of  b2 + (b1 - b2) / (1 + exp(-(x - b3) / |b4|))  fitted to (x = y_pred, y = y_true)
+ *   [8] iterations (trial points of the Levenberg-Marquardt loop)   [9] converged (1: the stopping rule was met; 0: the
+ *   iteration cap or the damping limit ended the loop)   [10] cost at p0   [11] final cost (sums of squared residuals)
+ *   [12] count of non-finite inputs   [13..16] p0 = max(y_true), min(y_true), mean(y_pred), 0.5 (the reference's beta)
+ * y_pred_logistic: DEVICE fp64 [n] or NULL, the fitted scores.  The fit replaces scipy.optimize.curve_fit's MINPACK run (analytic
+ * Jacobian; ftol = xtol = 1.49e-8 as curve_fit sets them) in ONE persistent launch, bit-reproducible from run to run.  Any
+ * non-finite input makes [0..7], [10], [11], [13..16] and the fitted scores NaN and [12] its count; that is not an error status.
+ * With `out` in device memory the call only enqueues on `stream`; with `out` in host memory it copies the results and waits for
+ * `stream`.  Uses a workspace the handle owns (20 bytes per element). */
+int relax_metrics_correlation(relax_handle* h, const double* y_true, const double* y_pred, int n, double* out, double* y_pred_logistic,
+                              relax_stream stream);
+/* The pair pass alone: scipy.stats.kendalltau / spearmanr of model_regression.py:154-157 (the per-epoch selection metric of
+ * :425-429).  x / y DEVICE fp64 [n], n as above; out: 8 doubles, DEVICE or HOST (as above) -
+ *   [0] krcc = S / sqrt((n0 - n1) (n0 - n2))   [1] srcc   [2] S = concordant - discordant pairs   [3] n1, [4] n2 = pairs tied in
+ *   x, in y   [5] n0 = n (n - 1) / 2   [6] count of non-finite inputs (then [0], [1] are NaN)   [7] 0
+ * All counting is in integers, so the result does not depend on the launch geometry; krcc / srcc are NaN for a constant input. */
+int relax_metrics_kendall(relax_handle* h, const double* x, const double* y, int n, double* out, relax_stream stream);
+/* The per-element counters the pair pass leaves (a test / inspection path): counts DEVICE int32 [5][n] = values below x[i],
+ * values equal to x[i] (itself included), the same two for y, and the sum over j of sign(x[i] - x[j]) sign(y[i] - y[j]).
+ * The average rank of x[i] is below + (equal + 1) / 2.  Enqueued on `stream`. */
+int relax_metrics_pair_counts(relax_handle* h, const double* x, const double* y, int n, int32_t* counts, relax_stream stream);
+
 /* ---- operator level (what the backbones are built from; parity-tested one by one) ------------ */
 /* out[M,N] = act(A[M,K] * W[N,K]^T + bias[N] + residual[M,N]);  act: 0 none, 1 relu, 2 gelu(erf).
  * fp32 in, fp32 MFMA accumulate.  K % 32 == 0 (bf16x6: K % 16 == 0), N % 64 == 0.  bias/residual may be NULL; every pointer

@@ -60,6 +60,9 @@ PROTOTYPES = {
     "relax_head_train_loss_read": (C.c_int, [c_vp, C.c_int, C.c_int, c_vp, c_vp]),
     "relax_head_train_pad_abs_sum": (C.c_int, [c_vp, c_vp, c_vp]),
     "relax_head_train_dw1": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, c_vp]),
+    "relax_metrics_correlation": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
+    "relax_metrics_kendall": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp]),
+    "relax_metrics_pair_counts": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp]),
     "relax_op_gemm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_op_conv2d_nhwc": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp] + [C.c_int] * 10 + [c_vp]),
     "relax_op_layernorm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_float, c_vp]),

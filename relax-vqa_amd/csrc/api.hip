@@ -218,6 +218,7 @@ int relax_destroy(relax_handle* h) {
     free_head(h);
     free_head_train(h);
     if (h->head_ws.p) (void)hipFree(h->head_ws.p);
+    if (h->metrics_ws.p) (void)hipFree(h->metrics_ws.p);
     if (h->flow_ws.p) (void)hipFree(h->flow_ws.p);
     if (h->arena.p) (void)hipFree(h->arena.p);
     if (h->scratch.p) (void)hipFree(h->scratch.p);

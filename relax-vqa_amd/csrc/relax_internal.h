@@ -334,6 +334,7 @@ struct relax_handle {
     relax::DevBuf resize_ws;    // uint8 intermediates of the two-pass resize
     relax::DevBuf flow_ws;      // optical-flow pyramid workspace
     relax::DevBuf head_ws;      // scaled features + hidden activations of the quality head
+    relax::DevBuf metrics_ws;   // pair counters and results of the correlation metrics (metrics.hip)
     relax::HeadW head;
     relax::HeadTrain head_train;
     std::vector<relax::ResizeTable> resize_tables;

@@ -184,6 +184,28 @@ class RelaxEngine:
         from . import head_train
         return head_train.fine_tune_head(self, state_dict, features, mos, config)
 
+    # ---- scoring a head (metrics.py, csrc/metrics.hip) -----------------------------------------------------------
+    def correlation_metrics(self, y_true, y_pred, return_fitted=False):
+        """compute_correlation_metrics (src/model_regression.py:149-161) on the device: {'plcc', 'rmse', 'srcc', 'krcc', 'popt',
+        'beta', 'converged', 'iterations', ...}; see metrics.correlation_metrics."""
+        from . import metrics
+        return metrics.correlation_metrics(self, y_true, y_pred, return_fitted)
+
+    def kendall(self, x, y):
+        """Kendall's tau-b and Spearman's rho from one pair pass on the device; see metrics.kendall."""
+        from . import metrics
+        return metrics.kendall(self, x, y)
+
+    def evaluate_head(self, features_train, mos_train, features_test, mos_test, config=None):
+        """One train / test split as the reference's main() runs it; see metrics.evaluate_head."""
+        from . import metrics
+        return metrics.evaluate_head(self, features_train, mos_train, features_test, mos_test, config)
+
+    def holdout_protocol(self, features, mos, config=None, n_repeats=21, test_size=0.2, groups=None):
+        """The repeated 80/20 hold-out with medians and the median model; see metrics.holdout_protocol."""
+        from . import metrics
+        return metrics.holdout_protocol(self, features, mos, config, n_repeats, test_size, groups)
+
     def load_fitted_head(self, result):
         """load_mlp_head on what fit_head / fine_tune_head returned."""
         state_dict, scaler = result[0], result[1]

@@ -9,8 +9,9 @@ Argument names and defaults are the reference's (model_regression.py:737-751).
 
 What differs from the reference: the dropout masks and the initial weights come from this project's own
 seeded generators, not torch's; only the 'sgd' optimizer and the 'MAERankLoss' criterion exist (the reference's MSELoss branch
-never assigns its criterion, :379); plots, .mat / .csv bookkeeping and the 21-repeat median-model protocol of main() are the
-caller's business.
+never assigns its criterion, :379); plots and .mat / .csv bookkeeping are the caller's business.  The per-epoch selection
+metric runs on the device (metrics.py, csrc/metrics.hip); kendall_tau_b and logistic_rmse below stay as its host yardsticks.
+The four reported metrics and the 21-repeat median-model protocol of main() are in metrics.py.
 """
 import ctypes as C
 import math
@@ -19,9 +20,11 @@ import warnings
 import numpy as np
 import torch
 
+from . import metrics as _metrics
+
 DEFAULTS = dict(n_splits=10, batch_size=256, epochs=20, hidden_features=256, drop_rate=0.1, loss_type="MAERankLoss",
                 optimizer_type="sgd", select_criteria="bykrcc", initial_lr=1e-1, weight_decay=0.005, patience=5, use_swa=True,
-                l1_w=0.6, rank_w=1.0, momentum=0.9, seed=0)
+                l1_w=0.6, rank_w=1.0, momentum=0.9, seed=0, logistic_fit="scipy")
 LIVE, SWA, BEST = 0, 1, 2      # parameter sets of the device state
 ETA_MIN = 1e-5                 # CosineAnnealingLR(eta_min=1e-5), model_regression.py:383
 SWA_ANNEAL_EPOCHS = 10         # SWALR's default anneal_epochs
@@ -307,9 +310,25 @@ def _config(config):
         raise ValueError("head training: only loss_type='MAERankLoss' is implemented (the reference's MSELoss branch is dead code)")
     if cfg["select_criteria"] not in ("bykrcc", "byrmse", "val_loss"):
         raise ValueError(f"head training: select_criteria {cfg['select_criteria']!r}")
-    if cfg["select_criteria"] == "byrmse":
-        import scipy.optimize  # noqa: F401  ('byrmse' needs curve_fit)
+    if cfg["logistic_fit"] not in ("scipy", "device"):
+        raise ValueError(f"head training: logistic_fit {cfg['logistic_fit']!r} (scipy | device)")
+    if cfg["select_criteria"] == "byrmse" and cfg["logistic_fit"] == "scipy" and not _have_scipy():
+        cfg["logistic_fit"] = "device"   # no curve_fit here: the device fit (csrc/metrics.hip) takes its place
     return cfg
+
+
+def _have_scipy():
+    try:
+        import scipy.optimize  # noqa: F401
+    except ImportError:
+        return False
+    return True
+
+
+def _device_krcc(engine, y_true, y_pred):
+    """kendall_tau_b on the device (the pair pass of csrc/metrics.hip): the same expression from the same integer counts, so
+    the two agree bit for bit and no selection changes; nan below two rows, as kendall_tau_b gives it."""
+    return _metrics.kendall(engine, y_true, y_pred)["krcc"] if len(y_true) >= 2 else float("nan")
 
 
 def _prepare(engine, features, mos):
@@ -372,9 +391,10 @@ def fit_head(engine, features, mos, config=None):
             val_loss, val_pred = _evaluate_set(tr, xp, y, val_idx, current, cfg)
             val_losses.append(val_loss)
             if cfg["select_criteria"] == "bykrcc":
-                metric = kendall_tau_b(y_host[val_idx], val_pred)
+                metric = _device_krcc(engine, y_host[val_idx], val_pred)
             elif cfg["select_criteria"] == "byrmse":
-                metric = logistic_rmse(y_host[val_idx], val_pred)
+                metric = (_metrics.device_logistic_rmse(engine, y_host[val_idx], val_pred) if cfg["logistic_fit"] == "device"
+                          else logistic_rmse(y_host[val_idx], val_pred))
             else:
                 metric = val_loss
             metrics.append(metric)
