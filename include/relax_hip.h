@@ -378,6 +378,32 @@ int relax_op_gemm(relax_handle* h, const float* A, const float* W, const float* 
 int relax_op_conv2d_nhwc(relax_handle* h, const float* in, const float* w, const float* bias,
                          const float* residual, float* out, int Nimg, int H, int W, int Cin, int Cout,
                          int KH, int KW, int stride, int pad, int act, relax_stream stream);
+/* relax_op_conv2d_nhwc under "gemm_precision" 3 with the outputs of the epilogue that only the model drivers use (a test / bench
+ * path like its neighbours; every other precision is refused).  Conversions, geometry rules and dispatch are those of
+ * relax_op_conv2d_nhwc under f16x2: the wide form (Cin % 32 == 0, Cout % 256 == 0) runs gemm_h3, the narrow form (a KxK filter,
+ * Cin % 16 == 0, K = KH*KW*Cin a multiple of 32 and >= 256, Cout % 64 == 0 but not % 256) runs gemm_x6<H2>; a geometry with neither
+ * form is refused, it does not fall back to another kernel.  M = Nimg*Ho*Wo.  The optional arguments go into the launch unchanged
+ * (NULL / 0 = absent); what the launchers refuse comes back as RELAX_ERR_INVALID with their message and nothing of it runs:
+ *   amax_out       DEVICE uint32 [Nimg], zeroed here: the bits of each image's largest output (needs act == 1: the integer maximum
+ *                  of float bits orders non-negative values only)
+ *   out_h2         DEVICE [M][Cout*4 B]: the outputs as two fp16 planes (csrc/h2.h: per 16 values 16 x hi, 16 x lo), image i's rows
+ *                  scaled by img_out_scale[i] (DEVICE fp32 [Nimg], powers of two from the caller); narrow form: needs act == 1
+ *   residual_h2    DEVICE [M][Cout*4 B] with img_res_inv [Nimg]: the residual as planes, (hi + lo) * img_res_inv[image], instead of
+ *                  `residual` (wide form only)
+ *   gap_groups     DEVICE fp32 [M/g][Cout]: the first stage of the fused spatial mean, sums over aligned groups of g rows; g = 4 on
+ *                  the wide form, 16 on the narrow form (4 where Ho*Wo % 16 != 0); needs Ho*Wo % 4 == 0.  Groups that start below
+ *                  gap_rows are written, rows below out_rows get the fp32 `out` (0 = all); `out` may be NULL if another output is asked for
+ *   no_split       never cut tail tiles along K
+ *   w3, bias3, Cout3   the back-to-back form, plain variant (narrow form, Cout = 64 or 128, act == 1, Ho*Wo >= 256 and % 16 == 0):
+ *                  relu(conv(in) + bias) stays on the chip as the A operand of a 1x1 onto Cout3 columns, w3 fp32 [Cout3][Cout] (packed
+ *                  here with the driver's K permutation), bias3 [Cout3]; `residual` (fp32, required), `out`, `out_h2`, `amax_out`
+ *                  and `gap_groups` then describe relu(that 1x1 + bias3 + residual), [M][Cout3].  The first-block variant (second
+ *                  conv3 source, concatenated downsample weights) and the stride-2 plane sample are not reachable from here. */
+int relax_op_conv2d_nhwc_ex(relax_handle* h, const float* in, const float* w, const float* bias, const float* residual,
+                            const void* residual_h2, const float* img_res_inv, float* out, void* out_h2, const float* img_out_scale,
+                            uint32_t* amax_out, float* gap_groups, int gap_rows, int out_rows, int no_split, const float* w3,
+                            const float* bias3, int Cout3, int Nimg, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                            int pad, int act, relax_stream stream);
 /* rows of `dim` floats: y = (x-mean)/sqrt(var+eps)*gamma+beta */
 int relax_op_layernorm(relax_handle* h, const float* x, const float* gamma, const float* beta, float* y,
                        int rows, int dim, float eps, relax_stream stream);
@@ -386,6 +412,10 @@ int relax_op_attention(relax_handle* h, const float* qkv, float* out, int Nimg, 
 /* relu(x*scale[c]+shift[c]) then 3x3/s2/p1 max-pool: [Nimg,H,W,C] -> [Nimg,H/2,W/2,C] */
 int relax_op_bn_relu_maxpool(relax_handle* h, const float* x, const float* scale, const float* shift, float* y,
                              int Nimg, int H, int W, int C, relax_stream stream);
+/* ... and with amax_out (DEVICE uint32 [Nimg], or NULL): the bits of each image's largest output, as ResNet-50's stem posts them
+ * (a test path).  Needs whole 256-thread blocks per image: (H/2)*(W/2)*(C/4) % 256 == 0; any other map is refused. */
+int relax_op_bn_relu_maxpool_amax(relax_handle* h, const float* x, const float* scale, const float* shift, float* y,
+                                  uint32_t* amax_out, int Nimg, int H, int W, int C, relax_stream stream);
 /* spatial mean: x [Nimg,HW,C] -> out[n*out_stride + c] */
 int relax_op_gap(relax_handle* h, const float* x, float* out, int Nimg, int HW, int C, int64_t out_stride,
                  relax_stream stream);

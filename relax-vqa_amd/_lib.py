@@ -65,9 +65,11 @@ PROTOTYPES = {
     "relax_metrics_pair_counts": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp]),
     "relax_op_gemm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_op_conv2d_nhwc": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp] + [C.c_int] * 10 + [c_vp]),
+    "relax_op_conv2d_nhwc_ex": (C.c_int, [c_vp] * 12 + [C.c_int] * 3 + [c_vp, c_vp] + [C.c_int] * 11 + [c_vp]),
     "relax_op_layernorm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_float, c_vp]),
     "relax_op_attention": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.c_int, c_vp]),
     "relax_op_bn_relu_maxpool": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
+    "relax_op_bn_relu_maxpool_amax": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_op_gap": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int64, c_vp]),
     "relax_op_token_stats": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_copy_bytes": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, c_vp]),

@@ -621,6 +621,41 @@ int launch_conv(relax_handle* h, const ConvDesc& d, hipStream_t s) {
 
 }  // namespace relax
 
+namespace relax {
+
+// The operand conversions of the operator-level convolution entries under "f16x2" (relax_op_conv2d_nhwc, relax_op_conv2d_nhwc_ex), into the
+// handle's conversion workspace: the input as fp16 planes with one scale per IMAGE from its measured maximum (inv = 1 / that scale), the
+// weights with one scale per output row (colscale = its inverse); `extra` = further bytes behind them, 256-byte aligned, for the caller
+struct H2OpOperands {
+    char* a;
+    char* w;
+    float* inv;
+    float* colscale;
+    char* extra;
+};
+
+static int h2_op_operands(relax_handle* h, const float* in, const float* w, int Nimg, int H, int W, int Cin, int Cout, int K, size_t extra,
+                          H2OpOperands& o, hipStream_t s) {
+    const size_t a_bytes = (size_t)Nimg * H * W * Cin * 4, w_bytes = (size_t)Cout * K * 4;
+    const size_t a_al = (a_bytes + 255) & ~(size_t)255, w_al = (w_bytes + 255) & ~(size_t)255, i_al = ((size_t)Nimg * 4 + 255) & ~(size_t)255;
+    const size_t c_al = ((size_t)Cout * 4 + 255) & ~(size_t)255;
+    RELAX_TRY(ensure_buf(h, h->sp3_ws, a_al + w_al + 3 * i_al + c_al + extra + 256));
+    o.a = static_cast<char*>(h->sp3_ws.p);
+    o.w = o.a + a_al;
+    unsigned* amax = reinterpret_cast<unsigned*>(o.w + w_al);
+    float* sc = reinterpret_cast<float*>(o.w + w_al + i_al);
+    o.inv = reinterpret_cast<float*>(o.w + w_al + 2 * i_al);
+    o.colscale = reinterpret_cast<float*>(o.w + w_al + 3 * i_al);
+    o.extra = o.w + w_al + 3 * i_al + c_al;
+    RELAX_TRY(launch_image_absmax(h, in, (int64_t)H * W * Cin, Nimg, amax, s));
+    RELAX_TRY(launch_h2_image_scales(h, amax, 1.f, nullptr, 0.f, nullptr, 0.f, sc, o.inv, Nimg, s));
+    RELAX_TRY(launch_to_h2(h, in, Cin, o.a, (int64_t)Nimg * H * W, Cin, 1.f, sc, s, H * W));
+    RELAX_TRY(launch_to_h2_rows(h, w, K, o.w, Cout, K, o.colscale, s));
+    return RELAX_OK;
+}
+
+}  // namespace relax
+
 using namespace relax;
 
 extern "C" {
@@ -695,31 +730,20 @@ int relax_op_conv2d_nhwc(relax_handle* h, const float* in, const float* w, const
     const bool h2_wide = Cin % 32 == 0 && Cout % 256 == 0 && (KH * KW > 1 || pad == 0);                       // ResNet-50 layer3 / layer4: gemm_h3
     const bool h2_narrow = h->gemm.rn_h2_early && Cin % 16 == 0 && KH * KW > 1 && Cout % 64 == 0 && Cout % 256 != 0 && d.Kpad >= 256;   // the 3x3s of layer1 / layer2: gemm_x6<H2>
     if (h->gemm.precision == 3 && d.Kpad == KH * KW * Cin && KH * KW <= 32 && (h2_wide || h2_narrow)) {
-        const size_t a_bytes = (size_t)Nimg * H * W * Cin * 4, w_bytes = (size_t)Cout * d.Kpad * 4;
-        const size_t a_al = (a_bytes + 255) & ~(size_t)255, w_al = (w_bytes + 255) & ~(size_t)255, i_al = ((size_t)Nimg * 4 + 255) & ~(size_t)255;
-        RELAX_TRY(ensure_buf(h, h->sp3_ws, a_al + w_al + 3 * i_al + (size_t)Cout * 4 + 256));
-        char* As = static_cast<char*>(h->sp3_ws.p);
-        char* Ws = As + a_al;
-        unsigned* amax = reinterpret_cast<unsigned*>(Ws + w_al);
-        float* sc = reinterpret_cast<float*>(Ws + w_al + i_al);
-        float* inv = reinterpret_cast<float*>(Ws + w_al + 2 * i_al);
-        float* cs = reinterpret_cast<float*>(Ws + w_al + 3 * i_al);
-        RELAX_TRY(launch_image_absmax(h, in, (int64_t)H * W * Cin, Nimg, amax, s));
-        RELAX_TRY(launch_h2_image_scales(h, amax, 1.f, nullptr, 0.f, nullptr, 0.f, sc, inv, Nimg, s));
-        RELAX_TRY(launch_to_h2(h, in, Cin, As, (int64_t)Nimg * H * W, Cin, 1.f, sc, s, H * W));
-        RELAX_TRY(launch_to_h2_rows(h, w, d.Kpad, Ws, Cout, d.Kpad, cs, s));
+        H2OpOperands o{};
+        RELAX_TRY(h2_op_operands(h, in, w, Nimg, H, W, Cin, Cout, d.Kpad, 0, o, s));
         if (h2_wide) {
             GemmDescH2 g{};
-            g.a = As; g.w = Ws; g.colscale = cs; g.bias = bias; g.residual = residual; g.out = out;
+            g.a = o.a; g.w = o.w; g.colscale = o.colscale; g.bias = bias; g.residual = residual; g.out = out;
             g.M = Nimg * d.Ho * d.Wo; g.N = Cout; g.K = d.Kpad; g.act = act;
             g.pixels = 1; g.Nimg = Nimg; g.H = H; g.W = W; g.Cin = Cin; g.Ho = d.Ho; g.Wo = d.Wo; g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-            g.rows_per_img = d.Ho * d.Wo; g.img_in_inv = inv;
+            g.rows_per_img = d.Ho * d.Wo; g.img_in_inv = o.inv;
             return launch_gemm_h2(h, g, s);
         }
         ConvDescX6 x{};
-        x.in = As; x.in_h2 = 1; x.colscale = cs; x.img_in_inv = inv; x.Nimg = Nimg; x.H = H; x.W = W; x.Cin = Cin; x.Ho = d.Ho; x.Wo = d.Wo;
+        x.in = o.a; x.in_h2 = 1; x.colscale = o.colscale; x.img_in_inv = o.inv; x.Nimg = Nimg; x.H = H; x.W = W; x.Cin = Cin; x.Ho = d.Ho; x.Wo = d.Wo;
         x.KH = KH; x.KW = KW; x.stride = stride; x.pad = pad;
-        x.w = Ws; x.Cout = Cout; x.bias = bias; x.residual = residual; x.out = out; x.act = act;
+        x.w = o.w; x.Cout = Cout; x.bias = bias; x.residual = residual; x.out = out; x.act = act;
         return launch_conv_x6(h, x, s);
     }
     // bf16x6 where the split-plane kernel takes the geometry (16-channel chunks, at most 32 taps, 64-column tiles); anything
@@ -742,6 +766,65 @@ int relax_op_conv2d_nhwc(relax_handle* h, const float* in, const float* w, const
         return launch_conv_x6(h, x, s);
     }
     return launch_conv(h, d, s);
+}
+
+int relax_op_conv2d_nhwc_ex(relax_handle* h, const float* in, const float* w, const float* bias, const float* residual,
+                            const void* residual_h2, const float* img_res_inv, float* out, void* out_h2, const float* img_out_scale,
+                            uint32_t* amax_out, float* gap_groups, int gap_rows, int out_rows, int no_split, const float* w3,
+                            const float* bias3, int Cout3, int Nimg, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                            int pad, int act, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, in && w && (out || out_h2 || gap_groups), "relax_op_conv2d_nhwc_ex: NULL operand / no output requested");
+    RELAX_REQUIRE(h, Nimg > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && H + 2 * pad >= KH && W + 2 * pad >= KW,
+                  "relax_op_conv2d_nhwc_ex: bad geometry");
+    RELAX_REQUIRE(h, act >= 0 && act <= 2, "relax_op_conv2d_nhwc_ex: act=%d", act);
+    RELAX_REQUIRE(h, gap_rows >= 0 && out_rows >= 0, "relax_op_conv2d_nhwc_ex: negative row limit");
+    RELAX_REQUIRE(h, h->gemm.precision == 3, "relax_op_conv2d_nhwc_ex: the per-image epilogue belongs to \"gemm_precision\" 3 (f16x2)");
+    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+    const int K = KH * KW * Cin;
+    // the two forms of relax_op_conv2d_nhwc under f16x2, by the same rules
+    const bool wide = Cin % 32 == 0 && Cout % 256 == 0 && (KH * KW > 1 || pad == 0);
+    const bool narrow = h->gemm.rn_h2_early && Cin % 16 == 0 && KH * KW > 1 && Cout % 64 == 0 && Cout % 256 != 0 && K >= 256;
+    RELAX_REQUIRE(h, K % 32 == 0 && KH * KW <= 32 && (wide || narrow),
+                  "relax_op_conv2d_nhwc_ex: %dx%d, Cin=%d, Cout=%d has no f16x2 form (wide: Cin %% 32 == 0, Cout %% 256 == 0; narrow: a KxK filter, "
+                  "Cin %% 16 == 0, K %% 32 == 0, K >= 256, Cout %% 64 == 0)", KH, KW, Cin, Cout);
+    const bool b2b = w3 != nullptr;
+    RELAX_REQUIRE(h, !b2b || (narrow && bias3 && Cout3 > 0 && Cout3 % 64 == 0 && Cout % 16 == 0),
+                  "relax_op_conv2d_nhwc_ex: the back-to-back form is a narrow KxK convolution followed by a 1x1 onto Cout3 %% 64 == 0 columns with its bias");
+    RELAX_REQUIRE(h, !residual_h2 || (wide && !b2b), "relax_op_conv2d_nhwc_ex: a residual as fp16 planes goes with the wide form (gemm_h3)");
+    if (amax_out) RELAX_HIP_CHECK(h, hipMemsetAsync(amax_out, 0, sizeof(uint32_t) * (size_t)Nimg, s));
+    const size_t w3_al = b2b ? (((size_t)Cout3 * Cout * 4 + 255) & ~(size_t)255) : 0;
+    H2OpOperands o{};
+    RELAX_TRY(h2_op_operands(h, in, w, Nimg, H, W, Cin, Cout, K, 2 * w3_al + (size_t)Cout3 * 4, o, s));
+    if (wide) {
+        GemmDescH2 g{};
+        g.a = o.a; g.w = o.w; g.colscale = o.colscale; g.bias = bias; g.residual = residual; g.out = out;
+        g.M = Nimg * Ho * Wo; g.N = Cout; g.K = K; g.act = act;
+        g.pixels = 1; g.Nimg = Nimg; g.H = H; g.W = W; g.Cin = Cin; g.Ho = Ho; g.Wo = Wo; g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
+        g.rows_per_img = Ho * Wo; g.img_in_inv = o.inv;
+        g.out_h2 = out_h2; g.img_out_scale = img_out_scale; g.amax_out = amax_out;
+        g.residual_h2 = residual_h2; g.img_res_inv = img_res_inv;
+        g.gap_groups = gap_groups; g.gap_rows = gap_rows; g.out_rows = out_rows; g.no_split = no_split != 0;
+        return launch_gemm_h2(h, g, s);
+    }
+    ConvDescX6 x{};
+    x.in = o.a; x.in_h2 = 1; x.colscale = o.colscale; x.img_in_inv = o.inv; x.Nimg = Nimg; x.H = H; x.W = W; x.Cin = Cin; x.Ho = Ho; x.Wo = Wo;
+    x.KH = KH; x.KW = KW; x.stride = stride; x.pad = pad;
+    x.w = o.w; x.Cout = Cout; x.bias = bias; x.residual = residual; x.out = out; x.act = act;
+    x.out_h2 = out_h2; x.img_out_scale = img_out_scale; x.amax_out = amax_out;
+    x.gap_groups = gap_groups; x.gap_rows = gap_rows; x.out_rows = out_rows; x.no_split = no_split != 0;
+    if (b2b) {
+        // conv3's rows with the K axis in the accumulator order of the 3x3's transposed tile (the driver's own permutation), then as fp16 planes
+        float* perm = reinterpret_cast<float*>(o.extra);
+        char* w3p = o.extra + w3_al;
+        float* cs3 = reinterpret_cast<float*>(o.extra + 2 * w3_al);
+        RELAX_TRY(launch_b2b_permute_k(h, w3, perm, Cout3, Cout, s));
+        RELAX_TRY(launch_to_h2_rows(h, perm, Cout, w3p, Cout3, Cout, cs3, s));
+        x.w3 = w3p; x.colscale3 = cs3; x.bias3 = bias3; x.Cout3 = Cout3;
+    }
+    return launch_conv_x6(h, x, s);
 }
 
 }  // extern "C"

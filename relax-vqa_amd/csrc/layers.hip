@@ -582,6 +582,21 @@ int relax_op_bn_relu_maxpool(relax_handle* h, const float* x, const float* scale
     return launch_bn_relu_maxpool(h, x, scale, shift, y, Nimg, H, W, C, static_cast<hipStream_t>(stream));
 }
 
+int relax_op_bn_relu_maxpool_amax(relax_handle* h, const float* x, const float* scale, const float* shift, float* y, uint32_t* amax_out,
+                                  int Nimg, int H, int W, int C, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, x && scale && shift && y, "relax_op_bn_relu_maxpool_amax: NULL operand");
+    RELAX_REQUIRE(h, Nimg > 0 && H > 0 && W > 0 && C > 0, "relax_op_bn_relu_maxpool_amax: bad shape");
+    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    unsigned* block_ws = nullptr;
+    if (amax_out) {   // one word per block of the pooling launch, in the handle's conversion workspace
+        const int64_t total = (int64_t)Nimg * (H / 2) * (W / 2) * (C / 4);
+        RELAX_TRY(ensure_buf(h, h->sp3_ws, (size_t)((total + 255) / 256) * sizeof(unsigned) + 256));
+        block_ws = static_cast<unsigned*>(h->sp3_ws.p);
+    }
+    return launch_bn_relu_maxpool_f32(h, x, scale, shift, y, Nimg, H, W, C, static_cast<hipStream_t>(stream), amax_out, block_ws);
+}
+
 int relax_op_gap(relax_handle* h, const float* x, float* out, int Nimg, int HW, int C, int64_t out_stride,
                  relax_stream stream) {
     if (!h) return RELAX_ERR_INVALID;

@@ -714,6 +714,43 @@ class RelaxEngine:
         self._check(rc, "relax_op_conv2d_nhwc")
         return out
 
+    def op_conv2d_nhwc_ex(self, x, w_packed, bias, Cout, KH, KW, stride, pad, act=1, residual=None, residual_h2=None, img_res_inv=None,
+                          out=True, out_h2=False, img_out_scale=None, amax=False, gap=False, gap_rows=0, out_rows=0, no_split=False,
+                          w3=None, bias3=None):
+        """relax_op_conv2d_nhwc_ex: the f16x2 convolution with the model drivers' epilogue outputs.  out / gap: True allocates, a
+        tensor is filled in place (a test pre-fills it with a sentinel), False / None leaves the output out; out_h2: True allocates
+        the planes as uint16 [M, 2 * Cn] (per 16 values: 16 x hi, 16 x lo), which needs img_out_scale [Nimg]; amax: the per-image
+        maxima as int32 bits [Nimg]; w3 [Cout3, Cout] with bias3: the back-to-back form, every output then has Cn = Cout3 columns.
+        Returns a dict: out [Nimg, Ho, Wo, Cn], out_h2, amax, gap [M / gap_group, Cn], gap_group."""
+        Nimg, H, W, Cin = x.shape
+        Ho = (H + 2 * pad - KH) // stride + 1
+        Wo = (W + 2 * pad - KW) // stride + 1
+        M = Nimg * Ho * Wo
+        Cn = w3.shape[0] if w3 is not None else Cout
+        wide = Cout % 256 == 0
+        group = 4 if wide or (Ho * Wo) % 16 else 16
+        if out is True:
+            out = torch.empty((Nimg, Ho, Wo, Cn), dtype=torch.float32, device=self.device)
+        elif out is False:
+            out = None
+        if gap is True:
+            gap = torch.empty((M // group, Cn), dtype=torch.float32, device=self.device)
+        elif gap is False:
+            gap = None
+        planes = torch.empty((M, 2 * Cn), dtype=torch.int16, device=self.device) if out_h2 else None
+        mx = torch.empty(Nimg, dtype=torch.int32, device=self.device) if amax else None
+        for t, shape in ((out, (Nimg, Ho, Wo, Cn)), (gap, (M // group, Cn)), (residual, (Nimg, Ho, Wo, Cn)), (residual_h2, (M, 2 * Cn)),
+                         (img_out_scale, (Nimg,)), (img_res_inv, (Nimg,)), (bias, (Cout,)), (bias3, (Cn,)), (w3, (Cn, Cout)),
+                         (w_packed, (Cout, KH * KW * Cin))):
+            if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"op_conv2d_nhwc_ex: an operand of shape {tuple(t.shape)} where contiguous {shape} on {self.device} is expected")
+        rc = self.lib.relax_op_conv2d_nhwc_ex(self.h, _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(residual), _ptr(residual_h2),
+                                              _ptr(img_res_inv), _ptr(out), _ptr(planes), _ptr(img_out_scale), _ptr(mx), _ptr(gap),
+                                              gap_rows, out_rows, int(bool(no_split)), _ptr(w3), _ptr(bias3), Cn if w3 is not None else 0,
+                                              Nimg, H, W, Cin, Cout, KH, KW, stride, pad, act, _stream())
+        self._check(rc, "relax_op_conv2d_nhwc_ex")
+        return {"out": out, "out_h2": planes, "amax": mx, "gap": gap, "gap_group": group}
+
     def op_layernorm(self, x, g, b, eps):
         rows, dim = x.shape
         y = torch.empty_like(x)
@@ -727,9 +764,16 @@ class RelaxEngine:
                     "relax_op_attention")
         return out
 
-    def op_bn_relu_maxpool(self, x, scale, shift):
+    def op_bn_relu_maxpool(self, x, scale, shift, amax_out=None):
+        """amax_out: an int32 [Nimg] tensor that receives the bits of each image's largest output (relax_op_bn_relu_maxpool_amax)."""
         Nimg, H, W, Cc = x.shape
         y = torch.empty((Nimg, H // 2, W // 2, Cc), dtype=torch.float32, device=self.device)
+        if amax_out is not None:
+            if tuple(amax_out.shape) != (Nimg,) or amax_out.dtype != torch.int32 or amax_out.device != self.device:
+                raise ValueError("op_bn_relu_maxpool: amax_out must be int32 [Nimg] on the engine's device")
+            self._check(self.lib.relax_op_bn_relu_maxpool_amax(self.h, _ptr(x), _ptr(scale), _ptr(shift), _ptr(y), _ptr(amax_out), Nimg,
+                                                           H, W, Cc, _stream()), "relax_op_bn_relu_maxpool_amax")
+            return y
         self._check(self.lib.relax_op_bn_relu_maxpool(self.h, _ptr(x), _ptr(scale), _ptr(shift), _ptr(y), Nimg, H, W,
                                                       Cc, _stream()), "relax_op_bn_relu_maxpool")
         return y
