@@ -206,6 +206,19 @@ int relax_flow_to_rgb(relax_handle* h, const float* flow, int T, int H, int W, u
 int relax_resize_frames(relax_handle* h, const uint8_t* frames, int64_t item_stride, int N, int H, int W,
                         uint8_t* out_bilinear, uint8_t* out_lanczos, relax_stream stream);
 
+/* The same resize of the frame difference of T pairs: the whole residual image of src/main_residual.py:223-231
+ * (cv2.absdiff(img_next, img_original), resized by the extractors: src/extractor/visualise_resnet_layer.py:39-43 BILINEAR,
+ * src/extractor/visualise_vit_layer.py:466-469 LANCZOS).  orig / next / pair_stride as in relax_fragment_pairs.
+ *   out_bilinear, out_lanczos : uint8 [T,224,224,3], what relax_resize_frames returns for the image |next - orig|
+ *   residual                  : uint8 [T,H,W,3] contiguous, the difference image itself (the reference's _residual.png)
+ * Any of the three may be NULL, not all.  The difference is taken while the rows are staged on the chip: a pair is read
+ * once, and the residual image is written only when asked for.
+ * `residual` must not overlap `orig` or `next` (the kernel treats the three as distinct memory).
+ * Rows move 16 bytes per lane only when W*3, pair_stride and all of orig, next and a non-NULL residual are multiples of
+ * 16; any one of them off (an odd residual pointer alone included) puts the whole call on the much slower bytewise path. */
+int relax_resize_residual(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
+                          uint8_t* out_bilinear, uint8_t* out_lanczos, uint8_t* residual, relax_stream stream);
+
 /* ---- stage B: backbones ---------------------------------------------------------------------- */
 /* ResNet-50 on N fragments (uint8 [N,224,224,3] BGR).  One forward per image yields everything
  * the reference gets from 15 hooked forwards + 1 avgpool forward:

@@ -221,15 +221,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_topn(const uint32_t* __res
 }
 
 // ---- fragment gather --------------------------------------------------------------------------------
-__device__ inline uint32_t absdiff_u8x4(uint32_t a, uint32_t b) {
-    uint32_t r = 0;
-#pragma unroll
-    for (int s = 0; s < 32; s += 8) {
-        const int x = (a >> s) & 255, y = (b >> s) & 255;
-        r |= (uint32_t)(x > y ? x - y : y - x) << s;
-    }
-    return r;
-}
+// (absdiff_u8x4: relax_internal.h, shared with the pair resize)
 
 // MODE 0: copy patches of `a`; MODE 1: |b - a| patches.  One work item = one 16-byte chunk of a patch row.
 template <int MODE, bool ALIGNED>

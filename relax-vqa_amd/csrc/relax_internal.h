@@ -40,6 +40,17 @@ void set_error(relax_handle* h, const char* fmt, ...);
         if (rc_ != RELAX_OK) return rc_;                                                     \
     } while (0)
 
+// ---- byte-wise |a - b| of four packed uint8 (cv2.absdiff): the fragment gather and the pair resize ------
+__device__ inline uint32_t absdiff_u8x4(uint32_t a, uint32_t b) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int s = 0; s < 32; s += 8) {
+        const int x = (a >> s) & 255, y = (b >> s) & 255;
+        r |= (uint32_t)(x > y ? x - y : y - x) << s;
+    }
+    return r;
+}
+
 // ---- device buffers -------------------------------------------------------------------------
 struct DevBuf {
     void* p = nullptr;

@@ -16,6 +16,9 @@ Array-in / array-out counterparts of the reference's path-based functions:
   vit_attention       <- get_last_selfattention + visualize_attention (src/extractor/visualise_vit.py:241-250,353-369)
   attention_overlay   <- map_attention_to_original (src/demo_visual.py:12-25)
   attention_overlays  <- the __main__ of src/demo_visual.py (:86-128) for a whole clip
+  residual_resize     <- cv2.absdiff + the extractors' resize of the whole residual image (src/main_residual.py:223-231)
+  whole_residual_*    <- the per-pair loop body of src/main_residual.py:221-254 (fragment-free ablation rows)
+  whole_frame_pool_features <- the per-frame loop body of src/main_layer.py:189-196
   extract_clip        <- the per-video loop body of src/main_fragment_layerstack.py:293-344 plus the ViT
                          branch of src/demo_test.py:137-161 (config 3 of BASELINE.json)
 """
@@ -359,6 +362,31 @@ class RelaxEngine:
                     "relax_resize_frames")
         return ob, ol
 
+    def residual_resize(self, frames, bilinear=True, lanczos=True, want_residual=False, out_bilinear=None, out_lanczos=None):
+        """frames uint8 [T,2,H,W,3] as fragment_pairs takes them -> (bilinear, lanczos, residual): the two uint8 [T,224,224,3]
+        resizes of the WHOLE frame difference cv2.absdiff(next, orig) (src/main_residual.py:223-231), bit-identical to
+        resize_frames on that image, and the uint8 [T,H,W,3] difference image itself; None for any output not requested.
+        One launch reads each pair once (relax_resize_residual); without want_residual the difference never reaches memory."""
+        frames = self._dev_u8(frames)
+        if frames.dim() != 5 or frames.shape[1] != 2 or frames.shape[4] != 3:
+            raise ValueError(f"frames must be [T,2,H,W,3], got {tuple(frames.shape)}")
+        T, _, H, W, _ = frames.shape
+        dev = self.device
+        ob = (out_bilinear if out_bilinear is not None else
+              torch.empty((T, TARGET, TARGET, 3), dtype=torch.uint8, device=dev)) if bilinear else None
+        ol = (out_lanczos if out_lanczos is not None else
+              torch.empty((T, TARGET, TARGET, 3), dtype=torch.uint8, device=dev)) if lanczos else None
+        for o in (ob, ol):
+            if o is not None and (o.dtype != torch.uint8 or tuple(o.shape) != (T, TARGET, TARGET, 3) or not o.is_contiguous()):
+                raise ValueError("residual_resize: output buffers must be contiguous uint8 [T,224,224,3]")
+        res = torch.empty((T, H, W, 3), dtype=torch.uint8, device=dev) if want_residual else None
+        fb = H * W * 3
+        base = frames.data_ptr()
+        rc = self.lib.relax_resize_residual(self.h, C.c_void_p(base), C.c_void_p(base + fb), 2 * fb, T, H, W, _ptr(ob), _ptr(ol),
+                                            _ptr(res), _stream())
+        self._check(rc, "relax_resize_residual")
+        return ob, ol, res
+
     # ---- stage B ------------------------------------------------------------------------------
     def _frags(self, frags):
         frags = self._dev_u8(frags)
@@ -618,6 +646,90 @@ class RelaxEngine:
         ls, _ = self.resnet50_features(bil, layer_stack=True, pool=False)
         _, vp = self.vit_features(lan, tokens=False, pooled=True)
         return ls, vp
+
+    # ---- fragment-free ablation rows (src/main_residual.py, src/main_layer.py) ---------------------------------
+    RESIDUAL_NAMES = ("frame_diff", "optical_flow")
+
+    def _whole_residual_inputs(self, frames, residual_name, bilinear, lanczos, flow_images=None, out_bilinear=None, out_lanczos=None):
+        """The two backbone inputs of one clip's whole residual images: the frame difference through the fused
+        difference + resize, the flow image (given, or Farneback on the GPU) through resize_frames."""
+        if residual_name == "frame_diff":
+            return self.residual_resize(frames, bilinear=bilinear, lanczos=lanczos, out_bilinear=out_bilinear,
+                                        out_lanczos=out_lanczos)[:2]
+        if flow_images is None:
+            _, flow_images = self.optical_flow(frames)
+        return self.resize_frames(flow_images, bilinear=bilinear, lanczos=lanczos, out_bilinear=out_bilinear, out_lanczos=out_lanczos)
+
+    def _check_residual_name(self, residual_name):
+        if residual_name not in self.RESIDUAL_NAMES:
+            raise ValueError(f"residual_name must be one of {self.RESIDUAL_NAMES}, got {residual_name!r}")
+
+    @staticmethod
+    def _check_backbones(resnet, vit, vgg16):
+        if not (resnet or vit or vgg16):
+            raise ValueError("no backbone requested")
+
+    def _pool_blocks(self, bil, lan, resnet, vit, vgg16):
+        """-> [(name, per-image pool rows)] in the column order resnet | vit | vgg16 of those requested."""
+        blocks = []
+        if resnet:
+            blocks.append(("resnet", self.resnet50_features(bil, layer_stack=False, pool=True)[1]))
+        if vit:
+            blocks.append(("vit", self.vit_features(lan, tokens=False, pooled=True)[1]))
+        if vgg16:
+            blocks.append(("vgg16", self.vgg16_features(bil, layer_stack=False, pool=True)[1]))
+        return blocks
+
+    def whole_residual_features(self, frames, residual_name="frame_diff", resnet=True, vit=True, vgg16=False, flow_images=None):
+        """frames uint8 [T,2,H,W,3] -> dict of per-frame fp32 device tensors, the rows src/main_residual.py:221-254 saves per
+        video: the WHOLE residual image (residual_name 'frame_diff': cv2.absdiff(next, orig); 'optical_flow': the flow image,
+        flow_images uint8 [T,H,W,3] or Farneback on the GPU) resized to 224 x 224 and pooled:
+          'resnet' [T,2051] avgpool | mean, max, std      'vgg16' [T,4099] fc2 | mean, max, std      (BILINEAR bytes)
+          'vit'    [T,3*dim] token mean | max | std                                                  (LANCZOS bytes)"""
+        self._check_residual_name(residual_name)
+        self._check_backbones(resnet, vit, vgg16)
+        bil, lan = self._whole_residual_inputs(frames, residual_name, resnet or vgg16, vit, flow_images)
+        return dict(self._pool_blocks(bil, lan, resnet, vit, vgg16))
+
+    def whole_residual_vectors(self, clips, residual_name="frame_diff", resnet=True, vit=True, vgg16=False, flow_images=None,
+                               per_frame=False):
+        """Several clips (list of uint8 [T_i,2,H_i,W_i,3], any mix of resolutions; flow_images: optional list of uint8
+        [T_i,H_i,W_i,3]) in ONE batched pass per backbone -> fp32 [len(clips), F] per-clip means of the whole_residual_features
+        rows, columns resnet | vit | vgg16 of those requested.  per_frame=True as in clip_vectors."""
+        self._check_residual_name(residual_name)
+        self._check_backbones(resnet, vit, vgg16)
+        counts = [int(c.shape[0]) for c in clips]
+        n = sum(counts)
+        bil = torch.empty((n, TARGET, TARGET, 3), dtype=torch.uint8, device=self.device) if resnet or vgg16 else None
+        lan = torch.empty((n, TARGET, TARGET, 3), dtype=torch.uint8, device=self.device) if vit else None
+        at = 0
+        for i, (c, t) in enumerate(zip(clips, counts)):
+            self._whole_residual_inputs(c, residual_name, bil is not None, lan is not None,
+                                        None if flow_images is None else flow_images[i],
+                                        None if bil is None else bil[at:at + t], None if lan is None else lan[at:at + t])
+            at += t
+        blocks, col = [], 0
+        for _, rows in self._pool_blocks(bil, lan, resnet, vit, vgg16):
+            blocks.append((rows, 0, col))
+            col += rows.shape[1]
+        out = torch.empty((len(clips), col), dtype=torch.float32, device=self.device)
+        self._segment_means(out, blocks, counts)
+        if not per_frame:
+            return out
+        return out, self._per_frame_rows(blocks, counts)
+
+    def whole_frame_pool_features(self, frames, resnet=True, vit=True, vgg16=False):
+        """frames uint8 [N,H,W,3] BGR (whole sampled frames) -> dict of per-frame fp32 device tensors, the rows of
+        src/main_layer.py:189-196: 'resnet' [N,2048] the avgpool vector WITHOUT the three statistics (:135-137), 'vgg16'
+        [N,4096] fc2, 'vit' [N,3*dim] token mean | max | std - views of the backbones' pool outputs."""
+        self._check_backbones(resnet, vit, vgg16)
+        bil, lan = self.resize_frames(frames, bilinear=resnet or vgg16, lanczos=vit)
+        out = dict(self._pool_blocks(bil, lan, resnet, vit, vgg16))
+        if resnet:
+            out["resnet"] = out["resnet"][:, :RN50_POOL_DIM - 3]
+        if vgg16:
+            out["vgg16"] = out["vgg16"][:, :VGG16_POOL_DIM - 3]
+        return out
 
     def full_clip_vector(self, frames, flow_images=None, flow=False, whole_frames=None):
         """frames uint8 [T,2,H,W,3] -> fp32 [35203]: the vector src/demo_test.py:171-175 assembles
