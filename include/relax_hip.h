@@ -294,11 +294,11 @@ int relax_head_train_transform(relax_handle* h, const float* x, int n, int F, co
                                float* xp, relax_stream stream);
 /* Allocates the training state of an Mlp(input_features, hidden_features) (model_regression.py:37-58; hidden_features a multiple of
  * 128): three parameter sets with their BatchNorm buffers - 0 the live model with its SGD momentum buffers, 1 the SWA average
- * (AveragedModel, :388), 2 a snapshot (copy.deepcopy(model), :445) - all zero until relax_head_train_import, and the workspace
+ * (AveragedModel, :388), 2 a snapshot (copy.deepcopy(model), :445) - all zero until relax_head_train_import, Adam's second-moment block, and the workspace
  * of batches of up to max_batch rows (2..1024).  Waits for the device. */
 int relax_head_train_init(relax_handle* h, int input_features, int hidden_features, int max_batch);
 /* Loads a state dict (the keys relax_load_mlp_head takes; HOST pointers) into a set: the initial model, or the checkpoint
- * fine_tune.py:130-136 starts from.  Into set 0 it also zeroes the momentum buffers (a new optimizer).  Waits for the device. */
+ * fine_tune.py:130-136 starts from.  Into set 0 it also zeroes the momentum buffers, Adam's second moments and its step count (a new optimizer).  Waits for the device. */
 int relax_head_train_import(relax_handle* h, int set, const float* const* tensors, const char* const* names, const int64_t* numels, int n,
                             int64_t num_batches_tracked, int64_t n_averaged);
 /* Floats of a set as relax_head_train_export writes them (-1 without a state). */
@@ -345,6 +345,31 @@ int relax_head_train_pad_abs_sum(relax_handle* h, double* out, relax_stream stre
  * fused != 0 the step's own kernel (dW1 = dz1^T X_b with the SGD update in its epilogue); fused == 0 the same tiles writing dW1 to
  * memory, then a separate update pass.  Both change fc1.weight and its momentum. */
 int relax_head_train_dw1(relax_handle* h, int fused, int B, float lr, float momentum, float weight_decay, relax_stream stream);
+/* The same iteration under optim.Adam (src/model_regression.py:381-386, src/model_regression_simple.py:377-382; decoupled == 0:
+ * g = grad + weight_decay w) or optim.AdamW (src/fine_tune.py:151-155; decoupled != 0: w *= 1 - lr weight_decay, g = grad), torch's
+ * single-tensor arithmetic without amsgrad: m = beta1 m + (1 - beta1) g, v = beta2 v + (1 - beta2) g g,
+ * w -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).  The live set keeps exp_avg where SGD keeps its momentum buffers,
+ * exp_avg_sq in a second block, and ONE step count t on the host (torch's per-parameter `step` values are all equal): this call
+ * increments it and computes the two bias corrections from it in double, so nothing waits for the device.  The optimizer's scalars are
+ * doubles, as torch holds them.  Everything else as relax_head_train_step, whose launches it shares.  Do not alternate the two step
+ * entries on one state without an import in between: they read the first block differently. */
+int relax_head_train_step_adam(relax_handle* h, const float* xp, const float* target, int n, const int32_t* index, int B, double lr,
+                               double beta1, double beta2, double eps, double weight_decay, int decoupled, float l1_w, float rank_w,
+                               float drop_rate, uint64_t seed, uint64_t step, uint8_t* mask1, uint8_t* mask2, relax_stream stream);
+/* optimizer.state_dict()['state'] of the Adam / AdamW above: which = 0 exp_avg, 1 exp_avg_sq of every parameter, HOST fp32 in the
+ * flat order of relax_head_train_export (zeros under the two buffer keys); *t_out = the step count.  Waits for `stream`. */
+int relax_head_train_export_optimizer(relax_handle* h, int which, float* out, int64_t* t_out, relax_stream stream);
+/* optimizer.load_state_dict(): both moments of every parameter (HOST pointers under the parameters' state-dict keys, marshalled as
+ * for relax_head_train_import: exp_avg[i] and exp_avg_sq[i] belong to names[i]) and the step count, to resume a run.
+ * relax_head_train_import into set 0 resets all three (a new optimizer), so call this after it.  Waits for the device. */
+int relax_head_train_import_optimizer(relax_handle* h, const float* const* exp_avg, const float* const* exp_avg_sq, const char* const* names,
+                                      const int64_t* numels, int n, int64_t t);
+/* relax_head_train_pad_abs_sum with exp_avg_sq as a third sum: out[3] HOST = sum | . [:, F:Fpad]| of fc1.weight, exp_avg, exp_avg_sq. */
+int relax_head_train_pad_abs_sum_adam(relax_handle* h, double* out, relax_stream stream);
+/* relax_head_train_dw1 under Adam / AdamW (a measurement, tools/head_train_bench.py): fused != 0 the Adam step's own kernel, fused == 0
+ * the same tiles writing dW1, then a separate update pass.  Both change fc1.weight and both moments; the step count stays. */
+int relax_head_train_dw1_adam(relax_handle* h, int fused, int B, double lr, double beta1, double beta2, double eps, double weight_decay,
+                              int decoupled, relax_stream stream);
 
 /* ---- correlation metrics of a head's predictions (csrc/metrics.hip, csrc/metrics_core.h) ----- */
 /* compute_correlation_metrics (src/model_regression.py:149-161) with fit_logistic_regression / logistic_func (:138-147) on the

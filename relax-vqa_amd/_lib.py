@@ -61,6 +61,13 @@ PROTOTYPES = {
     "relax_head_train_loss_read": (C.c_int, [c_vp, C.c_int, C.c_int, c_vp, c_vp]),
     "relax_head_train_pad_abs_sum": (C.c_int, [c_vp, c_vp, c_vp]),
     "relax_head_train_dw1": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, c_vp]),
+    "relax_head_train_step_adam": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_vp, C.c_int] + [C.c_double] * 5 + [C.c_int] + [C.c_float] * 3 +
+                                             [C.c_uint64, C.c_uint64, c_vp, c_vp, c_vp]),
+    "relax_head_train_export_optimizer": (C.c_int, [c_vp, C.c_int, c_vp, c_vp, c_vp]),
+    "relax_head_train_import_optimizer": (C.c_int, [c_vp, C.POINTER(c_vp), C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
+                                                    C.c_int, C.c_int64]),
+    "relax_head_train_pad_abs_sum_adam": (C.c_int, [c_vp, c_vp, c_vp]),
+    "relax_head_train_dw1_adam": (C.c_int, [c_vp, C.c_int, C.c_int] + [C.c_double] * 5 + [C.c_int, c_vp]),
     "relax_metrics_correlation": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
     "relax_metrics_kendall": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp]),
     "relax_metrics_pair_counts": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp]),

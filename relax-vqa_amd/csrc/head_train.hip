@@ -1,10 +1,11 @@
-// Training of the quality head on the device: scaler fit, one SGD step of the reference's Mlp under its
-// MAE + rank criterion, evaluation, the SWA average, the BatchNorm refresh, import / export.
+// Training of the quality head on the device: scaler fit, one SGD or Adam / AdamW step of the reference's Mlp
+// under its MAE + rank criterion, evaluation, the SWA average, the BatchNorm refresh, import / export.
 //   src/model_regression.py:122-135  preprocess_data: NaN / inf -> 0, SimpleImputer(mean).fit, MinMaxScaler.fit / transform
 //   src/model_regression.py:37-58    Mlp (train mode: BatchNorm1d on batch statistics, dropout)
 //   src/model_regression.py:69-89    MAEAndRankLoss.forward (use_margin off)
 //   src/model_regression.py:292-322  train_one_epoch / evaluate
-//   src/model_regression.py:381-389  optim.SGD(momentum=0.9), AveragedModel;  :459 torch.optim.swa_utils.update_bn
+//   src/model_regression.py:381-389  optim.SGD(momentum=0.9) | optim.Adam, AveragedModel;  :459 torch.optim.swa_utils.update_bn
+//   src/fine_tune.py:151-155         optim.AdamW
 // Everything of a step is enqueued on the caller's stream; nothing here waits for the device except the entries that
 // say so (init, import, export, loss_read).  All arithmetic is fp32 with fp32 accumulation (fc1 / fc2 forward on the
 // exact-fp32 contraction of gemm.hip whatever "gemm_precision" is set: ht_gemm).
@@ -352,12 +353,58 @@ __device__ inline void ht_sgd(float& w, float& m, float grad, const HtSgd o) {  
     w = fmaf(-o.lr, m, w);
 }
 
+// torch's Adam (wd: g = grad + wd w) or AdamW (decay = 1 - lr wd: w *= decay, then g = grad) for step t.  The bias corrections come
+// from the host, in double from t: step_size = lr / (1 - b1^t), inv_sqrt_bc2 = 1 / sqrt(1 - b2^t).  The form not in use is inert:
+// decay = 1 under Adam and wd = 0 under AdamW are both exact.
+struct HtAdam {
+    float b1, omb1, b2, omb2, eps, wd, decay, step_size, inv_sqrt_bc2;   // omb = 1 - b, rounded once from the double
+};
+
+__device__ inline void ht_adam(float& w, float& m, float& v, float grad, const HtAdam o) {
+    w *= o.decay;
+    const float g = fmaf(o.wd, w, grad);
+    m = fmaf(o.b1, m, o.omb1 * g);
+    v = fmaf(o.b2, v, o.omb2 * g * g);
+    w = fmaf(-o.step_size, m / fmaf(sqrtf(v), o.inv_sqrt_bc2, o.eps), w);   // g = 0 on m = v = 0 (the K padding): 0 / eps = 0
+}
+
+// Parameter i (or the float4 of them at i) under either optimizer: `m` is the momentum buffer / exp_avg, `v` exp_avg_sq, which SGD
+// never touches (it may be null there)
+__device__ inline void ht_update(float* w, float* m, float*, int64_t i, float grad, const HtSgd o) { ht_sgd(w[i], m[i], grad, o); }
+__device__ inline void ht_update(float* w, float* m, float* v, int64_t i, float grad, const HtAdam o) { ht_adam(w[i], m[i], v[i], grad, o); }
+
+__device__ inline void ht_update4(float* w1, float* m1, float*, int64_t i, const float4 g, const HtSgd o) {
+    float4 *wp = reinterpret_cast<float4*>(w1 + i), *mp = reinterpret_cast<float4*>(m1 + i);
+    float4 w = *wp, m = *mp;
+    ht_sgd(w.x, m.x, g.x, o);
+    ht_sgd(w.y, m.y, g.y, o);
+    ht_sgd(w.z, m.z, g.z, o);
+    ht_sgd(w.w, m.w, g.w, o);
+    *wp = w;
+    *mp = m;
+}
+
+__device__ inline void ht_update4(float* w1, float* m1, float* v1, int64_t i, const float4 g, const HtAdam o) {
+    float4 *wp = reinterpret_cast<float4*>(w1 + i), *mp = reinterpret_cast<float4*>(m1 + i), *vp = reinterpret_cast<float4*>(v1 + i);
+    float4 w = *wp, m = *mp, v = *vp;
+    ht_adam(w.x, m.x, v.x, g.x, o);
+    ht_adam(w.y, m.y, v.y, g.y, o);
+    ht_adam(w.z, m.z, v.z, g.z, o);
+    ht_adam(w.w, m.w, v.w, g.w, o);
+    *wp = w;
+    *mp = m;
+    *vp = v;
+}
+
 // BatchNorm backward, one block per column: dgamma, dbeta, dz1 = gamma invstd (du1 - mean(du1) - xhat mean(du1 xhat)), db1 = sum dz1
-// (zero but for rounding: a bias in front of a BatchNorm has no gradient), and the SGD update of gamma, beta, fc1.bias
+// (zero but for rounding: a bias in front of a BatchNorm has no gradient), and the optimizer's update of gamma, beta, fc1.bias
+// (m_*: momentum buffer / exp_avg, v_*: exp_avg_sq, null under SGD)
+template <class Opt>
 __global__ __launch_bounds__(256) void ht_bn_bwd(const float* __restrict__ du1, const float* __restrict__ xhat, const float* __restrict__ invstd,
                                                  int B, int H1, float* __restrict__ gamma, float* __restrict__ beta, float* __restrict__ b1,
                                                  float* __restrict__ m_gamma, float* __restrict__ m_beta, float* __restrict__ m_b1,
-                                                 HtSgd sgd, float* __restrict__ dz1) {
+                                                 float* __restrict__ v_gamma, float* __restrict__ v_beta, float* __restrict__ v_b1,
+                                                 Opt opt, float* __restrict__ dz1) {
     __shared__ float sh[256];
     const int j = blockIdx.x;
     float s = 0.f, sx = 0.f;
@@ -379,20 +426,18 @@ __global__ __launch_bounds__(256) void ht_bn_bwd(const float* __restrict__ du1, 
     }
     const float db1 = ht_block_sum(sz, sh);   // (also the barrier between every thread's read of gamma[j] and its update)
     if (threadIdx.x == 0) {
-        float w = gamma[j], m = m_gamma[j];
-        ht_sgd(w, m, dgamma, sgd); gamma[j] = w; m_gamma[j] = m;
-        w = beta[j]; m = m_beta[j];
-        ht_sgd(w, m, dbeta, sgd); beta[j] = w; m_beta[j] = m;
-        w = b1[j]; m = m_b1[j];
-        ht_sgd(w, m, db1, sgd); b1[j] = w; m_b1[j] = m;
+        ht_update(gamma, m_gamma, v_gamma, j, dgamma, opt);
+        ht_update(beta, m_beta, v_beta, j, dbeta, opt);
+        ht_update(b1, m_b1, v_b1, j, db1, opt);
     }
 }
 
-// fc2.weight (dW2 = dz2^T a1), fc2.bias, fc3.weight, fc3.bias: gradient and SGD update, one thread per parameter.  These four
-// tensors are contiguous in the set (W2 | b2 | w3 | b3), `par` / `mom` point at W2.
+// fc2.weight (dW2 = dz2^T a1), fc2.bias, fc3.weight, fc3.bias: gradient and the optimizer's update, one thread per parameter.  These
+// four tensors are contiguous in the set (W2 | b2 | w3 | b3), `par` / `mom` / `var` point at W2.
+template <class Opt>
 __global__ __launch_bounds__(256) void ht_update_small(const float* __restrict__ dz2, const float* __restrict__ a1, const float* __restrict__ a2,
                                                        const float* __restrict__ dp, int B, int H1, int H2, float* __restrict__ par,
-                                                       float* __restrict__ mom, HtSgd sgd) {
+                                                       float* __restrict__ mom, float* __restrict__ var, Opt opt) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int nw2 = H2 * H1;
     if (i >= nw2 + 2 * H2 + 1) return;
@@ -409,23 +454,21 @@ __global__ __launch_bounds__(256) void ht_update_small(const float* __restrict__
     } else {
         for (int b = 0; b < B; ++b) g += dp[b];
     }
-    float w = par[i], m = mom[i];
-    ht_sgd(w, m, g, sgd);
-    par[i] = w;
-    mom[i] = m;
+    ht_update(par, mom, var, i, g, opt);
 }
 
-// The hot kernel: dW1 = dz1^T X_b ([H1][Fpad], contracted over the B rows of the batch) with the SGD update in its epilogue -
-// the gradient of fc1.weight is never written; a tile of W1 and of its momentum is read and written once.
+// The hot kernel: dW1 = dz1^T X_b ([H1][Fpad], contracted over the B rows of the batch) with the optimizer's update in its epilogue -
+// the gradient of fc1.weight is never written; a tile of W1 and of its momentum (Adam: of both moments) is read and written once.
 // 64 (j) x 128 (f) tile per workgroup of 256 threads, 4 x 8 accumulators per thread in fp32, 16 batch rows per LDS stage.
 // Both operands have the contraction index as their slow one (dz1 [B][H1], X_b [B][Fpad]), so a stage is plain 16-byte
-// row loads.  Columns f >= F are zero in X_b and in W1, and stay exactly zero (g = 0 + wd * 0).
+// row loads.  Columns f >= F are zero in X_b and in W1, and stay exactly zero (SGD: g = 0 + wd * 0; Adam: 0 / (0 + eps)).
 constexpr int kDwTJ = 64, kDwTF = 128, kDwKB = 16;
 
-// kFused = false (tools/head_train_bench.py only): the same tiles write dW1 to `grad` and ht_sgd_apply updates in a second pass.
-template <bool kFused>
-__global__ __launch_bounds__(256) void ht_dw1_sgd(const float* __restrict__ dz1, const float* __restrict__ xb, int B, int H1, int Fpad,
-                                                  float* __restrict__ w1, float* __restrict__ m1, HtSgd sgd, float* __restrict__ grad) {
+// kFused = false (tools/head_train_bench.py only): the same tiles write dW1 to `grad` and ht_apply updates in a second pass.
+template <bool kFused, class Opt>
+__device__ __forceinline__ void ht_dw1(const float* __restrict__ dz1, const float* __restrict__ xb, int B, int H1, int Fpad,
+                                       float* __restrict__ w1, float* __restrict__ m1, float* __restrict__ v1, Opt opt,
+                                       float* __restrict__ grad) {
     __shared__ float4 As[kDwKB][kDwTJ / 4];
     __shared__ float4 Xs[kDwKB][kDwTF / 4];
     const int tid = threadIdx.x;
@@ -471,37 +514,48 @@ __global__ __launch_bounds__(256) void ht_dw1_sgd(const float* __restrict__ dz1,
         for (int half = 0; half < 2; ++half) {
             const int f = f0 + half * 64 + tx * 4;
             if (f >= Fpad) continue;
+            const float4 g = make_float4(acc[r][half * 4 + 0], acc[r][half * 4 + 1], acc[r][half * 4 + 2], acc[r][half * 4 + 3]);
+            const int64_t o = (int64_t)j * Fpad + f;
             if (!kFused) {
-                *reinterpret_cast<float4*>(grad + (int64_t)j * Fpad + f) =
-                    make_float4(acc[r][half * 4 + 0], acc[r][half * 4 + 1], acc[r][half * 4 + 2], acc[r][half * 4 + 3]);
+                *reinterpret_cast<float4*>(grad + o) = g;
                 continue;
             }
-            float4* wp = reinterpret_cast<float4*>(w1 + (int64_t)j * Fpad + f);
-            float4* mp = reinterpret_cast<float4*>(m1 + (int64_t)j * Fpad + f);
-            float4 w = *wp, m = *mp;
-            ht_sgd(w.x, m.x, acc[r][half * 4 + 0], sgd);
-            ht_sgd(w.y, m.y, acc[r][half * 4 + 1], sgd);
-            ht_sgd(w.z, m.z, acc[r][half * 4 + 2], sgd);
-            ht_sgd(w.w, m.w, acc[r][half * 4 + 3], sgd);
-            *wp = w;
-            *mp = m;
+            ht_update4(w1, m1, v1, o, g, opt);
         }
     }
 }
 
-// the separate update of the unfused form: one float4 of W1, momentum and gradient per thread
-__global__ __launch_bounds__(256) void ht_sgd_apply(const float* __restrict__ grad, float* __restrict__ w, float* __restrict__ m, int64_t n4,
-                                                    HtSgd sgd) {
+template <bool kFused>
+__global__ __launch_bounds__(256) void ht_dw1_sgd(const float* __restrict__ dz1, const float* __restrict__ xb, int B, int H1, int Fpad,
+                                                  float* __restrict__ w1, float* __restrict__ m1, HtSgd sgd, float* __restrict__ grad) {
+    ht_dw1<kFused>(dz1, xb, B, H1, Fpad, w1, m1, (float*)nullptr, sgd, grad);
+}
+
+// the Adam form: 252 MB per step at F = 35203, H1 = B = 256 (X_b once, W1 and both moments read and written) against SGD's 180 MB
+template <bool kFused>
+__global__ __launch_bounds__(256) void ht_dw1_adam(const float* __restrict__ dz1, const float* __restrict__ xb, int B, int H1, int Fpad,
+                                                   float* __restrict__ w1, float* __restrict__ m1, float* __restrict__ v1, HtAdam adam,
+                                                   float* __restrict__ grad) {
+    ht_dw1<kFused>(dz1, xb, B, H1, Fpad, w1, m1, v1, adam, grad);
+}
+
+// the separate update of the unfused form (ht_sgd_apply, ht_adam_apply): one float4 of W1, its optimizer state and the gradient per thread
+template <class Opt>
+__device__ __forceinline__ void ht_apply(const float* __restrict__ grad, float* __restrict__ w, float* __restrict__ m,
+                                         float* __restrict__ v, int64_t n4, Opt opt) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
-    const float4 g = reinterpret_cast<const float4*>(grad)[i];
-    float4 wv = reinterpret_cast<float4*>(w)[i], mv = reinterpret_cast<float4*>(m)[i];
-    ht_sgd(wv.x, mv.x, g.x, sgd);
-    ht_sgd(wv.y, mv.y, g.y, sgd);
-    ht_sgd(wv.z, mv.z, g.z, sgd);
-    ht_sgd(wv.w, mv.w, g.w, sgd);
-    reinterpret_cast<float4*>(w)[i] = wv;
-    reinterpret_cast<float4*>(m)[i] = mv;
+    ht_update4(w, m, v, 4 * i, reinterpret_cast<const float4*>(grad)[i], opt);
+}
+
+__global__ __launch_bounds__(256) void ht_sgd_apply(const float* __restrict__ grad, float* __restrict__ w, float* __restrict__ m, int64_t n4,
+                                                    HtSgd sgd) {
+    ht_apply(grad, w, m, (float*)nullptr, n4, sgd);
+}
+
+__global__ __launch_bounds__(256) void ht_adam_apply(const float* __restrict__ grad, float* __restrict__ w, float* __restrict__ m,
+                                                     float* __restrict__ v, int64_t n4, HtAdam adam) {
+    ht_apply(grad, w, m, v, n4, adam);
 }
 
 // ---- SWA ---------------------------------------------------------------------------------------------------------------
@@ -562,6 +616,96 @@ int ht_gemm(relax_handle* h, const float* A, const float* W, const float* bias, 
 }
 
 dim3 gather_grid(int B, int Fpad) { return dim3((unsigned)B, (unsigned)std::min(8, (Fpad / 4 + 255) / 256)); }
+
+// A block in a set's layout to HOST memory, in the order of the flat block below; `params_only`: the block is optimizer state, which has
+// the parameter part alone - zeros go under the two buffer keys
+int ht_export_block(relax_handle* h, const float* src, bool params_only, float* out) {
+    const HeadTrain& t = h->head_train;
+    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2);
+    float* o = out;
+    RELAX_HIP_CHECK(h, hipMemcpy2D(o, sizeof(float) * t.F, src + L.w1, sizeof(float) * t.Fpad, sizeof(float) * t.F, t.H1, hipMemcpyDeviceToHost));
+    o += (size_t)t.H1 * t.F;
+    auto put = [&](size_t off, size_t numel) -> hipError_t {
+        hipError_t e = hipSuccess;
+        if (params_only && off >= L.n_params) std::memset(o, 0, sizeof(float) * numel);
+        else e = hipMemcpy(o, src + off, sizeof(float) * numel, hipMemcpyDeviceToHost);
+        o += numel;
+        return e;
+    };
+    // order of the flat block: fc1.weight [H1,F], fc1.bias, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, fc2.weight, fc2.bias,
+    // fc3.weight, fc3.bias
+    RELAX_HIP_CHECK(h, put(L.b1, t.H1));
+    RELAX_HIP_CHECK(h, put(L.gamma, t.H1));
+    RELAX_HIP_CHECK(h, put(L.beta, t.H1));
+    RELAX_HIP_CHECK(h, put(L.rmean, t.H1));
+    RELAX_HIP_CHECK(h, put(L.rvar, t.H1));
+    RELAX_HIP_CHECK(h, put(L.w2, (size_t)t.H2 * t.H1));
+    RELAX_HIP_CHECK(h, put(L.b2, t.H2));
+    RELAX_HIP_CHECK(h, put(L.w3, t.H2));
+    RELAX_HIP_CHECK(h, put(L.b3, 1));
+    return RELAX_OK;
+}
+
+// Adam's constants for step t (>= 1), every one computed in double as torch computes its Python scalars and rounded once
+HtAdam make_adam(double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, int64_t t) {
+    HtAdam a{};
+    a.b1 = (float)beta1;
+    a.omb1 = (float)(1.0 - beta1);
+    a.b2 = (float)beta2;
+    a.omb2 = (float)(1.0 - beta2);
+    a.eps = (float)eps;
+    a.wd = decoupled ? 0.f : (float)weight_decay;
+    a.decay = decoupled ? (float)(1.0 - lr * weight_decay) : 1.f;
+    a.step_size = (float)(lr / (1.0 - std::pow(beta1, (double)t)));
+    a.inv_sqrt_bc2 = (float)(1.0 / std::sqrt(1.0 - std::pow(beta2, (double)t)));
+    return a;
+}
+
+void launch_dw1(const HeadTrain& t, const float* dz1, int B, float* P, const HtSgd sgd, hipStream_t s) {
+    hipLaunchKernelGGL(ht_dw1_sgd<true>, dim3((unsigned)(t.H1 / kDwTJ), (unsigned)((t.Fpad + kDwTF - 1) / kDwTF)), dim3(256), 0, s, dz1, t.xb,
+                       B, t.H1, t.Fpad, P, t.mom, sgd, (float*)nullptr);
+}
+
+void launch_dw1(const HeadTrain& t, const float* dz1, int B, float* P, const HtAdam adam, hipStream_t s) {
+    hipLaunchKernelGGL(ht_dw1_adam<true>, dim3((unsigned)(t.H1 / kDwTJ), (unsigned)((t.Fpad + kDwTF - 1) / kDwTF)), dim3(256), 0, s, dz1, t.xb,
+                       B, t.H1, t.Fpad, P, t.mom, t.var, adam, (float*)nullptr);
+}
+
+// One iteration of train_one_epoch on the live set under either optimizer: the launches of a step, enqueued on `s`
+template <class Opt>
+int ht_step(relax_handle* h, const float* xp, const float* target, int n, const int32_t* index, int B, Opt opt, float l1_w,
+            float rank_w, float drop_rate, uint64_t seed, uint64_t step, uint8_t* mask1, uint8_t* mask2, hipStream_t s) {
+    HeadTrain& t = h->head_train;
+    const int H1 = t.H1, H2 = t.H2, Fpad = t.Fpad;
+    const HtLayout L = ht_layout(Fpad, H1, H2);
+    const HtAct A = ht_act(t.max_batch, H1, H2);
+    float* P = t.set[0];
+    float* M = t.mom;
+    float* V = t.var;   // SGD's kernels take it and leave it alone
+    float* a = t.act;
+    const HtDrop drop = make_drop(drop_rate, seed, step);
+    const int64_t n1 = (int64_t)B * H1, n2 = (int64_t)B * H2;
+
+    hipLaunchKernelGGL(ht_gather, gather_grid(B, Fpad), dim3(256), 0, s, xp, target, index, n, Fpad, t.xb, a + A.yb, t.counters + 0);
+    RELAX_TRY(ht_gemm(h, t.xb, P + L.w1, P + L.b1, a + A.z1, B, H1, Fpad, 0, s));
+    hipLaunchKernelGGL(ht_bn_fwd, dim3((unsigned)H1), dim3(256), 0, s, a + A.z1, B, H1, P + L.gamma, P + L.beta, P + L.rmean, P + L.rvar,
+                       t.counters + 0, 0, a + A.xhat, a + A.invstd, a + A.a1, drop, mask1);
+    RELAX_TRY(ht_gemm(h, a + A.a1, P + L.w2, P + L.b2, a + A.z2, B, H2, H1, 0, s));
+    hipLaunchKernelGGL(ht_fwd_tail, dim3((unsigned)B), dim3(256), 0, s, a + A.z2, H2, P + L.w3, P + L.b3, 1, a + A.a2, a + A.p, drop, mask2);
+    hipLaunchKernelGGL(ht_criterion, dim3((unsigned)B), dim3(256), 0, s, a + A.p, a + A.yb, B, l1_w, rank_w, a + A.rowloss, a + A.dp);
+    hipLaunchKernelGGL(ht_loss_finish, dim3(1), dim3(256), 0, s, a + A.rowloss, B, t.loss, (float*)nullptr);
+    hipLaunchKernelGGL(ht_bwd_z2, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, a + A.dp, P + L.w3, a + A.z2, n2, H2, drop, a + A.dz2);
+    hipLaunchKernelGGL(ht_bwd_u1, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, a + A.dz2, P + L.w2, a + A.xhat, P + L.gamma, P + L.beta,
+                       n1, H1, H2, drop, a + A.du1);
+    hipLaunchKernelGGL(ht_bn_bwd<Opt>, dim3((unsigned)H1), dim3(256), 0, s, a + A.du1, a + A.xhat, a + A.invstd, B, H1, P + L.gamma, P + L.beta,
+                       P + L.b1, M + L.gamma, M + L.beta, M + L.b1, V + L.gamma, V + L.beta, V + L.b1, opt, a + A.dz1);
+    const int n_small = H2 * H1 + 2 * H2 + 1;
+    hipLaunchKernelGGL(ht_update_small<Opt>, dim3((unsigned)((n_small + 255) / 256)), dim3(256), 0, s, a + A.dz2, a + A.a1, a + A.a2, a + A.dp, B,
+                       H1, H2, P + L.w2, M + L.w2, V + L.w2, opt);
+    launch_dw1(t, a + A.dz1, B, P + L.w1, opt, s);   // L.w1 == 0 in the optimizer's blocks too
+    RELAX_HIP_CHECK(h, hipGetLastError());
+    return RELAX_OK;
+}
 
 }  // namespace
 
@@ -641,6 +785,7 @@ int relax_head_train_init(relax_handle* h, int input_features, int hidden_featur
     };
     for (int i = 0; i < HeadTrain::kSets; ++i) t.set[i] = static_cast<float*>(grab(sizeof(float) * L.n_all));
     t.mom = static_cast<float*>(grab(sizeof(float) * L.n_params));
+    t.var = static_cast<float*>(grab(sizeof(float) * L.n_params));
     t.counters = static_cast<int64_t*>(grab(sizeof(int64_t) * 2 * HeadTrain::kSets));
     t.loss = static_cast<double*>(grab(sizeof(double) * 6));
     t.act = static_cast<float*>(grab(sizeof(float) * ht_act(max_batch, t.H1, t.H2).total));
@@ -696,7 +841,11 @@ int relax_head_train_import(relax_handle* h, int set, const float* const* tensor
     }
     const int64_t c[2] = {num_batches_tracked, n_averaged};
     RELAX_HIP_CHECK(h, hipMemcpy(t.counters + 2 * set, c, sizeof(c), hipMemcpyHostToDevice));
-    if (set == 0) RELAX_HIP_CHECK(h, hipMemset(t.mom, 0, sizeof(float) * L.n_params));   // a fresh optimizer
+    if (set == 0) {   // a fresh optimizer
+        RELAX_HIP_CHECK(h, hipMemset(t.mom, 0, sizeof(float) * L.n_params));
+        RELAX_HIP_CHECK(h, hipMemset(t.var, 0, sizeof(float) * L.n_params));
+        t.adam_t = 0;
+    }
     RELAX_HIP_CHECK(h, hipDeviceSynchronize());   // copies and fills are complete before the caller enqueues on its own stream
     return RELAX_OK;
 }
@@ -715,30 +864,57 @@ int relax_head_train_export(relax_handle* h, int set, int momentum, float* out, 
     RELAX_REQUIRE(h, !momentum || set == 0, "relax_head_train_export: only the live set has momentum buffers");
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     RELAX_HIP_CHECK(h, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2);
-    const float* src = momentum ? t.mom : t.set[set];
-    float* o = out;
-    RELAX_HIP_CHECK(h, hipMemcpy2D(o, sizeof(float) * t.F, src + L.w1, sizeof(float) * t.Fpad, sizeof(float) * t.F, t.H1, hipMemcpyDeviceToHost));
-    o += (size_t)t.H1 * t.F;
-    auto put = [&](size_t off, size_t numel) -> hipError_t {
-        hipError_t e = hipSuccess;
-        if (momentum && off >= L.n_params) std::memset(o, 0, sizeof(float) * numel);   // buffers have no momentum
-        else e = hipMemcpy(o, src + off, sizeof(float) * numel, hipMemcpyDeviceToHost);
-        o += numel;
-        return e;
-    };
-    // order of the flat block: fc1.weight [H1,F], fc1.bias, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, fc2.weight, fc2.bias,
-    // fc3.weight, fc3.bias
-    RELAX_HIP_CHECK(h, put(L.b1, t.H1));
-    RELAX_HIP_CHECK(h, put(L.gamma, t.H1));
-    RELAX_HIP_CHECK(h, put(L.beta, t.H1));
-    RELAX_HIP_CHECK(h, put(L.rmean, t.H1));
-    RELAX_HIP_CHECK(h, put(L.rvar, t.H1));
-    RELAX_HIP_CHECK(h, put(L.w2, (size_t)t.H2 * t.H1));
-    RELAX_HIP_CHECK(h, put(L.b2, t.H2));
-    RELAX_HIP_CHECK(h, put(L.w3, t.H2));
-    RELAX_HIP_CHECK(h, put(L.b3, 1));
+    RELAX_TRY(ht_export_block(h, momentum ? t.mom : t.set[set], momentum != 0, out));
     RELAX_HIP_CHECK(h, hipMemcpy(counters, t.counters + 2 * set, sizeof(int64_t) * 2, hipMemcpyDeviceToHost));
+    return RELAX_OK;
+}
+
+int relax_head_train_export_optimizer(relax_handle* h, int which, float* out, int64_t* t_out, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    HeadTrain& t = h->head_train;
+    RELAX_REQUIRE(h, t.ready, "relax_head_train_export_optimizer: call relax_head_train_init first");
+    RELAX_REQUIRE(h, (which == 0 || which == 1) && out && t_out, "relax_head_train_export_optimizer: bad arguments");
+    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    RELAX_HIP_CHECK(h, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    RELAX_TRY(ht_export_block(h, which ? t.var : t.mom, true, out));
+    *t_out = t.adam_t;
+    return RELAX_OK;
+}
+
+int relax_head_train_import_optimizer(relax_handle* h, const float* const* exp_avg, const float* const* exp_avg_sq, const char* const* names,
+                                      const int64_t* numels, int n, int64_t t_in) {
+    if (!h) return RELAX_ERR_INVALID;
+    HeadTrain& t = h->head_train;
+    RELAX_REQUIRE(h, t.ready, "relax_head_train_import_optimizer: call relax_head_train_init first");
+    RELAX_REQUIRE(h, exp_avg && exp_avg_sq && names && numels && n > 0 && t_in >= 0, "relax_head_train_import_optimizer: bad arguments");
+    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2);
+    struct Item { const char* key; size_t off; int64_t numel; };
+    const Item items[] = {{"fc1.bias", L.b1, t.H1}, {"bn1.weight", L.gamma, t.H1}, {"bn1.bias", L.beta, t.H1},
+                          {"fc2.weight", L.w2, (int64_t)t.H2 * t.H1}, {"fc2.bias", L.b2, t.H2}, {"fc3.weight", L.w3, t.H2},
+                          {"fc3.bias", L.b3, 1}};
+    host::StateDict sd[2];
+    for (int i = 0; i < n; ++i) {
+        sd[0].add(names[i], exp_avg[i], numels[i], /*strip_module=*/true);
+        sd[1].add(names[i], exp_avg_sq[i], numels[i], /*strip_module=*/true);
+    }
+    const char* what[2] = {"optimizer state exp_avg", "optimizer state exp_avg_sq"};
+    std::string err;
+    for (int k = 0; k < 2; ++k) {   // every tensor is there with its size before anything is written
+        RELAX_REQUIRE(h, sd[k].get("fc1.weight", (int64_t)t.H1 * t.F, err, what[k]), "%s", err.c_str());
+        for (const Item& it : items) RELAX_REQUIRE(h, sd[k].get(it.key, it.numel, err, what[k]), "%s", err.c_str());
+    }
+    RELAX_HIP_CHECK(h, hipDeviceSynchronize());
+    float* dst[2] = {t.mom, t.var};
+    for (int k = 0; k < 2; ++k) {
+        RELAX_HIP_CHECK(h, hipMemset(dst[k], 0, sizeof(float) * L.n_params));
+        RELAX_HIP_CHECK(h, hipMemcpy2D(dst[k] + L.w1, sizeof(float) * t.Fpad, sd[k].get("fc1.weight", -1, err, what[k]), sizeof(float) * t.F,
+                                       sizeof(float) * t.F, t.H1, hipMemcpyHostToDevice));
+        for (const Item& it : items)
+            RELAX_HIP_CHECK(h, hipMemcpy(dst[k] + it.off, sd[k].get(it.key, it.numel, err, what[k]), sizeof(float) * it.numel, hipMemcpyHostToDevice));
+    }
+    t.adam_t = t_in;
+    RELAX_HIP_CHECK(h, hipDeviceSynchronize());   // copies and fills are complete before the caller enqueues on its own stream
     return RELAX_OK;
 }
 
@@ -779,37 +955,25 @@ int relax_head_train_step(relax_handle* h, const float* xp, const float* target,
     RELAX_REQUIRE(h, target, "relax_head_train_step: no targets");
     RELAX_REQUIRE(h, drop_rate >= 0.f && drop_rate < 1.f, "relax_head_train_step: drop_rate %g outside [0, 1)", (double)drop_rate);
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HeadTrain& t = h->head_train;
-    const int H1 = t.H1, H2 = t.H2, Fpad = t.Fpad;
-    const HtLayout L = ht_layout(Fpad, H1, H2);
-    const HtAct A = ht_act(t.max_batch, H1, H2);
-    float* P = t.set[0];
-    float* M = t.mom;
-    float* a = t.act;
-    const HtDrop drop = make_drop(drop_rate, seed, step);
-    const HtSgd sgd{lr, momentum, weight_decay};
-    const int64_t n1 = (int64_t)B * H1, n2 = (int64_t)B * H2;
+    return ht_step(h, xp, target, n, index, B, HtSgd{lr, momentum, weight_decay}, l1_w, rank_w, drop_rate, seed, step,
+                   mask1, mask2, static_cast<hipStream_t>(stream));
+}
 
-    hipLaunchKernelGGL(ht_gather, gather_grid(B, Fpad), dim3(256), 0, s, xp, target, index, n, Fpad, t.xb, a + A.yb, t.counters + 0);
-    RELAX_TRY(ht_gemm(h, t.xb, P + L.w1, P + L.b1, a + A.z1, B, H1, Fpad, 0, s));
-    hipLaunchKernelGGL(ht_bn_fwd, dim3((unsigned)H1), dim3(256), 0, s, a + A.z1, B, H1, P + L.gamma, P + L.beta, P + L.rmean, P + L.rvar,
-                       t.counters + 0, 0, a + A.xhat, a + A.invstd, a + A.a1, drop, mask1);
-    RELAX_TRY(ht_gemm(h, a + A.a1, P + L.w2, P + L.b2, a + A.z2, B, H2, H1, 0, s));
-    hipLaunchKernelGGL(ht_fwd_tail, dim3((unsigned)B), dim3(256), 0, s, a + A.z2, H2, P + L.w3, P + L.b3, 1, a + A.a2, a + A.p, drop, mask2);
-    hipLaunchKernelGGL(ht_criterion, dim3((unsigned)B), dim3(256), 0, s, a + A.p, a + A.yb, B, l1_w, rank_w, a + A.rowloss, a + A.dp);
-    hipLaunchKernelGGL(ht_loss_finish, dim3(1), dim3(256), 0, s, a + A.rowloss, B, t.loss, (float*)nullptr);
-    hipLaunchKernelGGL(ht_bwd_z2, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, a + A.dp, P + L.w3, a + A.z2, n2, H2, drop, a + A.dz2);
-    hipLaunchKernelGGL(ht_bwd_u1, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, a + A.dz2, P + L.w2, a + A.xhat, P + L.gamma, P + L.beta,
-                       n1, H1, H2, drop, a + A.du1);
-    hipLaunchKernelGGL(ht_bn_bwd, dim3((unsigned)H1), dim3(256), 0, s, a + A.du1, a + A.xhat, a + A.invstd, B, H1, P + L.gamma, P + L.beta,
-                       P + L.b1, M + L.gamma, M + L.beta, M + L.b1, sgd, a + A.dz1);
-    const int n_small = H2 * H1 + 2 * H2 + 1;
-    hipLaunchKernelGGL(ht_update_small, dim3((unsigned)((n_small + 255) / 256)), dim3(256), 0, s, a + A.dz2, a + A.a1, a + A.a2, a + A.dp, B,
-                       H1, H2, P + L.w2, M + L.w2, sgd);
-    hipLaunchKernelGGL(ht_dw1_sgd<true>, dim3((unsigned)(H1 / kDwTJ), (unsigned)((Fpad + kDwTF - 1) / kDwTF)), dim3(256), 0, s, a + A.dz1, t.xb,
-                       B, H1, Fpad, P + L.w1, M + L.w1, sgd, (float*)nullptr);
-    RELAX_HIP_CHECK(h, hipGetLastError());
+int relax_head_train_step_adam(relax_handle* h, const float* xp, const float* target, int n, const int32_t* index, int B, double lr,
+                               double beta1, double beta2, double eps, double weight_decay, int decoupled, float l1_w, float rank_w,
+                               float drop_rate, uint64_t seed, uint64_t step, uint8_t* mask1, uint8_t* mask2, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_TRY(ht_check_batch(h, "relax_head_train_step_adam", xp, index, n, B, 2));
+    RELAX_REQUIRE(h, target, "relax_head_train_step_adam: no targets");
+    RELAX_REQUIRE(h, drop_rate >= 0.f && drop_rate < 1.f, "relax_head_train_step_adam: drop_rate %g outside [0, 1)", (double)drop_rate);
+    RELAX_REQUIRE(h, beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
+                  "relax_head_train_step_adam: betas (%g, %g) outside [0, 1) or eps %g below 0", beta1, beta2, eps);
+    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    HeadTrain& t = h->head_train;
+    const HtAdam adam = make_adam(lr, beta1, beta2, eps, weight_decay, decoupled, t.adam_t + 1);
+    RELAX_TRY(ht_step(h, xp, target, n, index, B, adam, l1_w, rank_w, drop_rate, seed, step, mask1, mask2,
+                      static_cast<hipStream_t>(stream)));
+    t.adam_t += 1;
     return RELAX_OK;
 }
 
@@ -880,22 +1044,41 @@ int relax_head_train_swa_update(relax_handle* h, relax_stream stream) {
     return RELAX_OK;
 }
 
-int relax_head_train_pad_abs_sum(relax_handle* h, double* out, relax_stream stream) {
-    if (!h) return RELAX_ERR_INVALID;
+static int ht_pad_abs_sum(relax_handle* h, const char* what, int blocks, double* out, relax_stream stream) {
     HeadTrain& t = h->head_train;
-    RELAX_REQUIRE(h, t.ready && out, "relax_head_train_pad_abs_sum: no state, or bad arguments");
+    RELAX_REQUIRE(h, t.ready && out, "%s: no state, or bad arguments", what);
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     RELAX_HIP_CHECK(h, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    out[0] = out[1] = 0.0;
+    for (int k = 0; k < blocks; ++k) out[k] = 0.0;
     const int pad = t.Fpad - t.F;
     if (pad == 0) return RELAX_OK;
     std::vector<float> host((size_t)t.H1 * pad);
-    const float* src[2] = {t.set[0], t.mom};
-    for (int k = 0; k < 2; ++k) {
+    const float* src[3] = {t.set[0], t.mom, t.var};
+    for (int k = 0; k < blocks; ++k) {
         RELAX_HIP_CHECK(h, hipMemcpy2D(host.data(), sizeof(float) * pad, src[k] + t.F, sizeof(float) * t.Fpad, sizeof(float) * pad, t.H1,
                                        hipMemcpyDeviceToHost));
         for (float v : host) out[k] += std::fabs((double)v);
     }
+    return RELAX_OK;
+}
+
+int relax_head_train_pad_abs_sum(relax_handle* h, double* out, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    return ht_pad_abs_sum(h, "relax_head_train_pad_abs_sum", 2, out, stream);
+}
+
+int relax_head_train_pad_abs_sum_adam(relax_handle* h, double* out, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    return ht_pad_abs_sum(h, "relax_head_train_pad_abs_sum_adam", 3, out, stream);
+}
+
+static int ht_grad_w1(relax_handle* h) {   // only the unfused measurements ever materialise the gradient of fc1.weight
+    HeadTrain& t = h->head_train;
+    if (t.grad_w1) return RELAX_OK;
+    void* p = nullptr;
+    RELAX_HIP_CHECK(h, hipMalloc(&p, sizeof(float) * (size_t)t.H1 * t.Fpad));
+    t.allocs.push_back(p);
+    t.grad_w1 = static_cast<float*>(p);
     return RELAX_OK;
 }
 
@@ -915,16 +1098,34 @@ int relax_head_train_dw1(relax_handle* h, int fused, int B, float lr, float mome
                            (float*)nullptr);
     } else {
         const size_t nw1 = (size_t)t.H1 * t.Fpad;
-        if (!t.grad_w1) {   // only this measurement ever materialises the gradient of fc1.weight
-            void* p = nullptr;
-            RELAX_HIP_CHECK(h, hipMalloc(&p, sizeof(float) * nw1));
-            t.allocs.push_back(p);
-            t.grad_w1 = static_cast<float*>(p);
-        }
+        RELAX_TRY(ht_grad_w1(h));
         hipLaunchKernelGGL(ht_dw1_sgd<false>, grid, dim3(256), 0, s, t.act + A.dz1, t.xb, B, t.H1, t.Fpad, t.set[0] + L.w1, t.mom + L.w1, sgd,
                            t.grad_w1);
         const int64_t n4 = (int64_t)(nw1 / 4);
         hipLaunchKernelGGL(ht_sgd_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, t.grad_w1, t.set[0] + L.w1, t.mom + L.w1, n4, sgd);
+    }
+    RELAX_HIP_CHECK(h, hipGetLastError());
+    return RELAX_OK;
+}
+
+int relax_head_train_dw1_adam(relax_handle* h, int fused, int B, double lr, double beta1, double beta2, double eps, double weight_decay,
+                              int decoupled, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    HeadTrain& t = h->head_train;
+    RELAX_REQUIRE(h, t.ready, "relax_head_train_dw1_adam: call relax_head_train_init first");
+    RELAX_REQUIRE(h, B >= 2 && B <= t.max_batch, "relax_head_train_dw1_adam: batch of %d rows (this state takes 2..%d)", B, t.max_batch);
+    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const HtAct A = ht_act(t.max_batch, t.H1, t.H2);
+    const HtAdam adam = make_adam(lr, beta1, beta2, eps, weight_decay, decoupled, std::max<int64_t>(t.adam_t, 1));   // the step count stays
+    if (fused) {
+        launch_dw1(t, t.act + A.dz1, B, t.set[0], adam, s);
+    } else {
+        RELAX_TRY(ht_grad_w1(h));
+        hipLaunchKernelGGL(ht_dw1_adam<false>, dim3((unsigned)(t.H1 / kDwTJ), (unsigned)((t.Fpad + kDwTF - 1) / kDwTF)), dim3(256), 0, s,
+                           t.act + A.dz1, t.xb, B, t.H1, t.Fpad, t.set[0], t.mom, t.var, adam, t.grad_w1);
+        const int64_t n4 = (int64_t)t.H1 * t.Fpad / 4;
+        hipLaunchKernelGGL(ht_adam_apply, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, t.grad_w1, t.set[0], t.mom, t.var, n4, adam);
     }
     RELAX_HIP_CHECK(h, hipGetLastError());
     return RELAX_OK;

@@ -242,7 +242,7 @@ struct HeadW {
 // ---- quality head, training state (head_train.hip) -----------------------------------------------------------
 // One parameter set is ONE device block of floats: the parameters first (what SGD and the SWA average touch), then the BatchNorm
 // buffers:  W1 [H1][Fpad] | b1 | gamma | beta | W2 [H2][H1] | b2 | w3 [H2] | b3 | running_mean [H1] | running_var [H1]
-// and two int64 counters (num_batches_tracked, n_averaged).  Sets: 0 live (with one momentum block), 1 SWA average, 2 snapshot.
+// and two int64 counters (num_batches_tracked, n_averaged).  Sets: 0 live (with the optimizer's one or two state blocks), 1 SWA average, 2 snapshot.
 struct HeadTrain {
     static constexpr int kSets = 3;
     static constexpr int kMaxBatch = 1024;
@@ -250,7 +250,10 @@ struct HeadTrain {
     int F = 0, Fpad = 0, H1 = 0, H2 = 0, max_batch = 0;
     size_t n_params = 0, n_all = 0;   // floats of the parameter part / of the whole set
     float* set[kSets] = {};
-    float* mom = nullptr;             // SGD momentum buffers, parameter part's layout
+    float* mom = nullptr;             // SGD momentum buffers / Adam's exp_avg, parameter part's layout
+    float* var = nullptr;             // Adam's exp_avg_sq, the same layout; the SGD step never reads or writes it
+    int64_t adam_t = 0;               // Adam's step count (torch keeps one per parameter, all equal); lives on the host: the bias
+                                      // corrections of a step are computed there and passed to its kernels
     int64_t* counters = nullptr;      // [kSets][2]
     double* loss = nullptr;           // [2][3]: train / eval: sum of batch losses, sum of batch loss * batch size, batches
     float* act = nullptr;             // activations of one batch (head_train.hip lays them out)

@@ -2,14 +2,15 @@
 
 Follows the reference's src/model_regression.py and src/fine_tune.py:
   preprocess_data (:122-135)        RelaxEngine.fit_scaler + the training transform
-  train_and_evaluate (:335-471)     fit_head: K-fold, SGD + CosineAnnealingLR chained with SWALR, early stopping from
-                                    swa_start, model selection by validation KRCC, update_bn on the kept model
-  fine_tune_model (fine_tune.py:130-190)   fine_tune_head: one split, batches in order, swa_start = int(0.75 epochs)
+  train_and_evaluate (:335-471)     fit_head: K-fold, SGD + CosineAnnealingLR or Adam + StepLR (:381-386) chained with SWALR,
+                                    early stopping from swa_start, model selection by validation KRCC, update_bn on the kept model
+  fine_tune_model (fine_tune.py:130-190)   fine_tune_head: one split, batches in order, swa_start = int(0.75 epochs); its 'adam'
+                                    is AdamW (fine_tune.py:155)
 Argument names and defaults are the reference's (model_regression.py:737-751).
 
 What differs from the reference: the dropout masks and the initial weights come from this project's own
-seeded generators, not torch's; only the 'sgd' optimizer and the 'MAERankLoss' criterion exist (the reference's MSELoss branch
-never assigns its criterion, :379); plots and .mat / .csv bookkeeping are the caller's business.  The per-epoch selection
+seeded generators, not torch's; the optimizers are 'sgd' and 'adam', the only criterion 'MAERankLoss' (the reference's MSELoss
+branch never assigns its criterion, :379); plots and .mat / .csv bookkeeping are the caller's business.  The per-epoch selection
 metric runs on the device (metrics.py, csrc/metrics.hip); kendall_tau_b and logistic_rmse below stay as its host yardsticks.
 The four reported metrics and the 21-repeat median-model protocol of main() are in metrics.py.
 """
@@ -24,7 +25,8 @@ from . import metrics as _metrics
 
 DEFAULTS = dict(n_splits=10, batch_size=256, epochs=20, hidden_features=256, drop_rate=0.1, loss_type="MAERankLoss",
                 optimizer_type="sgd", select_criteria="bykrcc", initial_lr=1e-1, weight_decay=0.005, patience=5, use_swa=True,
-                l1_w=0.6, rank_w=1.0, momentum=0.9, seed=0, logistic_fit="scipy")
+                l1_w=0.6, rank_w=1.0, momentum=0.9, seed=0, logistic_fit="scipy",
+                beta1=0.9, beta2=0.999, adam_eps=1e-8, lr_step_size=2, lr_gamma=0.95)   # optimizer_type 'adam' only
 LIVE, SWA, BEST = 0, 1, 2      # parameter sets of the device state
 ETA_MIN = 1e-5                 # CosineAnnealingLR(eta_min=1e-5), model_regression.py:383
 SWA_ANNEAL_EPOCHS = 10         # SWALR's default anneal_epochs
@@ -33,11 +35,15 @@ STATE_KEYS = ("fc1.weight", "fc1.bias", "bn1.weight", "bn1.bias", "bn1.running_m
 
 
 # ---- pure host arithmetic ---------------------------------------------------------------------------------------------
-def lr_schedule(epochs, initial_lr, swa_start=None, use_swa=True, eta_min=ETA_MIN, anneal_epochs=SWA_ANNEAL_EPOCHS):
+def lr_schedule(epochs, initial_lr, swa_start=None, use_swa=True, eta_min=ETA_MIN, anneal_epochs=SWA_ANNEAL_EPOCHS,
+                scheduler="cosine", step_size=2, gamma=0.95):
     """The learning rate in force during each epoch (and after the last: epochs + 1 values) when CosineAnnealingLR(T_max=epochs,
-    eta_min) and, from swa_start on, SWALR(swa_lr=initial_lr, anneal_strategy='cos') both step on the same optimizer, as the
-    reference chains them (model_regression.py:408-411).  Both schedulers are recursive in the optimizer's current lr, so
-    each sees what the other wrote; this is torch's arithmetic, in float64, statement for statement."""
+    eta_min) - or, with scheduler='step', StepLR(step_size, gamma), the Adam branch's (model_regression.py:385-386) - and, from
+    swa_start on, SWALR(swa_lr=initial_lr, anneal_strategy='cos') both step on the same optimizer, as the reference chains
+    them (model_regression.py:408-411).  Both schedulers are recursive in the optimizer's current lr, so each sees what the
+    other wrote; this is torch's arithmetic, in float64, statement for statement."""
+    if scheduler not in ("cosine", "step"):
+        raise ValueError(f"head training: scheduler {scheduler!r} (cosine | step)")
     if swa_start is None:
         swa_start = int(epochs * 0.7)
     if not use_swa:
@@ -46,8 +52,11 @@ def lr_schedule(epochs, initial_lr, swa_start=None, use_swa=True, eta_min=ETA_MI
     out = [lr]
     swa_steps = 0   # SWALR's _step_count - 1: its construction is step 0 and leaves the lr as it is
     for epoch in range(epochs):
-        last = epoch + 1   # CosineAnnealingLR.last_epoch after this step
-        if (last - 1 - epochs) % (2 * epochs) == 0:
+        last = epoch + 1   # the scheduler's last_epoch after this step
+        if scheduler == "step":
+            if last % step_size == 0:
+                lr = lr * gamma
+        elif (last - 1 - epochs) % (2 * epochs) == 0:
             lr = lr + (initial_lr - eta_min) * (1 - math.cos(math.pi / epochs)) / 2
         else:
             lr = ((1 + math.cos(math.pi * last / epochs)) / (1 + math.cos(math.pi * (last - 1) / epochs)) * (lr - eta_min) + eta_min)
@@ -194,6 +203,9 @@ class HeadTrainer:
         counters = np.zeros(2, dtype=np.int64)
         self.eng._check(self.lib.relax_head_train_export(self.h, which, int(momentum), C.c_void_p(flat.ctypes.data),
                                                          C.c_void_p(counters.ctypes.data), _stream()), "relax_head_train_export")
+        return self._unflatten(flat), counters
+
+    def _unflatten(self, flat):
         shapes = [(self.H1, self.F), (self.H1,), (self.H1,), (self.H1,), (self.H1,), (self.H1,), (self.H2, self.H1), (self.H2,),
                   (1, self.H2), (1,)]
         out, o = {}, 0
@@ -201,7 +213,7 @@ class HeadTrainer:
             size = int(np.prod(shape))
             out[key] = flat[o:o + size].reshape(shape).copy()
             o += size
-        return out, counters
+        return out
 
     def export_state(self, which=LIVE):
         """The set as host fp32 arrays under the reference's key names and shapes (+ bn1.num_batches_tracked; n_averaged for
@@ -232,6 +244,49 @@ class HeadTrainer:
                                             rank_w, drop_rate, int(seed), int(step), _ptr(m1), _ptr(m2), _stream())
         self.eng._check(rc, "relax_head_train_step")
         return (m1, m2) if want_masks else None
+
+    def step_adam(self, xp, y, index, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.005, decoupled=False, l1_w=0.6, rank_w=1.0,
+                  drop_rate=0.1, seed=0, step=0, want_masks=False):
+        """One Adam (decoupled: AdamW) step on the rows `index`, otherwise as step().  One state takes either step() or step_adam()
+        between two import_state calls, not both: the first optimizer block is SGD's momentum to the one and exp_avg to the other."""
+        self._live(xp, y)
+        index = self._idx(index, xp.shape[0])
+        B = int(index.numel())
+        m1 = torch.empty((B, self.H1), dtype=torch.uint8, device=self.eng.device) if want_masks else None
+        m2 = torch.empty((B, self.H2), dtype=torch.uint8, device=self.eng.device) if want_masks else None
+        rc = self.lib.relax_head_train_step_adam(self.h, _ptr(xp), _ptr(y), xp.shape[0], _ptr(index), B, lr, beta1, beta2, eps,
+                                                 weight_decay, int(bool(decoupled)), l1_w, rank_w, drop_rate, int(seed), int(step),
+                                                 _ptr(m1), _ptr(m2), _stream())
+        self.eng._check(rc, "relax_head_train_step_adam")
+        return (m1, m2) if want_masks else None
+
+    def export_optimizer_state(self):
+        """Adam's state as torch's optimizer.state_dict() holds it: {'exp_avg': {key: array}, 'exp_avg_sq': {key: array}, 'step': t},
+        host fp32 arrays under the parameters' keys."""
+        self._live()
+        out = {}
+        for which, name in enumerate(("exp_avg", "exp_avg_sq")):
+            flat = np.empty(self.lib.relax_head_train_export_numel(self.h), dtype=np.float32)
+            t = C.c_int64(0)
+            self.eng._check(self.lib.relax_head_train_export_optimizer(self.h, which, C.c_void_p(flat.ctypes.data), C.byref(t), _stream()),
+                            "relax_head_train_export_optimizer")
+            out[name] = {k: v for k, v in self._unflatten(flat).items() if not k.startswith("bn1.running_")}
+            out["step"] = int(t.value)
+        return out
+
+    def import_optimizer_state(self, state):
+        """What export_optimizer_state returned (or the same from torch), after import_state, which starts a new optimizer."""
+        self._live()
+        keys = [k for k in STATE_KEYS if not k.startswith("bn1.running_")]
+        strip = lambda d: {(k[7:] if k.startswith("module.") else k): v for k, v in d.items()}
+        avg, sq = strip(state["exp_avg"]), strip(state["exp_avg_sq"])
+        ptrs, names, numels, n, keep = self.eng._marshal_state_dict({k: avg[k] for k in keys})
+        ptrs_sq, _, numels_sq, _, keep_sq = self.eng._marshal_state_dict({k: sq[k] for k in keys})
+        if list(numels) != list(numels_sq):
+            raise ValueError("head training: exp_avg and exp_avg_sq differ in their sizes")
+        self.eng._check(self.lib.relax_head_train_import_optimizer(self.h, ptrs, ptrs_sq, names, numels, n, int(state["step"])),
+                        "relax_head_train_import_optimizer")
+        del keep, keep_sq
 
     def evaluate(self, xp, y, index, which=LIVE, l1_w=0.6, rank_w=1.0):
         """Eval-mode predictions (device fp32 [B]) of one batch; with y its criterion goes into the evaluation accumulator."""
@@ -281,6 +336,19 @@ class HeadTrainer:
         self.eng._check(self.lib.relax_head_train_pad_abs_sum(self.h, out, _stream()), "relax_head_train_pad_abs_sum")
         return float(out[0]), float(out[1])
 
+    def pad_abs_sum_adam(self):
+        """pad_abs_sum with Adam's second moment as a third sum: (fc1.weight, exp_avg, exp_avg_sq)[:, F:Fpad], exactly 0 at all times."""
+        self._live()
+        out = (C.c_double * 3)()
+        self.eng._check(self.lib.relax_head_train_pad_abs_sum_adam(self.h, out, _stream()), "relax_head_train_pad_abs_sum_adam")
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def dw1_adam_only(self, fused, B, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.005, decoupled=False):
+        """dw1_only under Adam / AdamW."""
+        self._live()
+        self.eng._check(self.lib.relax_head_train_dw1_adam(self.h, int(bool(fused)), int(B), lr, beta1, beta2, eps, weight_decay,
+                                                           int(bool(decoupled)), _stream()), "relax_head_train_dw1_adam")
+
     def dw1_only(self, fused, B, lr=0.01, momentum=0.9, weight_decay=0.005):
         """The dW1 stage of a step alone, on what the last step left (tools/head_train_bench.py): fused, or GEMM + separate update."""
         self._live()
@@ -304,8 +372,8 @@ class HeadTrainer:
 def _config(config):
     cfg = dict(DEFAULTS)
     cfg.update(config or {})
-    if cfg["optimizer_type"] != "sgd":
-        raise ValueError("head training: only optimizer_type='sgd' is implemented (the reference's default)")
+    if cfg["optimizer_type"] not in ("sgd", "adam"):
+        raise ValueError(f"head training: optimizer_type {cfg['optimizer_type']!r} (sgd | adam)")
     if cfg["loss_type"] != "MAERankLoss":
         raise ValueError("head training: only loss_type='MAERankLoss' is implemented (the reference's MSELoss branch is dead code)")
     if cfg["select_criteria"] not in ("bykrcc", "byrmse", "val_loss"):
@@ -323,6 +391,23 @@ def _have_scipy():
     except ImportError:
         return False
     return True
+
+
+def _schedule(cfg, swa_start, use_swa):
+    """The reference pairs SGD with CosineAnnealingLR and Adam / AdamW with StepLR (model_regression.py:381-386, fine_tune.py:151-158)."""
+    if cfg["optimizer_type"] == "adam":
+        return lr_schedule(cfg["epochs"], cfg["initial_lr"], swa_start, use_swa, scheduler="step", step_size=cfg["lr_step_size"],
+                           gamma=cfg["lr_gamma"])
+    return lr_schedule(cfg["epochs"], cfg["initial_lr"], swa_start, use_swa)
+
+
+def _step(tr, cfg, xp, y, rows, lr, step, decoupled):
+    """One step of the configured optimizer; `decoupled`: 'adam' means AdamW (fine_tune.py:155), not Adam (model_regression.py:385)."""
+    if cfg["optimizer_type"] == "adam":
+        tr.step_adam(xp, y, rows, lr, cfg["beta1"], cfg["beta2"], cfg["adam_eps"], cfg["weight_decay"], decoupled, cfg["l1_w"],
+                     cfg["rank_w"], cfg["drop_rate"], cfg["seed"], step)
+    else:
+        tr.step(xp, y, rows, lr, cfg["momentum"], cfg["weight_decay"], cfg["l1_w"], cfg["rank_w"], cfg["drop_rate"], cfg["seed"], step)
 
 
 def _device_krcc(engine, y_true, y_pred):
@@ -354,7 +439,7 @@ def fit_head(engine, features, mos, config=None):
     reference's key names, {'imputer_statistics', 'scale', 'min'} float64 [F], and per-fold 'train_loss' / 'val_loss' /
     'metric' / 'lr' lists plus 'best' = (fold, epoch, metric) and 'predictions', the kept model's eval-mode scores of every row
     as the training path computes them (host arrays only: nothing of the device state outlives the call)."""
-    cfg = _config(config)
+    cfg = _config(config)   # optimizer_type 'adam': optim.Adam (weight decay as an L2 term) under StepLR, model_regression.py:385-386
     xp, y, scaler = _prepare(engine, features, mos)
     y_host = y.cpu().numpy().astype(np.float64)
     n, F = xp.shape[0], int(features.shape[1])
@@ -362,7 +447,7 @@ def fit_head(engine, features, mos, config=None):
     tr = HeadTrainer(engine, F, cfg["hidden_features"], max_batch=max(2, min(bs, 1024)))
     use_swa = bool(cfg["use_swa"])
     swa_start = int(epochs * 0.7) if use_swa else epochs
-    lrs = lr_schedule(epochs, cfg["initial_lr"], swa_start, use_swa)
+    lrs = _schedule(cfg, swa_start, use_swa)
     lower_is_better = cfg["select_criteria"] in ("byrmse", "val_loss")
     best_metric = float("inf") if lower_is_better else float("-inf")
     history = {"train_loss": [], "val_loss": [], "metric": [], "lr": lrs, "best": None, "folds": []}
@@ -378,8 +463,7 @@ def fit_head(engine, features, mos, config=None):
         for epoch in range(epochs):
             rows_seen = 0
             for b in epoch_batches(len(train_idx), bs, rng):
-                tr.step(xp, y, train_idx[b], lrs[epoch], cfg["momentum"], cfg["weight_decay"], cfg["l1_w"], cfg["rank_w"],
-                        cfg["drop_rate"], cfg["seed"], step)
+                _step(tr, cfg, xp, y, train_idx[b], lrs[epoch], step, decoupled=False)
                 step += 1
                 rows_seen += len(b)
             _, weighted, _ = tr.read_loss(0)
@@ -428,7 +512,9 @@ def fit_head(engine, features, mos, config=None):
 
 def fine_tune_head(engine, state_dict, features, mos, config=None):
     """fine_tune_model (fine_tune.py:130-190): start from state_dict, one split, batches in order, SWA from int(0.75 epochs);
-    the result is the SWA average after update_bn (or the live model without SWA).  Returns (state_dict, scaler, history).
+    the result is the SWA average after update_bn (or the live model without SWA).  optimizer_type 'adam' is AdamW here
+    (fine_tune.py:155).  Returns (state_dict, scaler, history); under 'adam' history['optimizer_state'] holds the live model's
+    moments and step count.
     The scaler is fitted on `features`, as the reference's fine-tuning script preprocesses its own data."""
     cfg = _config(config)
     xp, y, scaler = _prepare(engine, features, mos)
@@ -439,7 +525,7 @@ def fine_tune_head(engine, state_dict, features, mos, config=None):
     tr.import_state(state_dict, LIVE)
     use_swa = bool(cfg["use_swa"])
     swa_start = int(epochs * 0.75) if use_swa else epochs
-    lrs = lr_schedule(epochs, cfg["initial_lr"], swa_start, use_swa)
+    lrs = _schedule(cfg, swa_start, use_swa)
     if use_swa:
         tr.copy(SWA, LIVE)
     losses, step = [], 0
@@ -447,8 +533,7 @@ def fine_tune_head(engine, state_dict, features, mos, config=None):
     for epoch in range(epochs):
         rows_seen = 0
         for b in epoch_batches(n, bs, None):
-            tr.step(xp, y, rows[b], lrs[epoch], cfg["momentum"], cfg["weight_decay"], cfg["l1_w"], cfg["rank_w"], cfg["drop_rate"],
-                    cfg["seed"], step)
+            _step(tr, cfg, xp, y, rows[b], lrs[epoch], step, decoupled=True)
             step += 1
             rows_seen += len(b)
         _, weighted, _ = tr.read_loss(0)
@@ -460,4 +545,6 @@ def fine_tune_head(engine, state_dict, features, mos, config=None):
         tr.update_bn(xp, [rows[b] for b in epoch_batches(n, bs, np.random.RandomState(cfg["seed"]))], SWA)
         result = SWA
     history = {"train_loss": losses, "lr": lrs, "predictions": tr.predict(xp, None, result).cpu().numpy()}
+    if cfg["optimizer_type"] == "adam":
+        history["optimizer_state"] = tr.export_optimizer_state()   # of the live model: what HeadTrainer.import_optimizer_state resumes from
     return tr.export_state(result), scaler, history

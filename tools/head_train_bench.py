@@ -1,6 +1,7 @@
 """Times the quality head's training step (csrc/head_train.hip) and writes profiles/head_train_bench.json.
 
     python tools/head_train_bench.py [--out profiles/head_train_bench.json] [--steps 200] [--no-fit]
+    python tools/head_train_bench.py --optimizer adam          # the Adam step, into profiles/head_train_adam_bench.json
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o F35203 -- \
         python tools/head_train_bench.py --features 35203 --steps 50 --no-fit --no-torch --no-dw1 --out DIR/under_profiler.json
                                                        # per-kernel breakdown of ONE width per run (profiles/head_train_kernel_stats_F*.csv)
@@ -11,6 +12,10 @@ after a warm-up (HIP events around the run; min / max over the repeats are the s
 X_b + 2 x (W1 + momentum) bytes per step: it is timed alone (relax_head_train_dw1 on the batch the last step left), fused as the
 step runs it and unfused (the same tiles writing dW1, then a separate update pass), with bytes / s against that model.  Last: the wall time of one
 KoNViD-shaped fit (960 rows, 10 folds, 120 epochs).
+
+--optimizer adam times relax_head_train_step_adam instead (Adam with an L2 term, as fit_head runs it), torch.optim.Adam as the stock
+step, and the SGD step of the same state beside them in the same run; the dW1 + Adam kernel moves X_b + 2 x (W1 + both moments)
+bytes (252 MB at F = 35203).
 """
 import argparse
 import json
@@ -48,11 +53,14 @@ def timed(fn, steps, repeats, warmup):
     return {"median_ms": float(np.median(out)), "min_ms": float(min(out)), "max_ms": float(max(out)), "repeats": repeats, "steps": steps}
 
 
-def torch_step_fn(F, H1, x, y, rows):
+def torch_step_fn(F, H1, x, y, rows, optimizer="sgd"):
     import head_train_ref as R
     model = R.Mlp(F, H1, 0.0).cuda()
     drop = torch.nn.Dropout(0.1)
-    opt = torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9, weight_decay=0.005)
+    if optimizer == "adam":
+        opt = torch.optim.Adam(model.parameters(), lr=0.001, weight_decay=0.005)
+    else:
+        opt = torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9, weight_decay=0.005)
     model.train()
 
     def fn():
@@ -68,7 +76,8 @@ def torch_step_fn(F, H1, x, y, rows):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "head_train_bench.json"))
+    ap.add_argument("--optimizer", choices=("sgd", "adam"), default="sgd")
+    ap.add_argument("--out", default=None, help="default: profiles/head_train_bench.json, or head_train_adam_bench.json under --optimizer adam")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=20)
@@ -77,8 +86,11 @@ def main():
     ap.add_argument("--no-dw1", action="store_true")
     ap.add_argument("--features", default="35203,19779", help="comma-separated feature widths")
     args = ap.parse_args()
+    adam = args.optimizer == "adam"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "head_train_adam_bench.json" if adam else "head_train_bench.json")
     eng = RelaxEngine(0)
-    res = {"device": torch.cuda.get_device_name(0), "B": 256, "H1": 256, "drop_rate": 0.1, "arithmetic": "fp32 (the only one built)",
+    res = {"optimizer": args.optimizer, "device": torch.cuda.get_device_name(0), "B": 256, "H1": 256, "drop_rate": 0.1, "arithmetic": "fp32 (the only one built)",
            "shapes": {}}
     H1, B, n = 256, 256, 960
     for F in [int(v) for v in args.features.split(",")]:
@@ -94,19 +106,33 @@ def main():
         def hip_step():
             tr.step(xp, y, rows, 0.01, 0.9, 0.005, 0.6, 1.0, 0.1, seed=1, step=counter[0])
             counter[0] += 1
-        entry = {"hip": timed(hip_step, args.steps, args.repeats, args.warmup)}
+
+        def hip_step_adam():
+            tr.step_adam(xp, y, rows, 0.001, weight_decay=0.005, drop_rate=0.1, seed=1, step=counter[0])
+            counter[0] += 1
         fpad = xp.shape[1]
-        model_bytes = 4.0 * (B * fpad + 4 * H1 * fpad)
-        entry["dw1_sgd_model_bytes"] = model_bytes
-        entry["dw1_sgd_roofline_us"] = model_bytes / COPY_RATE * 1e6
+        if adam:
+            entry = {"hip": timed(hip_step_adam, args.steps, args.repeats, args.warmup)}
+            model_bytes = 4.0 * (B * fpad + 6 * H1 * fpad)
+            dw1_only = lambda fused: tr.dw1_adam_only(fused, B, lr=1e-6)
+        else:
+            entry = {"hip": timed(hip_step, args.steps, args.repeats, args.warmup)}
+            model_bytes = 4.0 * (B * fpad + 4 * H1 * fpad)
+            dw1_only = lambda fused: tr.dw1_only(fused, B, lr=1e-6)
+        entry[f"dw1_{args.optimizer}_model_bytes"] = model_bytes
+        entry[f"dw1_{args.optimizer}_roofline_us"] = model_bytes / COPY_RATE * 1e6
         if not args.no_dw1:
-            for name, fused in (("dw1_sgd_fused", True), ("dw1_gemm_then_update_unfused", False)):
-                t = timed(lambda: tr.dw1_only(fused, B, lr=1e-6), args.steps, args.repeats, args.warmup)
+            for name, fused in ((f"dw1_{args.optimizer}_fused", True), ("dw1_gemm_then_update_unfused", False)):
+                t = timed(lambda: dw1_only(fused), args.steps, args.repeats, args.warmup)
                 t["model_bytes_per_s"] = model_bytes / (t["median_ms"] * 1e-3)
                 t["frac_of_copy_rate"] = t["model_bytes_per_s"] / COPY_RATE
                 entry[name] = t
         if not args.no_torch:
-            entry["torch"] = timed(torch_step_fn(F, H1, xp[:, :F].contiguous(), y, rows.long()), args.steps, args.repeats, args.warmup)
+            entry["torch"] = timed(torch_step_fn(F, H1, xp[:, :F].contiguous(), y, rows.long(), args.optimizer), args.steps, args.repeats,
+                                   args.warmup)
+        if adam:   # the SGD step beside it, from a fresh optimizer on the same state
+            tr.import_state(head_train.init_state_dict(F, H1, seed=1))
+            entry["hip_sgd"] = timed(hip_step, args.steps, args.repeats, args.warmup)
         res["shapes"][str(F)] = entry
         print(F, json.dumps(entry))
     if not args.no_fit:
@@ -117,7 +143,10 @@ def main():
         mos = (1 + 4 * rng.uniform(size=n)).astype(np.float32)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        _, _, hist = eng.fit_head(x, mos, dict(n_splits=10, epochs=120, patience=10 ** 6))   # no early stop: every epoch runs
+        cfg = dict(n_splits=10, epochs=120, patience=10 ** 6)   # no early stop: every epoch runs
+        if adam:
+            cfg.update(optimizer_type="adam", initial_lr=1e-3)
+        _, _, hist = eng.fit_head(x, mos, cfg)
         torch.cuda.synchronize()
         res["konvid_shaped_fit"] = {"rows": n, "F": F, "folds": 10, "epochs": 120, "wall_s": time.perf_counter() - t0,
                                     "epochs_run": int(sum(len(v) for v in hist["train_loss"]))}
