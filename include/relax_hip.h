@@ -101,6 +101,9 @@ int relax_reserve(relax_handle* h, int max_images);
  * "rn_h2_early" (default 1): with "rn_h2", the stem and the 3x3 convolutions of layer1 / layer2 run f16x2 as well; 0 = bf16x6 there.
  * "att_h2" (default 1): under "gemm_precision" 3 the ViT's attention runs on fp16 planes too (csrc/attention_h2.hip: the qkv GEMM writes planes,
  * three partial products, K / V by LDS-DMA into the fragment images); 0 = the bf16x6 attention kernel on an fp32 qkv output (A/B switch).
+ * A patch-8 model (785 tokens) takes the "att_h2" = 0 route whatever the option says: csrc/attention_h2.hip holds all keys of an
+ * (image, head) on the chip, which ends at 224; its qkv GEMM writes fp32 and the streaming bf16x6 kernel (csrc/attention_stream.hip)
+ * writes the fp16 planes the projection reads.
  * "rn_fuse" (default 1): with "rn_h2_early", the layer1 / layer2 blocks without a downsample branch run their 3x3 and their conv3 back to back in ONE
  * launch (csrc/gemm_x6.hip, B2B: the 3x3's output tile stays in registers as the A operand of the 1x1, conv3 on f16x2 with one scale
  * per pixel row); 0 = two launches, conv3 on bf16x6 (A/B switch).  "b2b_rows" (256 or 128): rows per tile of layer1's such launches, same bits.
@@ -127,9 +130,19 @@ int relax_load_resnet50(relax_handle* h, const float* const* tensors, const char
 /* Replaces VitGenerator(name_model, patch_size=16, ...) + load_state_dict
  * (src/extractor/visualise_vit_layer.py:263-329).  DINO state-dict keys
  * ("cls_token", "blocks.0.attn.qkv.weight", ...).  dim/depth/heads: 768/12/12
- * for vit_base (:287-289); head_dim must be 64, input is always 224x224 (197 tokens). */
+ * for vit_base (:287-289); head_dim must be 64, input is always 224x224 (197 tokens).  = relax_load_vit_ex with patch_size 16. */
 int relax_load_vit(relax_handle* h, const float* const* tensors, const char* const* names,
                    const int64_t* numels, int n, int dim, int depth, int heads);
+/* VitGenerator(name_model, patch_size, ...) for patch_size 8 or 16 (:263-329 builds both): 224 / p patches per side, (224 / p)^2 + 1
+ * tokens (785 / 197), patch-embed K = 3 p^2.  patch_embed.proj.weight must hold dim * 3 p^2 values and pos_embed ntok * dim: a
+ * checkpoint of the other patch size is refused with both counts in the message, before the loaded model is touched.  Every later
+ * call sizes itself by the loaded geometry (relax_vit_features: tokens [N, ntok - 1, dim], cls_attention [N, heads, ntok];
+ * relax_reserve: ViT-B/8 takes 33.5 MB of arena per image, 3.7 times ViT-B/16).  197 tokens run the single-tile attention
+ * kernels, 785 the streaming ones (csrc/attention_stream.hip). */
+int relax_load_vit_ex(relax_handle* h, const float* const* tensors, const char* const* names,
+                      const int64_t* numels, int n, int dim, int depth, int heads, int patch_size);
+/* the geometry of the loaded ViT (any pointer may be NULL); refused before relax_load_vit */
+int relax_vit_geometry(relax_handle* h, int* patch, int* ntok, int* dim, int* heads);
 
 /* Replaces models.vgg16(pretrained=True) (src/extractor/visualise_vgg.py:21, visualise_vgg_layer.py:19; torchvision
  * configuration D, no BatchNorm).  torchvision keys: features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias} and
@@ -255,13 +268,13 @@ int relax_vgg16_features(relax_handle* h, const uint8_t* frags, int N, float* la
                          float* const* taps_nchw, relax_stream stream);
 
 /* ViT on N fragments.  tokens: fp32 [N,196,dim] final-norm patch tokens
- * (visualise_vit_layer.process_video_frame, :447-500) (may be NULL);
+ * (visualise_vit_layer.process_video_frame, :447-500; [N,784,dim] with a patch-8 model) (may be NULL);
  * pooled: fp32 [N,3*dim] mean|max|std over tokens (main_fragment_pool.py:124-133) (may be NULL). */
 int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled,
                        relax_stream stream);
 /* relax_vit_features plus the attention of the LAST block's CLS query (src/extractor/visualise_vit.py:241-250
  * get_last_selfattention, :123-127 Block.forward(return_attention=True), :353-369 visualize_attention):
- *   cls_attention : fp32 [N,heads,197] = softmax(q_0 . k_j / 8) over all 197 keys, per (image, head) (may be NULL).
+ *   cls_attention : fp32 [N,heads,ntok] = softmax(q_0 . k_j / 8) over all ntok keys (197; 785 at patch 8), per (image, head) (may be NULL).
  *                   Column 0 is the CLS key; the reference keeps columns 1..196 (attn[0, :, 0, 1:]).
  * Tokens and pooled are the same bits as relax_vit_features gives.  With cls_attention alone the forward stops after the
  * last block's qkv GEMM (the last block's attention core, proj, MLP and the final norm are skipped).  All three NULL: refused. */
@@ -447,6 +460,11 @@ int relax_op_layernorm(relax_handle* h, const float* x, const float* gamma, cons
                        int rows, int dim, float eps, relax_stream stream);
 /* qkv [Nimg*197, 3*heads*64] -> out [Nimg*197, heads*64]; softmax(q k^T / 8) v per (image, head) */
 int relax_op_attention(relax_handle* h, const float* qkv, float* out, int Nimg, int heads, relax_stream stream);
+/* The streaming kernel (csrc/attention_stream.hip: key tiles of 32, online softmax) at ANY token count ntok >= 1 - also at 197,
+ * where the forwards run the single-tile kernels (a test / benchmark entry point): qkv [Nimg*ntok, 3*heads*64] -> out
+ * [Nimg*ntok, heads*64].  The arithmetic is the one the ViT forward's attention has under the current "gemm_precision": exact
+ * fp32 MFMA under 0 (and 1), bf16x6 under 2 and 3. */
+int relax_op_attention_ex(relax_handle* h, const float* qkv, float* out, int Nimg, int ntok, int heads, relax_stream stream);
 /* relu(x*scale[c]+shift[c]) then 3x3/s2/p1 max-pool: [Nimg,H,W,C] -> [Nimg,H/2,W/2,C] */
 int relax_op_bn_relu_maxpool(relax_handle* h, const float* x, const float* scale, const float* shift, float* y,
                              int Nimg, int H, int W, int C, relax_stream stream);

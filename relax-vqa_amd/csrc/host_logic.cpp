@@ -299,6 +299,59 @@ bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* pla
     return true;
 }
 
+// ---- ViT geometry, arena sizes, streaming-attention plan -------------------------------------------------------------------------------
+bool vit_geometry(int patch, VitGeometry* g, std::string& err) {
+    if (patch != 8 && patch != 16) {
+        err = "vit: patch_size " + std::to_string(patch) + " is not built (8 or 16 at 224x224)";
+        return false;
+    }
+    const int side = 224 / patch;
+    *g = VitGeometry{patch, side, side * side, side * side + 1, 3 * patch * patch};
+    return true;
+}
+
+size_t vit_floats_per_image(int dim, int ntok, int npatch, int patch_k) {
+    return (size_t)npatch * patch_k        // P   patches
+           + (size_t)npatch * dim          // PE  patch-embed output
+           + (size_t)ntok * dim * 2        // X, Y
+           + (size_t)ntok * dim * 3        // QKV
+           + (size_t)ntok * dim * 4;       // Hid
+}
+
+size_t vit_floats_per_image_x6(int dim, int ntok, int npatch, int patch_k) {
+    return (size_t)npatch * patch_k * 3 / 2     // P    patches, sp3
+           + (size_t)npatch * dim               // PE   patch-embed output
+           + (size_t)ntok * dim                 // X    residual stream
+           + (size_t)ntok * dim * 3 / 2         // Y    LayerNorm / attention output, sp3
+           + (size_t)ntok * dim * 3             // QKV
+           + (size_t)ntok * dim                 // ATT  attention output / final LayerNorm, fp32
+           + (size_t)ntok * dim * 4 * 3 / 2;    // Hid  GELU(fc1), sp3
+}
+
+bool att_stream_plan(int Nimg, int heads, int ntok, int arith, AttStreamPlan* plan, std::string& err) {
+    if (Nimg < 1 || heads < 1 || ntok < 1 || (arith != kAttStreamF32 && arith != kAttStreamX6)) {
+        err = "attention_stream: Nimg=" + std::to_string(Nimg) + " heads=" + std::to_string(heads) + " ntok=" + std::to_string(ntok);
+        return false;
+    }
+    if (((int64_t)ntok + kAttStreamKeyTile) * heads * 64 * 3 * 4 > (int64_t)INT32_MAX) {   // (the last tile's padding rows are addressed too)
+        err = "attention_stream: the qkv rows of one image (" + std::to_string(ntok) + " tokens x " + std::to_string(heads) + " heads) pass 2^31 bytes";
+        return false;
+    }
+    AttStreamPlan p;
+    p.qblock = kAttStreamQBlock;
+    p.qblocks = (ntok + p.qblock - 1) / p.qblock;
+    p.key_tiles = (ntok + kAttStreamKeyTile - 1) / kAttStreamKeyTile;
+    p.lds_bytes = arith == kAttStreamF32 ? kAttStreamLdsF32 : kAttStreamLdsX6;
+    const int64_t items = (int64_t)Nimg * heads * p.qblocks;
+    if (items > (int64_t)INT32_MAX) {
+        err = "attention_stream: " + std::to_string(items) + " work items";
+        return false;
+    }
+    p.items = (int)items;
+    *plan = p;
+    return true;
+}
+
 }  // namespace host
 }  // namespace relax
 
@@ -418,6 +471,33 @@ int relax_host_rn_plan(const int* opts, const int* req, int max_slots, int* out,
 }
 // the 16 bottlenecks: block, layer, index, cin, width, cout, stride, has_down, tap (16 * 9 ints)
 void relax_host_rn_geometry(int* out) { std::memcpy(out, relax::host::rn_geometry(), sizeof(relax::host::RnBlockGeom) * relax::host::kRnBlocks); }
+
+// ViT geometry: out = patch, side, npatch, ntok, patch_k; 0, or -1 and a message.  Arena floats per image: out[0] fp32 layout, out[1] bf16x6 layout.
+int relax_host_vit_geometry(int patch, int* out, char* err, int err_len) {
+    relax::host::VitGeometry g;
+    std::string e;
+    if (!relax::host::vit_geometry(patch, &g, e)) {
+        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return -1;
+    }
+    std::memcpy(out, &g, sizeof(g));
+    return 0;
+}
+void relax_host_vit_arena_floats(int dim, int ntok, int npatch, int patch_k, int64_t* out) {
+    out[0] = (int64_t)relax::host::vit_floats_per_image(dim, ntok, npatch, patch_k);
+    out[1] = (int64_t)relax::host::vit_floats_per_image_x6(dim, ntok, npatch, patch_k);
+}
+// streaming-attention plan: out = qblock, qblocks, key_tiles, lds_bytes, items; 0, or -1 and a message
+int relax_host_att_stream_plan(int Nimg, int heads, int ntok, int arith, int* out, char* err, int err_len) {
+    relax::host::AttStreamPlan p;
+    std::string e;
+    if (!relax::host::att_stream_plan(Nimg, heads, ntok, arith, &p, e)) {
+        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return -1;
+    }
+    std::memcpy(out, &p, sizeof(p));
+    return 0;
+}
 
 }  // extern "C"
 #endif  // RELAX_HOST_TEST_API

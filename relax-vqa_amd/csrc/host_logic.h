@@ -148,5 +148,33 @@ struct RnPlan {
 // The schedule of one forward: host arithmetic only.  false and a message if it needs more than max_slots per-image tables.
 bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* plan, std::string& err);
 
+// ---- DINO ViT geometry (224x224 input, 64-d heads) and the streaming attention kernel's plan (vit.hip, attention_stream.hip) ----------
+struct VitGeometry { int patch, side, npatch, ntok, patch_k; };   // patch 16: 14 per side, 196 patches, 197 tokens, K = 768; patch 8: 28, 784, 785, 192
+// the geometry of patch size 8 or 16; anything else is refused (false and a message)
+bool vit_geometry(int patch, VitGeometry* g, std::string& err);
+// per-image floats of the forward's arena: the exact-fp32 layout and the bf16x6 / f16x2 one (sp3 operands take 6 bytes per value)
+size_t vit_floats_per_image(int dim, int ntok, int npatch, int patch_k);
+size_t vit_floats_per_image_x6(int dim, int ntok, int npatch, int patch_k);
+
+// attention_stream.hip: one workgroup = one (image, head, block of kAttStreamQBlock queries); it walks ceil(ntok / 32) key tiles, the K and V
+// images of ONE tile in LDS at a time (fp32 rows under kAttStreamF32, bf16 plane images under kAttStreamX6)
+constexpr int kAttStreamQBlock = 128;     // 4 waves x 32 queries
+constexpr int kAttStreamKeyTile = 32;
+constexpr int kAttStreamKLdF32 = 68, kAttStreamVLdF32 = 72;             // floats per K / V row of the fp32 images (conflict-free reads)
+constexpr int kAttStreamKRowX6 = 4 * 96 + 16, kAttStreamVRowX6 = 2 * 96 + 16;   // bytes per key of the K image, per d of the V^T image
+constexpr int kAttStreamLdsF32 = 4 * kAttStreamKeyTile * (kAttStreamKLdF32 + kAttStreamVLdF32);
+constexpr int kAttStreamLdsX6 = kAttStreamKeyTile * kAttStreamKRowX6 + 64 * kAttStreamVRowX6;
+constexpr int kLdsBytesPerCu = 160 * 1024;
+enum AttStreamArith { kAttStreamF32 = 0, kAttStreamX6 = 1 };
+struct AttStreamPlan {
+    int qblock;        // queries per item
+    int qblocks;       // items per (image, head): query block b covers queries [b * qblock, min(ntok, (b + 1) * qblock))
+    int key_tiles;     // ceil(ntok / 32); the last one may hold padding keys (masked)
+    int lds_bytes;
+    int items;         // Nimg * heads * qblocks = workgroups of the launch
+};
+// false and a message for Nimg / heads / ntok < 1, an image whose qkv rows pass 2^31 bytes (buffer-resource range) or more than 2^31 - 1 items
+bool att_stream_plan(int Nimg, int heads, int ntok, int arith, AttStreamPlan* plan, std::string& err);
+
 }  // namespace host
 }  // namespace relax

@@ -213,8 +213,9 @@ struct VitW {
     bool loaded = false;
     int dim = 0, depth = 0, heads = 0;
     float* cls = nullptr;   // [dim]
-    float* pos = nullptr;   // [197][dim]
-    LinearW patch;          // [dim][3*16*16], k = c*256 + py*16 + px (c in RGB order)
+    int patch = 16, ntok = 197, npatch = 196, patch_k = 768;   // host::vit_geometry of the loaded checkpoint's patch size (8: 785 tokens)
+    float* pos = nullptr;   // [ntok][dim]
+    LinearW patch_w;        // [dim][3*p*p], k = (c*p + py)*p + px (c in RGB order)
     std::vector<VitBlockW> blocks;
     float *norm_g = nullptr, *norm_b = nullptr;
     std::vector<void*> allocs;
@@ -421,9 +422,13 @@ int launch_attention_x6(relax_handle* h, const float* qkv, float* out, void* out
 // attention on the fp16 planes the qkv GEMM wrote (attention_h2.hip): qkv_planes [Nimg*197][3*dim*4 B] of qkv * s_qkv -> out_planes [..][dim*4 B] of out * out_scale
 int launch_attention_h2(relax_handle* h, const void* qkv_planes, float s_qkv, void* out_planes, float out_scale, int Nimg, int heads, hipStream_t s);
 int launch_attention_h2_op(relax_handle* h, const float* qkv, float* out, int Nimg, int heads, hipStream_t s);   // fp32 in / out (relax_op_attention)
-// the last block's CLS attention row (vit_attention_map.hip): qkv as fp32 rows [Nimg*197][3*dim] or, with planes, fp16 planes of
-// qkv * s_qkv (csrc/h2.h) -> out fp32 [Nimg, heads, 197] = softmax(q_0 k^T / 8) per (image, head)
-int launch_vit_cls_attention(relax_handle* h, const void* qkv, bool planes, float s_qkv, float* out, int Nimg, int heads, hipStream_t s);
+// streaming attention for any token count (attention_stream.hip): qkv fp32 [Nimg*ntok][3*dim]; the x6 form's outputs as launch_attention_x6's
+int launch_attention_stream_f32(relax_handle* h, const float* qkv, float* out, int Nimg, int ntok, int heads, hipStream_t s);
+int launch_attention_stream_x6(relax_handle* h, const float* qkv, float* out, void* out_planes, int Nimg, int ntok, int heads, hipStream_t s,
+                               float out_h2_scale = 0.f);
+// the last block's CLS attention row (vit_attention_map.hip): qkv as fp32 rows [Nimg*ntok][3*dim] or, with planes, fp16 planes of
+// qkv * s_qkv (csrc/h2.h) -> out fp32 [Nimg, heads, ntok] = softmax(q_0 k^T / 8) per (image, head)
+int launch_vit_cls_attention(relax_handle* h, const void* qkv, bool planes, float s_qkv, float* out, int Nimg, int ntok, int heads, hipStream_t s);
 int launch_bn_relu_maxpool(relax_handle* h, const float* x, const float* scale, const float* shift, float* y,
                            int Nimg, int H, int W, int C, hipStream_t s);
 int launch_bn_relu_maxpool_f32(relax_handle* h, const float* x, const float* scale, const float* shift, float* y, int Nimg, int H, int W, int C,

@@ -1,8 +1,10 @@
-// DINO ViT (patch 16, 224x224 input -> 197 tokens, 64-d heads) feature extractor on gfx950.
+// DINO ViT (patch 16 or 8, 224x224 input -> 197 or 785 tokens, 64-d heads) feature extractor on gfx950.  The geometry is a property of the
+// loaded checkpoint (VitW::patch / ntok / npatch / patch_k, from host::vit_geometry); 197 tokens run the single-tile attention kernels,
+// any other count the streaming ones (attention_stream.hip).
 //
 // Reference semantics (file:line in xinyiW915/ReLaX-VQA, src/extractor/visualise_vit_layer.py):
 //   :466-470,339-342,492-494  input: PIL RGB, /255, no mean/std normalisation
-//   :132-149  PatchEmbed conv 16x16/16            -> patchify kernel + GEMM (K = 3*16*16 = 768)
+//   :132-149  PatchEmbed conv pxp/p               -> patchify kernel + GEMM (K = 3*p*p = 768 / 192)
 //   :221-232  cls token prepend, + pos_embed       -> vit_assemble
 //   :93-129   pre-LN blocks: qkv, softmax(q k^T/8) v, proj, MLP with exact-erf GELU
 //   :234-239  final LayerNorm (eps 1e-6, :287-289), patch tokens x[:,1:]
@@ -14,64 +16,65 @@
 
 namespace relax {
 
-constexpr int NTOK = 197;
-constexpr int NPATCH = 196;
-constexpr int PATCH_K = 3 * 16 * 16;
+// patch geometry of a launch: lp = log2(patch), side = 224 / patch; k = (c << 2 lp) + (py << lp) + px
+struct PatchGeom { int lp, side, npatch, patch_k; };
+__device__ inline const uint8_t* patch_src(const uint8_t* frag, const PatchGeom g, int64_t n, int p, int k) {
+    const int pm = (1 << g.lp) - 1;
+    const int c = k >> (2 * g.lp), py = (k >> g.lp) & pm, px = k & pm;
+    const int y = ((p / g.side) << g.lp) + py, x = ((p % g.side) << g.lp) + px;
+    return frag + ((n * 224 + y) * 224 + x) * 3 + (2 - c);
+}
 constexpr float kLnEps = 1e-6f;
 constexpr float kPatchScale = 16384.f;   // patch values are value/255 in [0, 1]: as fp16 planes of value * 2^14 (csrc/h2.h)
 
-// uint8 BGR [N,224,224,3] -> fp32 [N*196, 768], k = c*256 + py*16 + px with c in RGB order, value/255
+// uint8 BGR [N,224,224,3] -> fp32 [N*npatch, patch_k], k = (c*p + py)*p + px with c in RGB order, value/255
 __global__ __launch_bounds__(256) void vit_patchify(const uint8_t* __restrict__ frag, float* __restrict__ P,
-                                                    int64_t total) {
+                                                    int64_t total, const PatchGeom g) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    const int k = (int)(i % PATCH_K);
-    const int64_t row = i / PATCH_K;
-    const int p = (int)(row % NPATCH);
-    const int64_t n = row / NPATCH;
-    const int c = k >> 8, py = (k >> 4) & 15, px = k & 15;
-    const int y = (p / 14) * 16 + py, x = (p % 14) * 16 + px;
-    P[i] = (float)frag[((n * 224 + y) * 224 + x) * 3 + (2 - c)] / 255.0f;
+    const int k = (int)(i % g.patch_k);
+    const int64_t row = i / g.patch_k;
+    const int p = (int)(row % g.npatch);
+    const int64_t n = row / g.npatch;
+    P[i] = (float)*patch_src(frag, g, n, p, k) / 255.0f;
 }
 
-// the same patches as split planes (bf16 hi + mid + lo of value/255, gemm_x6.hip): one thread per 8 k (8 pixels of a patch row)
-__global__ __launch_bounds__(256) void vit_patchify_sp3(const uint8_t* __restrict__ frag, char* __restrict__ P, int64_t total8) {
+// the same patches as split planes (bf16 hi + mid + lo of value/255, gemm_x6.hip): one thread per 8 k (8 pixels of a patch row: half a row
+// at patch 16, a whole one at patch 8)
+__global__ __launch_bounds__(256) void vit_patchify_sp3(const uint8_t* __restrict__ frag, char* __restrict__ P, int64_t total8, const PatchGeom g) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total8) return;
-    const int k = (int)(i % (PATCH_K / 8)) * 8;
-    const int64_t row = i / (PATCH_K / 8);
-    const int p = (int)(row % NPATCH);
-    const int64_t n = row / NPATCH;
-    const int c = k >> 8, py = (k >> 4) & 15, px = k & 15;
-    const int y = (p / 14) * 16 + py, x = (p % 14) * 16 + px;
-    const uint8_t* src = frag + ((n * 224 + y) * 224 + x) * 3 + (2 - c);
+    const int k = (int)(i % (g.patch_k / 8)) * 8;
+    const int64_t row = i / (g.patch_k / 8);
+    const int p = (int)(row % g.npatch);
+    const int64_t n = row / g.npatch;
+    const uint8_t* src = patch_src(frag, g, n, p, k);
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (float)src[3 * j] / 255.0f;
-    store_sp3_x8(P + row * (PATCH_K * 6), k, (sp3_f32x4){v[0], v[1], v[2], v[3]}, (sp3_f32x4){v[4], v[5], v[6], v[7]});
+    store_sp3_x8(P + row * (g.patch_k * 6), k, (sp3_f32x4){v[0], v[1], v[2], v[3]}, (sp3_f32x4){v[4], v[5], v[6], v[7]});
 }
 
 // the same patches as two fp16 planes of value/255 * scale (csrc/h2.h; the values are in [0, 1]: scale 2^14)
-__global__ __launch_bounds__(256) void vit_patchify_h2(const uint8_t* __restrict__ frag, char* __restrict__ P, int64_t total8, float scale) {
+__global__ __launch_bounds__(256) void vit_patchify_h2(const uint8_t* __restrict__ frag, char* __restrict__ P, int64_t total8, float scale, const PatchGeom g) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total8) return;
-    const int k = (int)(i % (PATCH_K / 8)) * 8;
-    const int64_t row = i / (PATCH_K / 8);
-    const int p = (int)(row % NPATCH);
-    const int64_t n = row / NPATCH;
-    const int c = k >> 8, py = (k >> 4) & 15, px = k & 15;
-    const int y = (p / 14) * 16 + py, x = (p % 14) * 16 + px;
-    const uint8_t* src = frag + ((n * 224 + y) * 224 + x) * 3 + (2 - c);
+    const int k = (int)(i % (g.patch_k / 8)) * 8;
+    const int64_t row = i / (g.patch_k / 8);
+    const int p = (int)(row % g.npatch);
+    const int64_t n = row / g.npatch;
+    const uint8_t* src = patch_src(frag, g, n, p, k);
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (float)src[3 * j] / 255.0f;
-    store_h2_x8(P + row * (PATCH_K * 4), k, (h2_f32x4){v[0], v[1], v[2], v[3]}, (h2_f32x4){v[4], v[5], v[6], v[7]}, scale);
+    store_h2_x8(P + row * (g.patch_k * 4), k, (h2_f32x4){v[0], v[1], v[2], v[3]}, (h2_f32x4){v[4], v[5], v[6], v[7]}, scale);
 }
 
-// X[n,0,:] = cls + pos[0];  X[n,1+p,:] = PE[n*196+p,:] + pos[1+p]
+// X[n,0,:] = cls + pos[0];  X[n,1+p,:] = PE[n*npatch+p,:] + pos[1+p]     (ntok = npatch + 1)
 __global__ __launch_bounds__(256) void vit_assemble(const float* __restrict__ PE, const float* __restrict__ cls,
                                                     const float* __restrict__ pos, float* __restrict__ X, int dim4,
-                                                    int64_t total) {
+                                                    int64_t total, int ntok) {
+    const int NTOK = ntok, NPATCH = ntok - 1;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int d = (int)(i % dim4);
@@ -84,9 +87,10 @@ __global__ __launch_bounds__(256) void vit_assemble(const float* __restrict__ PE
     reinterpret_cast<float4*>(X)[i] = make_float4(v.x + pp.x, v.y + pp.y, v.z + pp.z, v.w + pp.w);
 }
 
-// Y [N,197,dim] -> tokens [N,196,dim] (drop cls)
+// Y [N,ntok,dim] -> tokens [N,ntok-1,dim] (drop cls)
 __global__ __launch_bounds__(256) void vit_drop_cls(const float* __restrict__ Y, float* __restrict__ T, int dim4,
-                                                    int64_t total) {
+                                                    int64_t total, int ntok) {
+    const int NTOK = ntok, NPATCH = ntok - 1;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int d = (int)(i % dim4);
@@ -96,7 +100,7 @@ __global__ __launch_bounds__(256) void vit_drop_cls(const float* __restrict__ Y,
     reinterpret_cast<float4*>(T)[i] = reinterpret_cast<const float4*>(Y)[(n * NTOK + 1 + p) * dim4 + d];
 }
 
-// per (image, channel): mean, max, population std over tokens 1..196 -> out[n, 0:dim | dim:2dim | 2dim:3dim]
+// per (image, channel): mean, max, population std over tokens first .. first+count-1 (the forward: the patch tokens 1 .. npatch) -> out[n, 0:dim | dim:2dim | 2dim:3dim]
 __global__ __launch_bounds__(256) void vit_token_stats(const float* __restrict__ Y, float* __restrict__ out, int dim,
                                                        int tok_per_img, int first, int count) {
     __shared__ float red[4][64];
@@ -143,27 +147,8 @@ void free_vit(relax_handle* h) {
     h->vit = VitW();
 }
 
-static size_t vit_floats_per_image(int dim) {
-    return (size_t)NPATCH * PATCH_K        // P   patches
-           + (size_t)NPATCH * dim          // PE  patch-embed output
-           + (size_t)NTOK * dim * 2        // X, Y
-           + (size_t)NTOK * dim * 3        // QKV
-           + (size_t)NTOK * dim * 4;       // Hid
-}
-
-// bf16x6 path: sp3 operands take 6 bytes per value (1.5 floats)
-static size_t vit_floats_per_image_x6(int dim) {
-    return (size_t)NPATCH * PATCH_K * 3 / 2     // P    patches, sp3
-           + (size_t)NPATCH * dim               // PE   patch-embed output
-           + (size_t)NTOK * dim                 // X    residual stream
-           + (size_t)NTOK * dim * 3 / 2         // Y    LayerNorm / attention output, sp3
-           + (size_t)NTOK * dim * 3             // QKV
-           + (size_t)NTOK * dim                 // ATT  attention output / final LayerNorm, fp32
-           + (size_t)NTOK * dim * 4 * 3 / 2;    // Hid  GELU(fc1), sp3
-}
-
 size_t vit_arena_bytes(const VitW& v, int n) {
-    const size_t a = vit_floats_per_image(v.dim), b = vit_floats_per_image_x6(v.dim);
+    const size_t a = host::vit_floats_per_image(v.dim, v.ntok, v.npatch, v.patch_k), b = host::vit_floats_per_image_x6(v.dim, v.ntok, v.npatch, v.patch_k);
     return sizeof(float) * (a > b ? a : b) * (size_t)n;
 }
 
@@ -175,14 +160,33 @@ extern "C" {
 
 int relax_load_vit(relax_handle* h, const float* const* tensors, const char* const* names, const int64_t* numels,
                    int n, int dim, int depth, int heads) {
+    return relax_load_vit_ex(h, tensors, names, numels, n, dim, depth, heads, 16);
+}
+
+int relax_load_vit_ex(relax_handle* h, const float* const* tensors, const char* const* names, const int64_t* numels,
+                      int n, int dim, int depth, int heads, int patch_size) {
     if (!h) return RELAX_ERR_INVALID;
     RELAX_REQUIRE(h, tensors && names && numels && n > 0, "relax_load_vit: bad arguments");
     RELAX_REQUIRE(h, heads > 0 && dim == heads * 64, "relax_load_vit: dim=%d must be heads*64 (heads=%d)", dim, heads);
     RELAX_REQUIRE(h, dim <= 768 && depth > 0, "relax_load_vit: dim=%d depth=%d unsupported", dim, depth);
-    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
-    free_vit(h);
+    host::VitGeometry geo;
+    {
+        std::string err;
+        RELAX_REQUIRE(h, host::vit_geometry(patch_size, &geo, err), "relax_load_vit: %s", err.c_str());
+    }
     host::StateDict sd;
     for (int i = 0; i < n; ++i) sd.add(names[i], tensors[i], numels[i]);
+    // the two tensors that carry the geometry, checked before anything is freed or uploaded: a checkpoint of the other patch size is
+    // refused with both counts in the message
+    const int64_t n_pos = sd.numel("pos_embed"), n_pw = sd.numel("patch_embed.proj.weight");
+    RELAX_REQUIRE(h, n_pos < 0 || n_pos == (int64_t)geo.ntok * dim,
+                  "vit state dict: pos_embed has %lld values = %lld tokens of dim %d, patch size %d needs %d tokens", (long long)n_pos,
+                  (long long)(n_pos / dim), dim, geo.patch, geo.ntok);
+    RELAX_REQUIRE(h, n_pw < 0 || n_pw == (int64_t)dim * geo.patch_k,
+                  "vit state dict: patch_embed.proj.weight has %lld values = %lld per output channel of %d, patch size %d needs %d (3 x %d x %d)",
+                  (long long)n_pw, (long long)(n_pw / dim), dim, geo.patch, geo.patch_k, geo.patch, geo.patch);
+    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    free_vit(h);
     VitW& v = h->vit;
     int rc = RELAX_OK;
     auto up = [&](const std::string& key, int64_t numel, float** dst) {
@@ -203,9 +207,10 @@ int relax_load_vit(relax_handle* h, const float* const* tensors, const char* con
         up(p + ".bias", out, &l->b);
     };
     v.dim = dim; v.depth = depth; v.heads = heads;
+    v.patch = geo.patch; v.ntok = geo.ntok; v.npatch = geo.npatch; v.patch_k = geo.patch_k;
     up("cls_token", dim, &v.cls);
-    up("pos_embed", (int64_t)NTOK * dim, &v.pos);
-    lin("patch_embed.proj", PATCH_K, dim, &v.patch);  // OIHW [dim][3][16][16] is already [dim][c*256+py*16+px]
+    up("pos_embed", (int64_t)geo.ntok * dim, &v.pos);
+    lin("patch_embed.proj", geo.patch_k, dim, &v.patch_w);  // OIHW [dim][3][p][p] is already [dim][(c*p+py)*p+px]
     v.blocks.resize(depth);
     for (int i = 0; i < depth; ++i) {
         const std::string p = "blocks." + std::to_string(i) + ".";
@@ -234,7 +239,7 @@ int relax_load_vit(relax_handle* h, const float* const* tensors, const char* con
         l->w_sp3 = q;
         rc = launch_to_sp3(h, l->w, l->in, q, l->out, l->in, nullptr);
     };
-    sp3(&v.patch);
+    sp3(&v.patch_w);
     for (VitBlockW& b : v.blocks) {
         sp3(&b.qkv);
         sp3(&b.proj);
@@ -270,7 +275,8 @@ int relax_load_vit(relax_handle* h, const float* const* tensors, const char* con
         if (rc == RELAX_OK) rc = launch_to_h2(h, l->w, l->in, q, l->out, l->in, 1.f, d_scale, nullptr);
     };
     if (rc == RELAX_OK && dim % 256 == 0) {   // (the f16x2 tile takes N % 256 == 0: ViT-B; smaller models run bf16x6 under "gemm_precision" 3)
-        h2w(&v.patch, "patch_embed.proj", kPatchScale);
+        // (patch 8: the patch-embed GEMM runs on bf16x6 under f16x2 too - see vit_forward - and needs no fp16 planes)
+        if (geo.patch == 16) h2w(&v.patch_w, "patch_embed.proj", kPatchScale);
         for (int i = 0; i < depth && rc == RELAX_OK; ++i) {
             const std::string p = "blocks." + std::to_string(i) + ".";
             VitBlockW& b = v.blocks[i];
@@ -317,6 +323,14 @@ static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* toke
     const int dim = v.dim;
     RELAX_TRY(ensure_buf(h, h->arena, vit_arena_bytes(v, N)));
     const size_t n = (size_t)N;
+    const int NTOK = v.ntok, NPATCH = v.npatch, PATCH_K = v.patch_k;
+    const PatchGeom pg{v.patch == 8 ? 3 : 4, 224 / v.patch, NPATCH, PATCH_K};
+    // 197 tokens: the single-tile kernels (every key of an (image, head) on the chip at once); any other count: the streaming ones
+    const bool single_tile = NTOK == 197;
+    auto attention_x6 = [&](const float* qkv, void* out_planes, float out_h2_scale) {
+        return single_tile ? launch_attention_x6(h, qkv, nullptr, out_planes, N, v.heads, s, out_h2_scale)
+                           : launch_attention_stream_x6(h, qkv, nullptr, out_planes, N, NTOK, v.heads, s, out_h2_scale);
+    };
     float* P = static_cast<float*>(h->arena.p);
     float* PE = P + n * NPATCH * PATCH_K;
     float* X = PE + n * NPATCH * dim;
@@ -348,24 +362,31 @@ static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* toke
             return launch_gemm_h2(h, d, s);
         };
         const int64_t p8 = (int64_t)N * NPATCH * (PATCH_K / 8);
-        hipLaunchKernelGGL(vit_patchify_h2, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Ps, p8, kPatchScale);
-        RELAX_TRY(gemm(Ps, v.patch, nullptr, PEx, nullptr, 0.f, N * NPATCH, 0));
+        if (v.patch == 16) {
+            hipLaunchKernelGGL(vit_patchify_h2, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Ps, p8, kPatchScale, pg);
+            RELAX_TRY(gemm(Ps, v.patch_w, nullptr, PEx, nullptr, 0.f, N * NPATCH, 0));
+        } else {
+            // patch 8: K = 192 is below the 256 from which the f16x2 kernel runs its three-product form, and this GEMM is 0.3 % of the forward's
+            // FLOPs: it runs on bf16x6 (split planes fit the slot: the layout reserves 6 bytes per value)
+            hipLaunchKernelGGL(vit_patchify_sp3, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Ps, p8, pg);
+            RELAX_TRY(launch_gemm_x6(h, Ps, v.patch_w.w_sp3, v.patch_w.b, nullptr, PEx, nullptr, N * NPATCH, dim, PATCH_K, 0, s));
+        }
         const int64_t at = (int64_t)rows * (dim / 4);
-        hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, v.pos, Xx, dim / 4, at);
+        hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, v.pos, Xx, dim / 4, at, NTOK);
         RELAX_HIP_CHECK(h, hipGetLastError());
         for (int i = 0; i < v.depth; ++i) {
             const VitBlockW& b = v.blocks[i];
             RELAX_TRY(launch_layernorm_h2(h, Xx, b.ln1_g, b.ln1_b, Ys, b.s_ln1, rows, dim, kLnEps, s));
-            if (h->gemm.att_h2) {   // q, k, v leave the GEMM as fp16 planes (the same 4 bytes per value) and attention reads them as they are
+            if (h->gemm.att_h2 && single_tile) {   // (attention_h2 is single-tile only: a patch-8 model takes the other branch whatever "att_h2" says)  q, k, v leave the GEMM as fp16 planes (the same 4 bytes per value) and attention reads them as they are
                 RELAX_TRY(gemm(Ys, b.qkv, nullptr, nullptr, QKVx, b.s_qkv, rows, 0));
-                if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, true, b.s_qkv, cls_attention, N, v.heads, s));
+                if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, true, b.s_qkv, cls_attention, N, NTOK, v.heads, s));
                 if (attention_only && i == last) return RELAX_OK;
                 RELAX_TRY(launch_attention_h2(h, QKVx, b.s_qkv, Ys, b.s_att, N, v.heads, s));
             } else {
                 RELAX_TRY(gemm(Ys, b.qkv, nullptr, QKVx, nullptr, 0.f, rows, 0));
-                if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, false, 0.f, cls_attention, N, v.heads, s));
+                if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, false, 0.f, cls_attention, N, NTOK, v.heads, s));
                 if (attention_only && i == last) return RELAX_OK;
-                RELAX_TRY(launch_attention_x6(h, QKVx, nullptr, Ys, N, v.heads, s, b.s_att));   // output straight into fp16 planes
+                RELAX_TRY(attention_x6(QKVx, Ys, b.s_att));   // output straight into fp16 planes
             }
             RELAX_TRY(gemm(Ys, b.proj, Xx, Xx, nullptr, 0.f, rows, 0));                     // x += proj(attn)
             RELAX_TRY(launch_layernorm_h2(h, Xx, b.ln2_g, b.ln2_b, Ys, b.s_ln2, rows, dim, kLnEps, s));
@@ -375,7 +396,7 @@ static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* toke
         RELAX_TRY(launch_layernorm(h, Xx, v.norm_g, v.norm_b, ATT, rows, dim, kLnEps, s));
         if (tokens) {
             const int64_t t = (int64_t)N * NPATCH * (dim / 4);
-            hipLaunchKernelGGL(vit_drop_cls, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, ATT, tokens, dim / 4, t);
+            hipLaunchKernelGGL(vit_drop_cls, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, ATT, tokens, dim / 4, t, NTOK);
         }
         if (pooled) hipLaunchKernelGGL(vit_token_stats, dim3(dim / 64, N), dim3(256), 0, s, ATT, pooled, dim, NTOK, 1, NPATCH);
         RELAX_HIP_CHECK(h, hipGetLastError());
@@ -394,18 +415,18 @@ static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* toke
         float* ATT = QKVx + n * NTOK * dim * 3;
         char* Hs = reinterpret_cast<char*>(ATT + n * NTOK * dim);
         const int64_t p8 = (int64_t)N * NPATCH * (PATCH_K / 8);
-        hipLaunchKernelGGL(vit_patchify_sp3, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Ps, p8);
-        RELAX_TRY(launch_gemm_x6(h, Ps, v.patch.w_sp3, v.patch.b, nullptr, PEx, nullptr, N * NPATCH, dim, PATCH_K, 0, s));
+        hipLaunchKernelGGL(vit_patchify_sp3, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Ps, p8, pg);
+        RELAX_TRY(launch_gemm_x6(h, Ps, v.patch_w.w_sp3, v.patch_w.b, nullptr, PEx, nullptr, N * NPATCH, dim, PATCH_K, 0, s));
         const int64_t at = (int64_t)rows * (dim / 4);
-        hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, v.pos, Xx, dim / 4, at);
+        hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, v.pos, Xx, dim / 4, at, NTOK);
         RELAX_HIP_CHECK(h, hipGetLastError());
         for (int i = 0; i < v.depth; ++i) {
             const VitBlockW& b = v.blocks[i];
             RELAX_TRY(launch_layernorm_sp3(h, Xx, b.ln1_g, b.ln1_b, Ys, rows, dim, kLnEps, s));
             RELAX_TRY(launch_gemm_x6(h, Ys, b.qkv.w_sp3, b.qkv.b, nullptr, QKVx, nullptr, rows, 3 * dim, dim, 0, s));
-            if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, false, 0.f, cls_attention, N, v.heads, s));
+            if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, false, 0.f, cls_attention, N, NTOK, v.heads, s));
             if (attention_only && i == last) return RELAX_OK;
-            RELAX_TRY(launch_attention_x6(h, QKVx, nullptr, Ys, N, v.heads, s));   // output straight into split planes
+            RELAX_TRY(attention_x6(QKVx, Ys, 0.f));   // output straight into split planes
             RELAX_TRY(launch_gemm_x6(h, Ys, b.proj.w_sp3, b.proj.b, Xx, Xx, nullptr, rows, dim, dim, 0, s));      // x += proj(attn)
             RELAX_TRY(launch_layernorm_sp3(h, Xx, b.ln2_g, b.ln2_b, Ys, rows, dim, kLnEps, s));
             RELAX_TRY(launch_gemm_x6(h, Ys, b.fc1.w_sp3, b.fc1.b, nullptr, nullptr, Hs, rows, 4 * dim, dim, 2, s)); // GELU(erf) -> sp3
@@ -414,7 +435,7 @@ static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* toke
         RELAX_TRY(launch_layernorm(h, Xx, v.norm_g, v.norm_b, ATT, rows, dim, kLnEps, s));
         if (tokens) {
             const int64_t t = (int64_t)N * NPATCH * (dim / 4);
-            hipLaunchKernelGGL(vit_drop_cls, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, ATT, tokens, dim / 4, t);
+            hipLaunchKernelGGL(vit_drop_cls, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, ATT, tokens, dim / 4, t, NTOK);
         }
         if (pooled) hipLaunchKernelGGL(vit_token_stats, dim3(dim / 64, N), dim3(256), 0, s, ATT, pooled, dim, NTOK, 1, NPATCH);
         RELAX_HIP_CHECK(h, hipGetLastError());
@@ -422,19 +443,19 @@ static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* toke
     }
 
     const int64_t ptotal = (int64_t)N * NPATCH * PATCH_K;
-    hipLaunchKernelGGL(vit_patchify, dim3((unsigned)((ptotal + 255) / 256)), dim3(256), 0, s, frags, P, ptotal);
-    RELAX_TRY(launch_gemm(h, P, v.patch.w, v.patch.b, nullptr, PE, N * NPATCH, dim, PATCH_K, 0, s));
+    hipLaunchKernelGGL(vit_patchify, dim3((unsigned)((ptotal + 255) / 256)), dim3(256), 0, s, frags, P, ptotal, pg);
+    RELAX_TRY(launch_gemm(h, P, v.patch_w.w, v.patch_w.b, nullptr, PE, N * NPATCH, dim, PATCH_K, 0, s));
     const int64_t atotal = (int64_t)rows * (dim / 4);
     hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((atotal + 255) / 256)), dim3(256), 0, s, PE, v.cls, v.pos, X,
-                       dim / 4, atotal);
+                       dim / 4, atotal, NTOK);
     RELAX_HIP_CHECK(h, hipGetLastError());
     for (int i = 0; i < v.depth; ++i) {
         const VitBlockW& b = v.blocks[i];
         RELAX_TRY(launch_layernorm(h, X, b.ln1_g, b.ln1_b, Y, rows, dim, kLnEps, s));
         RELAX_TRY(launch_gemm(h, Y, b.qkv.w, b.qkv.b, nullptr, QKV, rows, 3 * dim, dim, 0, s));
-        if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKV, false, 0.f, cls_attention, N, v.heads, s));
+        if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKV, false, 0.f, cls_attention, N, NTOK, v.heads, s));
         if (attention_only && i == last) return RELAX_OK;
-        RELAX_TRY(launch_attention(h, QKV, Y, N, v.heads, s));
+        RELAX_TRY(single_tile ? launch_attention(h, QKV, Y, N, v.heads, s) : launch_attention_stream_f32(h, QKV, Y, N, NTOK, v.heads, s));
         RELAX_TRY(launch_gemm(h, Y, b.proj.w, b.proj.b, X, X, rows, dim, dim, 0, s));       // x += proj(attn)
         RELAX_TRY(launch_layernorm(h, X, b.ln2_g, b.ln2_b, Y, rows, dim, kLnEps, s));
         RELAX_TRY(launch_gemm(h, Y, b.fc1.w, b.fc1.b, nullptr, Hid, rows, 4 * dim, dim, 2, s));   // GELU(erf)
@@ -443,7 +464,7 @@ static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* toke
     RELAX_TRY(launch_layernorm(h, X, v.norm_g, v.norm_b, Y, rows, dim, kLnEps, s));
     if (tokens) {
         const int64_t t = (int64_t)N * NPATCH * (dim / 4);
-        hipLaunchKernelGGL(vit_drop_cls, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, Y, tokens, dim / 4, t);
+        hipLaunchKernelGGL(vit_drop_cls, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, Y, tokens, dim / 4, t, NTOK);
     }
     if (pooled) hipLaunchKernelGGL(vit_token_stats, dim3(dim / 64, N), dim3(256), 0, s, Y, pooled, dim, NTOK, 1, NPATCH);
     RELAX_HIP_CHECK(h, hipGetLastError());
@@ -462,6 +483,16 @@ int relax_vit_features_ex(relax_handle* h, const uint8_t* frags, int N, float* t
     if (!h) return RELAX_ERR_INVALID;
     RELAX_REQUIRE(h, tokens || pooled || cls_attention, "relax_vit_features_ex: no output requested");
     return vit_forward(h, frags, N, tokens, pooled, cls_attention, stream);
+}
+
+int relax_vit_geometry(relax_handle* h, int* patch, int* ntok, int* dim, int* heads) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, h->vit.loaded, "relax_vit_geometry: call relax_load_vit first");
+    if (patch) *patch = h->vit.patch;
+    if (ntok) *ntok = h->vit.ntok;
+    if (dim) *dim = h->vit.dim;
+    if (heads) *heads = h->vit.heads;
+    return RELAX_OK;
 }
 
 int relax_op_token_stats(relax_handle* h, const float* x, float* out, int Nimg, int tokens, int dim,

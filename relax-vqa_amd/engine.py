@@ -65,6 +65,7 @@ class RelaxEngine:
             raise RuntimeError(f"relax_create failed ({rc}): {self.lib.relax_last_error(None).decode()}")
         self.h = h
         self.vit_dim = None
+        self.vit_patch = self.vit_ntok = self.vit_npatch = None   # geometry of the loaded ViT (load_vit)
 
     def close(self):
         if getattr(self, "h", None):
@@ -122,13 +123,30 @@ class RelaxEngine:
         self._check(self.lib.relax_load_vgg16(self.h, ptrs, names, numels, n), "relax_load_vgg16")
         del keep
 
-    def load_vit(self, state_dict, name_model="vit_base"):
-        """state_dict: DINO ViT key names -> fp32 arrays/tensors."""
+    def load_vit(self, state_dict, name_model="vit_base", patch_size=None):
+        """state_dict: DINO ViT key names -> fp32 arrays/tensors.  patch_size 8 or 16 (VitGenerator's second argument,
+        src/extractor/visualise_vit_layer.py:263-329); None reads it from patch_embed.proj.weight's shape [dim,3,p,p].
+        Sets vit_patch, vit_ntok ((224/p)^2 + 1: 197 / 785) and vit_npatch; every ViT call sizes its outputs by them."""
         dim, depth, heads = VIT_CONFIGS[name_model]
+        if patch_size is None:
+            w = state_dict.get("patch_embed.proj.weight")
+            if w is None or len(w.shape) != 4 or w.shape[2] != w.shape[3]:
+                raise ValueError("load_vit: patch_size=None needs patch_embed.proj.weight of shape [dim,3,p,p] to read p from")
+            patch_size = int(w.shape[2])
+        if patch_size not in (8, 16):
+            raise ValueError(f"load_vit: patch_size {patch_size} is not built (8 or 16)")
         ptrs, names, numels, n, keep = self._marshal_state_dict(state_dict)
-        self._check(self.lib.relax_load_vit(self.h, ptrs, names, numels, n, dim, depth, heads), "relax_load_vit")
+        self._check(self.lib.relax_load_vit_ex(self.h, ptrs, names, numels, n, dim, depth, heads, int(patch_size)), "relax_load_vit_ex")
         self.vit_dim = dim
+        self.vit_patch, self.vit_ntok, _, _ = self.vit_geometry()
+        self.vit_npatch = self.vit_ntok - 1
         del keep
+
+    def vit_geometry(self):
+        """(patch, ntok, dim, heads) of the loaded ViT, read back from the library (relax_vit_geometry)."""
+        v = [C.c_int(0) for _ in range(4)]
+        self._check(self.lib.relax_vit_geometry(self.h, *[C.byref(x) for x in v]), "relax_vit_geometry")
+        return tuple(int(x.value) for x in v)
 
     def load_mlp_head(self, state_dict, scaler_scale, scaler_min, imputer_statistics=None):
         """state_dict: the reference Mlp's keys (src/model_regression.py:37-58); scaler_* / imputer_statistics: the
@@ -239,6 +257,8 @@ class RelaxEngine:
         return v.value
 
     def reserve(self, max_images):
+        """Size the activation arena for batches of max_images fragments, for the models loaded NOW (load first, then reserve): the
+        ViT's share follows its geometry - ViT-B/8 (785 tokens) takes 33.5 MB per image, 3.7 times ViT-B/16's 9.1 MB."""
         self._check(self.lib.relax_reserve(self.h, int(max_images)), "relax_reserve")
 
     # ---- stage A ------------------------------------------------------------------------------
@@ -457,34 +477,35 @@ class RelaxEngine:
         return ls, pl
 
     def vit_features(self, frags, tokens=False, pooled=True, attention=False):
-        """frags uint8 [N,224,224,3] BGR -> (tokens fp32 [N,196,dim] | None, pooled fp32 [N,3*dim] | None).
-        attention=True adds a third element: the last block's CLS attention to the 196 patches, fp32 [N,heads,196]
-        (src/extractor/visualise_vit.py:241-250,353-369: attn[:, :, 0, 1:]); tokens and pooled are unchanged by it."""
+        """frags uint8 [N,224,224,3] BGR -> (tokens fp32 [N,npatch,dim] | None, pooled fp32 [N,3*dim] | None); npatch = 196, or 784
+        with a patch-8 model.  attention=True adds a third element: the last block's CLS attention to the patches, fp32
+        [N,heads,npatch] (src/extractor/visualise_vit.py:241-250,353-369: attn[:, :, 0, 1:]); tokens and pooled are unchanged by it."""
         if self.vit_dim is None:
             raise RuntimeError("load_vit first")
         frags = self._frags(frags)
         N = frags.shape[0]
         dev = self.device
-        tk = torch.empty((N, 196, self.vit_dim), dtype=torch.float32, device=dev) if tokens else None
+        tk = torch.empty((N, self.vit_npatch, self.vit_dim), dtype=torch.float32, device=dev) if tokens else None
         pl = torch.empty((N, 3 * self.vit_dim), dtype=torch.float32, device=dev) if pooled else None
         if not attention:
             self._check(self.lib.relax_vit_features(self.h, _ptr(frags), N, _ptr(tk), _ptr(pl), _stream()),
                         "relax_vit_features")
             return tk, pl
-        at = torch.empty((N, self.vit_dim // 64, 197), dtype=torch.float32, device=dev)
+        at = torch.empty((N, self.vit_dim // 64, self.vit_ntok), dtype=torch.float32, device=dev)
         self._check(self.lib.relax_vit_features_ex(self.h, _ptr(frags), N, _ptr(tk), _ptr(pl), _ptr(at), _stream()),
                     "relax_vit_features_ex")
         return tk, pl, at[:, :, 1:]
 
     def vit_attention(self, frags, with_cls=False):
-        """frags uint8 [N,224,224,3] BGR -> fp32 [N,heads,196]: get_last_selfattention's CLS row without the CLS column
+        """frags uint8 [N,224,224,3] BGR -> fp32 [N,heads,npatch]: get_last_selfattention's CLS row without the CLS column
         (src/extractor/visualise_vit.py:241-250,353-369).  The forward stops after the last block's qkv GEMM.
-        with_cls=True returns the whole row [N,heads,197] (column 0 = the CLS key; each row sums to 1)."""
+        with_cls=True returns the whole row [N,heads,ntok] (column 0 = the CLS key; each row sums to 1).  npatch / ntok = 196 / 197,
+        or 784 / 785 with a patch-8 model."""
         if self.vit_dim is None:
             raise RuntimeError("load_vit first")
         frags = self._frags(frags)
         N = frags.shape[0]
-        at = torch.empty((N, self.vit_dim // 64, 197), dtype=torch.float32, device=self.device)
+        at = torch.empty((N, self.vit_dim // 64, self.vit_ntok), dtype=torch.float32, device=self.device)
         self._check(self.lib.relax_vit_features_ex(self.h, _ptr(frags), N, None, None, _ptr(at), _stream()),
                     "relax_vit_features_ex")
         return at if with_cls else at[:, :, 1:]
@@ -493,7 +514,10 @@ class RelaxEngine:
         """map_attention_to_original (src/demo_visual.py:12-25) on the GPU.
         frames uint8 [T,H,W,3] BGR (items may be strided, pixels packed); positions int32 [T,196,2] / counts int32 [T] as
         fragment_pairs returns them; patch_values fp32 [T,196] in slot order; lut uint8 [256,3] BGR (None: colormap.jet_lut_bgr(),
-        see there for passing cv2's own table) -> uint8 [T,H,W,3] = 0.6 frame + 0.4 lut[level] (csrc/vit_attention_map.hip)."""
+        see there for passing cv2's own table) -> uint8 [T,H,W,3] = 0.6 frame + 0.4 lut[level] (csrc/vit_attention_map.hip).
+        The slots are the fragment's 16x16 source patches, one per token of a patch-16 ViT: with a patch-8 model loaded (784 tokens of
+        8x8) there is no such map - the reference's demo_visual.py is patch-16 only - and the call raises ValueError."""
+        self._overlay_needs_patch16("attention_overlay")
         if isinstance(frames, np.ndarray):
             frames = torch.from_numpy(np.ascontiguousarray(frames))
         frames = frames.to(self.device, non_blocking=True)
@@ -523,6 +547,11 @@ class RelaxEngine:
         self._check(rc, "relax_attention_overlay")
         return out
 
+    def _overlay_needs_patch16(self, what):
+        if self.vit_patch is not None and self.vit_patch != 16:
+            raise ValueError(f"{what}: the overlay maps the fragment's 196 slots of 16x16 pixels to the tokens of a patch-16 ViT; the loaded "
+                             f"model has patch size {self.vit_patch} ({self.vit_npatch} patch tokens)")
+
     OVERLAY_FRAGMENTS = ("residual_imp", "residual_of_imp", "ori_frag", "residual_merged_frag")
 
     def attention_overlays(self, frames, fragment="ori_frag", flow_images=None, lut=None):
@@ -536,6 +565,7 @@ class RelaxEngine:
                 attention fp32 [T,heads,196], positions, counts)."""
         if fragment not in self.OVERLAY_FRAGMENTS:
             raise ValueError(f"fragment must be one of {self.OVERLAY_FRAGMENTS}, got {fragment!r}")
+        self._overlay_needs_patch16("attention_overlays")
         frames = self._dev_u8(frames)
         fr = self.fragment_pairs(frames)
         positions, counts = fr["positions"], fr["counts"]
@@ -874,6 +904,17 @@ class RelaxEngine:
         out = torch.empty((qkv.shape[0], heads * 64), dtype=torch.float32, device=self.device)
         self._check(self.lib.relax_op_attention(self.h, _ptr(qkv), _ptr(out), n_img, heads, _stream()),
                     "relax_op_attention")
+        return out
+
+    def op_attention_ex(self, qkv, n_img, ntok, heads):
+        """The streaming attention kernel (csrc/attention_stream.hip) at any token count: qkv fp32 [n_img*ntok, 3*heads*64] ->
+        fp32 [n_img*ntok, heads*64]; exact fp32 under "gemm_precision" 0 / 1, bf16x6 under 2 / 3 (relax_op_attention_ex)."""
+        if qkv.dim() != 2 or tuple(qkv.shape) != (n_img * ntok, 3 * heads * 64) or qkv.dtype != torch.float32:
+            raise ValueError(f"op_attention_ex: qkv must be fp32 [{n_img * ntok}, {3 * heads * 64}], got {qkv.dtype} {tuple(qkv.shape)}")
+        qkv = qkv.to(self.device).contiguous()
+        out = torch.empty((qkv.shape[0], heads * 64), dtype=torch.float32, device=self.device)
+        self._check(self.lib.relax_op_attention_ex(self.h, _ptr(qkv), _ptr(out), n_img, ntok, heads, _stream()),
+                    "relax_op_attention_ex")
         return out
 
     def op_bn_relu_maxpool(self, x, scale, shift, amax_out=None):

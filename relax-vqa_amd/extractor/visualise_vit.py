@@ -16,19 +16,20 @@ from .visualise_vit_layer import VitGenerator  # noqa: F401  (the same generator
 
 
 def _attention(model, frag_bgr_u8):
-    eng = runtime.ensure_vit(model.name_model)
+    eng = runtime.ensure_vit(model.name_model, model.patch_size)
     frags = torch.from_numpy(np.ascontiguousarray(frag_bgr_u8)) if isinstance(frag_bgr_u8, np.ndarray) else frag_bgr_u8
     return eng.vit_attention(frags)
 
 
 def visualize_attention(model, img, patch_size, device):
     """img: uint8 [224,224,3] BGR (a fragment, or a frame through runtime.to_model_input(.., "vit")) -> fp32 numpy
-    [heads, 224, 224]: attn[0, :, 0, 1:] as [heads, 14, 14], each value repeated over its 16 x 16 patch (mode="nearest")."""
-    if patch_size != 16:
-        raise NotImplementedError("only patch_size 16 (197 tokens at 224x224) is built")
-    att = _attention(model, img).cpu().numpy()[0]                    # [heads, 196]
+    [heads, 224, 224]: attn[0, :, 0, 1:] as [heads, 14, 14] ([heads, 28, 28] at patch size 8), each value repeated over its
+    patch (mode="nearest")."""
+    if patch_size != model.patch_size:
+        raise ValueError(f"visualize_attention: patch_size {patch_size}, the model was built with {model.patch_size}")
+    att = _attention(model, img).cpu().numpy()[0]                    # [heads, npatch]
     nh = att.shape[0]
-    att = att.reshape(nh, 14, 14)
+    att = att.reshape(nh, 224 // patch_size, 224 // patch_size)
     return np.repeat(np.repeat(att, patch_size, axis=1), patch_size, axis=2)
 
 

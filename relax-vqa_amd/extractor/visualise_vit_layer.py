@@ -2,7 +2,7 @@
 
 Reference: VitGenerator(name_model, patch_size, device, evaluate=True, random=False, verbose=False) builds the model
 and loads hub weights (:263-329); process_video_frame(image_path, video_name, qp, model, patch_size, device) returns
-the final-norm patch tokens [196, dim] (:447-500).  The reference rebuilds the generator for every frame
+the final-norm patch tokens [196, dim] (:447-500; [784, dim] at patch size 8).  The reference rebuilds the generator for every frame
 (src/main_fragment_layerstack.py:118); here the weights live in the engine and the generator is a light handle."""
 import os
 
@@ -17,25 +17,25 @@ class VitGenerator(object):
     def __init__(self, name_model, patch_size, device=None, evaluate=True, random=False, verbose=False):
         if name_model not in ("vit_tiny", "vit_small", "vit_base"):
             raise ValueError(f"No model found with {name_model}")   # the reference raises a bare string here (:291)
-        if patch_size != 16:
-            raise NotImplementedError("only patch_size 16 (197 tokens at 224x224) is built")
+        if patch_size not in (8, 16):
+            raise ValueError(f"patch_size {patch_size}: DINO checkpoints exist for 8 and 16 (:309-320)")
         self.name_model = name_model
         self.patch_size = patch_size
         self.device = device
         self.evaluate = evaluate
         self.verbose = verbose
         if random:
-            runtime.set_weights(vit=synth.vit_state_dict(name_model), vit_name=name_model)
+            runtime.set_weights(vit=synth.vit_state_dict(name_model, patch=patch_size), vit_name=name_model, vit_patch=patch_size)
         else:
-            runtime.ensure_vit(name_model)
+            runtime.ensure_vit(name_model, patch_size)   # ValueError naming both sizes if the configured weights have the other one
 
     def tokens(self, frag_bgr_u8):
-        eng = runtime.ensure_vit(self.name_model)
+        eng = runtime.ensure_vit(self.name_model, self.patch_size)
         t, _ = eng.vit_features(torch.from_numpy(np.ascontiguousarray(frag_bgr_u8)), tokens=True, pooled=False)
         return t
 
     def __call__(self, frag_bgr_u8):
-        """-> (None, tokens [N,196,dim]); the cls token is not part of the hot path."""
+        """-> (None, tokens [N,196,dim] ([N,784,dim] at patch size 8)); the cls token is not part of the hot path."""
         return None, self.tokens(frag_bgr_u8)
 
 

@@ -12,7 +12,7 @@ import numpy as np
 from . import synth
 
 log = logging.getLogger("relax_vqa_amd")
-_state = {"engine": None, "rn": False, "vit": None, "vgg": None}
+_state = {"engine": None, "rn": False, "vit": None, "vit_synthetic": False, "vgg": None}
 
 
 _WRAPPER_KEYS = ("state_dict", "model", "teacher", "student")   # torch.save({"state_dict": ...}), DINO full checkpoints
@@ -77,12 +77,18 @@ def ensure_resnet50():
     return eng
 
 
-def ensure_vit(name_model="vit_base"):
+def ensure_vit(name_model="vit_base", patch_size=16):
+    """The engine with a ViT loaded.  A RELAX_VIT_WEIGHTS file carries its own patch size (read from its shapes by load_vit);
+    patch_size picks the synthetic weights' and is what the loaded model must have: ValueError naming both sizes otherwise."""
     eng = get_engine()
-    if _state["vit"] != name_model:
-        sd = _weights_or_synthetic("RELAX_VIT_WEIGHTS", name_model, lambda: synth.vit_state_dict(name_model))
+    # (synthetic weights this function made itself are made again at the other patch size; injected weights and files are what they are)
+    if _state["vit"] != name_model or (_state["vit_synthetic"] and eng.vit_patch != patch_size):
+        sd = _weights_or_synthetic("RELAX_VIT_WEIGHTS", name_model, lambda: synth.vit_state_dict(name_model, patch=patch_size))
         eng.load_vit(sd, name_model)
         _state["vit"] = name_model
+        _state["vit_synthetic"] = not os.environ.get("RELAX_VIT_WEIGHTS")
+    if eng.vit_patch != patch_size:
+        raise ValueError(f"ensure_vit: patch size {patch_size} requested, the loaded {name_model} weights have patch size {eng.vit_patch}")
     return eng
 
 
@@ -101,8 +107,8 @@ def ensure_vgg16():
     return eng
 
 
-def set_weights(resnet50=None, vit=None, vit_name="vit_base", vgg16=None):
-    """Explicit weight injection (tests, real checkpoints already in memory)."""
+def set_weights(resnet50=None, vit=None, vit_name="vit_base", vgg16=None, vit_patch=None):
+    """Explicit weight injection (tests, real checkpoints already in memory).  vit_patch: 8 or 16, None = from the weights' shapes."""
     eng = get_engine()
     if vgg16 is not None:
         eng.load_vgg16(vgg16)
@@ -111,8 +117,9 @@ def set_weights(resnet50=None, vit=None, vit_name="vit_base", vgg16=None):
         eng.load_resnet50(resnet50)
         _state["rn"] = True
     if vit is not None:
-        eng.load_vit(vit, vit_name)
+        eng.load_vit(vit, vit_name, patch_size=vit_patch)
         _state["vit"] = vit_name
+        _state["vit_synthetic"] = False
     return eng
 
 
@@ -120,6 +127,7 @@ def reset_weights():
     """Forget which weights are loaded: the next ensure_resnet50() / ensure_vit() / ensure_vgg16() reads RELAX_*_WEIGHTS again."""
     _state["rn"] = False
     _state["vit"] = None
+    _state["vit_synthetic"] = False
     _state["vgg"] = None
 
 

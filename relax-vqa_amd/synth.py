@@ -146,7 +146,7 @@ def vit_state_dict(name_model="vit_base", patch=16, seed=11, adversarial=False):
 
     sd = {
         "cls_token": nrm((1, 1, dim), 0.02),
-        "pos_embed": nrm((1, 197, dim), 0.02),
+        "pos_embed": nrm((1, (224 // patch) ** 2 + 1, dim), 0.02),   # 197 rows at patch 16, 785 at patch 8
         "patch_embed.proj.weight": nrm((dim, 3, patch, patch), 0.02),
         "patch_embed.proj.bias": nrm((dim,), 0.02),
     }
