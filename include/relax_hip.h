@@ -507,6 +507,7 @@ int relax_segment_mean(relax_handle* h, const float* src, int64_t src_stride, in
 #define RELAX_PNG_OUTPUT_TOO_SHORT 11    /* fewer than H * (1 + W*C) bytes */
 #define RELAX_PNG_BAD_FILTER 12          /* a row filter byte above 4 */
 #define RELAX_PNG_BAD_ADLER 13           /* the Adler-32 of the inflated bytes differs from the stream's */
+#define RELAX_PNG_OUT_TOO_SMALL 14       /* relax_png_encode: the item's output slot is shorter than its stream */
 
 /* The image data of N PNG files -> uint8 BGR, as cv2.imread (src/main_fragment_layerstack.py:295-296) returns it: RGB
  * swapped, alpha dropped, gray replicated.  The caller parses the container (signature, IHDR, chunk CRCs) and concatenates
@@ -525,6 +526,46 @@ int relax_segment_mean(relax_handle* h, const float* src, int64_t src_stride, in
  * RELAX_ERR_INVALID for bad arguments, RELAX_ERR_HIP if the launch fails; the per-image outcome is in `status`. */
 int relax_png_decode(const uint8_t* src, int64_t src_bytes, const int64_t* items, int N, uint8_t* out, int64_t out_bytes,
                      uint8_t* raw, int64_t raw_bytes, int32_t* status, relax_stream stream);
+
+/* ---- PNG encode ------------------------------------------------------------------------------- */
+/* Device images -> the zlib streams of their PNG files, what cv2.imwrite leaves behind for the fragments, residuals, flow
+ * images and overlays (src/main_fragment_layerstack.py:310,325, src/main_residual.py:230,241, src/demo_test.py:120,135): BGR
+ * (C = 3) is written as RGB, colour type 2; C = 1 is colour type 0.  Equality with OpenCV's files is on the decoded pixels.
+ * The caller wraps each stream into the container (signature, IHDR, IDAT, IEND, CRCs).  The stream is cut into bands of whole
+ * rows, one workgroup per band, all bands of all N images in one launch; per band: the row filter with the smallest sum of
+ * absolute values (ties to the lower number), run-length matches (distance 1), one dynamic Huffman block or - where shorter -
+ * a stored block, and an empty stored block that byte-aligns the band; a second pass places the bands of each image behind the
+ * header 78 01 and appends the combined Adler-32.
+ *
+ * relax_png_encode_bound: host arithmetic.  Returns the largest stream an H x W x C image can produce (exactly what an
+ * incompressible image produces), < 0 for a refused geometry (C not 1 or 3, W*C > 16384, H > 2^24, filter outside -1..4);
+ * *scratch_bytes = the scratch the image needs (a call needs the sum over its items), *band_rows = rows per band. */
+int64_t relax_png_encode_bound(int H, int W, int C, int filter, int64_t* scratch_bytes, int* band_rows);
+/*   images  DEVICE uint8 [images_bytes]
+ *   items   DEVICE int64 [N][8]: image offset, row stride (bytes, >= W*C), H, W, C (1 or 3), out offset, out capacity,
+ *           filter (-1: chosen per row, 0..4: that filter for every row)
+ *   out     DEVICE uint8 [out_bytes]: item n's stream at its out offset
+ *   scratch DEVICE uint8 [scratch_bytes], 8-byte aligned, at least 64 + 64 * N bytes; contents on entry are ignored
+ *   lengths DEVICE int64 [N]: stream length (0 unless status is RELAX_PNG_OK)
+ *   status  DEVICE int32 [N]: RELAX_PNG_OK, RELAX_PNG_BAD_ARGS (geometry, or a range of the item outside images / out /
+ *           scratch) or RELAX_PNG_OUT_TOO_SMALL
+ * Every read of item n stays inside its rows and every write inside its scratch range and its output slot; a bad item stops
+ * only itself.  No handle and no library state, as relax_png_decode: writer threads may call it at the same time, each with
+ * its own scratch and stream.  The same input gives the same bytes on every call (and the bytes of the host build of
+ * csrc/png_deflate.h).  Returns RELAX_ERR_INVALID for bad arguments, RELAX_ERR_HIP if a launch fails. */
+int relax_png_encode(const uint8_t* images, int64_t images_bytes, const int64_t* items, int N, uint8_t* out, int64_t out_bytes,
+                     uint8_t* scratch, int64_t scratch_bytes, int64_t* lengths, int32_t* status, relax_stream stream);
+/* The same call cut into its launches, for measurement (tools/png_encode_bench.py times the compaction alone on a scratch
+ * that PLAN | BANDS of an earlier call left behind): `passes` is a set of the bits below, run in this order; all of them is
+ * relax_png_encode.  PLACE and COPY read only what the same arguments' PLAN and BANDS wrote into `scratch`. */
+#define RELAX_PNG_ENCODE_PLAN 1          /* items -> bands and their scratch slots (one workgroup) */
+#define RELAX_PNG_ENCODE_BANDS 2         /* filter + deflate, one workgroup per band */
+#define RELAX_PNG_ENCODE_PLACE 4         /* per image: prefix sums, zlib header, Adler-32, length, status */
+#define RELAX_PNG_ENCODE_COPY 8          /* every band to its place in the output slot */
+#define RELAX_PNG_ENCODE_ALL 15
+int relax_png_encode_passes(const uint8_t* images, int64_t images_bytes, const int64_t* items, int N, uint8_t* out,
+                            int64_t out_bytes, uint8_t* scratch, int64_t scratch_bytes, int64_t* lengths, int32_t* status,
+                            int passes, relax_stream stream);
 
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* While enabled, every launch of the contraction kernel (GEMM / implicit-GEMM conv) and of the patch-score

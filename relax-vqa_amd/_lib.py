@@ -87,6 +87,9 @@ PROTOTYPES = {
     "relax_copy_bytes": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, c_vp]),
     "relax_segment_mean": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int, C.c_int, c_vp, C.c_int, c_vp, C.c_int64, C.c_int, c_vp]),
     "relax_png_decode": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, c_vp, C.c_int64, c_vp, C.c_int64, c_vp, c_vp]),
+    "relax_png_encode_bound": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "relax_png_encode": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, c_vp, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, c_vp]),
+    "relax_png_encode_passes": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, c_vp, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, C.c_int, c_vp]),
     "relax_profile_enable": (C.c_int, [c_vp, C.c_int]),
     "relax_profile_read": (C.c_int, [c_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_int64)]),

@@ -65,6 +65,9 @@ class RelaxEngine:
             raise RuntimeError(f"relax_create failed ({rc}): {self.lib.relax_last_error(None).decode()}")
         self.h = h
         self.vit_dim = None
+        # opt-in, default off: (directory, video_name[, numbers]) makes full_clip_vector - the demo driver's pass,
+        # demo_test.evaluate_video_quality - also write every pair's PNG files (visualisation.write_example_set)
+        self.demo_write_png = None
         self.vit_patch = self.vit_ntok = self.vit_npatch = None   # geometry of the loaded ViT (load_vit)
 
     def close(self):
@@ -93,6 +96,22 @@ class RelaxEngine:
         stats['fallback'])."""
         from . import pngdecode
         return pngdecode.decoder_for(self.device).decode(sources, out=out, statuses=statuses, stats=stats)
+
+    def encode_png(self, images, filter=None, stats=None):
+        """uint8 device images -> list of bytes, one PNG file each, as cv2.imwrite (src/main_fragment_layerstack.py:310,325)
+        writes them: BGR as RGB, [H,W] as gray; equal to OpenCV's files on the decoded pixels.  images: [N,H,W,3] or [N,H,W],
+        or a list of [H,W,3] / [H,W] tensors of differing sizes; items may sit in strided slots with packed rows (a view of a
+        [T,2,H,W,3] clip, attention_overlay's frames).  filter: None = per row the filter with the smallest sum of absolute
+        values, or 0..4 for every row.  All images go through one relax_png_encode call on this thread's own stream
+        (pngencode.encoder_for), which has finished when this returns.  Channels other than 1 or 3 and rows over 16 KiB are
+        written by Pillow (counted in stats['fallback'])."""
+        from . import pngencode
+        return pngencode.encoder_for(self.device).encode(images, filter=filter, stats=stats)
+
+    def write_png(self, paths, images, filter=None, stats=None):
+        """encode_png, each file written to its path."""
+        from . import pngencode
+        pngencode.encoder_for(self.device).write(paths, images, filter=filter, stats=stats)
 
     # ---- weights ------------------------------------------------------------------------------
     def _marshal_state_dict(self, sd):
@@ -765,7 +784,11 @@ class RelaxEngine:
         """frames uint8 [T,2,H,W,3] -> fp32 [35203]: the vector src/demo_test.py:171-175 assembles
         (whole-frame ResNet-50 LS | whole-frame ViT | fragment ResNet-50 LS+pool | fragment ViT x2), each part averaged
         over the sampled frames.  Without flow_images the residual fragment is the frame-difference fragment alone.
-        whole_frames uint8 [Ts,H,W,3]: all sampled frames when the last one has no pair (see full_clip_vectors)."""
+        whole_frames uint8 [Ts,H,W,3]: all sampled frames when the last one has no pair (see full_clip_vectors).
+        With self.demo_write_png set, the pairs' files are written too (src/demo_test.py:120,135); the vector is the same."""
+        if self.demo_write_png is not None:
+            from . import visualisation
+            visualisation.write_for_driver(self, frames, self.demo_write_png, flow=flow or flow_images is not None)
         return self.full_clip_vectors([frames], flow=flow, flow_images=None if flow_images is None else [flow_images],
                                       whole_frames=None if whole_frames is None else [whole_frames])[0]
 

@@ -60,11 +60,16 @@ def process_patches(original_path, residual_name, residual, patch_size=16, targe
     return original_path.replace(".png", suffix), frag, positions
 
 
-def fragment_pair(img_original, img_next, top_n=196):
+def fragment_pair(img_original, img_next, top_n=196, write_png=None):
     """Fused form of cv2.absdiff + process_patches('frame_diff') + get_original_frame_patches (reference :302-310).
-    -> (diff_fragment, original_fragment, positions)"""
+    -> (diff_fragment, original_fragment, positions).  write_png (opt-in, default off): (directory, video_name, [n]) also
+    writes the pair's files as the reference's cv2.imwrite calls leave them (:310, :325; visualisation.write_example_set,
+    encoded on the GPU); the return value is the same."""
     frames = torch.from_numpy(np.stack([_u8(img_original), _u8(img_next)])[None])
     out = runtime.get_engine().fragment_pairs(frames, top_n=top_n)
+    if write_png is not None:
+        from . import visualisation
+        visualisation.write_for_driver(runtime.get_engine(), frames, write_png)
     n = int(out["counts"][0])
     pos = [(int(y), int(x)) for y, x in out["positions"][0, :n].cpu().numpy()]
     return out["diff_frag"][0].cpu().numpy(), out["ori_frag"][0].cpu().numpy(), pos

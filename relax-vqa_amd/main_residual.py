@@ -59,6 +59,12 @@ def get_deep_feature(network_name, video_name, image_path, qp, layer_name):
     return png_path, npy_path, _activation(network_name, runtime.to_model_input(image, network_name), layer_name)
 
 
+# Opt-in, default off: (directory, video_name, [n]) makes process_pair also write the pair's files as the reference's cv2.imwrite
+# calls leave them (:230, :241; visualisation.write_example_set, encoded on the GPU).  A module flag, not a keyword: process_pair
+# keeps the reference's parameter list.  Its return value does not change.
+WRITE_PNG = None
+
+
 def process_pair(img_original, img_next, network_name, residual_name, layer_name="pool"):
     """One (frame, next frame) pair -> residual_npy, the activation the loop body at reference :221-252 appends."""
     if residual_name not in RESIDUAL_NAMES:
@@ -67,6 +73,9 @@ def process_pair(img_original, img_next, network_name, residual_name, layer_name
     eng = runtime.get_engine()
     frames = torch.from_numpy(np.stack([np.ascontiguousarray(img_original), np.ascontiguousarray(img_next)])[None])
     vit = network_name == "vit"
+    if WRITE_PNG is not None:
+        from . import visualisation
+        visualisation.write_for_driver(eng, frames, WRITE_PNG)
     if residual_name == "frame_diff":
         bil, lan, _ = eng.residual_resize(frames, bilinear=not vit, lanczos=vit)
     else:

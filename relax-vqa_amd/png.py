@@ -1,5 +1,5 @@
-"""PNG container parsing for the GPU decoder (csrc/png_decode.hip): the signature, IHDR, the IDAT payloads joined into one
-zlib stream, IEND, and every chunk's CRC.  Ancillary chunks (gAMA, cHRM, cICP, pHYs, tEXt, ...) are skipped, as
+"""The PNG container around the GPU decoder and encoder (csrc/png_decode.hip, csrc/png_encode.hip).  parse(): the signature,
+IHDR, the IDAT payloads joined into one zlib stream, IEND, and every chunk's CRC.  build(): the file around a zlib stream.  Ancillary chunks (gAMA, cHRM, cICP, pHYs, tEXt, ...) are skipped, as
 cv2.imread and the Pillow path (sampling.read_frame_bgr) ignore them.  Pure Python over chunk headers: the CRCs run in zlib."""
 import struct
 import zlib
@@ -76,6 +76,19 @@ def parse(data, name="<bytes>"):
     return PngInfo(w, h, depth, ctype_, interlace, zdata)
 
 
+def _chunk(ctype, body):
+    return struct.pack(">I", len(body)) + ctype + bytes(body) + struct.pack(">I", zlib.crc32(body, zlib.crc32(ctype)))
+
+
+def build(zdata, width, height, color_type):
+    """A zlib stream of filtered rows (relax_png_encode's output) -> the bytes of an 8-bit, non-interlaced PNG file: signature,
+    IHDR, one IDAT, IEND.  The CRCs run on the host in zlib (a v1 choice: DESIGN.md section 8 has its measured share)."""
+    if color_type not in (0, 2) or width < 1 or height < 1:
+        raise PngError(f"cannot build a {width}x{height} PNG of colour type {color_type}")
+    return b"".join((SIGNATURE, _chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, color_type, 0, 0, 0)),
+                     _chunk(b"IDAT", zdata), _chunk(b"IEND", b"")))
+
+
 def read_source(src):
     """A file path or the bytes of a file -> (name for messages, bytes)."""
     if isinstance(src, (bytes, bytearray, memoryview)):
@@ -99,6 +112,7 @@ STATUS = {
     11: "inflated data shorter than H*(1+W*C)",
     12: "unknown PNG row filter",
     13: "Adler-32 mismatch",
+    14: "encode: the output slot is shorter than the stream",
 }
 
 
