@@ -21,7 +21,9 @@
  *     one handle must be ordered: issue them on ONE stream (or order the streams with
  *     events); two backbone calls running concurrently on different streams would race.
  *   - images are uint8 HWC **BGR** exactly as cv2.imread holds them
- *     (src/main_fragment_layerstack.py:295-296); fragments are 224x224x3.
+ *     (src/main_fragment_layerstack.py:295-296); fragments are 224x224x3 (the
+ *     *_ex fragment entry points cut target_size x target_size x 3 canvases; the
+ *     backbones take 224 only).
  */
 #ifndef RELAX_HIP_H
 #define RELAX_HIP_H
@@ -34,10 +36,14 @@ extern "C" {
 
 #define RELAX_ABI_VERSION 1
 
+/* the reference's literals: the geometry of the entry points without a patch_size / target_size argument, and the only canvas
+ * the backbones take.  The *_ex fragment entry points take patch_size 8 / 16 / 32 and any canvas up to RELAX_MAX_TARGET. */
 #define RELAX_PATCH 16           /* patch_size  (main_fragment_layerstack.py:298) */
 #define RELAX_TARGET 224         /* target_size (main_fragment_layerstack.py:297) */
 #define RELAX_TOP_N 196          /* top_n = (224/16)^2 (main_fragment_layerstack.py:299) */
 #define RELAX_FRAG_BYTES (224 * 224 * 3)
+#define RELAX_MAX_PATCH 32       /* 32*32*3*255 = 783360 < 2^20, the range of the selection's two 10-bit radix levels */
+#define RELAX_MAX_TARGET 448     /* (448/8)^2 = 3136 slots at most */
 #define RELAX_RN50_LAYER_STACK_DIM 13120 /* 64+3*256+4*512+4*1024+3*2048 */
 #define RELAX_RN50_POOL_DIM 2051         /* 2048 + mean,max,std */
 #define RELAX_RN50_NUM_TAPS 15
@@ -166,6 +172,24 @@ int relax_fragment_pairs(relax_handle* h, const uint8_t* orig, const uint8_t* ne
                          int T, int H, int W, int top_n, int32_t* positions, int32_t* counts,
                          uint8_t* ori_frag, uint8_t* diff_frag, uint32_t* scores, relax_stream stream);
 
+/* The same with the reference's patch_size / target_size arguments (get_patch_diff :177, extract_important_patches :191,
+ * get_original_frame_patches :212, process_patches :232 all take them; main_residual_fragment.py:173-214 likewise).
+ * relax_fragment_pairs = this at (RELAX_PATCH, RELAX_TARGET), byte for byte.
+ *   patch_size  : 8, 16 or 32.  A score sums patch_size^2 * 3 bytes; the selection's two 10-bit radix levels hold 2^20 and
+ *                 32*32*3*255 = 783360 is the largest that fits, so anything above 32 is refused, as is any other value
+ *   target_size : a positive multiple of patch_size, at most RELAX_MAX_TARGET; slots = (target_size / patch_size)^2
+ *   top_n       : in [0, slots]
+ *   positions   : int32 [T,slots,2], (-1,-1) past counts[t];  counts : int32 [T] = min(top_n, (H/patch_size)*(W/patch_size))
+ *   ori_frag, diff_frag : uint8 [T,target_size,target_size,3], patch k at tile (k / (target/patch), k % (target/patch)), zero
+ *                 tiles past counts[t] (may be NULL)
+ *   scores      : uint32 [T,(H/patch_size)*(W/patch_size)] (may be NULL)
+ * A rejected geometry returns RELAX_ERR_INVALID with the offending value in the message and launches nothing.
+ * Rows are read 16 bytes per lane when W*3, pair_stride and both pointers are multiples of 16 (at patch_size 8 every third
+ * chunk is split between two patches; columns past the last whole patch are not read), byte by byte otherwise; same results. */
+int relax_fragment_pairs_ex(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride,
+                            int T, int H, int W, int patch_size, int target_size, int top_n, int32_t* positions,
+                            int32_t* counts, uint8_t* ori_frag, uint8_t* diff_frag, uint32_t* scores, relax_stream stream);
+
 /* Same selection on an already-computed residual image (the optical-flow image of
  * process_patches('optical_flow'), main_fragment_layerstack.py:319; main_residual_fragment.py:206-214).
  *   image: uint8 [H,W,3] per item, item t at image + t*item_stride. */
@@ -173,9 +197,21 @@ int relax_fragment_image(relax_handle* h, const uint8_t* image, int64_t item_str
                          int top_n, int32_t* positions, int32_t* counts, uint8_t* frag, uint32_t* scores,
                          relax_stream stream);
 
+/* process_patches(.., patch_size, target_size, top_n) on a residual image (main_fragment_layerstack.py:232-240,
+ * main_residual_fragment.py:206-214): relax_fragment_image with the geometry arguments of relax_fragment_pairs_ex. */
+int relax_fragment_image_ex(relax_handle* h, const uint8_t* image, int64_t item_stride, int T, int H, int W,
+                            int patch_size, int target_size, int top_n, int32_t* positions, int32_t* counts, uint8_t* frag,
+                            uint32_t* scores, relax_stream stream);
+
 /* get_original_frame_patches (main_fragment_layerstack.py:212-230) with given positions. */
 int relax_gather_patches(relax_handle* h, const uint8_t* image, int64_t item_stride, int T, int H, int W,
                          const int32_t* positions, const int32_t* counts, uint8_t* frag, relax_stream stream);
+/* get_original_frame_patches(original_frame, positions, patch_size, target_size) (main_fragment_layerstack.py:212-230):
+ * positions int32 [T,slots,2], frag uint8 [T,target_size,target_size,3], geometry as in relax_fragment_pairs_ex.  The
+ * positions are the caller's: a slot outside the (H/patch_size) x (W/patch_size) grid, negative ones included, gives a zero tile. */
+int relax_gather_patches_ex(relax_handle* h, const uint8_t* image, int64_t item_stride, int T, int H, int W,
+                            int patch_size, int target_size, const int32_t* positions, const int32_t* counts, uint8_t* frag,
+                            relax_stream stream);
 
 /* merge_fragments = cv2.addWeighted(a,.5,b,.5,0) (main_fragment_layerstack.py:242-245):
  * round-half-to-even(0.5a+0.5b) on uint8. n_bytes elements. */
@@ -197,6 +233,14 @@ int relax_merge_fragments(relax_handle* h, const uint8_t* a, const uint8_t* b, u
 int relax_attention_overlay(relax_handle* h, const uint8_t* frames, int64_t frame_stride, int T, int H, int W,
                             const int32_t* positions, const int32_t* counts, const float* patch_values,
                             const uint8_t* lut_bgr, uint8_t* out, relax_stream stream);
+/* map_attention_to_original(original_frame, attention_map, positions, patch_size) (src/demo_visual.py:12-25) with its patch_size
+ * argument: positions int32 [T,slots,2] in units of patch_size x patch_size patches, patch_values fp32 [T,slots]; patch_size 8, 16
+ * or 32, slots in [1, 3136].  Same semantics: a later slot on the same patch wins, out-of-range positions paint nothing, max over
+ * the whole frame with zeros included, level 0 for max <= 0, negative and NaN values.  relax_attention_overlay = this at
+ * (RELAX_PATCH, RELAX_TOP_N), byte for byte. */
+int relax_attention_overlay_ex(relax_handle* h, const uint8_t* frames, int64_t frame_stride, int T, int H, int W,
+                               int patch_size, int slots, const int32_t* positions, const int32_t* counts,
+                               const float* patch_values, const uint8_t* lut_bgr, uint8_t* out, relax_stream stream);
 
 /* ---- optical flow --------------------------------------------------------------- */
 /* Replaces cv2.calcOpticalFlowFarneback(gray(orig), gray(next), None, 0.5, 3, 15, 3, 5, 1.2, 0) and flow_to_rgb

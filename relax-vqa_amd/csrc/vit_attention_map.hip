@@ -4,16 +4,17 @@
 //   src/extractor/visualise_vit.py:241-250   get_last_selfattention: blocks 0..10, then block 11's softmax(q k^T / 8)
 //   src/extractor/visualise_vit.py:123-127   Block.forward(return_attention=True)
 //   src/extractor/visualise_vit.py:353-369   visualize_attention: attn[0, :, 0, 1:] (the CLS query against the 196 patches)
-//   src/demo_visual.py:12-25                 map_attention_to_original: per-patch values painted at their source positions,
-//                                            / max * 255 -> uint8, applyColorMap(JET), addWeighted(frame, .6, heat, .4, 0)
+//   src/demo_visual.py:12-25                 map_attention_to_original(.., patch_size): per-patch values painted at their source
+//                                            positions, / max * 255 -> uint8, applyColorMap(JET), addWeighted(frame, .6, heat, .4, 0);
+//                                            patch_size 8 / 16 / 32 and any slot count up to (448 / 8)^2 (relax_attention_overlay_ex)
 #include "relax_internal.h"
 
 namespace relax {
 
 constexpr int AM_KPT = 4;               // keys per thread: thread j owns keys j, j + 256, ... (up to 1024 tokens; 197 tokens: one key each)
 constexpr int AM_HD = 64;              // head_dim of vit_tiny / vit_small / vit_base: the scale 64^-0.5 is exactly 1/8
-constexpr int OV_P = RELAX_PATCH;      // 16
-constexpr int OV_SLOTS = RELAX_TOP_N;  // 196
+constexpr int OV_MAX_SLOTS = (448 / 8) * (448 / 8);   // 3136: the largest canvas of the fragment stage at its smallest patch
+constexpr int OV_SPT = (OV_MAX_SLOTS + 255) / 256;    // slots per thread of overlay_levels: thread j owns slots j, j + 256, ...
 
 // ---- 1. CLS-row attention ---------------------------------------------------------------------------------------------------
 // value j of a qkv row: fp32 rows [3*dim], or two fp16 planes (csrc/h2.h: chunks of [16 hi][16 lo], value = (hi + lo) / s_qkv;
@@ -118,38 +119,54 @@ int launch_vit_cls_attention(relax_handle* h, const void* qkv, bool planes, floa
 // so it includes 0 unless the painted patches cover every pixel; level = trunc((double)v / (double)max * 255) as numpy computes it
 // on the reference's float64 array.  max <= 0 (undefined in the reference): every level is 0; so are negative and NaN values.
 __global__ __launch_bounds__(256) void overlay_levels(const int32_t* __restrict__ positions, const int32_t* __restrict__ counts,
-                                                      const float* __restrict__ vals, int ph, int pw, int edge, uint8_t* __restrict__ lvl) {
-    __shared__ int key[OV_SLOTS];
+                                                      const float* __restrict__ vals, int slots, int ph, int pw, int edge,
+                                                      uint8_t* __restrict__ lvl) {
+    extern __shared__ int key[];   // [slots]: the flat patch a slot paints, -1 for none
     __shared__ float red[4];
-    const int t = blockIdx.x, k = threadIdx.x;
+    const int t = blockIdx.x;
     const int npatch = ph * pw;
     uint8_t* L = lvl + (int64_t)t * npatch;
     const int cnt = counts[t];
-    int my = -1;
-    float v = 0.f;
-    if (k < OV_SLOTS && k < cnt) {
-        const int y = positions[((int64_t)t * OV_SLOTS + k) * 2], x = positions[((int64_t)t * OV_SLOTS + k) * 2 + 1];
-        if ((unsigned)y < (unsigned)ph && (unsigned)x < (unsigned)pw) {
-            my = y * pw + x;
-            v = vals[(int64_t)t * OV_SLOTS + k];
+    for (int k = threadIdx.x; k < slots; k += 256) {
+        int my = -1;
+        if (k < cnt) {
+            const int y = positions[((int64_t)t * slots + k) * 2], x = positions[((int64_t)t * slots + k) * 2 + 1];
+            if ((unsigned)y < (unsigned)ph && (unsigned)x < (unsigned)pw) my = y * pw + x;
+        }
+        key[k] = my;
+    }
+    for (int i = threadIdx.x; i < npatch; i += 256) L[i] = 0;
+    __syncthreads();
+    // a slot is final when no later slot names its patch
+    uint32_t final_mask = 0;
+    float lmax = -INFINITY, lpainted = 0.f;
+#pragma unroll 1
+    for (int j = 0; j < OV_SPT; ++j) {
+        const int k = threadIdx.x + 256 * j;
+        if (k >= slots) break;
+        const int my = key[k];
+        bool final_ = my >= 0;
+        for (int k2 = k + 1; k2 < slots && final_; ++k2) final_ = key[k2] != my;
+        if (final_) {
+            final_mask |= 1u << j;
+            lmax = fmaxf(lmax, vals[(int64_t)t * slots + k]);
+            lpainted += 1.f;
         }
     }
-    if (k < OV_SLOTS) key[k] = my;
-    for (int i = k; i < npatch; i += 256) L[i] = 0;
-    __syncthreads();
-    bool final_ = my >= 0;
-    for (int k2 = k + 1; k2 < OV_SLOTS && final_; ++k2) final_ = key[k2] != my;
-    float mx = block_reduce_256(final_ ? v : -INFINITY, red, true);
-    const float painted = block_reduce_256(final_ ? 1.f : 0.f, red, false);
+    float mx = block_reduce_256(lmax, red, true);
+    const float painted = block_reduce_256(lpainted, red, false);
     if (edge || painted < (float)npatch) mx = fmaxf(mx, 0.f);
-    if (final_) {
+#pragma unroll 1
+    for (int j = 0; j < OV_SPT; ++j) {
+        if (!((final_mask >> j) & 1u)) continue;
+        const int k = threadIdx.x + 256 * j;
         int l = 0;
         if (mx > 0.f) {
-            const double q = (double)v / (double)mx * 255.0;
+            const double q = (double)vals[(int64_t)t * slots + k] / (double)mx * 255.0;
             l = q > 0.0 ? (int)q : 0;
             l = l > 255 ? 255 : l;
         }
-        L[my] = (uint8_t)l;
+        L[key[k]] = (uint8_t)l;
     }
 }
 
@@ -159,41 +176,45 @@ __device__ inline uint32_t blend_u8x4(uint32_t a, uint32_t b4p5_0, uint32_t b4p5
            (((((a >> 16) & 255u) * 6u + b4p5_2) / 10u) << 16) | ((((a >> 24) * 6u + b4p5_3) / 10u) << 24);
 }
 
-// W % 16 == 0, 16-byte aligned frames and rows: one thread per 16 pixels of a row (48 bytes = 3 x 16-byte loads and stores),
-// which is exactly one patch column, so one level and one colour per thread
+// W % 16 == 0, 16-byte aligned frames and rows: one thread per 16 pixels of a row (48 bytes = 3 x 16-byte loads and stores).
+// psh = log2(patch size).  At 16 (and inside one patch at 32) that is one patch column: one level and one colour per thread; at 8 the
+// 16 pixels are two patches - bytes 0..23 take the level of patch 2g (colours c*), bytes 24..47 that of patch 2g+1 (colours d*).
 __global__ __launch_bounds__(256) void overlay_blend16(const uint8_t* __restrict__ frames, int64_t frame_stride, int H, int W,
-                                                       int ph, int pw, const uint8_t* __restrict__ lvl, const uint8_t* __restrict__ lut,
-                                                       uint8_t* __restrict__ out) {
+                                                       int psh, int ph, int pw, const uint8_t* __restrict__ lvl,
+                                                       const uint8_t* __restrict__ lut, uint8_t* __restrict__ out) {
     const int t = blockIdx.y;
-    const int gw = W / OV_P;
+    const int gw = W / 16;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= H * gw) return;
     const int y = i / gw, g = i - y * gw;
-    const int py = y / OV_P;
-    const int l = (py < ph && g < pw) ? lvl[((int64_t)t * ph + py) * pw + g] : 0;
+    const int py = y >> psh;
+    const int pxa = (g * 16) >> psh, pxb = (g * 16 + 8) >> psh;
+    const int l = (py < ph && pxa < pw) ? lvl[((int64_t)t * ph + py) * pw + pxa] : 0;
+    const int lb = (py < ph && pxb < pw) ? lvl[((int64_t)t * ph + py) * pw + pxb] : 0;
     const uint32_t c0 = 4u * lut[3 * l] + 5u, c1 = 4u * lut[3 * l + 1] + 5u, c2 = 4u * lut[3 * l + 2] + 5u;
-    const int64_t off = ((int64_t)y * W + (int64_t)g * OV_P) * 3;
+    const uint32_t d0 = 4u * lut[3 * lb] + 5u, d1 = 4u * lut[3 * lb + 1] + 5u, d2 = 4u * lut[3 * lb + 2] + 5u;
+    const int64_t off = ((int64_t)y * W + (int64_t)g * 16) * 3;
     const uint4* src = reinterpret_cast<const uint4*>(frames + t * frame_stride + off);
     uint4* dst = reinterpret_cast<uint4*>(out + (int64_t)t * H * W * 3 + off);
     const uint4 a = src[0], b = src[1], c = src[2];
     // byte 16 u + 4 w + j of the 48 has channel (16 u + 4 w + j) % 3
     dst[0] = make_uint4(blend_u8x4(a.x, c0, c1, c2, c0), blend_u8x4(a.y, c1, c2, c0, c1), blend_u8x4(a.z, c2, c0, c1, c2),
                         blend_u8x4(a.w, c0, c1, c2, c0));
-    dst[1] = make_uint4(blend_u8x4(b.x, c1, c2, c0, c1), blend_u8x4(b.y, c2, c0, c1, c2), blend_u8x4(b.z, c0, c1, c2, c0),
-                        blend_u8x4(b.w, c1, c2, c0, c1));
-    dst[2] = make_uint4(blend_u8x4(c.x, c2, c0, c1, c2), blend_u8x4(c.y, c0, c1, c2, c0), blend_u8x4(c.z, c1, c2, c0, c1),
-                        blend_u8x4(c.w, c2, c0, c1, c2));
+    dst[1] = make_uint4(blend_u8x4(b.x, c1, c2, c0, c1), blend_u8x4(b.y, c2, c0, c1, c2), blend_u8x4(b.z, d0, d1, d2, d0),
+                        blend_u8x4(b.w, d1, d2, d0, d1));
+    dst[2] = make_uint4(blend_u8x4(c.x, d2, d0, d1, d2), blend_u8x4(c.y, d0, d1, d2, d0), blend_u8x4(c.z, d1, d2, d0, d1),
+                        blend_u8x4(c.w, d2, d0, d1, d2));
 }
 
 // any shape / alignment: one thread per pixel
 __global__ __launch_bounds__(256) void overlay_blend1(const uint8_t* __restrict__ frames, int64_t frame_stride, int H, int W,
-                                                      int ph, int pw, const uint8_t* __restrict__ lvl, const uint8_t* __restrict__ lut,
-                                                      uint8_t* __restrict__ out) {
+                                                      int psh, int ph, int pw, const uint8_t* __restrict__ lvl,
+                                                      const uint8_t* __restrict__ lut, uint8_t* __restrict__ out) {
     const int t = blockIdx.y;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)H * W) return;
     const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
-    const int py = y / OV_P, px = x / OV_P;
+    const int py = y >> psh, px = x >> psh;
     const int l = (py < ph && px < pw) ? lvl[((int64_t)t * ph + py) * pw + px] : 0;
     const uint8_t* a = frames + t * frame_stride + i * 3;
     uint8_t* o = out + ((int64_t)t * H * W + i) * 3;
@@ -209,33 +230,45 @@ using namespace relax;
 
 extern "C" {
 
-int relax_attention_overlay(relax_handle* h, const uint8_t* frames, int64_t frame_stride, int T, int H, int W,
-                            const int32_t* positions, const int32_t* counts, const float* patch_values,
-                            const uint8_t* lut_bgr, uint8_t* out, relax_stream stream) {
+int relax_attention_overlay_ex(relax_handle* h, const uint8_t* frames, int64_t frame_stride, int T, int H, int W, int patch_size,
+                               int slots, const int32_t* positions, const int32_t* counts, const float* patch_values,
+                               const uint8_t* lut_bgr, uint8_t* out, relax_stream stream) {
     if (!h) return RELAX_ERR_INVALID;
     RELAX_REQUIRE(h, frames && positions && counts && patch_values && lut_bgr && out, "relax_attention_overlay: NULL pointer");
     RELAX_REQUIRE(h, T > 0 && H > 0 && W > 0, "relax_attention_overlay: bad shape T=%d H=%d W=%d", T, H, W);
+    RELAX_REQUIRE(h, patch_size == 8 || patch_size == 16 || patch_size == 32, "relax_attention_overlay: patch_size=%d is not built (8, 16 or 32)",
+                  patch_size);
+    RELAX_REQUIRE(h, slots > 0 && slots <= OV_MAX_SLOTS, "relax_attention_overlay: slots=%d must be in [1,%d]", slots, OV_MAX_SLOTS);
     RELAX_REQUIRE(h, frame_stride >= (int64_t)H * W * 3 || T == 1, "relax_attention_overlay: frame stride smaller than a frame");
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ph = H / OV_P, pw = W / OV_P;
+    const int psh = patch_size == 8 ? 3 : patch_size == 16 ? 4 : 5;
+    const int ph = H >> psh, pw = W >> psh;
     const size_t map_bytes = (size_t)T * ph * pw;
     RELAX_TRY(ensure_buf(h, h->scratch, map_bytes > 0 ? map_bytes : 16));
     uint8_t* lvl = static_cast<uint8_t*>(h->scratch.p);
-    const int edge = (H % OV_P) != 0 || (W % OV_P) != 0;
-    hipLaunchKernelGGL(overlay_levels, dim3(T), dim3(256), 0, s, positions, counts, patch_values, ph, pw, edge, lvl);
-    const bool vec = W % OV_P == 0 && (frame_stride % 16 == 0 || T == 1) && aligned16(frames) && aligned16(out);
+    const int edge = (H % patch_size) != 0 || (W % patch_size) != 0;
+    hipLaunchKernelGGL(overlay_levels, dim3(T), dim3(256), sizeof(int) * (size_t)slots, s, positions, counts, patch_values, slots, ph, pw,
+                       edge, lvl);
+    const bool vec = W % 16 == 0 && (frame_stride % 16 == 0 || T == 1) && aligned16(frames) && aligned16(out);
     if (vec) {
-        const int64_t items = (int64_t)H * (W / OV_P);
-        hipLaunchKernelGGL(overlay_blend16, dim3((unsigned)((items + 255) / 256), T), dim3(256), 0, s, frames, frame_stride, H, W, ph, pw,
-                           lvl, lut_bgr, out);
+        const int64_t items = (int64_t)H * (W / 16);
+        hipLaunchKernelGGL(overlay_blend16, dim3((unsigned)((items + 255) / 256), T), dim3(256), 0, s, frames, frame_stride, H, W, psh, ph,
+                           pw, lvl, lut_bgr, out);
     } else {
         const int64_t items = (int64_t)H * W;
-        hipLaunchKernelGGL(overlay_blend1, dim3((unsigned)((items + 255) / 256), T), dim3(256), 0, s, frames, frame_stride, H, W, ph, pw,
-                           lvl, lut_bgr, out);
+        hipLaunchKernelGGL(overlay_blend1, dim3((unsigned)((items + 255) / 256), T), dim3(256), 0, s, frames, frame_stride, H, W, psh, ph,
+                           pw, lvl, lut_bgr, out);
     }
     RELAX_HIP_CHECK(h, hipGetLastError());
     return RELAX_OK;
+}
+
+int relax_attention_overlay(relax_handle* h, const uint8_t* frames, int64_t frame_stride, int T, int H, int W,
+                            const int32_t* positions, const int32_t* counts, const float* patch_values,
+                            const uint8_t* lut_bgr, uint8_t* out, relax_stream stream) {
+    return relax_attention_overlay_ex(h, frames, frame_stride, T, H, W, RELAX_PATCH, RELAX_TOP_N, positions, counts, patch_values, lut_bgr,
+                                      out, stream);
 }
 
 }  // extern "C"

@@ -9,26 +9,28 @@ import numpy as np
 import torch
 
 from . import runtime
-from .engine import TOP_N
+from .fragment_geometry import fragment_geometry
 from .extractor import visualise_vit
 
 
 def map_attention_to_original(original_frame, attention_map, positions, patch_size, lut=None):
     """original_frame uint8 [H,W,3] BGR; attention_map: one value per slot (patch_means.flatten()); positions: (y, x) patch
-    coordinates per slot ((-1, -1) or out-of-range slots paint nothing) -> uint8 [H,W,3].  lut: see colormap.py."""
-    if patch_size != 16:
-        raise NotImplementedError("only patch_size 16 is built")
+    coordinates per slot, in units of patch_size (8, 16 or 32) pixels ((-1, -1) or out-of-range slots paint nothing) -> uint8
+    [H,W,3].  lut: see colormap.py.  The slots of a 224 x 224 canvas are taken ((224 / patch_size)^2: 784 / 196 / 49); a longer list
+    is cut there, as it was at 196.  With a ViT loaded, patch_size has to go with it (RelaxEngine.attention_overlay)."""
+    geo = fragment_geometry(patch_size, 224)
     eng = runtime.get_engine()
     values = np.asarray(attention_map, dtype=np.float32).reshape(-1)
     pos = np.asarray(positions, dtype=np.int64).reshape(-1, 2)
-    count = min(len(values), len(pos), TOP_N)          # zip(positions, attention_map) stops at the shorter one
-    pos_full = np.full((1, TOP_N, 2), -1, dtype=np.int32)
-    val_full = np.zeros((1, TOP_N), dtype=np.float32)
+    slots = geo.slots
+    count = min(len(values), len(pos), slots)          # zip(positions, attention_map) stops at the shorter one
+    pos_full = np.full((1, slots, 2), -1, dtype=np.int32)
+    val_full = np.zeros((1, slots), dtype=np.float32)
     pos_full[0, :count] = np.clip(pos[:count], -1, np.iinfo(np.int32).max)
     val_full[0, :count] = values[:count]
     frame = torch.from_numpy(np.ascontiguousarray(original_frame)[None])
     out = eng.attention_overlay(frame, torch.from_numpy(pos_full), torch.tensor([count], dtype=torch.int32),
-                                torch.from_numpy(val_full), lut=lut)
+                                torch.from_numpy(val_full), lut=lut, patch_size=geo.patch_size)
     return out[0].cpu().numpy()
 
 

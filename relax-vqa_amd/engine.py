@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib, colormap
+from .fragment_geometry import backbone_geometry, fragment_geometry, overlay_slot_rule
 
 LAYER_STACK_DIM = 13120
 RN50_POOL_DIM = 2051
@@ -289,61 +290,78 @@ class RelaxEngine:
             raise TypeError(f"expected uint8, got {a.dtype}")
         return a.contiguous()
 
-    def fragment_pairs(self, frames, top_n=TOP_N, want_scores=False, out_ori=None, out_diff=None):
+    def fragment_pairs(self, frames, top_n=TOP_N, want_scores=False, out_ori=None, out_diff=None, patch_size=16, target_size=TARGET):
         """frames: uint8 [T,2,H,W,3] BGR (frames[t,0] = sampled frame, frames[t,1] = the next one).
         -> dict(positions int32 [T,196,2], counts int32 [T], ori_frag, diff_frag uint8 [T,224,224,3][, scores])
-        out_ori / out_diff: optional preallocated [T,224,224,3] uint8 views (slices of a batch buffer) to write into."""
+        out_ori / out_diff: optional preallocated [T,224,224,3] uint8 views (slices of a batch buffer) to write into.
+        patch_size 8 / 16 / 32, target_size a multiple of it up to 448 (fragment_geometry.py): slots = (target_size / patch_size)^2,
+        positions [T,slots,2], canvases [T,target_size,target_size,3], scores [T,H//patch_size,W//patch_size]; top_n=None = all slots."""
+        geo = fragment_geometry(patch_size, target_size)      # (top_n out of range: refused by the library, a RuntimeError)
+        top_n = geo.slots if top_n is None else int(top_n)
         frames = self._dev_u8(frames)
         if frames.dim() != 5 or frames.shape[1] != 2 or frames.shape[4] != 3:
             raise ValueError(f"frames must be [T,2,H,W,3], got {tuple(frames.shape)}")
         T, _, H, W, _ = frames.shape
         dev = self.device
-        positions = torch.empty((T, TOP_N, 2), dtype=torch.int32, device=dev)
+        P, tgt = geo.patch_size, geo.target_size
+        positions = torch.empty((T, geo.slots, 2), dtype=torch.int32, device=dev)
         counts = torch.empty((T,), dtype=torch.int32, device=dev)
-        ori = out_ori if out_ori is not None else torch.empty((T, TARGET, TARGET, 3), dtype=torch.uint8, device=dev)
-        diff = out_diff if out_diff is not None else torch.empty((T, TARGET, TARGET, 3), dtype=torch.uint8, device=dev)
+        ori = out_ori if out_ori is not None else torch.empty((T, tgt, tgt, 3), dtype=torch.uint8, device=dev)
+        diff = out_diff if out_diff is not None else torch.empty((T, tgt, tgt, 3), dtype=torch.uint8, device=dev)
         for o in (ori, diff):
-            if o.dtype != torch.uint8 or tuple(o.shape) != (T, TARGET, TARGET, 3) or not o.is_contiguous():
-                raise ValueError("fragment_pairs: output buffers must be contiguous uint8 [T,224,224,3]")
-        scores = torch.empty((T, (H // 16) * (W // 16)), dtype=torch.int32, device=dev) if want_scores else None
+            if o.dtype != torch.uint8 or tuple(o.shape) != (T, tgt, tgt, 3) or not o.is_contiguous():
+                raise ValueError(f"fragment_pairs: output buffers must be contiguous uint8 [T,{tgt},{tgt},3]")
+        scores = torch.empty((T, (H // P) * (W // P)), dtype=torch.int32, device=dev) if want_scores else None
         frame_bytes = H * W * 3
         base = frames.data_ptr()
-        rc = self.lib.relax_fragment_pairs(self.h, C.c_void_p(base), C.c_void_p(base + frame_bytes), 2 * frame_bytes,
-                                           T, H, W, int(top_n), _ptr(positions), _ptr(counts), _ptr(ori), _ptr(diff),
-                                           _ptr(scores), _stream())
+        rc = self.lib.relax_fragment_pairs_ex(self.h, C.c_void_p(base), C.c_void_p(base + frame_bytes), 2 * frame_bytes,
+                                              T, H, W, P, tgt, top_n, _ptr(positions), _ptr(counts), _ptr(ori), _ptr(diff),
+                                              _ptr(scores), _stream())
         self._check(rc, "relax_fragment_pairs")
         out = dict(positions=positions, counts=counts, ori_frag=ori, diff_frag=diff)
         if want_scores:
-            out["scores"] = scores.view(T, H // 16, W // 16)
+            out["scores"] = scores.view(T, H // P, W // P)
         return out
 
-    def fragment_image(self, images, top_n=TOP_N, want_scores=False, out=None):
-        """images: uint8 [T,H,W,3] residual images (e.g. flow_to_rgb output). -> dict(positions, counts, frag[, scores])"""
+    def fragment_image(self, images, top_n=TOP_N, want_scores=False, out=None, patch_size=16, target_size=TARGET):
+        """images: uint8 [T,H,W,3] residual images (e.g. flow_to_rgb output). -> dict(positions, counts, frag[, scores]);
+        patch_size / target_size / top_n=None as in fragment_pairs."""
+        geo = fragment_geometry(patch_size, target_size)      # (top_n out of range: refused by the library, a RuntimeError)
+        top_n = geo.slots if top_n is None else int(top_n)
         images = self._dev_u8(images)
         if images.dim() != 4 or images.shape[3] != 3:
             raise ValueError(f"images must be [T,H,W,3], got {tuple(images.shape)}")
         T, H, W, _ = images.shape
         dev = self.device
-        positions = torch.empty((T, TOP_N, 2), dtype=torch.int32, device=dev)
+        P, tgt = geo.patch_size, geo.target_size
+        positions = torch.empty((T, geo.slots, 2), dtype=torch.int32, device=dev)
         counts = torch.empty((T,), dtype=torch.int32, device=dev)
-        frag = out if out is not None else torch.empty((T, TARGET, TARGET, 3), dtype=torch.uint8, device=dev)
-        scores = torch.empty((T, (H // 16) * (W // 16)), dtype=torch.int32, device=dev) if want_scores else None
-        rc = self.lib.relax_fragment_image(self.h, _ptr(images), H * W * 3, T, H, W, int(top_n), _ptr(positions),
-                                           _ptr(counts), _ptr(frag), _ptr(scores), _stream())
+        frag = out if out is not None else torch.empty((T, tgt, tgt, 3), dtype=torch.uint8, device=dev)
+        if frag.dtype != torch.uint8 or tuple(frag.shape) != (T, tgt, tgt, 3) or not frag.is_contiguous():
+            raise ValueError(f"fragment_image: the output buffer must be contiguous uint8 [T,{tgt},{tgt},3]")
+        scores = torch.empty((T, (H // P) * (W // P)), dtype=torch.int32, device=dev) if want_scores else None
+        rc = self.lib.relax_fragment_image_ex(self.h, _ptr(images), H * W * 3, T, H, W, P, tgt, top_n, _ptr(positions),
+                                              _ptr(counts), _ptr(frag), _ptr(scores), _stream())
         self._check(rc, "relax_fragment_image")
         out = dict(positions=positions, counts=counts, frag=frag)
         if want_scores:
-            out["scores"] = scores.view(T, H // 16, W // 16)
+            out["scores"] = scores.view(T, H // P, W // P)
         return out
 
-    def gather_patches(self, images, positions, counts):
+    def gather_patches(self, images, positions, counts, patch_size=16, target_size=TARGET):
+        """get_original_frame_patches with given positions: int32 [T,slots,2] (slots of the geometry), counts int32 [T]
+        -> uint8 [T,target_size,target_size,3]; a position outside the patch grid gives a zero tile."""
+        geo = fragment_geometry(patch_size, target_size)
         images = self._dev_u8(images)
         T, H, W, _ = images.shape
         positions = positions.to(self.device, torch.int32).contiguous()
         counts = counts.to(self.device, torch.int32).contiguous()
-        frag = torch.empty((T, TARGET, TARGET, 3), dtype=torch.uint8, device=self.device)
-        rc = self.lib.relax_gather_patches(self.h, _ptr(images), H * W * 3, T, H, W, _ptr(positions), _ptr(counts),
-                                           _ptr(frag), _stream())
+        if tuple(positions.shape) != (T, geo.slots, 2) or tuple(counts.shape) != (T,):
+            raise ValueError(f"gather_patches: positions [T,{geo.slots},2] and counts [T] expected for T={T}, got "
+                             f"{tuple(positions.shape)}, {tuple(counts.shape)}")
+        frag = torch.empty((T, geo.target_size, geo.target_size, 3), dtype=torch.uint8, device=self.device)
+        rc = self.lib.relax_gather_patches_ex(self.h, _ptr(images), H * W * 3, T, H, W, geo.patch_size, geo.target_size, _ptr(positions),
+                                              _ptr(counts), _ptr(frag), _stream())
         self._check(rc, "relax_gather_patches")
         return frag
 
@@ -529,14 +547,15 @@ class RelaxEngine:
                     "relax_vit_features_ex")
         return at if with_cls else at[:, :, 1:]
 
-    def attention_overlay(self, frames, positions, counts, patch_values, lut=None):
+    def attention_overlay(self, frames, positions, counts, patch_values, lut=None, patch_size=16):
         """map_attention_to_original (src/demo_visual.py:12-25) on the GPU.
-        frames uint8 [T,H,W,3] BGR (items may be strided, pixels packed); positions int32 [T,196,2] / counts int32 [T] as
-        fragment_pairs returns them; patch_values fp32 [T,196] in slot order; lut uint8 [256,3] BGR (None: colormap.jet_lut_bgr(),
+        frames uint8 [T,H,W,3] BGR (items may be strided, pixels packed); positions int32 [T,slots,2] / counts int32 [T] as
+        fragment_pairs returns them at this patch_size (8 / 16 / 32; the slot count is read from positions: 196 at 16 / 224);
+        patch_values fp32 [T,slots] in slot order; lut uint8 [256,3] BGR (None: colormap.jet_lut_bgr(),
         see there for passing cv2's own table) -> uint8 [T,H,W,3] = 0.6 frame + 0.4 lut[level] (csrc/vit_attention_map.hip).
-        The slots are the fragment's 16x16 source patches, one per token of a patch-16 ViT: with a patch-8 model loaded (784 tokens of
-        8x8) there is no such map - the reference's demo_visual.py is patch-16 only - and the call raises ValueError."""
-        self._overlay_needs_patch16("attention_overlay")
+        With a ViT loaded, patch_size has to agree with it by fragment_geometry.overlay_slot_rule (one slot per token: a patch-8 model
+        takes patch_size=8, 784 slots; a 16 x 16 fragment under it raises ValueError; 32 goes with either model)."""
+        self._overlay_tokens_per_slot("attention_overlay", patch_size)
         if isinstance(frames, np.ndarray):
             frames = torch.from_numpy(np.ascontiguousarray(frames))
         frames = frames.to(self.device, non_blocking=True)
@@ -548,8 +567,9 @@ class RelaxEngine:
         positions = torch.as_tensor(positions).to(self.device, torch.int32).contiguous()
         counts = torch.as_tensor(counts).to(self.device, torch.int32).contiguous()
         values = torch.as_tensor(patch_values).to(self.device, torch.float32).contiguous()
-        if tuple(positions.shape) != (T, TOP_N, 2) or tuple(counts.shape) != (T,) or tuple(values.shape) != (T, TOP_N):
-            raise ValueError(f"attention_overlay: positions [T,196,2], counts [T], patch_values [T,196] expected for T={T}, got "
+        slots = int(positions.shape[1]) if positions.dim() == 3 else -1
+        if slots < 1 or tuple(positions.shape) != (T, slots, 2) or tuple(counts.shape) != (T,) or tuple(values.shape) != (T, slots):
+            raise ValueError(f"attention_overlay: positions [T,slots,2], counts [T], patch_values [T,slots] expected for T={T}, got "
                              f"{tuple(positions.shape)}, {tuple(counts.shape)}, {tuple(values.shape)}")
         if lut is None:
             if getattr(self, "_jet_lut", None) is None:
@@ -561,37 +581,50 @@ class RelaxEngine:
                 raise ValueError(f"lut must be uint8 [256,3] BGR, got {lut.dtype} {tuple(lut.shape)}")
         out = torch.empty((T, H, W, 3), dtype=torch.uint8, device=self.device)
         stride = frames.stride(0) if T > 1 else H * W * 3
-        rc = self.lib.relax_attention_overlay(self.h, _ptr(frames), stride, T, H, W, _ptr(positions), _ptr(counts), _ptr(values),
-                                              _ptr(lut), _ptr(out), _stream())
+        rc = self.lib.relax_attention_overlay_ex(self.h, _ptr(frames), stride, T, H, W, int(patch_size), slots, _ptr(positions), _ptr(counts),
+                                                 _ptr(values), _ptr(lut), _ptr(out), _stream())
         self._check(rc, "relax_attention_overlay")
         return out
 
-    def _overlay_needs_patch16(self, what):
-        if self.vit_patch is not None and self.vit_patch != 16:
-            raise ValueError(f"{what}: the overlay maps the fragment's 196 slots of 16x16 pixels to the tokens of a patch-16 ViT; the loaded "
-                             f"model has patch size {self.vit_patch} ({self.vit_npatch} patch tokens)")
+    def _overlay_tokens_per_slot(self, what, patch_size):
+        """fragment_geometry.overlay_slot_rule against the loaded ViT (no model loaded: nothing to disagree with)."""
+        fragment_geometry(patch_size, patch_size)
+        if self.vit_patch is None:
+            return 1
+        try:
+            return overlay_slot_rule(int(patch_size), self.vit_patch)
+        except ValueError as e:
+            raise ValueError(f"{what}: {e} ({self.vit_npatch} patch tokens)") from None
 
     OVERLAY_FRAGMENTS = ("residual_imp", "residual_of_imp", "ori_frag", "residual_merged_frag")
 
-    def attention_overlays(self, frames, fragment="ori_frag", flow_images=None, lut=None):
+    def attention_overlays(self, frames, fragment="ori_frag", flow_images=None, lut=None, patch_size=16, top_n=None, target_size=None):
         """The __main__ of src/demo_visual.py (:86-128) for a whole clip: frames uint8 [T,2,H,W,3] as fragment_pairs takes them;
         fragment one of OVERLAY_FRAGMENTS:
           residual_imp          the frame-difference fragment, frame-difference positions
           ori_frag              the original fragment, frame-difference positions
           residual_merged_frag  merge_fragments(difference fragment, flow fragment), frame-difference positions
           residual_of_imp       the flow fragment, flow positions (flow_images, or Farneback on the GPU when None)
-        -> dict(overlay uint8 [T,H,W,3] over frames[:, 0], patch_means fp32 [T,196] (head mean, slot order),
-                attention fp32 [T,heads,196], positions, counts)."""
+        patch_size / top_n: the fragment's geometry on the 224 x 224 canvas (slots = (224 / patch_size)^2: 784 / 196 / 49; top_n=None
+        = all).  patch_size must go with the loaded ViT (fragment_geometry.overlay_slot_rule): equal to its patch size - a patch-8
+        model with patch_size=8 paints its 784 tokens one to one -, or 32, where a slot takes the mean of the head-mean attention
+        of the tokens it covers (get_activation_png's reshape-and-mean, src/demo_visual.py:41-60).
+        -> dict(overlay uint8 [T,H,W,3] over frames[:, 0], patch_means fp32 [T,slots] (head mean, slot order),
+                attention fp32 [T,heads,npatch], positions, counts)."""
         if fragment not in self.OVERLAY_FRAGMENTS:
             raise ValueError(f"fragment must be one of {self.OVERLAY_FRAGMENTS}, got {fragment!r}")
-        self._overlay_needs_patch16("attention_overlays")
+        geo = backbone_geometry(patch_size, top_n, target_size)
+        if self.vit_dim is None:
+            raise RuntimeError("load_vit first")
+        per = self._overlay_tokens_per_slot("attention_overlays", geo.patch_size)
+        kw = dict(patch_size=geo.patch_size, top_n=geo.top_n)
         frames = self._dev_u8(frames)
-        fr = self.fragment_pairs(frames)
+        fr = self.fragment_pairs(frames, **kw)
         positions, counts = fr["positions"], fr["counts"]
         if fragment in ("residual_of_imp", "residual_merged_frag"):
             if flow_images is None:
                 _, flow_images = self.optical_flow(frames)
-            fl = self.fragment_image(flow_images)
+            fl = self.fragment_image(flow_images, **kw)
         if fragment == "residual_imp":
             image = fr["diff_frag"]
         elif fragment == "ori_frag":
@@ -602,22 +635,28 @@ class RelaxEngine:
             image, positions, counts = fl["frag"], fl["positions"], fl["counts"]
         attention = self.vit_attention(image)
         patch_means = attention.mean(dim=1)
-        overlay = self.attention_overlay(frames[:, 0], positions, counts, patch_means, lut=lut)
+        if per > 1:      # a slot of per x per tokens: the mean of the block (file-free visualisation path: aten)
+            side = geo.tiles_per_row
+            patch_means = patch_means.view(-1, side, per, side, per).mean(dim=(2, 4)).reshape(-1, geo.slots)
+        overlay = self.attention_overlay(frames[:, 0], positions, counts, patch_means, lut=lut, patch_size=geo.patch_size)
         return dict(overlay=overlay, patch_means=patch_means, attention=attention, positions=positions, counts=counts)
 
     # ---- whole clip ---------------------------------------------------------------------------
-    def extract_clip(self, frames, resnet=True, vit=True, flow_images=None, flow=False):
+    def extract_clip(self, frames, resnet=True, vit=True, flow_images=None, flow=False, patch_size=16, top_n=None, target_size=None):
         """frames uint8 [T,2,H,W,3] on the device -> per-frame features (all fp32, on the device):
              resnet: [T,15171] = layer-stack of the original fragment | pool of the residual fragment
              vit:    [T,4608]  = pool of the original fragment | pool of the residual fragment
         The residual fragment is the frame-difference fragment, merged 50/50 with the optical-flow
-        fragment when flow_images (uint8 [T,H,W,3]) are supplied (src/main_fragment_layerstack.py:313-325)."""
-        fr = self.fragment_pairs(frames)
+        fragment when flow_images (uint8 [T,H,W,3]) are supplied (src/main_fragment_layerstack.py:313-325).
+        patch_size / top_n: the fragments' geometry on the 224 x 224 canvas (8 / 16 / 32; top_n=None = all (224 / patch_size)^2 slots;
+        positions come back as [T,slots,2]); target_size is refused: the backbones take 224 (fragment_geometry.backbone_geometry)."""
+        kw = self._clip_geometry(patch_size, top_n, target_size)
+        fr = self.fragment_pairs(frames, **kw)
         resid = fr["diff_frag"]
         if flow and flow_images is None:
             _, flow_images = self.optical_flow(frames)     # full ReLaX: Farneback + flow_to_rgb on the GPU
         if flow_images is not None:
-            fl = self.fragment_image(flow_images)
+            fl = self.fragment_image(flow_images, **kw)
             resid = self.merge_fragments(resid, fl["frag"])
         T = resid.shape[0]
         both = torch.cat([fr["ori_frag"], resid], dim=0)
@@ -630,6 +669,12 @@ class RelaxEngine:
             out["vit"] = torch.cat([pooled[:T], pooled[T:]], dim=1)
         return out
 
+    @staticmethod
+    def _clip_geometry(patch_size, top_n, target_size):
+        """The fragment keywords of a clip path (224 x 224 canvases for the backbones), checked."""
+        geo = backbone_geometry(patch_size, top_n, target_size)
+        return dict(patch_size=geo.patch_size, top_n=geo.top_n)
+
     def _segment_means(self, out, blocks, counts):
         """out [len(counts), F] <- per-clip means; blocks: list of (src [rows, cols] fp32, first row, dst column)."""
         offs = np.ascontiguousarray(np.concatenate([[0], np.cumsum(counts)]), dtype=np.int32)   # host array, passed by value
@@ -639,20 +684,21 @@ class RelaxEngine:
             self._check(rc, "relax_segment_mean")
         return out
 
-    def clip_vectors(self, clips, resnet=True, vit=True, per_frame=False):
+    def clip_vectors(self, clips, resnet=True, vit=True, per_frame=False, patch_size=16, top_n=None, target_size=None):
         """Several clips (list of uint8 [T,2,H,W,3] device tensors, any mix of resolutions) in ONE batched pass of
         both backbones -> fp32 [len(clips), F] per-clip mean vectors.  Bigger batches fill the 256 CUs better
         (more tiles per launch, fewer partial rounds).  A clip's row equals the row it gets alone to fp32 rounding; it is
         bit-identical across batch compositions (and therefore across ranks of a sharded run) only with
         set_option("gemm_split_k", 0): the default tail split cuts the last tiles of a GEMM along K by the batch size.
         per_frame=True: -> (matrix, [fp32 [T_i, F] per clip]) - the per-frame rows the reference saves per video
-        (src/main_fragment_layerstack.py:345-354) next to their means."""
+        (src/main_fragment_layerstack.py:345-354) next to their means.  patch_size / top_n / target_size as in extract_clip."""
+        kw = self._clip_geometry(patch_size, top_n, target_size)
         counts = [int(c.shape[0]) for c in clips]
         n = sum(counts)
         both = torch.empty((2 * n, TARGET, TARGET, 3), dtype=torch.uint8, device=self.device)   # [originals | residuals]
         at = 0
         for c, t in zip(clips, counts):
-            self.fragment_pairs(c, out_ori=both[at:at + t], out_diff=both[n + at:n + at + t])
+            self.fragment_pairs(c, out_ori=both[at:at + t], out_diff=both[n + at:n + at + t], **kw)
             at += t
         F = (LAYER_STACK_DIM + RN50_POOL_DIM if resnet else 0) + (6 * self.vit_dim if vit else 0)
         out = torch.empty((len(clips), F), dtype=torch.float32, device=self.device)
@@ -780,19 +826,21 @@ class RelaxEngine:
             out["vgg16"] = out["vgg16"][:, :VGG16_POOL_DIM - 3]
         return out
 
-    def full_clip_vector(self, frames, flow_images=None, flow=False, whole_frames=None):
+    def full_clip_vector(self, frames, flow_images=None, flow=False, whole_frames=None, patch_size=16, top_n=None, target_size=None):
         """frames uint8 [T,2,H,W,3] -> fp32 [35203]: the vector src/demo_test.py:171-175 assembles
         (whole-frame ResNet-50 LS | whole-frame ViT | fragment ResNet-50 LS+pool | fragment ViT x2), each part averaged
         over the sampled frames.  Without flow_images the residual fragment is the frame-difference fragment alone.
         whole_frames uint8 [Ts,H,W,3]: all sampled frames when the last one has no pair (see full_clip_vectors).
-        With self.demo_write_png set, the pairs' files are written too (src/demo_test.py:120,135); the vector is the same."""
+        With self.demo_write_png set, the pairs' files are written too (src/demo_test.py:120,135; at the reference's 16 / 196
+        geometry whatever patch_size says); the vector is the same.  patch_size / top_n / target_size as in extract_clip."""
         if self.demo_write_png is not None:
             from . import visualisation
             visualisation.write_for_driver(self, frames, self.demo_write_png, flow=flow or flow_images is not None)
         return self.full_clip_vectors([frames], flow=flow, flow_images=None if flow_images is None else [flow_images],
-                                      whole_frames=None if whole_frames is None else [whole_frames])[0]
+                                      whole_frames=None if whole_frames is None else [whole_frames], patch_size=patch_size, top_n=top_n,
+                                      target_size=target_size)[0]
 
-    def full_clip_vectors(self, clips, flow=True, flow_images=None, whole_frames=None):
+    def full_clip_vectors(self, clips, flow=True, flow_images=None, whole_frames=None, patch_size=16, top_n=None, target_size=None):
         """Several clips -> fp32 [len(clips), 35203] in ONE batched pass of each backbone (3*T fragments / frames per
         clip: original fragment, residual fragment, whole frame).  Same layout as full_clip_vector.  Batch-invariant to
         fp32 rounding; bit for bit only with set_option("gemm_split_k", 0) (see clip_vectors).
@@ -801,12 +849,15 @@ class RelaxEngine:
         pair); default: the first frame of every pair.
         = full_features(full_prepare(...)): full_prepare is the byte / HBM work (fragments, Farneback flow, resizes), full_features
         the contractions.  Running the two halves of consecutive batches on two streams was measured at 1.01 x
-        (tools/flow_overlap_try.py) and is not done in the product; the split stays because the dataset driver stages on it."""
-        return self.full_features(self.full_prepare(clips, flow=flow, flow_images=flow_images, whole_frames=whole_frames))
+        (tools/flow_overlap_try.py) and is not done in the product; the split stays because the dataset driver stages on it.
+        patch_size / top_n / target_size as in extract_clip."""
+        return self.full_features(self.full_prepare(clips, flow=flow, flow_images=flow_images, whole_frames=whole_frames,
+                                                    patch_size=patch_size, top_n=top_n, target_size=target_size))
 
-    def full_prepare(self, clips, flow=True, flow_images=None, whole_frames=None):
+    def full_prepare(self, clips, flow=True, flow_images=None, whole_frames=None, patch_size=16, top_n=None, target_size=None):
         """The input half of full_clip_vectors: fragments (difference + flow, merged), whole-frame resizes -> the two backbone
         input batches.  Everything is enqueued on the current stream."""
+        kw = self._clip_geometry(patch_size, top_n, target_size)
         counts = [int(c.shape[0]) for c in clips]
         wf = [c[:, 0] for c in clips] if whole_frames is None else list(whole_frames)
         wcounts = [int(w.shape[0]) for w in wf]
@@ -818,12 +869,12 @@ class RelaxEngine:
         at = aw = 0
         for i, (c, t) in enumerate(zip(clips, counts)):
             res = vit_in[n + at:n + at + t]
-            self.fragment_pairs(c, out_ori=vit_in[at:at + t], out_diff=res)
+            self.fragment_pairs(c, out_ori=vit_in[at:at + t], out_diff=res, **kw)
             fimg = None if flow_images is None else flow_images[i]
             if flow and fimg is None:
                 _, fimg = self.optical_flow(c)
             if fimg is not None:
-                self.merge_fragments(res, self.fragment_image(fimg)["frag"], out=res)
+                self.merge_fragments(res, self.fragment_image(fimg, **kw)["frag"], out=res)
             tw = wcounts[i]
             self.resize_frames(wf[i], out_bilinear=rn_in[n + aw:n + aw + tw], out_lanczos=vit_in[2 * n + aw:2 * n + aw + tw])
             at += t

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import runtime
+from .fragment_geometry import fragment_geometry
 from .extractor import visualise_resnet, visualise_resnet_layer, visualise_vgg, visualise_vgg_layer, visualise_vit_layer
 
 ALL_LAYERS = list(visualise_resnet.LAYER_INDEX)
@@ -23,34 +24,38 @@ def _u8(a):
 
 
 def _check_geometry(patch_size, target_size, top_n):
-    if patch_size != 16 or target_size != 224 or top_n > 196:
-        raise NotImplementedError("the HIP fragment stage is built for patch_size=16, target_size=224, top_n<=196")
+    """The supported set (fragment_geometry.py): patch_size 8 / 16 / 32, target_size a multiple of it up to 448, top_n within the
+    canvas's slots; ValueError naming the offending value otherwise.  -> Geometry"""
+    return fragment_geometry(patch_size, target_size, top_n)
 
 
 def get_patch_diff(residual_frame, patch_size=16):
-    """-> float64 [H//16, W//16] patch sums (reference :177-189)."""
-    _check_geometry(patch_size, 224, 196)
-    out = runtime.get_engine().fragment_image(torch.from_numpy(_u8(residual_frame)[None]), want_scores=True)
+    """-> float64 [H//patch_size, W//patch_size] patch sums (reference :177-189)."""
+    geo = _check_geometry(patch_size, patch_size, 0)
+    out = runtime.get_engine().fragment_image(torch.from_numpy(_u8(residual_frame)[None]), top_n=0, want_scores=True,
+                                              patch_size=geo.patch_size, target_size=geo.target_size)
     return out["scores"][0].cpu().numpy().astype(np.float64)
 
 
 def extract_important_patches(residual_frame, diff=None, patch_size=16, target_size=224, top_n=196):
-    """-> (fragment uint8 [224,224,3], positions list of (y,x)) (reference :191-210).  `diff` is recomputed on the
+    """-> (fragment uint8 [target_size,target_size,3], positions list of (y,x)) (reference :191-210).  `diff` is recomputed on the
     GPU (score, selection and gather are one fused pass); it is accepted for signature compatibility."""
-    _check_geometry(patch_size, target_size, top_n)
-    out = runtime.get_engine().fragment_image(torch.from_numpy(_u8(residual_frame)[None]), top_n=top_n)
+    geo = _check_geometry(patch_size, target_size, top_n)
+    out = runtime.get_engine().fragment_image(torch.from_numpy(_u8(residual_frame)[None]), top_n=geo.top_n,
+                                              patch_size=geo.patch_size, target_size=geo.target_size)
     n = int(out["counts"][0])
     pos = out["positions"][0, :n].cpu().numpy()
     return out["frag"][0].cpu().numpy(), [(int(y), int(x)) for y, x in pos]
 
 
 def get_original_frame_patches(original_frame, positions, patch_size=16, target_size=224):
-    _check_geometry(patch_size, target_size, len(positions))
-    pos = torch.full((1, 196, 2), -1, dtype=torch.int32)
+    geo = _check_geometry(patch_size, target_size, len(positions))
+    pos = torch.full((1, geo.slots, 2), -1, dtype=torch.int32)
     if len(positions):
         pos[0, :len(positions)] = torch.as_tensor(np.asarray(positions, dtype=np.int32))
     cnt = torch.tensor([len(positions)], dtype=torch.int32)
-    return runtime.get_engine().gather_patches(torch.from_numpy(_u8(original_frame)[None]), pos, cnt)[0].cpu().numpy()
+    return runtime.get_engine().gather_patches(torch.from_numpy(_u8(original_frame)[None]), pos, cnt, patch_size=geo.patch_size,
+                                               target_size=geo.target_size)[0].cpu().numpy()
 
 
 def process_patches(original_path, residual_name, residual, patch_size=16, target_size=224, top_n=196):
@@ -60,13 +65,14 @@ def process_patches(original_path, residual_name, residual, patch_size=16, targe
     return original_path.replace(".png", suffix), frag, positions
 
 
-def fragment_pair(img_original, img_next, top_n=196, write_png=None):
+def fragment_pair(img_original, img_next, top_n=196, write_png=None, patch_size=16, target_size=224):
     """Fused form of cv2.absdiff + process_patches('frame_diff') + get_original_frame_patches (reference :302-310).
-    -> (diff_fragment, original_fragment, positions).  write_png (opt-in, default off): (directory, video_name, [n]) also
+    -> (diff_fragment, original_fragment, positions).  patch_size / target_size: the reference's arguments of those functions.  write_png (opt-in, default off): (directory, video_name, [n]) also
     writes the pair's files as the reference's cv2.imwrite calls leave them (:310, :325; visualisation.write_example_set,
     encoded on the GPU); the return value is the same."""
+    geo = _check_geometry(patch_size, target_size, top_n)
     frames = torch.from_numpy(np.stack([_u8(img_original), _u8(img_next)])[None])
-    out = runtime.get_engine().fragment_pairs(frames, top_n=top_n)
+    out = runtime.get_engine().fragment_pairs(frames, top_n=geo.top_n, patch_size=geo.patch_size, target_size=geo.target_size)
     if write_png is not None:
         from . import visualisation
         visualisation.write_for_driver(runtime.get_engine(), frames, write_png)

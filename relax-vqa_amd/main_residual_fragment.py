@@ -20,12 +20,13 @@ _MAX_HELD = 256
 
 
 def extract_important_patches(residual_frame, diff=None, patch_size=16, target_size=224, top_n=196):
-    """-> fragment uint8 [224,224,3] only (reference :187-204)."""
+    """-> fragment uint8 [target_size,target_size,3] only (reference :187-204); patch_size 8 / 16 / 32 (fragment_geometry.py)."""
     return _ls.extract_important_patches(residual_frame, diff, patch_size, target_size, top_n)[0]
 
 
 def process_patches(original_path, residual_name, residual, patch_size=16, target_size=224, top_n=196):
-    """-> residual_frag_path (reference :206-214).  The fragment is held in memory under that name instead of a PNG."""
+    """-> residual_frag_path (reference :206-214).  The fragment is held in memory under that name instead of a PNG; patch_size,
+    target_size and top_n are passed through (get_deep_feature takes 224 x 224 fragments only)."""
     path, frag, _ = _ls.process_patches(original_path, residual_name, residual, patch_size, target_size, top_n)
     if len(_fragments_by_path) >= _MAX_HELD:
         _fragments_by_path.pop(next(iter(_fragments_by_path)))
