@@ -47,18 +47,36 @@ int ensure_buf(relax_handle* h, DevBuf& b, size_t bytes) {
     return poison_buf(h, b);
 }
 
-int upload(relax_handle* h, const float* host, size_t n, float** dev, std::vector<void*>& allocs) {
+void* DeviceOwner::keep(relax_handle* h, size_t bytes, const char* what) {
     void* p = nullptr;
-    hipError_t e = hipMalloc(&p, n * sizeof(float));
+    const hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) {
-        set_error(h, "hipMalloc(%zu floats) failed: %s", n, hipGetErrorString(e));
-        return RELAX_ERR_NOMEM;
+        set_error(h, "hipMalloc of %s (%zu bytes) failed: %s", what, bytes, hipGetErrorString(e));
+        return nullptr;
     }
-    allocs.push_back(p);
+    ptrs.push_back(p);
+    return p;
+}
+
+int DeviceOwner::upload(relax_handle* h, const float* host, size_t n, float** dev) {
+    void* p = keep(h, n * sizeof(float), "an uploaded tensor");
+    if (!p) return RELAX_ERR_NOMEM;
     RELAX_HIP_CHECK(h, hipMemcpy(p, host, n * sizeof(float), hipMemcpyHostToDevice));
     *dev = static_cast<float*>(p);
     return RELAX_OK;
 }
+
+void DeviceOwner::release() {
+    for (void* p : ptrs) (void)hipFree(p);
+    ptrs.clear();
+}
+
+bool ScopedDev::alloc(relax_handle* h, size_t floats, const char* what) {
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), sizeof(float) * floats);
+    if (e != hipSuccess) set_error(h, "hipMalloc of staging rows for %s (%zu floats) failed: %s", what, floats, hipGetErrorString(e));
+    return e == hipSuccess;
+}
+ScopedDev::~ScopedDev() { if (p) (void)hipFree(p); }
 
 // folds the finished spans at the front of the list into the totals (in order; stops at the first span that is still open or whose stop
 // event has not completed) and gives their events back to the pool

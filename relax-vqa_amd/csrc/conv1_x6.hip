@@ -233,50 +233,35 @@ __global__ __launch_bounds__(512) void conv1_x6(const uint8_t* __restrict__ frag
 #endif
 }
 
-// w_f32 [64][224] scratch -> w_sp3 [64][224 * 6 B]
-int make_conv1_x6_weights(relax_handle* h, const float* w_packed, int kpad, void** w_sp3_out, std::vector<void*>& allocs) {
-    float* tmp = nullptr;
-    void* q = nullptr;
-    if (hipMalloc(&tmp, sizeof(float) * 64 * C1_K) != hipSuccess || hipMalloc(&q, (size_t)64 * C1_K * 6) != hipSuccess) {
-        if (tmp) (void)hipFree(tmp);
-        set_error(h, "resnet50: hipMalloc of the conv1 split-plane weights failed");
-        return RELAX_ERR_NOMEM;
-    }
-    allocs.push_back(q);
-    hipLaunchKernelGGL(conv1_repack, dim3((64 * C1_K + 255) / 256), dim3(256), 0, nullptr, w_packed, kpad, tmp);
-    int rc = launch_to_sp3(h, tmp, C1_K, q, 64, C1_K, nullptr);
+// fp32 staging rows [64][224]: the packed conv1 rows in this kernel's K layout
+static int conv1_staged(relax_handle* h, const float* w_packed, int kpad, ScopedDev& tmp, const char* what) {
+    if (!tmp.alloc(h, 64 * C1_K, what)) return RELAX_ERR_NOMEM;
+    hipLaunchKernelGGL(conv1_repack, dim3((64 * C1_K + 255) / 256), dim3(256), 0, nullptr, w_packed, kpad, tmp.p);
+    return RELAX_OK;
+}
+// the conversion is through before the caller's scope frees the staging rows
+static int conv1_converted(relax_handle* h, int rc) {
     if (hipDeviceSynchronize() != hipSuccess && rc == RELAX_OK) {
         set_error(h, "resnet50: conv1 weight conversion failed");
         rc = RELAX_ERR_HIP;
     }
-    (void)hipFree(tmp);
-    *w_sp3_out = q;
     return rc;
 }
 
+// w_f32 [64][224] scratch -> w_sp3 [64][224 * 6 B]
+int make_conv1_x6_weights(relax_handle* h, const float* w_packed, int kpad, void** w_sp3_out, DeviceOwner& mem) {
+    const char* what = "the conv1 split-plane weights";
+    ScopedDev tmp;
+    RELAX_TRY(conv1_staged(h, w_packed, kpad, tmp, what));
+    return conv1_converted(h, derive_sp3(h, mem, tmp.p, 64, C1_K, w_sp3_out, what));
+}
+
 // the same weights as two fp16 planes [64][224 * 4 B] with one power-of-two scale per filter (w_inv_out [64]: the inverse scales)
-int make_conv1_h2_weights(relax_handle* h, const float* w_packed, int kpad, void** w_h2_out, float** w_inv_out, std::vector<void*>& allocs) {
-    float *tmp = nullptr, *inv = nullptr;
-    void* q = nullptr;
-    if (hipMalloc(&tmp, sizeof(float) * 64 * C1_K) != hipSuccess || hipMalloc(&q, (size_t)64 * C1_K * 4) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&inv), sizeof(float) * 64) != hipSuccess) {
-        if (tmp) (void)hipFree(tmp);
-        if (q) (void)hipFree(q);
-        set_error(h, "resnet50: hipMalloc of the conv1 fp16-plane weights failed");
-        return RELAX_ERR_NOMEM;
-    }
-    allocs.push_back(q);
-    allocs.push_back(inv);
-    hipLaunchKernelGGL(conv1_repack, dim3((64 * C1_K + 255) / 256), dim3(256), 0, nullptr, w_packed, kpad, tmp);
-    int rc = launch_to_h2_rows(h, tmp, C1_K, q, 64, C1_K, inv, nullptr);
-    if (hipDeviceSynchronize() != hipSuccess && rc == RELAX_OK) {
-        set_error(h, "resnet50: conv1 weight conversion failed");
-        rc = RELAX_ERR_HIP;
-    }
-    (void)hipFree(tmp);
-    *w_h2_out = q;
-    *w_inv_out = inv;
-    return rc;
+int make_conv1_h2_weights(relax_handle* h, const float* w_packed, int kpad, void** w_h2_out, float** w_inv_out, DeviceOwner& mem) {
+    const char* what = "the conv1 fp16-plane weights";
+    ScopedDev tmp;
+    RELAX_TRY(conv1_staged(h, w_packed, kpad, tmp, what));
+    return conv1_converted(h, derive_h2_rows(h, mem, tmp.p, 64, C1_K, w_h2_out, w_inv_out, what));
 }
 
 // frags uint8 [N,224,224,3] BGR -> out fp32 [N,112,112,64] (raw conv1), gap_groups [N*784][64] (16-pixel sums) or null.

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(128) void head_fc3(const float* __restrict__ hid, c
 }
 
 void free_head(relax_handle* h) {
-    for (void* p : h->head.allocs) (void)hipFree(p);
+    h->head.mem.release();
     h->head = HeadW();
 }
 
@@ -87,21 +87,19 @@ int relax_load_mlp_head(relax_handle* h, const float* const* tensors, const char
     // fold BatchNorm1d (eval) into fc1: y = (x W^T + b - mu) * s + beta, s = gamma / sqrt(var + eps)   (host_logic.cpp)
     std::vector<float> w1p((size_t)H1 * hw.Fpad), b1p(H1);
     host::fold_fc_bn(w1, b1, g, be, mu, var, 1e-5f, H1, F, hw.Fpad, w1p.data(), b1p.data());
-    int rc = upload(h, w1p.data(), w1p.size(), &hw.w1, hw.allocs);
-    if (rc == RELAX_OK) rc = upload(h, b1p.data(), H1, &hw.b1, hw.allocs);
-    if (rc == RELAX_OK) rc = upload(h, w2, (size_t)H2 * H1, &hw.w2, hw.allocs);
-    if (rc == RELAX_OK) rc = upload(h, b2, H2, &hw.b2, hw.allocs);
-    if (rc == RELAX_OK) rc = upload(h, w3, H2, &hw.w3, hw.allocs);
+    int rc = hw.mem.upload(h, w1p.data(), w1p.size(), &hw.w1);
+    if (rc == RELAX_OK) rc = hw.mem.upload(h, b1p.data(), H1, &hw.b1);
+    if (rc == RELAX_OK) rc = hw.mem.upload(h, w2, (size_t)H2 * H1, &hw.w2);
+    if (rc == RELAX_OK) rc = hw.mem.upload(h, b2, H2, &hw.b2);
+    if (rc == RELAX_OK) rc = hw.mem.upload(h, w3, H2, &hw.w3);
     hw.b3 = b3[0];
     auto up_d = [&](const double* src, double** dst) {
         if (rc != RELAX_OK) return;
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(double) * F) != hipSuccess) {
-            set_error(h, "mlp head: hipMalloc failed");
+        void* p = hw.mem.keep(h, sizeof(double) * F, "the mlp head's per-feature table");
+        if (!p) {
             rc = RELAX_ERR_NOMEM;
             return;
         }
-        hw.allocs.push_back(p);
         if (hipMemcpy(p, src, sizeof(double) * F, hipMemcpyHostToDevice) != hipSuccess) {
             set_error(h, "mlp head: hipMemcpy failed");
             rc = RELAX_ERR_HIP;

@@ -581,7 +581,7 @@ __global__ __launch_bounds__(256) void ht_bn_reset(float* __restrict__ rmean, fl
 
 void free_head_train(relax_handle* h) {
     HeadTrain& t = h->head_train;
-    for (void* p : t.allocs) (void)hipFree(p);
+    t.mem.release();
     if (t.scaler_ws.p) (void)hipFree(t.scaler_ws.p);
     t = HeadTrain();
 }
@@ -770,13 +770,11 @@ int relax_head_train_init(relax_handle* h, int input_features, int hidden_featur
     int rc = RELAX_OK;
     auto grab = [&](size_t bytes) -> void* {
         if (rc != RELAX_OK) return nullptr;
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) {
-            set_error(h, "relax_head_train_init: hipMalloc(%zu bytes) failed", bytes);
+        void* p = t.mem.keep(h, bytes, "relax_head_train_init's state");
+        if (!p) {
             rc = RELAX_ERR_NOMEM;
             return nullptr;
         }
-        t.allocs.push_back(p);
         if (hipMemset(p, 0, bytes) != hipSuccess) {
             set_error(h, "relax_head_train_init: hipMemset failed");
             rc = RELAX_ERR_HIP;
@@ -1075,11 +1073,8 @@ int relax_head_train_pad_abs_sum_adam(relax_handle* h, double* out, relax_stream
 static int ht_grad_w1(relax_handle* h) {   // only the unfused measurements ever materialise the gradient of fc1.weight
     HeadTrain& t = h->head_train;
     if (t.grad_w1) return RELAX_OK;
-    void* p = nullptr;
-    RELAX_HIP_CHECK(h, hipMalloc(&p, sizeof(float) * (size_t)t.H1 * t.Fpad));
-    t.allocs.push_back(p);
-    t.grad_w1 = static_cast<float*>(p);
-    return RELAX_OK;
+    t.grad_w1 = static_cast<float*>(t.mem.keep(h, sizeof(float) * (size_t)t.H1 * t.Fpad, "the unfused fc1.weight gradient"));
+    return t.grad_w1 ? RELAX_OK : RELAX_ERR_NOMEM;
 }
 
 int relax_head_train_dw1(relax_handle* h, int fused, int B, float lr, float momentum, float weight_decay, relax_stream stream) {

@@ -50,6 +50,41 @@ void fold_bn(const float* gamma, const float* beta, const float* mean, const flo
     }
 }
 
+bool read_bn(const StateDict& sd, const std::string& prefix, int channels, float eps, float* scale, float* shift, std::string& err) {
+    const float* g = sd.get(prefix + ".weight", channels, err);
+    const float* b = g ? sd.get(prefix + ".bias", channels, err) : nullptr;
+    const float* mu = b ? sd.get(prefix + ".running_mean", channels, err) : nullptr;
+    const float* var = mu ? sd.get(prefix + ".running_var", channels, err) : nullptr;
+    if (var) fold_bn(g, b, mu, var, eps, channels, scale, shift);
+    return var != nullptr;
+}
+
+// A row's sum stays sequential in column order (its bits are the contract); rows are independent, so four of them advance together: one
+// chain of double additions is bound by the addition's latency, and VGG-16's fc1 alone has 10^8 terms.
+void conv_hoelder(const float* rows, const float* bias_or_null, int cout, int k, float* l1max, float* bmax) {
+    *l1max = 0.f;
+    *bmax = 0.f;
+    auto row_done = [&](double l1) { *l1max = std::fmax(*l1max, (float)(l1 * (1.0 + 1e-6))); };
+    int o = 0;
+    for (; o + 4 <= cout; o += 4) {
+        const float *r0 = rows + (size_t)o * k, *r1 = r0 + k, *r2 = r1 + k, *r3 = r2 + k;
+        double a = 0.0, b = 0.0, c = 0.0, d = 0.0;
+        for (int kk = 0; kk < k; ++kk) {
+            a += std::fabs((double)r0[kk]);
+            b += std::fabs((double)r1[kk]);
+            c += std::fabs((double)r2[kk]);
+            d += std::fabs((double)r3[kk]);
+        }
+        row_done(a); row_done(b); row_done(c); row_done(d);
+    }
+    for (; o < cout; ++o) {
+        double l1 = 0.0;
+        for (int kk = 0; kk < k; ++kk) l1 += std::fabs((double)rows[(size_t)o * k + kk]);
+        row_done(l1);
+    }
+    for (o = 0; bias_or_null && o < cout; ++o) *bmax = std::fmax(*bmax, std::fabs(bias_or_null[o]));
+}
+
 int conv_kpad(int k, int cin_pad) { return ((k * k * cin_pad + 31) / 32) * 32; }
 
 void pack_conv_oihw(const float* w, const float* scale, int cout, int cin, int cin_pad, int k, int kpad, float* out) {
@@ -378,18 +413,31 @@ int relax_host_pack_conv(const float* const* tensors, const char* const* names, 
     float* scale = nullptr;
     std::vector<float> storage;
     if (bn && *bn) {
-        const std::string b(bn);
-        const float* g = sd.get(b + ".weight", cout, e);
-        const float* be = g ? sd.get(b + ".bias", cout, e) : nullptr;
-        const float* mu = be ? sd.get(b + ".running_mean", cout, e) : nullptr;
-        const float* var = mu ? sd.get(b + ".running_var", cout, e) : nullptr;
-        if (!var) return fail();
         storage.resize((size_t)cout);
         scale = storage.data();
-        fold_bn(g, be, mu, var, 1e-5f, cout, scale, shift);
+        if (!read_bn(sd, bn, cout, 1e-5f, scale, shift, e)) return fail();
     }
     pack_conv_oihw(w, scale, cout, cin, cin_pad, k, conv_kpad(k, cin_pad), out);
     return 0;
+}
+
+// the BatchNorm under `prefix` folded into scale / shift [channels]: 0, or -1 and the message naming the missing / mis-sized key
+int relax_host_read_bn(const float* const* tensors, const char* const* names, const int64_t* numels, int n, const char* prefix, int channels,
+                       float eps, float* scale, float* shift, char* err, int err_len) {
+    relax::host::StateDict sd;
+    for (int i = 0; i < n; ++i) sd.add(names[i], tensors[i], numels[i]);
+    std::string e;
+    if (relax::host::read_bn(sd, prefix, channels, eps, scale, shift, e)) return 0;
+    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+    return -1;
+}
+
+void relax_host_fold_bn(const float* gamma, const float* beta, const float* mean, const float* var, float eps, int channels, float* scale, float* shift) {
+    relax::host::fold_bn(gamma, beta, mean, var, eps, channels, scale, shift);
+}
+
+void relax_host_conv_hoelder(const float* rows, const float* bias_or_null, int cout, int k, float* l1max, float* bmax) {
+    relax::host::conv_hoelder(rows, bias_or_null, cout, k, l1max, bmax);
 }
 
 int relax_host_conv_kpad(int k, int cin_pad) { return relax::host::conv_kpad(k, cin_pad); }

@@ -1,6 +1,7 @@
 // Pure-host half of librelax_hip.so: everything the model loaders and the launchers compute on the CPU before a byte goes
-// to the GPU - state-dict key matching, BatchNorm folding, OIHW -> packed [Cout][K] weight layout, the quality head's
-// fc1 + BatchNorm1d fold, and the tail split-K cost model of the contraction launchers.  No HIP type appears here, so the file
+// to the GPU - state-dict key matching, reading and folding a BatchNorm (read_bn), OIHW -> packed [Cout][K] weight layout, the Hoelder
+// constants of a folded convolution (conv_hoelder), the quality head's fc1 + BatchNorm1d fold, and the tail split-K cost model of the
+// contraction launchers.  No HIP type appears here, so the file
 // builds with plain g++ and runs under AddressSanitizer / UBSan on a CPU box (tests/test_host_logic_sanitized.py drives it with the
 // synthetic and the deliberately malformed state dicts; sanitizers are never run on the GPU).
 #pragma once
@@ -25,6 +26,15 @@ struct StateDict {
 // eval-mode BatchNorm as y = x * scale + shift:  scale = gamma / sqrt(var + eps),  shift = beta - mean * scale
 void fold_bn(const float* gamma, const float* beta, const float* mean, const float* var, float eps, int channels, float* scale,
              float* shift);
+
+// The BatchNorm under `prefix` (.weight, .bias, .running_mean, .running_var, `channels` values each) folded into scale / shift [channels];
+// false and StateDict::get's message (it names the key) if one of the four is missing or mis-sized
+bool read_bn(const StateDict& sd, const std::string& prefix, int channels, float eps, float* scale, float* shift, std::string& err);
+
+// Hoelder constants of a convolution as packed rows [cout][k]:  |out[n]| <= l1max * max |in| + bmax  - what every per-image fp16 scale of the
+// f16x2 ResNet-50 and VGG-16 rests on.  l1max = max_n (float)(sum_k |rows[n][k]| * (1 + 1e-6)), the sum in double in column order;
+// bmax = max_n |bias[n]|, 0 without a bias
+void conv_hoelder(const float* rows, const float* bias_or_null, int cout, int k, float* l1max, float* bmax);
 
 // K of a packed convolution weight row: KH*KW*cin_pad rounded up to a multiple of 32
 int conv_kpad(int k, int cin_pad);

@@ -57,6 +57,22 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// device memory that lives as long as a loaded model (or a training state): every pointer is recorded the moment its allocation succeeds, so
+// a load that fails half-way gives back exactly what it took (api.hip)
+struct DeviceOwner {
+    std::vector<void*> ptrs;
+    void* keep(relax_handle* h, size_t bytes, const char* what);            // nullptr and a message naming `what` and the size on failure
+    int upload(relax_handle* h, const float* host, size_t n, float** dev);  // keep + copy of n floats
+    void release();                                                         // frees everything kept
+};
+
+// fp32 staging rows of a weight conversion: device memory freed at the end of the scope
+struct ScopedDev {
+    float* p = nullptr;
+    bool alloc(relax_handle* h, size_t floats, const char* what);   // false and a message on failure
+    ~ScopedDev();
+};
+
 // ---- contraction kernel description -----------------------------------------------------------
 struct ConvDesc {
     // A operand: NHWC activation, gathered on the fly (implicit GEMM)
@@ -188,7 +204,7 @@ struct ResNet50W {
     float* bn1_scale = nullptr;  // [64]
     float* bn1_shift = nullptr;  // [64]
     std::vector<Bottleneck> blocks;  // 16
-    std::vector<void*> allocs;
+    DeviceOwner mem;
 };
 
 struct LinearW {
@@ -218,7 +234,7 @@ struct VitW {
     LinearW patch_w;        // [dim][3*p*p], k = (c*p + py)*p + px (c in RGB order)
     std::vector<VitBlockW> blocks;
     float *norm_g = nullptr, *norm_b = nullptr;
-    std::vector<void*> allocs;
+    DeviceOwner mem;
 };
 
 // ---- VGG-16 (csrc/vgg16.hip) -------------------------------------------------------------------------------------------------
@@ -227,7 +243,7 @@ struct VggW {
     ConvW conv[13];         // conv[0]: [64][32] fp32 (k = (dy*3+dx)*3 + c, RGB, zero padded): vgg_conv1_1 reads it directly; the others as ResNet's
     ConvW fc[2];            // classifier.0 (columns permuted to the NHWC flatten of pool5) and classifier.3 as 1x1 convolutions over 1x1 images
     float conv1_scale = 1.f;   // static power of two of conv1_1's fp16-plane output (a bound from the normalised input range)
-    std::vector<void*> allocs;
+    DeviceOwner mem;
 };
 
 // ---- quality head (imputer + scaler + MLP), BatchNorm folded into fc1 ----------------------------------------
@@ -237,7 +253,7 @@ struct HeadW {
     float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr;
     float b3 = 0.f;
     double *stats = nullptr, *scale = nullptr, *mn = nullptr;
-    std::vector<void*> allocs;
+    DeviceOwner mem;
 };
 
 // ---- quality head, training state (head_train.hip) -----------------------------------------------------------
@@ -261,7 +277,7 @@ struct HeadTrain {
     float* xb = nullptr;              // the gathered batch rows [max_batch][Fpad]
     float* grad_w1 = nullptr;         // dW1 of the UNFUSED form (relax_head_train_dw1 with fused = 0, a measurement): allocated on its first use
     DevBuf scaler_ws;                 // partial column sums / minima / maxima of the scaler fit
-    std::vector<void*> allocs;
+    DeviceOwner mem;
 };
 
 // ---- resize coefficient tables (Pillow-exact), cached per (input size, filter) ------------------------------
@@ -362,7 +378,12 @@ struct relax_handle {
 namespace relax {
 
 int ensure_buf(relax_handle* h, DevBuf& b, size_t bytes);
-int upload(relax_handle* h, const float* host, size_t n, float** dev, std::vector<void*>& allocs);
+
+// derived copies of a packed fp32 [rows][K] matrix on the device, kept by `mem` (weights.hip): split planes (sp3.h), and two fp16 planes with
+// one power-of-two scale per row + the inverse scales (h2.h).  The conversions are enqueued on the null stream; `what` names the matrix in an
+// allocation failure's message
+int derive_sp3(relax_handle* h, DeviceOwner& mem, const float* w_dev, int rows, int K, void** out, const char* what);
+int derive_h2_rows(relax_handle* h, DeviceOwner& mem, const float* w_dev, int rows, int K, void** planes, float** inv, const char* what);
 
 // profiling helpers: call around a launch; no-ops when profiling is off
 int prof_begin(relax_handle* h, hipStream_t s, int kind, double work, int* span_idx, double bytes = 0);
@@ -386,10 +407,10 @@ int launch_conv_x6(relax_handle* h, const ConvDescX6& d, hipStream_t s);
 int launch_b2b_permute_k(relax_handle* h, const float* w, float* wp, int rows, int K, hipStream_t s);   // gemm_x6.hip: K order of the back-to-back form
 int launch_to_sp3(relax_handle* h, const float* x, int64_t ld, void* y, int64_t rows, int K, hipStream_t s);
 // conv1_x6.hip: ResNet-50 conv1 on the bf16x6 arithmetic, straight from the uint8 fragments
-int make_conv1_x6_weights(relax_handle* h, const float* w_packed, int kpad, void** w_sp3_out, std::vector<void*>& allocs);
+int make_conv1_x6_weights(relax_handle* h, const float* w_packed, int kpad, void** w_sp3_out, DeviceOwner& mem);
 int launch_conv1_x6(relax_handle* h, const uint8_t* frags, const void* w_sp3, float* out, float* gap_groups, int N, hipStream_t s,
                     const float* w_inv = nullptr);   // w_inv: `w_sp3` holds fp16 planes and the f16x2 form runs
-int make_conv1_h2_weights(relax_handle* h, const float* w_packed, int kpad, void** w_h2_out, float** w_inv_out, std::vector<void*>& allocs);
+int make_conv1_h2_weights(relax_handle* h, const float* w_packed, int kpad, void** w_h2_out, float** w_inv_out, DeviceOwner& mem);
 inline int launch_gemm_x6(relax_handle* h, const void* A_sp3, const void* W_sp3, const float* bias, const float* residual,
                           float* out, void* out_sp3, int M, int N, int K, int act, hipStream_t s) {
     ConvDescX6 d{};

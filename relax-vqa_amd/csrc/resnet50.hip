@@ -101,55 +101,32 @@ int launch_pool_stats(relax_handle* h, const float* v, int64_t v_stride, float* 
 
 // ---- weights ---------------------------------------------------------------------------------------
 // (key matching, BatchNorm folding and the OIHW -> [Cout][K] packing are host_logic.cpp: pure C++, sanitizer-tested on the CPU)
-using HostSD = host::StateDict;
-
-static const float* sd_get(relax_handle* h, const HostSD& sd, const std::string& k, int64_t numel) {
-    std::string err;
-    const float* p = sd.get(k, numel, err);
-    if (!p) set_error(h, "%s", err.c_str());
-    return p;
-}
-
 static constexpr float kBnEps = 1e-5f;
 
 // conv (OIHW) [+ BN] -> device [Cout][Kpad] (+ bias).  cin_pad >= cin (conv1: 3 -> 4).
-static int make_conv(relax_handle* h, const HostSD& sd, const std::string& conv, const std::string& bn, int cout,
-                     int cin, int cin_pad, int k, int stride, int pad, ConvW* out, std::vector<void*>& allocs,
+static int make_conv(relax_handle* h, const host::StateDict& sd, const std::string& conv, const std::string& bn, int cout,
+                     int cin, int cin_pad, int k, int stride, int pad, ConvW* out, DeviceOwner& mem,
                      std::vector<float>* shift_out = nullptr) {
-    const float* w = sd_get(h, sd, conv + ".weight", (int64_t)cout * cin * k * k);
-    if (!w) return RELAX_ERR_INVALID;
+    std::string err;
+    const float* w = sd.get(conv + ".weight", (int64_t)cout * cin * k * k, err);
     std::vector<float> scale(cout, 1.f), shift(cout, 0.f);
-    if (!bn.empty()) {
-        const float* g = sd_get(h, sd, bn + ".weight", cout);
-        const float* b = g ? sd_get(h, sd, bn + ".bias", cout) : nullptr;
-        const float* mu = b ? sd_get(h, sd, bn + ".running_mean", cout) : nullptr;
-        const float* var = mu ? sd_get(h, sd, bn + ".running_var", cout) : nullptr;
-        if (!var) return RELAX_ERR_INVALID;
-        host::fold_bn(g, b, mu, var, kBnEps, cout, scale.data(), shift.data());
-    }
+    RELAX_REQUIRE(h, w && (bn.empty() || host::read_bn(sd, bn, cout, kBnEps, scale.data(), shift.data(), err)), "%s", err.c_str());
     const int kpad = host::conv_kpad(k, cin_pad);
     std::vector<float> packed((size_t)cout * kpad);
     host::pack_conv_oihw(w, scale.data(), cout, cin, cin_pad, k, kpad, packed.data());
     out->Cin = cin_pad; out->Cout = cout; out->KH = k; out->KW = k; out->stride = stride; out->pad = pad;
     out->Kpad = kpad;
     // Hoelder constants of the folded convolution: |out[n]| <= l1max * max |in| + bmax  (per-image scales of the f16x2 layers, gemm_h2.hip)
-    out->l1max = 0.f;
-    out->bmax = 0.f;
-    for (int o = 0; o < cout; ++o) {
-        double l1 = 0.0;
-        for (int kk = 0; kk < kpad; ++kk) l1 += std::fabs((double)packed[(size_t)o * kpad + kk]);
-        out->l1max = std::fmax(out->l1max, (float)(l1 * (1.0 + 1e-6)));
-        if (!bn.empty()) out->bmax = std::fmax(out->bmax, std::fabs(shift[o]));
-    }
-    RELAX_TRY(upload(h, packed.data(), packed.size(), &out->w, allocs));
-    if (!bn.empty()) RELAX_TRY(upload(h, shift.data(), shift.size(), &out->bias, allocs));
+    host::conv_hoelder(packed.data(), bn.empty() ? nullptr : shift.data(), cout, kpad, &out->l1max, &out->bmax);
+    RELAX_TRY(mem.upload(h, packed.data(), packed.size(), &out->w));
+    if (!bn.empty()) RELAX_TRY(mem.upload(h, shift.data(), shift.size(), &out->bias));
     else out->bias = nullptr;
     if (shift_out) *shift_out = shift;
     return RELAX_OK;
 }
 
 void free_resnet(relax_handle* h) {
-    for (void* p : h->rn.allocs) (void)hipFree(p);
+    h->rn.mem.release();
     h->rn = ResNet50W();
 }
 
@@ -205,58 +182,34 @@ static int run_conv(relax_handle* h, const ConvW& c, const float* in, int Nimg, 
     return launch_conv(h, d, s);
 }
 
-// ---- derived weights: device memory, conversions ------------------------------------------------------
-// fp32 staging rows of a weight conversion: device memory freed at the end of the scope
-struct ScopedDev {
-    float* p = nullptr;
-    bool alloc(size_t floats) { return hipMalloc(reinterpret_cast<void**>(&p), sizeof(float) * floats) == hipSuccess; }
-    ~ScopedDev() { if (p) (void)hipFree(p); }
-};
-
-// device memory that lives with the model (free_resnet), or nullptr
-static void* keep_alloc(ResNet50W& rn, size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    rn.allocs.push_back(p);
-    return p;
-}
-
-// room for [rows][K] as two fp16 planes and their inverse row scales
-static bool alloc_h2(ResNet50W& rn, int rows, int K, void** q, float** inv) {
-    *q = keep_alloc(rn, (size_t)rows * K * 4);
-    *inv = *q ? static_cast<float*>(keep_alloc(rn, sizeof(float) * (size_t)rows)) : nullptr;
-    return *inv != nullptr;
-}
-
+// ---- derived weights --------------------------------------------------------------------------------------
 // dst [rows][Ka + Kb] = [a | b] rows side by side
-static hipError_t concat_rows(float* dst, const float* a, int Ka, const float* b, int Kb, int rows) {
+static int concat_rows(relax_handle* h, float* dst, const float* a, int Ka, const float* b, int Kb, int rows) {
     const size_t ld = sizeof(float) * (Ka + Kb);
-    hipError_t e = hipMemcpy2D(dst, ld, a, sizeof(float) * Ka, sizeof(float) * Ka, rows, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy2D(dst + Ka, ld, b, sizeof(float) * Kb, sizeof(float) * Kb, rows, hipMemcpyDeviceToDevice);
-    return e;
+    RELAX_HIP_CHECK(h, hipMemcpy2D(dst, ld, a, sizeof(float) * Ka, sizeof(float) * Ka, rows, hipMemcpyDeviceToDevice));
+    RELAX_HIP_CHECK(h, hipMemcpy2D(dst + Ka, ld, b, sizeof(float) * Kb, sizeof(float) * Kb, rows, hipMemcpyDeviceToDevice));
+    return RELAX_OK;
 }
 
-// the end of a conversion through staging rows: it is through before they are freed, and a failure carries the step's name
+// the end of a conversion through staging rows: it is through (after a failed step too) before they are freed
 static int built(relax_handle* h, int rc, const char* what) {
-    if (rc == RELAX_OK && hipDeviceSynchronize() != hipSuccess) rc = RELAX_ERR_HIP;
-    if (rc != RELAX_OK) set_error(h, "resnet50: building %s failed", what);
+    if (hipDeviceSynchronize() != hipSuccess && rc == RELAX_OK) {
+        set_error(h, "resnet50: building %s failed", what);
+        rc = RELAX_ERR_HIP;
+    }
     return rc;
 }
 
 // everything relax_load_resnet50 puts on the device; the caller frees it all if this fails
-static int load_resnet(relax_handle* h, const HostSD& sd) {
+static int load_resnet(relax_handle* h, const host::StateDict& sd) {
     ResNet50W& rn = h->rn;
-    RELAX_TRY(make_conv(h, sd, "conv1", "", 64, 3, 4, 7, 2, 3, &rn.conv1, rn.allocs));
+    RELAX_TRY(make_conv(h, sd, "conv1", "", 64, 3, 4, 7, 2, 3, &rn.conv1, rn.mem));
     {
-        const float* g = sd_get(h, sd, "bn1.weight", 64);
-        const float* b = g ? sd_get(h, sd, "bn1.bias", 64) : nullptr;
-        const float* mu = b ? sd_get(h, sd, "bn1.running_mean", 64) : nullptr;
-        const float* var = mu ? sd_get(h, sd, "bn1.running_var", 64) : nullptr;
-        if (!var) return RELAX_ERR_INVALID;
         std::vector<float> sc(64), sh(64);
-        host::fold_bn(g, b, mu, var, kBnEps, 64, sc.data(), sh.data());
-        RELAX_TRY(upload(h, sc.data(), 64, &rn.bn1_scale, rn.allocs));
-        RELAX_TRY(upload(h, sh.data(), 64, &rn.bn1_shift, rn.allocs));
+        std::string err;
+        RELAX_REQUIRE(h, host::read_bn(sd, "bn1", 64, kBnEps, sc.data(), sh.data(), err), "%s", err.c_str());
+        RELAX_TRY(rn.mem.upload(h, sc.data(), 64, &rn.bn1_scale));
+        RELAX_TRY(rn.mem.upload(h, sh.data(), 64, &rn.bn1_shift));
     }
     const host::RnBlockGeom* geom = host::rn_geometry();
     for (int b = 0; b < host::kRnBlocks; ++b) {
@@ -264,21 +217,21 @@ static int load_resnet(relax_handle* h, const HostSD& sd) {
         Bottleneck blk;
         const std::string p = "layer" + std::to_string(k.layer) + "." + std::to_string(k.index);
         std::vector<float> shift3, shiftd;
-        RELAX_TRY(make_conv(h, sd, p + ".conv1", p + ".bn1", k.width, k.cin, k.cin, 1, 1, 0, &blk.c1, rn.allocs));
-        RELAX_TRY(make_conv(h, sd, p + ".conv2", p + ".bn2", k.width, k.width, k.width, 3, k.stride, 1, &blk.c2, rn.allocs));
-        RELAX_TRY(make_conv(h, sd, p + ".conv3", p + ".bn3", k.cout, k.width, k.width, 1, 1, 0, &blk.c3, rn.allocs, &shift3));
+        RELAX_TRY(make_conv(h, sd, p + ".conv1", p + ".bn1", k.width, k.cin, k.cin, 1, 1, 0, &blk.c1, rn.mem));
+        RELAX_TRY(make_conv(h, sd, p + ".conv2", p + ".bn2", k.width, k.width, k.width, 3, k.stride, 1, &blk.c2, rn.mem));
+        RELAX_TRY(make_conv(h, sd, p + ".conv3", p + ".bn3", k.cout, k.width, k.width, 1, 1, 0, &blk.c3, rn.mem, &shift3));
         blk.has_down = k.has_down;
         if (blk.has_down) {
-            RELAX_TRY(make_conv(h, sd, p + ".downsample.0", p + ".downsample.1", k.cout, k.cin, k.cin, 1, k.stride, 0, &blk.down, rn.allocs, &shiftd));
+            RELAX_TRY(make_conv(h, sd, p + ".downsample.0", p + ".downsample.1", k.cout, k.cin, k.cin, 1, k.stride, 0, &blk.down, rn.mem, &shiftd));
             for (size_t o = 0; o < shift3.size(); ++o) shift3[o] += shiftd[o];   // bias of the fused conv3 + downsample contraction
-            RELAX_TRY(upload(h, shift3.data(), shift3.size(), &blk.c3d_bias, rn.allocs));
+            RELAX_TRY(rn.mem.upload(h, shift3.data(), shift3.size(), &blk.c3d_bias));
         }
         blk.tap = k.tap;
         rn.blocks.push_back(blk);
     }
     // split planes for the bf16x6 kernels (made on the device from the packed fp32 copies): conv1 in its own K layout ...
-    RELAX_TRY(make_conv1_x6_weights(h, rn.conv1.w, rn.conv1.Kpad, &rn.conv1.w_sp3, rn.allocs));
-    RELAX_TRY(make_conv1_h2_weights(h, rn.conv1.w, rn.conv1.Kpad, &rn.conv1.w_h2, &rn.conv1.w_inv, rn.allocs));
+    RELAX_TRY(make_conv1_x6_weights(h, rn.conv1.w, rn.conv1.Kpad, &rn.conv1.w_sp3, rn.mem));
+    RELAX_TRY(make_conv1_h2_weights(h, rn.conv1.w, rn.conv1.Kpad, &rn.conv1.w_h2, &rn.conv1.w_inv, rn.mem));
     for (int b = 0; b < host::kRnBlocks; ++b) {
         Bottleneck& blk = rn.blocks[b];
         const host::RnBlockGeom& k = geom[b];
@@ -292,62 +245,45 @@ static int load_resnet(relax_handle* h, const HostSD& sd) {
         for (const auto& [c, as_h2] : convs) {
             if (!c->w) continue;
             const int K = c->KH * c->KW * c->Cin;
-            if (K != c->Kpad || c->Cin % 16 != 0) {
-                set_error(h, "resnet50: conv K=%d (padded %d) does not fit the split-plane layout", K, c->Kpad);
-                return RELAX_ERR_INVALID;
-            }
-            c->w_sp3 = keep_alloc(rn, (size_t)c->Cout * K * 6);
-            if (!c->w_sp3) {
-                set_error(h, "resnet50: hipMalloc of split-plane weights failed");
-                return RELAX_ERR_NOMEM;
-            }
-            RELAX_TRY(launch_to_sp3(h, c->w, K, c->w_sp3, c->Cout, K, nullptr));
+            RELAX_REQUIRE(h, K == c->Kpad && c->Cin % 16 == 0, "resnet50: conv K=%d (padded %d) does not fit the split-plane layout", K, c->Kpad);
+            RELAX_TRY(derive_sp3(h, rn.mem, c->w, c->Cout, K, &c->w_sp3, "resnet50 split-plane weights"));
             if (!as_h2) continue;
-            if ((late && (c->Cin % 32 != 0 || c->Cout % 256 != 0)) || !alloc_h2(rn, c->Cout, K, &c->w_h2, &c->w_inv)) {
-                set_error(h, "resnet50: fp16-plane weights of block %d (Cin %d, Cout %d) could not be made", b, c->Cin, c->Cout);
-                return RELAX_ERR_NOMEM;
-            }
-            RELAX_TRY(launch_to_h2_rows(h, c->w, K, c->w_h2, c->Cout, K, c->w_inv, nullptr));
+            RELAX_REQUIRE(h, !late || (c->Cin % 32 == 0 && c->Cout % 256 == 0), "resnet50: fp16-plane weights of block %d (Cin %d, Cout %d) could not be made",
+                          b, c->Cin, c->Cout);
+            RELAX_TRY(derive_h2_rows(h, rn.mem, c->w, c->Cout, K, &c->w_h2, &c->w_inv, "resnet50 fp16-plane weights"));
         }
         const int Co = blk.c3.Cout;
         // ... conv3 of a block that can run back to back once more as fp16 planes with the K axis in the order of that form ("rn_fuse":
         // gemm_x6.hip, B2B - the 3x3's transposed accumulator tile is the A operand)
         if (host::rn_can_b2b(k)) {
             const int K = blk.c3.Cin;
+            const char* what = "the back-to-back conv3 weights";
             ScopedDev perm;
-            if (!perm.alloc((size_t)Co * K) || !alloc_h2(rn, Co, K, &blk.c3.w_h2p, &blk.c3.w_invp)) {
-                set_error(h, "resnet50: hipMalloc of the back-to-back conv3 weights failed");
-                return RELAX_ERR_NOMEM;
-            }
+            if (!perm.alloc(h, (size_t)Co * K, what)) return RELAX_ERR_NOMEM;
             int rc = launch_b2b_permute_k(h, blk.c3.w, perm.p, Co, K, nullptr);
-            if (rc == RELAX_OK) rc = launch_to_h2_rows(h, perm.p, K, blk.c3.w_h2p, Co, K, blk.c3.w_invp, nullptr);
-            RELAX_TRY(built(h, rc, "the back-to-back conv3 weights"));
+            if (rc == RELAX_OK) rc = derive_h2_rows(h, rn.mem, perm.p, Co, K, &blk.c3.w_h2p, &blk.c3.w_invp, what);
+            RELAX_TRY(built(h, rc, what));
         }
         // ... for layer1[0] [conv3 (K permuted) | downsample (natural K)] rows of 128 as fp16 planes: its back-to-back form contracts conv3 and
         // the downsample convolution in one accumulator (gemm_x6.hip, B2B == 2)
         if (host::rn_can_b2b_x2(k)) {
+            const char* what = "the two-source back-to-back weights";
             ScopedDev perm, cat;
-            if (!perm.alloc((size_t)Co * 64) || !cat.alloc((size_t)Co * 128) || !alloc_h2(rn, Co, 128, &blk.c3d_w_h2p, &blk.c3d_w_invp)) {
-                set_error(h, "resnet50: hipMalloc of the two-source back-to-back weights failed");
-                return RELAX_ERR_NOMEM;
-            }
-            hipError_t e = launch_b2b_permute_k(h, blk.c3.w, perm.p, Co, 64, nullptr) == RELAX_OK ? hipDeviceSynchronize() : hipErrorUnknown;
-            if (e == hipSuccess) e = concat_rows(cat.p, perm.p, 64, blk.down.w, 64, Co);
-            RELAX_TRY(built(h, e == hipSuccess ? launch_to_h2_rows(h, cat.p, 128, blk.c3d_w_h2p, Co, 128, blk.c3d_w_invp, nullptr) : RELAX_ERR_HIP,
-                            "the two-source back-to-back weights"));
+            if (!perm.alloc(h, (size_t)Co * 64, what) || !cat.alloc(h, (size_t)Co * 128, what)) return RELAX_ERR_NOMEM;
+            int rc = built(h, launch_b2b_permute_k(h, blk.c3.w, perm.p, Co, 64, nullptr), what);
+            if (rc == RELAX_OK) rc = concat_rows(h, cat.p, perm.p, 64, blk.down.w, 64, Co);
+            if (rc == RELAX_OK) rc = derive_h2_rows(h, rn.mem, cat.p, Co, 128, &blk.c3d_w_h2p, &blk.c3d_w_invp, what);
+            RELAX_TRY(built(h, rc, what));
         }
         // ... and, for the four blocks with a downsample branch, [conv3 | downsample] rows side by side as split planes
         if (blk.has_down) {
             const int K1 = blk.c3.Cin, K2 = blk.down.Cin;
+            const char* what = "the fused conv3 + downsample weights";
             ScopedDev cat;
-            blk.c3d_w_sp3 = cat.alloc((size_t)Co * (K1 + K2)) ? keep_alloc(rn, (size_t)Co * (K1 + K2) * 6) : nullptr;
-            if (!blk.c3d_w_sp3) {
-                set_error(h, "resnet50: hipMalloc of the fused conv3 + downsample weights failed");
-                return RELAX_ERR_NOMEM;
-            }
-            const hipError_t e = concat_rows(cat.p, blk.c3.w, K1, blk.down.w, K2, Co);
-            RELAX_TRY(built(h, e == hipSuccess ? launch_to_sp3(h, cat.p, K1 + K2, blk.c3d_w_sp3, Co, K1 + K2, nullptr) : RELAX_ERR_HIP,
-                            "the fused conv3 + downsample weights"));
+            if (!cat.alloc(h, (size_t)Co * (K1 + K2), what)) return RELAX_ERR_NOMEM;
+            int rc = concat_rows(h, cat.p, blk.c3.w, K1, blk.down.w, K2, Co);
+            if (rc == RELAX_OK) rc = derive_sp3(h, rn.mem, cat.p, Co, K1 + K2, &blk.c3d_w_sp3, what);
+            RELAX_TRY(built(h, rc, what));
         }
     }
     if (hipDeviceSynchronize() != hipSuccess) {
@@ -369,7 +305,7 @@ int relax_load_resnet50(relax_handle* h, const float* const* tensors, const char
     RELAX_REQUIRE(h, tensors && names && numels && n > 0, "relax_load_resnet50: bad arguments");
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     free_resnet(h);
-    HostSD sd;
+    host::StateDict sd;
     for (int i = 0; i < n; ++i) sd.add(names[i], tensors[i], numels[i]);
     const int rc = load_resnet(h, sd);
     if (rc == RELAX_OK) h->rn.loaded = true;

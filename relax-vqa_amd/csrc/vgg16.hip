@@ -179,43 +179,20 @@ __global__ __launch_bounds__(256) void vgg_maxpool2x2(const float* __restrict__ 
 
 // ---- weights ---------------------------------------------------------------------------------------
 void free_vgg(relax_handle* h) {
-    for (void* p : h->vgg.allocs) (void)hipFree(p);
+    h->vgg.mem.release();
     h->vgg = VggW();
 }
 
 // packed fp32 [Cout][K] rows on the host -> device copies in the three formats (fp32, split planes, fp16 planes + inverse row scales),
 // and the Hoelder constants |out[n]| <= l1max * max |in| + bmax
-static int make_rows(relax_handle* h, const std::vector<float>& packed, const float* bias, int cout, int k, ConvW* c, std::vector<void*>& allocs,
-                     bool planes) {
+static int make_rows(relax_handle* h, const std::vector<float>& packed, const float* bias, int cout, int k, ConvW* c, DeviceOwner& mem, bool planes) {
     c->Cout = cout; c->Kpad = k;
-    c->l1max = 0.f;
-    c->bmax = 0.f;
-    for (int o = 0; o < cout; ++o) {
-        double l1 = 0.0;
-        for (int kk = 0; kk < k; ++kk) l1 += std::fabs((double)packed[(size_t)o * k + kk]);
-        c->l1max = std::fmax(c->l1max, (float)(l1 * (1.0 + 1e-6)));
-        c->bmax = std::fmax(c->bmax, std::fabs(bias[o]));
-    }
-    RELAX_TRY(upload(h, packed.data(), packed.size(), &c->w, allocs));
-    RELAX_TRY(upload(h, bias, (size_t)cout, &c->bias, allocs));
+    host::conv_hoelder(packed.data(), bias, cout, k, &c->l1max, &c->bmax);
+    RELAX_TRY(mem.upload(h, packed.data(), packed.size(), &c->w));
+    RELAX_TRY(mem.upload(h, bias, (size_t)cout, &c->bias));
     if (!planes) return RELAX_OK;
-    void* q = nullptr;
-    void* q2 = nullptr;
-    float* inv = nullptr;
-    if (hipMalloc(&q, (size_t)cout * k * 6) != hipSuccess) { set_error(h, "vgg16: hipMalloc of split-plane weights failed"); return RELAX_ERR_NOMEM; }
-    allocs.push_back(q);
-    if (hipMalloc(&q2, (size_t)cout * k * 4) != hipSuccess) { set_error(h, "vgg16: hipMalloc of fp16-plane weights failed"); return RELAX_ERR_NOMEM; }
-    allocs.push_back(q2);
-    if (hipMalloc(reinterpret_cast<void**>(&inv), sizeof(float) * (size_t)cout) != hipSuccess) {
-        set_error(h, "vgg16: hipMalloc of weight scales failed");
-        return RELAX_ERR_NOMEM;
-    }
-    allocs.push_back(inv);
-    c->w_sp3 = q;
-    c->w_h2 = q2;
-    c->w_inv = inv;
-    RELAX_TRY(launch_to_sp3(h, c->w, k, q, cout, k, nullptr));
-    RELAX_TRY(launch_to_h2_rows(h, c->w, k, q2, cout, k, inv, nullptr));
+    RELAX_TRY(derive_sp3(h, mem, c->w, cout, k, &c->w_sp3, "vgg16 split-plane weights"));
+    RELAX_TRY(derive_h2_rows(h, mem, c->w, cout, k, &c->w_h2, &c->w_inv, "vgg16 fp16-plane weights"));
     RELAX_HIP_CHECK(h, hipDeviceSynchronize());
     return RELAX_OK;
 }
@@ -236,7 +213,7 @@ static int load_vgg(relax_handle* h, const host::StateDict& sd) {
         std::vector<float> packed((size_t)cout * kpad);
         host::pack_conv_oihw(w, nullptr, cout, cin, cin, 3, kpad, packed.data());
         ConvW& c = v.conv[i];
-        RELAX_TRY(make_rows(h, packed, b, cout, kpad, &c, v.allocs, i > 0));
+        RELAX_TRY(make_rows(h, packed, b, cout, kpad, &c, v.mem, i > 0));
         c.Cin = cin; c.KH = 3; c.KW = 3; c.stride = 1; c.pad = 1;
     }
     {   // conv1_1 writes fp16 planes with one static scale: its input is bounded by the normalisation, |(x - mean) / std| <= max over the
@@ -255,7 +232,7 @@ static int load_vgg(relax_handle* h, const host::StateDict& sd) {
         if (i == 0) host::vgg16_fc1_to_nhwc(w, 4096, 512, 49, rows.data());
         else std::memcpy(rows.data(), w, sizeof(float) * rows.size());
         ConvW& c = v.fc[i];
-        RELAX_TRY(make_rows(h, rows, b, 4096, k, &c, v.allocs, true));
+        RELAX_TRY(make_rows(h, rows, b, 4096, k, &c, v.mem, true));
         c.Cin = k; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
     }
     v.loaded = true;

@@ -143,13 +143,109 @@ __global__ __launch_bounds__(256) void vit_token_stats(const float* __restrict__
 }
 
 void free_vit(relax_handle* h) {
-    for (void* p : h->vit.allocs) (void)hipFree(p);
+    h->vit.mem.release();
     h->vit = VitW();
 }
 
 size_t vit_arena_bytes(const VitW& v, int n) {
     const size_t a = host::vit_floats_per_image(v.dim, v.ntok, v.npatch, v.patch_k), b = host::vit_floats_per_image_x6(v.dim, v.ntok, v.npatch, v.patch_k);
     return sizeof(float) * (a > b ? a : b) * (size_t)n;
+}
+
+// everything relax_load_vit_ex puts on the device; the caller frees it all if this fails
+static int load_vit(relax_handle* h, const host::StateDict& sd, const host::VitGeometry& geo, int dim, int depth, int heads) {
+    VitW& v = h->vit;
+    auto host_of = [&](const std::string& key, int64_t numel) -> const float* {
+        std::string err;
+        const float* src = sd.get(key, numel, err, "vit state dict");
+        if (!src) set_error(h, "%s", err.c_str());
+        return src;
+    };
+    auto up = [&](const std::string& key, int64_t numel, float** dst) -> int {
+        const float* src = host_of(key, numel);
+        return src ? v.mem.upload(h, src, (size_t)numel, dst) : RELAX_ERR_INVALID;
+    };
+    auto lin = [&](const std::string& p, int in, int out, LinearW* l) -> int {
+        l->in = in;
+        l->out = out;
+        RELAX_TRY(up(p + ".weight", (int64_t)in * out, &l->w));
+        return up(p + ".bias", out, &l->b);
+    };
+    v.dim = dim; v.depth = depth; v.heads = heads;
+    v.patch = geo.patch; v.ntok = geo.ntok; v.npatch = geo.npatch; v.patch_k = geo.patch_k;
+    RELAX_TRY(up("cls_token", dim, &v.cls));
+    RELAX_TRY(up("pos_embed", (int64_t)geo.ntok * dim, &v.pos));
+    RELAX_TRY(lin("patch_embed.proj", geo.patch_k, dim, &v.patch_w));  // OIHW [dim][3][p][p] is already [dim][(c*p+py)*p+px]
+    v.blocks.resize(depth);
+    for (int i = 0; i < depth; ++i) {
+        const std::string p = "blocks." + std::to_string(i) + ".";
+        VitBlockW& b = v.blocks[i];
+        RELAX_TRY(up(p + "norm1.weight", dim, &b.ln1_g));
+        RELAX_TRY(up(p + "norm1.bias", dim, &b.ln1_b));
+        RELAX_TRY(lin(p + "attn.qkv", dim, 3 * dim, &b.qkv));
+        RELAX_TRY(lin(p + "attn.proj", dim, dim, &b.proj));
+        RELAX_TRY(up(p + "norm2.weight", dim, &b.ln2_g));
+        RELAX_TRY(up(p + "norm2.bias", dim, &b.ln2_b));
+        RELAX_TRY(lin(p + "mlp.fc1", dim, 4 * dim, &b.fc1));
+        RELAX_TRY(lin(p + "mlp.fc2", 4 * dim, dim, &b.fc2));
+    }
+    RELAX_TRY(up("norm.weight", dim, &v.norm_g));
+    RELAX_TRY(up("norm.bias", dim, &v.norm_b));
+    // split planes of every GEMM weight for the bf16x6 kernel (made on the device from the uploaded fp32 copy)
+    auto sp3 = [&](LinearW* l) { return derive_sp3(h, v.mem, l->w, l->out, l->in, &l->w_sp3, "vit split-plane weights"); };
+    RELAX_TRY(sp3(&v.patch_w));
+    for (VitBlockW& b : v.blocks) {
+        RELAX_TRY(sp3(&b.qkv));
+        RELAX_TRY(sp3(&b.proj));
+        RELAX_TRY(sp3(&b.fc1));
+        RELAX_TRY(sp3(&b.fc2));
+    }
+    // two fp16 planes of every GEMM weight for the f16x2 kernel: row n scaled by 2^t_n (from the row's maximum); colscale[n] =
+    // 2^-t_n / (the static scale of the activation tensor the layer reads).  The activation scales come from bounds that hold for
+    // EVERY input (host_logic.h), evaluated here in double on the host copies of the weights (present: `up` has checked every key).
+    std::vector<float> tmp_scale, tmp_col;
+    auto h2w = [&](LinearW* l, const std::string& p, float act_scale) -> int {
+        const float* hw = host_of(p + ".weight", (int64_t)l->in * l->out);
+        tmp_scale.resize((size_t)l->out);
+        tmp_col.resize((size_t)l->out);
+        host::h2_weight_row_scales(hw, l->out, l->in, tmp_scale.data());
+        for (int n = 0; n < l->out; ++n) tmp_col[(size_t)n] = (1.f / tmp_scale[(size_t)n]) * (1.f / act_scale);   // powers of two: exact
+        float* d_scale = nullptr;
+        l->w_h2 = v.mem.keep(h, (size_t)l->in * l->out * 4, "vit fp16-plane weights");
+        if (!l->w_h2) return RELAX_ERR_NOMEM;
+        RELAX_TRY(v.mem.upload(h, tmp_scale.data(), (size_t)l->out, &d_scale));
+        RELAX_TRY(v.mem.upload(h, tmp_col.data(), (size_t)l->out, &l->colscale));
+        return launch_to_h2(h, l->w, l->in, l->w_h2, l->out, l->in, 1.f, d_scale, nullptr);
+    };
+    if (dim % 256 == 0) {   // (the f16x2 tile takes N % 256 == 0: ViT-B; smaller models run bf16x6 under "gemm_precision" 3)
+        // (patch 8: the patch-embed GEMM runs on bf16x6 under f16x2 too - see vit_forward - and needs no fp16 planes)
+        if (geo.patch == 16) RELAX_TRY(h2w(&v.patch_w, "patch_embed.proj", kPatchScale));
+        for (int i = 0; i < depth; ++i) {
+            const std::string p = "blocks." + std::to_string(i) + ".";
+            VitBlockW& b = v.blocks[i];
+            const float *g1 = host_of(p + "norm1.weight", dim), *b1 = host_of(p + "norm1.bias", dim);
+            const float *g2 = host_of(p + "norm2.weight", dim), *b2 = host_of(p + "norm2.bias", dim);
+            b.s_ln1 = host::h2_scale_for_bound(host::layernorm_out_bound(g1, b1, dim));
+            b.s_ln2 = host::h2_scale_for_bound(host::layernorm_out_bound(g2, b2, dim));
+            // attention output = convex combinations of the V rows of qkv(LayerNorm1(x)): columns 2 dim .. 3 dim of the qkv Linear
+            b.s_att = host::h2_scale_for_bound(host::linear_of_layernorm_bound(host_of(p + "attn.qkv.weight", (int64_t)3 * dim * dim),
+                                                                               host_of(p + "attn.qkv.bias", 3 * dim), g1, b1, dim, 2 * dim, 3 * dim));
+            b.s_qkv = host::h2_scale_for_bound(host::linear_of_layernorm_bound(host_of(p + "attn.qkv.weight", (int64_t)3 * dim * dim),
+                                                                               host_of(p + "attn.qkv.bias", 3 * dim), g1, b1, dim, 0, 3 * dim));
+            // |GELU(x)| <= |x|, x = fc1(LayerNorm2(.))
+            b.s_hid = host::h2_scale_for_bound(host::linear_of_layernorm_bound(host_of(p + "mlp.fc1.weight", (int64_t)4 * dim * dim),
+                                                                               host_of(p + "mlp.fc1.bias", 4 * dim), g2, b2, dim, 0, 4 * dim));
+            RELAX_TRY(h2w(&b.qkv, p + "attn.qkv", b.s_ln1));
+            RELAX_TRY(h2w(&b.proj, p + "attn.proj", b.s_att));
+            RELAX_TRY(h2w(&b.fc1, p + "mlp.fc1", b.s_ln2));
+            RELAX_TRY(h2w(&b.fc2, p + "mlp.fc2", b.s_hid));
+        }
+    }
+    if (hipDeviceSynchronize() != hipSuccess) {
+        set_error(h, "vit: weight conversion failed");
+        return RELAX_ERR_HIP;
+    }
+    return RELAX_OK;
 }
 
 }  // namespace relax
@@ -187,127 +283,10 @@ int relax_load_vit_ex(relax_handle* h, const float* const* tensors, const char* 
                   (long long)n_pw, (long long)(n_pw / dim), dim, geo.patch, geo.patch_k, geo.patch, geo.patch);
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     free_vit(h);
-    VitW& v = h->vit;
-    int rc = RELAX_OK;
-    auto up = [&](const std::string& key, int64_t numel, float** dst) {
-        if (rc != RELAX_OK) return;
-        std::string err;
-        const float* src = sd.get(key, numel, err, "vit state dict");
-        if (!src) {
-            set_error(h, "%s", err.c_str());
-            rc = RELAX_ERR_INVALID;
-            return;
-        }
-        rc = upload(h, src, (size_t)numel, dst, v.allocs);
-    };
-    auto lin = [&](const std::string& p, int in, int out, LinearW* l) {
-        l->in = in;
-        l->out = out;
-        up(p + ".weight", (int64_t)in * out, &l->w);
-        up(p + ".bias", out, &l->b);
-    };
-    v.dim = dim; v.depth = depth; v.heads = heads;
-    v.patch = geo.patch; v.ntok = geo.ntok; v.npatch = geo.npatch; v.patch_k = geo.patch_k;
-    up("cls_token", dim, &v.cls);
-    up("pos_embed", (int64_t)geo.ntok * dim, &v.pos);
-    lin("patch_embed.proj", geo.patch_k, dim, &v.patch_w);  // OIHW [dim][3][p][p] is already [dim][(c*p+py)*p+px]
-    v.blocks.resize(depth);
-    for (int i = 0; i < depth; ++i) {
-        const std::string p = "blocks." + std::to_string(i) + ".";
-        VitBlockW& b = v.blocks[i];
-        up(p + "norm1.weight", dim, &b.ln1_g);
-        up(p + "norm1.bias", dim, &b.ln1_b);
-        lin(p + "attn.qkv", dim, 3 * dim, &b.qkv);
-        lin(p + "attn.proj", dim, dim, &b.proj);
-        up(p + "norm2.weight", dim, &b.ln2_g);
-        up(p + "norm2.bias", dim, &b.ln2_b);
-        lin(p + "mlp.fc1", dim, 4 * dim, &b.fc1);
-        lin(p + "mlp.fc2", 4 * dim, dim, &b.fc2);
-    }
-    up("norm.weight", dim, &v.norm_g);
-    up("norm.bias", dim, &v.norm_b);
-    // split planes of every GEMM weight for the bf16x6 kernel (made on the device from the uploaded fp32 copy)
-    auto sp3 = [&](LinearW* l) {
-        if (rc != RELAX_OK) return;
-        void* q = nullptr;
-        if (hipMalloc(&q, (size_t)l->in * l->out * 6) != hipSuccess) {
-            set_error(h, "vit: hipMalloc of split-plane weights failed");
-            rc = RELAX_ERR_NOMEM;
-            return;
-        }
-        v.allocs.push_back(q);
-        l->w_sp3 = q;
-        rc = launch_to_sp3(h, l->w, l->in, q, l->out, l->in, nullptr);
-    };
-    sp3(&v.patch_w);
-    for (VitBlockW& b : v.blocks) {
-        sp3(&b.qkv);
-        sp3(&b.proj);
-        sp3(&b.fc1);
-        sp3(&b.fc2);
-    }
-    // two fp16 planes of every GEMM weight for the f16x2 kernel: row n scaled by 2^t_n (from the row's maximum); colscale[n] =
-    // 2^-t_n / (the static scale of the activation tensor the layer reads).  The activation scales come from bounds that hold for
-    // EVERY input (host_logic.h), evaluated here in double on the host copies of the weights.
-    auto host_of = [&](const std::string& key, int64_t numel) -> const float* {
-        std::string err;
-        return sd.get(key, numel, err, "vit state dict");   // (present: `up` has already checked every key)
-    };
-    std::vector<float> tmp_scale, tmp_col;
-    auto h2w = [&](LinearW* l, const std::string& p, float act_scale) {
-        if (rc != RELAX_OK) return;
-        const float* hw = host_of(p + ".weight", (int64_t)l->in * l->out);
-        tmp_scale.resize((size_t)l->out);
-        tmp_col.resize((size_t)l->out);
-        host::h2_weight_row_scales(hw, l->out, l->in, tmp_scale.data());
-        for (int n = 0; n < l->out; ++n) tmp_col[(size_t)n] = (1.f / tmp_scale[(size_t)n]) * (1.f / act_scale);   // powers of two: exact
-        float* d_scale = nullptr;
-        void* q = nullptr;
-        if (hipMalloc(&q, (size_t)l->in * l->out * 4) != hipSuccess) {
-            set_error(h, "vit: hipMalloc of fp16-plane weights failed");
-            rc = RELAX_ERR_NOMEM;
-            return;
-        }
-        v.allocs.push_back(q);
-        l->w_h2 = q;
-        rc = upload(h, tmp_scale.data(), (size_t)l->out, &d_scale, v.allocs);
-        if (rc == RELAX_OK) rc = upload(h, tmp_col.data(), (size_t)l->out, &l->colscale, v.allocs);
-        if (rc == RELAX_OK) rc = launch_to_h2(h, l->w, l->in, q, l->out, l->in, 1.f, d_scale, nullptr);
-    };
-    if (rc == RELAX_OK && dim % 256 == 0) {   // (the f16x2 tile takes N % 256 == 0: ViT-B; smaller models run bf16x6 under "gemm_precision" 3)
-        // (patch 8: the patch-embed GEMM runs on bf16x6 under f16x2 too - see vit_forward - and needs no fp16 planes)
-        if (geo.patch == 16) h2w(&v.patch_w, "patch_embed.proj", kPatchScale);
-        for (int i = 0; i < depth && rc == RELAX_OK; ++i) {
-            const std::string p = "blocks." + std::to_string(i) + ".";
-            VitBlockW& b = v.blocks[i];
-            const float *g1 = host_of(p + "norm1.weight", dim), *b1 = host_of(p + "norm1.bias", dim);
-            const float *g2 = host_of(p + "norm2.weight", dim), *b2 = host_of(p + "norm2.bias", dim);
-            b.s_ln1 = host::h2_scale_for_bound(host::layernorm_out_bound(g1, b1, dim));
-            b.s_ln2 = host::h2_scale_for_bound(host::layernorm_out_bound(g2, b2, dim));
-            // attention output = convex combinations of the V rows of qkv(LayerNorm1(x)): columns 2 dim .. 3 dim of the qkv Linear
-            b.s_att = host::h2_scale_for_bound(host::linear_of_layernorm_bound(host_of(p + "attn.qkv.weight", (int64_t)3 * dim * dim),
-                                                                               host_of(p + "attn.qkv.bias", 3 * dim), g1, b1, dim, 2 * dim, 3 * dim));
-            b.s_qkv = host::h2_scale_for_bound(host::linear_of_layernorm_bound(host_of(p + "attn.qkv.weight", (int64_t)3 * dim * dim),
-                                                                               host_of(p + "attn.qkv.bias", 3 * dim), g1, b1, dim, 0, 3 * dim));
-            // |GELU(x)| <= |x|, x = fc1(LayerNorm2(.))
-            b.s_hid = host::h2_scale_for_bound(host::linear_of_layernorm_bound(host_of(p + "mlp.fc1.weight", (int64_t)4 * dim * dim),
-                                                                               host_of(p + "mlp.fc1.bias", 4 * dim), g2, b2, dim, 0, 4 * dim));
-            h2w(&b.qkv, p + "attn.qkv", b.s_ln1);
-            h2w(&b.proj, p + "attn.proj", b.s_att);
-            h2w(&b.fc1, p + "mlp.fc1", b.s_ln2);
-            h2w(&b.fc2, p + "mlp.fc2", b.s_hid);
-        }
-    }
-    if (rc == RELAX_OK && hipDeviceSynchronize() != hipSuccess) {
-        set_error(h, "vit: weight conversion failed");
-        rc = RELAX_ERR_HIP;
-    }
-    if (rc != RELAX_OK) {
-        free_vit(h);
-        return rc;
-    }
-    v.loaded = true;
-    return RELAX_OK;
+    const int rc = load_vit(h, sd, geo, dim, depth, heads);
+    if (rc == RELAX_OK) h->vit.loaded = true;
+    else free_vit(h);   // a failed load leaves nothing behind
+    return rc;
 }
 
 }  // extern "C"

@@ -1,0 +1,87 @@
+// Stand-alone program (its own main) for AddressSanitizer + UBSan: csrc/host_logic.cpp's conv_hoelder and read_bn on the shapes of
+// tests/test_conv_hoelder_cpu.py and on malformed BatchNorm dicts.  Every input and output sits in a heap block of exactly its size, so a
+// read or write past an end is reported.  Built and run by tests/test_conv_hoelder_cpu.py; exit status 0 and "host_logic_san: OK" if all holds.
+#include <cmath>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "host_logic.h"
+
+using namespace relax::host;
+
+static int failures = 0;
+#define CHECK(cond)                                                     \
+    do {                                                                \
+        if (!(cond)) {                                                  \
+            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+            ++failures;                                                 \
+        }                                                               \
+    } while (0)
+
+static void hoelder_cases(int cout, int k) {
+    std::vector<float> rows((size_t)cout * k), bias((size_t)cout), zeros((size_t)cout * k, 0.f);
+    unsigned s = 12345u + (unsigned)cout * 7919u + (unsigned)k;
+    auto next = [&]() { s = s * 1664525u + 1013904223u; return (float)((int)(s >> 8) % 2001 - 1000) / 512.f; };
+    for (float& v : rows) v = next();
+    for (float& v : bias) v = next();
+    float want_l1 = 0.f, want_b = 0.f;   // the definition, written out once more
+    for (int o = 0; o < cout; ++o) {
+        double l1 = 0.0;
+        for (int j = 0; j < k; ++j) l1 += std::fabs((double)rows[(size_t)o * k + j]);
+        want_l1 = std::fmax(want_l1, (float)(l1 * (1.0 + 1e-6)));
+        want_b = std::fmax(want_b, std::fabs(bias[(size_t)o]));
+    }
+    float l1 = -1.f, b = -1.f;
+    conv_hoelder(rows.data(), bias.data(), cout, k, &l1, &b);
+    CHECK(l1 == want_l1 && b == want_b && l1 > 0.f);
+    conv_hoelder(rows.data(), nullptr, cout, k, &l1, &b);
+    CHECK(l1 == want_l1 && b == 0.f);
+    conv_hoelder(zeros.data(), bias.data(), cout, k, &l1, &b);
+    CHECK(l1 == 0.f && b == want_b);
+}
+
+static void read_bn_cases() {
+    const char* keys[4] = {"weight", "bias", "running_mean", "running_var"};
+    const std::string prefix = "layer1.0.bn2";
+    std::vector<float> t[4] = {{1.f, -2.f, 0.5f}, {0.25f, 0.f, -1.f}, {0.125f, 3.f, -0.75f}, {1.f, 0.1f, 4.f}};
+    std::vector<float> four(4, 0.f), scale(3), shift(3), want_scale(3), want_shift(3);
+    std::string err;
+    {
+        StateDict sd;
+        for (int i = 0; i < 4; ++i) sd.add((prefix + "." + keys[i]).c_str(), t[i].data(), 3);
+        CHECK(read_bn(sd, prefix, 3, 1e-5f, scale.data(), shift.data(), err) && err.empty());
+        fold_bn(t[0].data(), t[1].data(), t[2].data(), t[3].data(), 1e-5f, 3, want_scale.data(), want_shift.data());
+        CHECK(scale == want_scale && shift == want_shift);
+    }
+    for (int missing = 0; missing < 4; ++missing) {
+        StateDict sd;
+        for (int i = 0; i < 4; ++i)
+            if (i != missing) sd.add((prefix + "." + keys[i]).c_str(), t[i].data(), 3);
+        err.clear();
+        CHECK(!read_bn(sd, prefix, 3, 1e-5f, scale.data(), shift.data(), err));
+        CHECK(err.find("missing key '" + prefix + "." + keys[missing] + "'") != std::string::npos);
+    }
+    for (int bad = 0; bad < 4; ++bad) {   // one key with four values where three are expected; and with a null pointer
+        StateDict sd, sd0;
+        for (int i = 0; i < 4; ++i) {
+            sd.add((prefix + "." + keys[i]).c_str(), i == bad ? four.data() : t[i].data(), i == bad ? 4 : 3);
+            sd0.add((prefix + "." + keys[i]).c_str(), i == bad ? nullptr : t[i].data(), 3);
+        }
+        err.clear();
+        CHECK(!read_bn(sd, prefix, 3, 1e-5f, scale.data(), shift.data(), err));
+        CHECK(err.find(prefix + "." + keys[bad] + "' has 4 elements, expected 3") != std::string::npos);
+        err.clear();
+        CHECK(!read_bn(sd0, prefix, 3, 1e-5f, scale.data(), shift.data(), err));
+        CHECK(err.find(prefix + "." + keys[bad] + "' has a NULL data pointer") != std::string::npos);
+    }
+}
+
+int main() {
+    const int shapes[4][2] = {{1, 32}, {3, 64}, {64, 224}, {5, 4608}};
+    for (const auto& sh : shapes) hoelder_cases(sh[0], sh[1]);
+    read_bn_cases();
+    if (failures) return 1;
+    std::printf("host_logic_san: OK\n");
+    return 0;
+}
