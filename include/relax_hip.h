@@ -136,7 +136,8 @@ int relax_load_resnet50(relax_handle* h, const float* const* tensors, const char
 /* Replaces VitGenerator(name_model, patch_size=16, ...) + load_state_dict
  * (src/extractor/visualise_vit_layer.py:263-329).  DINO state-dict keys
  * ("cls_token", "blocks.0.attn.qkv.weight", ...).  dim/depth/heads: 768/12/12
- * for vit_base (:287-289); head_dim must be 64, input is always 224x224 (197 tokens).  = relax_load_vit_ex with patch_size 16. */
+ * for vit_base (:287-289); head_dim must be 64.  The checkpoint's pos_embed is the 224x224 table (197 tokens); the canvas of a call
+ * is an argument of relax_vit_features_canvas.  = relax_load_vit_ex with patch_size 16. */
 int relax_load_vit(relax_handle* h, const float* const* tensors, const char* const* names,
                    const int64_t* numels, int n, int dim, int depth, int heads);
 /* VitGenerator(name_model, patch_size, ...) for patch_size 8 or 16 (:263-329 builds both): 224 / p patches per side, (224 / p)^2 + 1
@@ -147,8 +148,21 @@ int relax_load_vit(relax_handle* h, const float* const* tensors, const char* con
  * kernels, 785 the streaming ones (csrc/attention_stream.hip). */
 int relax_load_vit_ex(relax_handle* h, const float* const* tensors, const char* const* names,
                       const int64_t* numels, int n, int dim, int depth, int heads, int patch_size);
-/* the geometry of the loaded ViT (any pointer may be NULL); refused before relax_load_vit */
+/* the geometry of the loaded ViT at 224x224 (any pointer may be NULL); refused before relax_load_vit */
 int relax_vit_geometry(relax_handle* h, int* patch, int* ntok, int* dim, int* heads);
+/* The patch grid of an [Hc, Wc] canvas under the loaded ViT: gh = Hc / p, gw = Wc / p (floors: PatchEmbed's stride-p convolution ignores
+ * the trailing rows and columns of pixels, src/extractor/visualise_vit_layer.py:132-149), ntok = gh * gw + 1 (any pointer may be NULL).
+ * Refused with the value in the message: Hc or Wc below the patch size, more than 4096 patches (4097 tokens: 1024^2 px at patch 16). */
+int relax_vit_canvas_geometry(relax_handle* h, int Hc, int Wc, int* gh, int* gw, int* ntok);
+/* interpolate_pos_encoding (src/extractor/visualise_vit_layer.py:197-219) for a gh x gw patch grid: out = device fp32 [1 + gh*gw, dim],
+ * row 0 the class row, the others the loaded [side, side] table resampled by F.interpolate(scale_factor=((gh + .1) / side,
+ * (gw + .1) / side), mode='bicubic') as torch evaluates it in fp32 (align_corners=False, A = -0.75, border taps clamped).  gh = gw = side
+ * returns the loaded table (:200-201).  The tables of the last four grids stay on the handle; a ViT load drops them.  A grid that is not
+ * among them is built inside the call: device memory is allocated (and the least recently used table freed, which waits for the device), the
+ * kernel runs on `stream` and the call waits for `stream`.  Such a call cannot be captured into a graph, and a workload that cycles through
+ * more than four grids pays a device-wide wait per call; a call on a cached grid, or on the loaded one, does neither.  The same holds for
+ * relax_vit_features_canvas, which gets its table here. */
+int relax_vit_pos_embed(relax_handle* h, int gh, int gw, float* out, relax_stream stream);
 
 /* Replaces models.vgg16(pretrained=True) (src/extractor/visualise_vgg.py:21, visualise_vgg_layer.py:19; torchvision
  * configuration D, no BatchNorm).  torchvision keys: features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias} and
@@ -324,6 +338,15 @@ int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* toke
  * last block's qkv GEMM (the last block's attention core, proj, MLP and the final norm are skipped).  All three NULL: refused. */
 int relax_vit_features_ex(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled, float* cls_attention,
                           relax_stream stream);
+/* relax_vit_features_ex on images of any size: VisionTransformer.forward / get_last_selfattention with prepare_tokens'
+ * interpolate_pos_encoding (src/extractor/visualise_vit_layer.py:197-232, 234-250; src/extractor/visualise_vit.py:353-370 runs an
+ * image cropped to patch multiples at its own size).  images uint8 [N,Hc,Wc,3] BGR; the grid is relax_vit_canvas_geometry's
+ * (gh = Hc / p, gw = Wc / p, trailing pixels ignored), npatch = gh * gw, ntok = npatch + 1:
+ *   tokens [N,npatch,dim], pooled [N,3*dim], cls_attention [N,heads,ntok]   (each may be NULL, not all three).
+ * The position table is relax_vit_pos_embed(gh, gw).  197 tokens run the single-tile attention kernels, any other count the
+ * streaming ones.  Hc = Wc = 224 is relax_vit_features_ex: the same launches, the same bits. */
+int relax_vit_features_canvas(relax_handle* h, const uint8_t* images, int N, int Hc, int Wc, float* tokens, float* pooled,
+                              float* cls_attention, relax_stream stream);
 
 /* ---- quality head at inference --------------------------------------------------- */
 /* Replaces imputer.transform + scaler.transform + Mlp.forward (src/demo_test.py:177-208, src/model_regression.py:37-58).

@@ -51,6 +51,9 @@ PROTOTYPES = {
     "relax_vgg16_features": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, C.POINTER(c_vp), c_vp]),
     "relax_vit_features": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
     "relax_vit_features_ex": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "relax_vit_features_canvas": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "relax_vit_pos_embed": (C.c_int, [c_vp, C.c_int, C.c_int, c_vp, c_vp]),
+    "relax_vit_canvas_geometry": (C.c_int, [c_vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "relax_load_mlp_head": (C.c_int, [c_vp, C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
                                       c_vp, c_vp, c_vp, C.c_int]),
     "relax_mlp_head": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp]),

@@ -345,6 +345,64 @@ bool vit_geometry(int patch, VitGeometry* g, std::string& err) {
     return true;
 }
 
+bool vit_canvas_geometry(int patch, int Hc, int Wc, VitCanvasGeometry* g, std::string& err) {
+    VitGeometry base;
+    if (!vit_geometry(patch, &base, err)) return false;
+    if (Hc < patch || Wc < patch) {
+        const bool h_bad = Hc < patch;
+        err = std::string("vit: canvas ") + (h_bad ? "height " : "width ") + std::to_string(h_bad ? Hc : Wc) + " is below the patch size " +
+              std::to_string(patch) + " (canvas " + std::to_string(Hc) + " x " + std::to_string(Wc) + ")";
+        return false;
+    }
+    const int64_t gh = Hc / patch, gw = Wc / patch, npatch = gh * gw;
+    if (npatch > kVitMaxPatches) {
+        err = "vit: canvas " + std::to_string(Hc) + " x " + std::to_string(Wc) + " has " + std::to_string(gh) + " x " + std::to_string(gw) + " = " +
+              std::to_string(npatch) + " patches at patch size " + std::to_string(patch) + ", the limit is " + std::to_string(kVitMaxPatches) +
+              " patches (" + std::to_string(kVitMaxPatches + 1) + " tokens)";
+        return false;
+    }
+    *g = VitCanvasGeometry{(int)gh, (int)gw, (int)npatch, (int)npatch + 1, gh == base.side && gw == base.side};
+    return true;
+}
+
+// What is specified: an fp32 coordinate from a double-derived scale, fp32 cubic weights.  Which of those fp32 operations are fused is not
+// specified by torch: it is what its compiler contracted.  The roundings below (fmaf for the coordinate scale * (dst + 0.5) - 0.5 and the first
+// Horner steps of the two cubics, a separately rounded product elsewhere) are those of torch 2.10's x86-64 CPU build, written out so that the
+// taps do not depend on THIS file's compiler flags; with them the weights equal that build's bit for bit on every tap inside the table
+// (tests/test_vit_canvas_cpu.py asserts it, and says what to do when another torch build contracts differently: the difference is then one
+// or two ulp of a weight, far inside the gates; an unfused coordinate alone moves a weight by up to 1.2e-6 and costs the 28-wide grids their
+// margin).
+static inline float mul_then_add(float a, float b, float c) {
+    volatile float p = a * b;   // (volatile: rounded to fp32 here, whatever the compiler may contract)
+    return p + c;
+}
+void pos_interp_taps(int side, int g, int32_t* idx, float* w) {
+    const float A = -0.75f;
+    const float scale = (float)(1.0 / (((double)g + 0.1) / (double)side));
+    auto conv1 = [&](float x) {   // ((A + 2) x - (A + 3)) x x + 1,  |x| <= 1
+        volatile float q = std::fmaf(A + 2.f, x, -(A + 3.f)) * x;
+        return mul_then_add(q, x, 1.f);
+    };
+    auto conv2 = [&](float x) {   // ((A x - 5 A) x + 8 A) x - 4 A,  1 <= |x| <= 2
+        return mul_then_add(std::fmaf(std::fmaf(A, x, -5.f * A), x, 8.f * A), x, -4.f * A);
+    };
+    for (int i = 0; i < g; ++i) {
+        const float real = std::fmaf(scale, (float)i + 0.5f, -0.5f);
+        const float fl = std::floor(real);
+        const float t = std::fmin(std::fmax(real - fl, 0.f), 1.f);   // (real - floor(real) is exact in fp32)
+        const int i0 = (int)fl;
+        const float x2 = 1.f - t;
+        w[4 * i + 0] = conv2(t + 1.f);
+        w[4 * i + 1] = conv1(t);
+        w[4 * i + 2] = conv1(x2);
+        w[4 * i + 3] = conv2(x2 + 1.f);
+        for (int k = 0; k < 4; ++k) {
+            const int j = i0 - 1 + k;
+            idx[4 * i + k] = j < 0 ? 0 : (j > side - 1 ? side - 1 : j);
+        }
+    }
+}
+
 size_t vit_floats_per_image(int dim, int ntok, int npatch, int patch_k) {
     return (size_t)npatch * patch_k        // P   patches
            + (size_t)npatch * dim          // PE  patch-embed output
@@ -531,6 +589,19 @@ int relax_host_vit_geometry(int patch, int* out, char* err, int err_len) {
     std::memcpy(out, &g, sizeof(g));
     return 0;
 }
+// the grid of a call: out = gh, gw, npatch, ntok, identity; 0, or -1 and a message
+int relax_host_vit_canvas_geometry(int patch, int Hc, int Wc, int* out, char* err, int err_len) {
+    relax::host::VitCanvasGeometry g;
+    std::string e;
+    if (!relax::host::vit_canvas_geometry(patch, Hc, Wc, &g, e)) {
+        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return -1;
+    }
+    std::memcpy(out, &g, sizeof(g));
+    return 0;
+}
+// one axis of the position table's bicubic resampling: idx[4 g], w[4 g]
+void relax_host_pos_interp_taps(int side, int g, int32_t* idx, float* w) { relax::host::pos_interp_taps(side, g, idx, w); }
 void relax_host_vit_arena_floats(int dim, int ntok, int npatch, int patch_k, int64_t* out) {
     out[0] = (int64_t)relax::host::vit_floats_per_image(dim, ntok, npatch, patch_k);
     out[1] = (int64_t)relax::host::vit_floats_per_image_x6(dim, ntok, npatch, patch_k);

@@ -162,6 +162,19 @@ bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* pla
 struct VitGeometry { int patch, side, npatch, ntok, patch_k; };   // patch 16: 14 per side, 196 patches, 197 tokens, K = 768; patch 8: 28, 784, 785, 192
 // the geometry of patch size 8 or 16; anything else is refused (false and a message)
 bool vit_geometry(int patch, VitGeometry* g, std::string& err);
+// The patch grid of one CALL: an [Hc, Wc] canvas under patch size `patch` (8 or 16).  gh = Hc / patch, gw = Wc / patch are floors - the
+// reference's stride-p convolution ignores the trailing rows and columns of pixels -, npatch = gh * gw, ntok = npatch + 1; identity: the grid is
+// the loaded table's (gh == gw == side), where interpolate_pos_encoding returns pos_embed as it is.  Refused (false and a message): a patch
+// size vit_geometry refuses, Hc or Wc below the patch size (the value is named), more than kVitMaxPatches patches (Hc and Wc are named).
+constexpr int kVitMaxPatches = 4096;   // the one declared limit: 1024^2 px at patch 16, 512^2 at patch 8 (4097 tokens with the class token)
+struct VitCanvasGeometry { int gh, gw, npatch, ntok, identity; };
+bool vit_canvas_geometry(int patch, int Hc, int Wc, VitCanvasGeometry* g, std::string& err);
+// One axis of interpolate_pos_encoding's bicubic resampling, side -> g positions, as torch evaluates F.interpolate(scale_factor = (g + 0.1) /
+// side, mode = 'bicubic', align_corners = False) on fp32: the coordinate scale is 1 / scale_factor computed in double and rounded to fp32, the
+// source coordinate scale * (dst + 0.5) - 0.5 (one fused multiply-add, as torch's builds evaluate it) and the cubic-convolution weights
+// (A = -0.75) are evaluated in fp32.  Output position i reads
+// source positions idx[4 i .. 4 i + 3] (floor - 1 .. floor + 2, clamped to [0, side - 1]) with weights w[4 i .. 4 i + 3].
+void pos_interp_taps(int side, int g, int32_t* idx, float* w);
 // per-image floats of the forward's arena: the exact-fp32 layout and the bf16x6 / f16x2 one (sp3 operands take 6 bytes per value)
 size_t vit_floats_per_image(int dim, int ntok, int npatch, int patch_k);
 size_t vit_floats_per_image_x6(int dim, int ntok, int npatch, int patch_k);

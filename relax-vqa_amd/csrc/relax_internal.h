@@ -225,12 +225,22 @@ struct VitBlockW {
     float s_qkv = 1.f;   // ... and the whole qkv output (attention_h2.hip reads q, k, v as planes)
 };
 
+// interpolate_pos_encoding's table of one patch grid (vit_pos_interp, vit.hip): [1 + gh*gw][dim] on the device, complete when cached
+struct VitPosTable {
+    int gh = 0, gw = 0;
+    float* table = nullptr;
+    uint64_t used = 0;      // VitW::pos_clock of the last call that read it (the least recent entry is replaced)
+};
+constexpr int kVitPosCache = 4;
+
 struct VitW {
     bool loaded = false;
     int dim = 0, depth = 0, heads = 0;
     float* cls = nullptr;   // [dim]
     int patch = 16, ntok = 197, npatch = 196, patch_k = 768;   // host::vit_geometry of the loaded checkpoint's patch size (8: 785 tokens)
-    float* pos = nullptr;   // [ntok][dim]
+    float* pos = nullptr;   // [ntok][dim]: the checkpoint's table, the grid of a 224 x 224 call
+    VitPosTable pos_cache[kVitPosCache];   // the tables of the last few other grids (relax_vit_features_canvas, relax_vit_pos_embed); free_vit drops them
+    uint64_t pos_clock = 0;
     LinearW patch_w;        // [dim][3*p*p], k = (c*p + py)*p + px (c in RGB order)
     std::vector<VitBlockW> blocks;
     float *norm_g = nullptr, *norm_b = nullptr;
@@ -449,6 +459,7 @@ int launch_attention_stream_x6(relax_handle* h, const float* qkv, float* out, vo
                                float out_h2_scale = 0.f);
 // the last block's CLS attention row (vit_attention_map.hip): qkv as fp32 rows [Nimg*ntok][3*dim] or, with planes, fp16 planes of
 // qkv * s_qkv (csrc/h2.h) -> out fp32 [Nimg, heads, ntok] = softmax(q_0 k^T / 8) per (image, head)
+// (ntok <= 4352: 256 threads x 4 keys up to 1024 tokens, x 17 above)
 int launch_vit_cls_attention(relax_handle* h, const void* qkv, bool planes, float s_qkv, float* out, int Nimg, int ntok, int heads, hipStream_t s);
 int launch_bn_relu_maxpool(relax_handle* h, const float* x, const float* scale, const float* shift, float* y,
                            int Nimg, int H, int W, int C, hipStream_t s);
@@ -475,6 +486,7 @@ void free_head_train(relax_handle* h);
 void free_vgg(relax_handle* h);
 size_t vgg_arena_bytes(int n_images);
 size_t resnet_arena_bytes(int n_images);
-size_t vit_arena_bytes(const VitW& v, int n_images);
+size_t vit_arena_bytes(const VitW& v, int n_images);                          // at the loaded geometry (224 x 224: relax_reserve)
+size_t vit_arena_bytes(const VitW& v, int n_images, int ntok, int npatch);    // at a call's geometry
 
 }  // namespace relax

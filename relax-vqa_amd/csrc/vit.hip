@@ -1,10 +1,13 @@
-// DINO ViT (patch 16 or 8, 224x224 input -> 197 or 785 tokens, 64-d heads) feature extractor on gfx950.  The geometry is a property of the
-// loaded checkpoint (VitW::patch / ntok / npatch / patch_k, from host::vit_geometry); 197 tokens run the single-tile attention kernels,
-// any other count the streaming ones (attention_stream.hip).
+// DINO ViT (patch 16 or 8, 64-d heads) feature extractor on gfx950.  The patch size and the position table's side are properties of the
+// loaded checkpoint (VitW::patch / ntok / npatch / patch_k, from host::vit_geometry: the 224x224 table, 197 or 785 tokens); the canvas is a
+// property of the CALL (host::vit_canvas_geometry: gh x gw patches of an [Hc, Wc] image, any token count up to 4097), its position table the
+// loaded one resampled bicubically (vit_pos_interp).  197 tokens run the single-tile attention kernels, any other count the streaming ones
+// (attention_stream.hip).
 //
 // Reference semantics (file:line in xinyiW915/ReLaX-VQA, src/extractor/visualise_vit_layer.py):
 //   :466-470,339-342,492-494  input: PIL RGB, /255, no mean/std normalisation
 //   :132-149  PatchEmbed conv pxp/p               -> patchify kernel + GEMM (K = 3*p*p = 768 / 192)
+//   :197-219  interpolate_pos_encoding             -> vit_pos_interp (the loaded table itself on the 224x224 grid, :200-201)
 //   :221-232  cls token prepend, + pos_embed       -> vit_assemble
 //   :93-129   pre-LN blocks: qkv, softmax(q k^T/8) v, proj, MLP with exact-erf GELU
 //   :234-239  final LayerNorm (eps 1e-6, :287-289), patch tokens x[:,1:]
@@ -16,18 +19,19 @@
 
 namespace relax {
 
-// patch geometry of a launch: lp = log2(patch), side = 224 / patch; k = (c << 2 lp) + (py << lp) + px
-struct PatchGeom { int lp, side, npatch, patch_k; };
+// patch geometry of a launch: lp = log2(patch), images [Hc][Wc] cut into rows of gw patches (npatch = gh * gw: pixels to the right of column
+// gw * patch and below row gh * patch are never read); k = (c << 2 lp) + (py << lp) + px
+struct PatchGeom { int lp, gw, npatch, patch_k, Hc, Wc; };
 __device__ inline const uint8_t* patch_src(const uint8_t* frag, const PatchGeom g, int64_t n, int p, int k) {
     const int pm = (1 << g.lp) - 1;
     const int c = k >> (2 * g.lp), py = (k >> g.lp) & pm, px = k & pm;
-    const int y = ((p / g.side) << g.lp) + py, x = ((p % g.side) << g.lp) + px;
-    return frag + ((n * 224 + y) * 224 + x) * 3 + (2 - c);
+    const int y = ((p / g.gw) << g.lp) + py, x = ((p % g.gw) << g.lp) + px;
+    return frag + ((n * g.Hc + y) * g.Wc + x) * 3 + (2 - c);
 }
 constexpr float kLnEps = 1e-6f;
 constexpr float kPatchScale = 16384.f;   // patch values are value/255 in [0, 1]: as fp16 planes of value * 2^14 (csrc/h2.h)
 
-// uint8 BGR [N,224,224,3] -> fp32 [N*npatch, patch_k], k = (c*p + py)*p + px with c in RGB order, value/255
+// uint8 BGR [N,Hc,Wc,3] -> fp32 [N*npatch, patch_k], k = (c*p + py)*p + px with c in RGB order, value/255
 __global__ __launch_bounds__(256) void vit_patchify(const uint8_t* __restrict__ frag, float* __restrict__ P,
                                                     int64_t total, const PatchGeom g) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -87,6 +91,42 @@ __global__ __launch_bounds__(256) void vit_assemble(const float* __restrict__ PE
     reinterpret_cast<float4*>(X)[i] = make_float4(v.x + pp.x, v.y + pp.y, v.z + pp.z, v.w + pp.w);
 }
 
+// interpolate_pos_encoding for a gh x gw grid: out[0] = pos[0]; out[1 + oy*gw + ox] = sum_a wy[4 oy + a] * (sum_b wx[4 ox + b] *
+// pos[1 + iy[4 oy + a] * side + ix[4 ox + b]]) - across x first, then across y, each sum in tap order: the order of torch's bicubic kernel.
+// taps: [iy 4 gh | ix 4 gw] int32 and [wy 4 gh | wx 4 gw] fp32 from host::pos_interp_taps (indices clamped to [0, side - 1] there).
+// One thread per 4 channels of an output row (16-byte loads along dim).
+__global__ __launch_bounds__(256) void vit_pos_interp(const float* __restrict__ pos, const int32_t* __restrict__ tap_idx,
+                                                      const float* __restrict__ tap_w, float* __restrict__ out, int dim4, int side,
+                                                      int gh, int gw, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int d = (int)(i % dim4);
+    const int row = (int)(i / dim4);
+    const float4* P = reinterpret_cast<const float4*>(pos);
+    if (row == 0) {
+        reinterpret_cast<float4*>(out)[i] = P[d];
+        return;
+    }
+    const int oy = (row - 1) / gw, ox = (row - 1) % gw;
+    const int32_t *iy = tap_idx + 4 * oy, *ix = tap_idx + 4 * gh + 4 * ox;
+    const float *wy = tap_w + 4 * oy, *wx = tap_w + 4 * gh + 4 * ox;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const float4* line = P + ((int64_t)1 + (int64_t)iy[a] * side) * dim4 + d;
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const float4 v = line[(int64_t)ix[b] * dim4];
+            const float w = wx[b];
+            r = b == 0 ? make_float4(v.x * w, v.y * w, v.z * w, v.w * w) : make_float4(r.x + v.x * w, r.y + v.y * w, r.z + v.z * w, r.w + v.w * w);
+        }
+        const float w = wy[a];
+        acc = a == 0 ? make_float4(r.x * w, r.y * w, r.z * w, r.w * w) : make_float4(acc.x + r.x * w, acc.y + r.y * w, acc.z + r.z * w, acc.w + r.w * w);
+    }
+    reinterpret_cast<float4*>(out)[i] = acc;
+}
+
 // Y [N,ntok,dim] -> tokens [N,ntok-1,dim] (drop cls)
 __global__ __launch_bounds__(256) void vit_drop_cls(const float* __restrict__ Y, float* __restrict__ T, int dim4,
                                                     int64_t total, int ntok) {
@@ -143,13 +183,72 @@ __global__ __launch_bounds__(256) void vit_token_stats(const float* __restrict__
 }
 
 void free_vit(relax_handle* h) {
+    for (VitPosTable& t : h->vit.pos_cache)
+        if (t.table) (void)hipFree(t.table);
     h->vit.mem.release();
     h->vit = VitW();
 }
 
-size_t vit_arena_bytes(const VitW& v, int n) {
-    const size_t a = host::vit_floats_per_image(v.dim, v.ntok, v.npatch, v.patch_k), b = host::vit_floats_per_image_x6(v.dim, v.ntok, v.npatch, v.patch_k);
+size_t vit_arena_bytes(const VitW& v, int n, int ntok, int npatch) {
+    const size_t a = host::vit_floats_per_image(v.dim, ntok, npatch, v.patch_k), b = host::vit_floats_per_image_x6(v.dim, ntok, npatch, v.patch_k);
     return sizeof(float) * (a > b ? a : b) * (size_t)n;
+}
+size_t vit_arena_bytes(const VitW& v, int n) { return vit_arena_bytes(v, n, v.ntok, v.npatch); }
+
+// The position table of a gh x gw grid (g from host::vit_canvas_geometry): the loaded table on the identity grid, else the cached table of
+// the grid, built on a miss (taps on the host, vit_pos_interp on `s`, then a wait for `s`: a cached table is complete, whatever stream reads
+// it next; the least recently used of the kVitPosCache entries is replaced).
+static int vit_pos_table(relax_handle* h, const host::VitCanvasGeometry& g, hipStream_t s, const float** out) {
+    VitW& v = h->vit;
+    if (g.identity) {
+        *out = v.pos;
+        return RELAX_OK;
+    }
+    VitPosTable* slot = &v.pos_cache[0];
+    for (VitPosTable& t : v.pos_cache) {
+        if (t.table && t.gh == g.gh && t.gw == g.gw) {
+            t.used = ++v.pos_clock;
+            *out = t.table;
+            return RELAX_OK;
+        }
+        if (t.used < slot->used) slot = &t;
+    }
+    const int side = 224 / v.patch, ntaps = 4 * (g.gh + g.gw);
+    std::vector<int32_t> idx((size_t)ntaps);
+    std::vector<float> w((size_t)ntaps);
+    host::pos_interp_taps(side, g.gh, idx.data(), w.data());
+    host::pos_interp_taps(side, g.gw, idx.data() + 4 * g.gh, w.data() + 4 * g.gh);
+    if (slot->table) {   // (hipFree waits for the device: no launch still reads the table that goes)
+        RELAX_HIP_CHECK(h, hipFree(slot->table));
+        *slot = VitPosTable();
+    }
+    // [table (1 + gh*gw) * dim floats | tap indices | tap weights] in one allocation
+    const size_t table_floats = (size_t)g.ntok * v.dim;
+    float* mem = nullptr;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&mem), sizeof(float) * (table_floats + 2 * (size_t)ntaps));
+    if (e != hipSuccess) {
+        set_error(h, "hipMalloc of the %d x %d position table (%zu floats) failed: %s", g.gh, g.gw, table_floats, hipGetErrorString(e));
+        return RELAX_ERR_NOMEM;
+    }
+    int32_t* d_idx = reinterpret_cast<int32_t*>(mem + table_floats);
+    float* d_w = mem + table_floats + ntaps;
+    const int64_t total = (int64_t)g.ntok * (v.dim / 4);
+    hipError_t rc = hipMemcpyAsync(d_idx, idx.data(), sizeof(int32_t) * (size_t)ntaps, hipMemcpyHostToDevice, s);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(d_w, w.data(), sizeof(float) * (size_t)ntaps, hipMemcpyHostToDevice, s);
+    if (rc == hipSuccess) {
+        hipLaunchKernelGGL(vit_pos_interp, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, v.pos, d_idx, d_w, mem, v.dim / 4, side, g.gh,
+                           g.gw, total);
+        rc = hipGetLastError();
+    }
+    if (rc == hipSuccess) rc = hipStreamSynchronize(s);   // (the host tap arrays live until here)
+    if (rc != hipSuccess) {
+        (void)hipFree(mem);
+        set_error(h, "vit_pos_interp (%d x %d) failed: %s", g.gh, g.gw, hipGetErrorString(rc));
+        return RELAX_ERR_HIP;
+    }
+    slot->gh = g.gh; slot->gw = g.gw; slot->table = mem; slot->used = ++v.pos_clock;
+    *out = mem;
+    return RELAX_OK;
 }
 
 // everything relax_load_vit_ex puts on the device; the caller frees it all if this fails
@@ -291,19 +390,29 @@ int relax_load_vit_ex(relax_handle* h, const float* const* tensors, const char* 
 
 }  // extern "C"
 
-static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled, float* cls_attention,
-                       relax_stream stream) {
+// frags: N images [Hc][Wc][3].  Hc = Wc = 224 is the loaded geometry: v.pos, the arena relax_reserve sized, the launches of always.
+// `what`: the entry point that was called, for the messages.
+static int vit_forward(relax_handle* h, const char* what, const uint8_t* frags, int N, int Hc, int Wc, float* tokens, float* pooled,
+                       float* cls_attention, relax_stream stream) {
     if (!h) return RELAX_ERR_INVALID;
-    RELAX_REQUIRE(h, h->vit.loaded, "relax_vit_features: call relax_load_vit first");
-    RELAX_REQUIRE(h, frags && N > 0, "relax_vit_features: bad arguments");
+    RELAX_REQUIRE(h, h->vit.loaded, "%s: call relax_load_vit first", what);
+    RELAX_REQUIRE(h, frags && N > 0, "%s: bad arguments", what);
+    host::VitCanvasGeometry cg;
+    {
+        std::string err;
+        RELAX_REQUIRE(h, host::vit_canvas_geometry(h->vit.patch, Hc, Wc, &cg, err), "%s: %s", what, err.c_str());
+    }
+    RELAX_REQUIRE(h, (int64_t)N * cg.ntok <= (int64_t)INT32_MAX, "%s: %d images of %d tokens pass 2^31 - 1 rows", what, N, cg.ntok);
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const VitW& v = h->vit;
     const int dim = v.dim;
-    RELAX_TRY(ensure_buf(h, h->arena, vit_arena_bytes(v, N)));
+    const float* pos = nullptr;
+    RELAX_TRY(vit_pos_table(h, cg, s, &pos));
+    RELAX_TRY(ensure_buf(h, h->arena, vit_arena_bytes(v, N, cg.ntok, cg.npatch)));
     const size_t n = (size_t)N;
-    const int NTOK = v.ntok, NPATCH = v.npatch, PATCH_K = v.patch_k;
-    const PatchGeom pg{v.patch == 8 ? 3 : 4, 224 / v.patch, NPATCH, PATCH_K};
+    const int NTOK = cg.ntok, NPATCH = cg.npatch, PATCH_K = v.patch_k;
+    const PatchGeom pg{v.patch == 8 ? 3 : 4, cg.gw, NPATCH, PATCH_K, Hc, Wc};
     // 197 tokens: the single-tile kernels (every key of an (image, head) on the chip at once); any other count: the streaming ones
     const bool single_tile = NTOK == 197;
     auto attention_x6 = [&](const float* qkv, void* out_planes, float out_h2_scale) {
@@ -351,7 +460,7 @@ static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* toke
             RELAX_TRY(launch_gemm_x6(h, Ps, v.patch_w.w_sp3, v.patch_w.b, nullptr, PEx, nullptr, N * NPATCH, dim, PATCH_K, 0, s));
         }
         const int64_t at = (int64_t)rows * (dim / 4);
-        hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, v.pos, Xx, dim / 4, at, NTOK);
+        hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, pos, Xx, dim / 4, at, NTOK);
         RELAX_HIP_CHECK(h, hipGetLastError());
         for (int i = 0; i < v.depth; ++i) {
             const VitBlockW& b = v.blocks[i];
@@ -397,7 +506,7 @@ static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* toke
         hipLaunchKernelGGL(vit_patchify_sp3, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Ps, p8, pg);
         RELAX_TRY(launch_gemm_x6(h, Ps, v.patch_w.w_sp3, v.patch_w.b, nullptr, PEx, nullptr, N * NPATCH, dim, PATCH_K, 0, s));
         const int64_t at = (int64_t)rows * (dim / 4);
-        hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, v.pos, Xx, dim / 4, at, NTOK);
+        hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, pos, Xx, dim / 4, at, NTOK);
         RELAX_HIP_CHECK(h, hipGetLastError());
         for (int i = 0; i < v.depth; ++i) {
             const VitBlockW& b = v.blocks[i];
@@ -425,7 +534,7 @@ static int vit_forward(relax_handle* h, const uint8_t* frags, int N, float* toke
     hipLaunchKernelGGL(vit_patchify, dim3((unsigned)((ptotal + 255) / 256)), dim3(256), 0, s, frags, P, ptotal, pg);
     RELAX_TRY(launch_gemm(h, P, v.patch_w.w, v.patch_w.b, nullptr, PE, N * NPATCH, dim, PATCH_K, 0, s));
     const int64_t atotal = (int64_t)rows * (dim / 4);
-    hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((atotal + 255) / 256)), dim3(256), 0, s, PE, v.cls, v.pos, X,
+    hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((atotal + 255) / 256)), dim3(256), 0, s, PE, v.cls, pos, X,
                        dim / 4, atotal, NTOK);
     RELAX_HIP_CHECK(h, hipGetLastError());
     for (int i = 0; i < v.depth; ++i) {
@@ -454,14 +563,49 @@ extern "C" {
 
 int relax_vit_features(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled,
                        relax_stream stream) {
-    return vit_forward(h, frags, N, tokens, pooled, nullptr, stream);
+    return vit_forward(h, "relax_vit_features", frags, N, 224, 224, tokens, pooled, nullptr, stream);
 }
 
 int relax_vit_features_ex(relax_handle* h, const uint8_t* frags, int N, float* tokens, float* pooled, float* cls_attention,
                           relax_stream stream) {
     if (!h) return RELAX_ERR_INVALID;
     RELAX_REQUIRE(h, tokens || pooled || cls_attention, "relax_vit_features_ex: no output requested");
-    return vit_forward(h, frags, N, tokens, pooled, cls_attention, stream);
+    return vit_forward(h, "relax_vit_features", frags, N, 224, 224, tokens, pooled, cls_attention, stream);
+}
+
+int relax_vit_features_canvas(relax_handle* h, const uint8_t* images, int N, int Hc, int Wc, float* tokens, float* pooled,
+                              float* cls_attention, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, tokens || pooled || cls_attention, "relax_vit_features_canvas: no output requested");
+    return vit_forward(h, "relax_vit_features_canvas", images, N, Hc, Wc, tokens, pooled, cls_attention, stream);
+}
+
+int relax_vit_canvas_geometry(relax_handle* h, int Hc, int Wc, int* gh, int* gw, int* ntok) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, h->vit.loaded, "relax_vit_canvas_geometry: call relax_load_vit first");
+    host::VitCanvasGeometry cg;
+    std::string err;
+    RELAX_REQUIRE(h, host::vit_canvas_geometry(h->vit.patch, Hc, Wc, &cg, err), "relax_vit_canvas_geometry: %s", err.c_str());
+    if (gh) *gh = cg.gh;
+    if (gw) *gw = cg.gw;
+    if (ntok) *ntok = cg.ntok;
+    return RELAX_OK;
+}
+
+int relax_vit_pos_embed(relax_handle* h, int gh, int gw, float* out, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, h->vit.loaded, "relax_vit_pos_embed: call relax_load_vit first");
+    RELAX_REQUIRE(h, out, "relax_vit_pos_embed: out is NULL");
+    RELAX_REQUIRE(h, gh >= 1 && gw >= 1 && (int64_t)gh * gw <= host::kVitMaxPatches, "relax_vit_pos_embed: grid %d x %d (at least 1 x 1, at most %d patches)",
+                  gh, gw, host::kVitMaxPatches);
+    const int side = 224 / h->vit.patch;
+    const host::VitCanvasGeometry cg{gh, gw, gh * gw, gh * gw + 1, gh == side && gw == side};
+    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const float* table = nullptr;
+    RELAX_TRY(vit_pos_table(h, cg, s, &table));
+    RELAX_HIP_CHECK(h, hipMemcpyAsync(out, table, sizeof(float) * (size_t)cg.ntok * h->vit.dim, hipMemcpyDeviceToDevice, s));
+    return RELAX_OK;
 }
 
 int relax_vit_geometry(relax_handle* h, int* patch, int* ntok, int* dim, int* heads) {

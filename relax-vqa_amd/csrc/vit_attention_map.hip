@@ -12,6 +12,7 @@
 namespace relax {
 
 constexpr int AM_KPT = 4;               // keys per thread: thread j owns keys j, j + 256, ... (up to 1024 tokens; 197 tokens: one key each)
+constexpr int AM_KPT_WIDE = 17;         // ... of the second instantiation: up to 4352 tokens (host::kVitMaxPatches + 1 = 4097 needs 17)
 constexpr int AM_HD = 64;              // head_dim of vit_tiny / vit_small / vit_base: the scale 64^-0.5 is exactly 1/8
 constexpr int OV_MAX_SLOTS = (448 / 8) * (448 / 8);   // 3136: the largest canvas of the fragment stage at its smallest patch
 constexpr int OV_SPT = (OV_MAX_SLOTS + 255) / 256;    // slots per thread of overlay_levels: thread j owns slots j, j + 256, ...
@@ -52,10 +53,10 @@ __device__ inline float block_reduce_256(float x, float* red, bool is_max) {
     return is_max ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// one workgroup per (image, head); thread j owns keys j, j + 256, ... (at most AM_KPT; 197 tokens: key j alone, the arithmetic of the
+// one workgroup per (image, head); thread j owns keys j, j + 256, ... (at most KPT; 197 tokens: key j alone, the arithmetic of the
 // one-key-per-thread form bit for bit).  fp32 logits (q_0 . k_j sequential FMA, * 1/8), max subtracted, fp32 sum in a fixed tree: an
 // image's row depends on nothing else in the batch.
-template <bool H2>
+template <bool H2, int KPT>
 __global__ __launch_bounds__(256) void vit_cls_attention(const void* __restrict__ qkv, float inv_s, float* __restrict__ out, int heads, int ntok) {
     __shared__ float q[AM_HD];
     __shared__ float red[4];
@@ -64,10 +65,10 @@ __global__ __launch_bounds__(256) void vit_cls_attention(const void* __restrict_
     const int j = threadIdx.x;
     if (j < AM_HD / 16) load16<H2>(qkv, (int64_t)n * ntok, ld, hd * AM_HD + j * 16, inv_s, q + j * 16);
     __syncthreads();
-    float logit[AM_KPT];
+    float logit[KPT];
     float lmax = -INFINITY;
 #pragma unroll
-    for (int t = 0; t < AM_KPT; ++t) {
+    for (int t = 0; t < KPT; ++t) {
         const int key = j + 256 * t;
         logit[t] = -INFINITY;
         if (key < ntok) {
@@ -85,28 +86,32 @@ __global__ __launch_bounds__(256) void vit_cls_attention(const void* __restrict_
         lmax = fmaxf(lmax, logit[t]);
     }
     const float mx = block_reduce_256(lmax, red, true);
-    float e[AM_KPT];
+    float e[KPT];
     float lsum = 0.f;
 #pragma unroll
-    for (int t = 0; t < AM_KPT; ++t) {
+    for (int t = 0; t < KPT; ++t) {
         e[t] = j + 256 * t < ntok ? expf(logit[t] - mx) : 0.f;
         lsum = t == 0 ? e[0] : lsum + e[t];
     }
     const float sum = block_reduce_256(lsum, red, false);
 #pragma unroll
-    for (int t = 0; t < AM_KPT; ++t)
+    for (int t = 0; t < KPT; ++t)
         if (j + 256 * t < ntok) out[(int64_t)blockIdx.x * ntok + j + 256 * t] = e[t] / sum;
 }
 
 int launch_vit_cls_attention(relax_handle* h, const void* qkv, bool planes, float s_qkv, float* out, int N, int ntok, int heads, hipStream_t s) {
     RELAX_REQUIRE(h, qkv && out && N > 0 && heads > 0, "vit_cls_attention: bad arguments");
-    RELAX_REQUIRE(h, ntok > 0 && ntok <= 256 * AM_KPT, "vit_cls_attention: ntok=%d (1 .. %d)", ntok, 256 * AM_KPT);
+    RELAX_REQUIRE(h, ntok > 0 && ntok <= 256 * AM_KPT_WIDE, "vit_cls_attention: ntok=%d (1 .. %d)", ntok, 256 * AM_KPT_WIDE);
     const dim3 grid((unsigned)(N * heads));
+    const bool wide = ntok > 256 * AM_KPT;   // (197 and 785 tokens keep the instantiation they always ran)
     if (planes) {
         RELAX_REQUIRE(h, s_qkv > 0.f && s_qkv < 3.0e38f, "vit_cls_attention: bad qkv scale");
-        hipLaunchKernelGGL(vit_cls_attention<true>, grid, dim3(256), 0, s, qkv, 1.f / s_qkv, out, heads, ntok);
+        // (fp16 planes come from the single-tile forward alone: 197 tokens)
+        RELAX_REQUIRE(h, !wide, "vit_cls_attention: ntok=%d as fp16 planes (1 .. %d)", ntok, 256 * AM_KPT);
+        hipLaunchKernelGGL((vit_cls_attention<true, AM_KPT>), grid, dim3(256), 0, s, qkv, 1.f / s_qkv, out, heads, ntok);
     } else {
-        hipLaunchKernelGGL(vit_cls_attention<false>, grid, dim3(256), 0, s, qkv, 1.f, out, heads, ntok);
+        if (wide) hipLaunchKernelGGL((vit_cls_attention<false, AM_KPT_WIDE>), grid, dim3(256), 0, s, qkv, 1.f, out, heads, ntok);
+        else hipLaunchKernelGGL((vit_cls_attention<false, AM_KPT>), grid, dim3(256), 0, s, qkv, 1.f, out, heads, ntok);
     }
     RELAX_HIP_CHECK(h, hipGetLastError());
     return RELAX_OK;

@@ -146,7 +146,8 @@ class RelaxEngine:
     def load_vit(self, state_dict, name_model="vit_base", patch_size=None):
         """state_dict: DINO ViT key names -> fp32 arrays/tensors.  patch_size 8 or 16 (VitGenerator's second argument,
         src/extractor/visualise_vit_layer.py:263-329); None reads it from patch_embed.proj.weight's shape [dim,3,p,p].
-        Sets vit_patch, vit_ntok ((224/p)^2 + 1: 197 / 785) and vit_npatch; every ViT call sizes its outputs by them."""
+        Sets vit_patch, vit_ntok ((224/p)^2 + 1: 197 / 785) and vit_npatch: the geometry of a 224 x 224 call.  A ViT call sizes its
+        outputs by the canvas it is given (vit_canvas_geometry)."""
         dim, depth, heads = VIT_CONFIGS[name_model]
         if patch_size is None:
             w = state_dict.get("patch_embed.proj.weight")
@@ -162,8 +163,30 @@ class RelaxEngine:
         self.vit_npatch = self.vit_ntok - 1
         del keep
 
+    def vit_canvas_geometry(self, Hc, Wc):
+        """(gh, gw, ntok) of an [Hc, Wc] canvas under the loaded ViT: gh = Hc // patch, gw = Wc // patch (the trailing pixels are ignored, as the
+        reference's stride-p convolution ignores them, src/extractor/visualise_vit_layer.py:132-149), ntok = gh * gw + 1.  A side below the patch
+        size or more than 4096 patches is refused (RuntimeError naming the value)."""
+        if self.vit_dim is None:
+            raise RuntimeError("load_vit first")
+        v = [C.c_int(0) for _ in range(3)]
+        self._check(self.lib.relax_vit_canvas_geometry(self.h, int(Hc), int(Wc), *[C.byref(x) for x in v]), "relax_vit_canvas_geometry")
+        return tuple(int(x.value) for x in v)
+
+    def vit_pos_embed(self, gh, gw):
+        """interpolate_pos_encoding (src/extractor/visualise_vit_layer.py:197-219) for a gh x gw patch grid -> fp32 [1 + gh*gw, dim]: the class
+        row, then the loaded table resampled bicubically as torch does it in fp32; the loaded table itself on the 224 x 224 grid."""
+        if self.vit_dim is None:
+            raise RuntimeError("load_vit first")
+        gh, gw = int(gh), int(gw)
+        if gh < 1 or gw < 1:
+            raise ValueError(f"vit_pos_embed: grid {gh} x {gw}")
+        out = torch.empty((1 + gh * gw, self.vit_dim), dtype=torch.float32, device=self.device)
+        self._check(self.lib.relax_vit_pos_embed(self.h, gh, gw, _ptr(out), _stream()), "relax_vit_pos_embed")
+        return out
+
     def vit_geometry(self):
-        """(patch, ntok, dim, heads) of the loaded ViT, read back from the library (relax_vit_geometry)."""
+        """(patch, ntok, dim, heads) of the loaded ViT at 224 x 224, read back from the library (relax_vit_geometry)."""
         v = [C.c_int(0) for _ in range(4)]
         self._check(self.lib.relax_vit_geometry(self.h, *[C.byref(x) for x in v]), "relax_vit_geometry")
         return tuple(int(x.value) for x in v)
@@ -513,38 +536,47 @@ class RelaxEngine:
         self._check(rc, "relax_resnet50_clip_features")
         return ls, pl
 
-    def vit_features(self, frags, tokens=False, pooled=True, attention=False):
-        """frags uint8 [N,224,224,3] BGR -> (tokens fp32 [N,npatch,dim] | None, pooled fp32 [N,3*dim] | None); npatch = 196, or 784
-        with a patch-8 model.  attention=True adds a third element: the last block's CLS attention to the patches, fp32
-        [N,heads,npatch] (src/extractor/visualise_vit.py:241-250,353-369: attn[:, :, 0, 1:]); tokens and pooled are unchanged by it."""
+    def _canvas(self, images):
+        """-> (uint8 [N,Hc,Wc,3] on the device, ntok of that canvas under the loaded ViT)"""
         if self.vit_dim is None:
             raise RuntimeError("load_vit first")
-        frags = self._frags(frags)
-        N = frags.shape[0]
+        images = self._dev_u8(images)
+        if images.dim() == 3:
+            images = images.unsqueeze(0)
+        if images.dim() != 4 or images.shape[3] != 3 or images.shape[0] < 1:
+            raise ValueError(f"images must be [N,Hc,Wc,3], got {tuple(images.shape)}")
+        if tuple(images.shape[1:3]) == (TARGET, TARGET):
+            return images, self.vit_ntok
+        return images, self.vit_canvas_geometry(images.shape[1], images.shape[2])[2]
+
+    def vit_features(self, frags, tokens=False, pooled=True, attention=False):
+        """frags uint8 [N,Hc,Wc,3] BGR, any canvas (vit_canvas_geometry: gh x gw = npatch patches, the position table resampled onto that grid
+        as the reference's prepare_tokens does, src/extractor/visualise_vit_layer.py:197-232) -> (tokens fp32 [N,npatch,dim] | None, pooled fp32
+        [N,3*dim] | None); at 224 x 224 npatch = 196, or 784 with a patch-8 model.  attention=True adds a third element: the last block's CLS
+        attention to the patches, fp32 [N,heads,npatch] (src/extractor/visualise_vit.py:241-250,353-369: attn[:, :, 0, 1:]); tokens and
+        pooled are unchanged by it."""
+        frags, ntok = self._canvas(frags)
+        N, Hc, Wc, _ = frags.shape
         dev = self.device
-        tk = torch.empty((N, self.vit_npatch, self.vit_dim), dtype=torch.float32, device=dev) if tokens else None
+        tk = torch.empty((N, ntok - 1, self.vit_dim), dtype=torch.float32, device=dev) if tokens else None
         pl = torch.empty((N, 3 * self.vit_dim), dtype=torch.float32, device=dev) if pooled else None
-        if not attention:
-            self._check(self.lib.relax_vit_features(self.h, _ptr(frags), N, _ptr(tk), _ptr(pl), _stream()),
-                        "relax_vit_features")
-            return tk, pl
-        at = torch.empty((N, self.vit_dim // 64, self.vit_ntok), dtype=torch.float32, device=dev)
-        self._check(self.lib.relax_vit_features_ex(self.h, _ptr(frags), N, _ptr(tk), _ptr(pl), _ptr(at), _stream()),
-                    "relax_vit_features_ex")
-        return tk, pl, at[:, :, 1:]
+        at = torch.empty((N, self.vit_dim // 64, ntok), dtype=torch.float32, device=dev) if attention else None
+        if tk is None and pl is None and at is None:
+            raise ValueError("vit_features: no output requested")
+        self._check(self.lib.relax_vit_features_canvas(self.h, _ptr(frags), N, Hc, Wc, _ptr(tk), _ptr(pl), _ptr(at), _stream()),
+                    "relax_vit_features_canvas")
+        return (tk, pl, at[:, :, 1:]) if attention else (tk, pl)
 
     def vit_attention(self, frags, with_cls=False):
-        """frags uint8 [N,224,224,3] BGR -> fp32 [N,heads,npatch]: get_last_selfattention's CLS row without the CLS column
-        (src/extractor/visualise_vit.py:241-250,353-369).  The forward stops after the last block's qkv GEMM.
-        with_cls=True returns the whole row [N,heads,ntok] (column 0 = the CLS key; each row sums to 1).  npatch / ntok = 196 / 197,
-        or 784 / 785 with a patch-8 model."""
-        if self.vit_dim is None:
-            raise RuntimeError("load_vit first")
-        frags = self._frags(frags)
-        N = frags.shape[0]
-        at = torch.empty((N, self.vit_dim // 64, self.vit_ntok), dtype=torch.float32, device=self.device)
-        self._check(self.lib.relax_vit_features_ex(self.h, _ptr(frags), N, None, None, _ptr(at), _stream()),
-                    "relax_vit_features_ex")
+        """frags uint8 [N,Hc,Wc,3] BGR (any canvas, as vit_features) -> fp32 [N,heads,npatch]: get_last_selfattention's CLS row without the
+        CLS column (src/extractor/visualise_vit.py:241-250,353-369).  The forward stops after the last block's qkv GEMM.
+        with_cls=True returns the whole row [N,heads,ntok] (column 0 = the CLS key; each row sums to 1).  At 224 x 224 npatch / ntok =
+        196 / 197, or 784 / 785 with a patch-8 model."""
+        frags, ntok = self._canvas(frags)
+        N, Hc, Wc, _ = frags.shape
+        at = torch.empty((N, self.vit_dim // 64, ntok), dtype=torch.float32, device=self.device)
+        self._check(self.lib.relax_vit_features_canvas(self.h, _ptr(frags), N, Hc, Wc, None, None, _ptr(at), _stream()),
+                    "relax_vit_features_canvas")
         return at if with_cls else at[:, :, 1:]
 
     def attention_overlay(self, frames, positions, counts, patch_values, lut=None, patch_size=16):
@@ -668,6 +700,15 @@ class RelaxEngine:
             _, pooled = self.vit_features(both, tokens=False, pooled=True)
             out["vit"] = torch.cat([pooled[:T], pooled[T:]], dim=1)
         return out
+
+    def fragment_vit_vectors(self, frames, patch_size=16, target_size=TARGET, top_n=None):
+        """frames uint8 [T,2,H,W,3] -> fp32 [T, 6*dim]: the ViT pool of the original fragment | the pool of the frame-difference fragment, both
+        cut by fragment_pairs at patch_size on a target_size x target_size canvas (any multiple of patch_size up to 448) and run through the ViT
+        at that canvas - the row of extract_clip's 'vit' block, which is this at target_size 224."""
+        fr = self.fragment_pairs(frames, top_n=top_n, patch_size=patch_size, target_size=target_size)
+        T = fr["ori_frag"].shape[0]
+        _, pooled = self.vit_features(torch.cat([fr["ori_frag"], fr["diff_frag"]], dim=0), tokens=False, pooled=True)
+        return torch.cat([pooled[:T], pooled[T:]], dim=1)
 
     @staticmethod
     def _clip_geometry(patch_size, top_n, target_size):

@@ -2,7 +2,7 @@
 
 Reference: get_last_selfattention runs blocks 0..10 and returns block 11's softmax(q k^T / 8) (:241-250, :123-127);
 visualize_attention keeps the CLS query's row against the 196 patches for every head and nearest-upsamples it to
-[heads, 224, 224] (:353-369); process_video_frame returns it as a per-head dict (:414-431, :457-500).  The reference rebuilds
+[heads, H, W] at the (cropped) size of its input (:353-369); process_video_frame resizes to 224 x 224 first and returns it as a per-head dict (:414-431, :457-500).  The reference rebuilds
 the model for every image and runs a full forward; here the weights live in the engine and the forward stops after block 11's
 qkv GEMM (RelaxEngine.vit_attention)."""
 import os
@@ -22,14 +22,21 @@ def _attention(model, frag_bgr_u8):
 
 
 def visualize_attention(model, img, patch_size, device):
-    """img: uint8 [224,224,3] BGR (a fragment, or a frame through runtime.to_model_input(.., "vit")) -> fp32 numpy
-    [heads, 224, 224]: attn[0, :, 0, 1:] as [heads, 14, 14] ([heads, 28, 28] at patch size 8), each value repeated over its
-    patch (mode="nearest")."""
+    """img: uint8 [H,W,3] BGR of any size at least one patch (a fragment; a frame, as it is or through runtime.to_model_input(.., "vit")).
+    As the reference (:355-357) the image is cropped to multiples of the patch size, img[:H - H % p, :W - W % p], and runs at that size
+    (the position table resampled onto its grid) -> fp32 numpy [heads, gh*p, gw*p]: attn[0, :, 0, 1:] as [heads, gh, gw] ([heads, 14, 14]
+    at 224 x 224 and patch 16), each value repeated over its patch (mode="nearest")."""
     if patch_size != model.patch_size:
         raise ValueError(f"visualize_attention: patch_size {patch_size}, the model was built with {model.patch_size}")
+    if not torch.is_tensor(img):
+        img = np.asarray(img)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"visualize_attention: img must be [H,W,3], got {tuple(img.shape)}")
+    gh, gw = img.shape[0] // patch_size, img.shape[1] // patch_size
+    img = img[:gh * patch_size, :gw * patch_size]
     att = _attention(model, img).cpu().numpy()[0]                    # [heads, npatch]
     nh = att.shape[0]
-    att = att.reshape(nh, 224 // patch_size, 224 // patch_size)
+    att = att.reshape(nh, gh, gw)
     return np.repeat(np.repeat(att, patch_size, axis=1), patch_size, axis=2)
 
 

@@ -35,11 +35,13 @@ class VitGenerator(object):
         return t
 
     def __call__(self, frag_bgr_u8):
-        """-> (None, tokens [N,196,dim] ([N,784,dim] at patch size 8)); the cls token is not part of the hot path."""
+        """frag_bgr_u8 uint8 [N,Hc,Wc,3] (any canvas: VisionTransformer.forward interpolates the position table, :197-232) -> (None, tokens
+        [N,(Hc//p)*(Wc//p),dim]: [N,196,dim] at 224 x 224, [N,784,dim] at patch size 8); the cls token is not part of the hot path."""
         return None, self.tokens(frag_bgr_u8)
 
 
 def process_fragment_array(frag_bgr_u8, model):
+    """frag_bgr_u8 uint8 [Hc,Wc,3] or [1,Hc,Wc,3], any canvas -> fp32 numpy [(Hc//p)*(Wc//p), dim]"""
     return model.tokens(frag_bgr_u8)[0].cpu().numpy()
 
 
