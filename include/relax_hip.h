@@ -347,6 +347,17 @@ int relax_vit_features_ex(relax_handle* h, const uint8_t* frags, int N, float* t
  * streaming ones.  Hc = Wc = 224 is relax_vit_features_ex: the same launches, the same bits. */
 int relax_vit_features_canvas(relax_handle* h, const uint8_t* images, int N, int Hc, int Wc, float* tokens, float* pooled,
                               float* cls_attention, relax_stream stream);
+/* VisionTransformer.get_intermediate_layers(x, n) (src/extractor/visualise_vit_layer.py:252-260): the final norm (:234-239, eps 1e-6)
+ * applied to the output of each of the last n_last blocks, in ONE forward on any canvas (images, Hc, Wc as relax_vit_features_canvas).
+ * Tap k = 0 .. n_last - 1 is block depth - n_last + k, the reference's order; the last tap is forward's own norm:
+ *   tokens [n_last,N,ntok,dim]   the normed rows, row 0 the CLS token (forward's x[:, 0]), rows 1.. the patch tokens
+ *   cls    [n_last,N,dim]        the normed CLS row alone: the same bits as tokens[k][:, 0]
+ *   pooled [n_last,N,3*dim]      mean | max | population std over the normed patch tokens: the same bits as relax_op_token_stats of
+ *                                tokens[k][:, 1:], and for the last tap as relax_vit_features' pooled
+ * (each may be NULL, not all three).  cls and pooled come from one launch per tap that reads the residual stream and writes no normed
+ * tokens (csrc/vit_layers.hip).  n_last outside [1, depth] is refused. */
+int relax_vit_intermediate_layers(relax_handle* h, const uint8_t* images, int N, int Hc, int Wc, int n_last, float* tokens, float* cls,
+                                  float* pooled, relax_stream stream);
 
 /* ---- quality head at inference --------------------------------------------------- */
 /* Replaces imputer.transform + scaler.transform + Mlp.forward (src/demo_test.py:177-208, src/model_regression.py:37-58).
@@ -547,6 +558,12 @@ int relax_op_gap(relax_handle* h, const float* x, float* out, int Nimg, int HW, 
  * (process_video_feature, vit branch: src/main_residual_fragment.py:128-136; src/main_fragment_pool.py:124-133) */
 int relax_op_token_stats(relax_handle* h, const float* x, float* out, int Nimg, int tokens, int dim,
                          relax_stream stream);
+/* One tap of relax_vit_intermediate_layers as an op (csrc/vit_layers.hip): LayerNorm of x [Nimg, ntok, dim] fused with the statistics of
+ * its rows - cls_out [Nimg, dim] = the normed row 0, pooled_out [Nimg, 3*dim] = mean | max | std over the normed rows 1 .. ntok - 1 (either
+ * may be NULL, not both); the bits of relax_op_layernorm followed by relax_op_token_stats on rows 1...  dim a multiple of 64 up to 768,
+ * ntok 2 .. 4097. */
+int relax_op_vit_norm_token_stats(relax_handle* h, const float* x, const float* gamma, const float* beta, float eps, float* cls_out,
+                                  float* pooled_out, int Nimg, int ntok, int dim, relax_stream stream);
 
 /* Device-to-device copy on the caller's stream (the fragment batch of one backbone duplicated for the other). */
 int relax_copy_bytes(relax_handle* h, const void* src, void* dst, int64_t n_bytes, relax_stream stream);

@@ -52,6 +52,7 @@ PROTOTYPES = {
     "relax_vit_features": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
     "relax_vit_features_ex": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp]),
     "relax_vit_features_canvas": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "relax_vit_intermediate_layers": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp]),
     "relax_vit_pos_embed": (C.c_int, [c_vp, C.c_int, C.c_int, c_vp, c_vp]),
     "relax_vit_canvas_geometry": (C.c_int, [c_vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "relax_load_mlp_head": (C.c_int, [c_vp, C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
@@ -94,6 +95,7 @@ PROTOTYPES = {
     "relax_op_bn_relu_maxpool_amax": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_op_gap": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int64, c_vp]),
     "relax_op_token_stats": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp]),
+    "relax_op_vit_norm_token_stats": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_float, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_copy_bytes": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, c_vp]),
     "relax_segment_mean": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int, C.c_int, c_vp, C.c_int, c_vp, C.c_int64, C.c_int, c_vp]),
     "relax_png_decode": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, c_vp, C.c_int64, c_vp, C.c_int64, c_vp, c_vp]),

@@ -460,6 +460,10 @@ int launch_attention_stream_x6(relax_handle* h, const float* qkv, float* out, vo
 // the last block's CLS attention row (vit_attention_map.hip): qkv as fp32 rows [Nimg*ntok][3*dim] or, with planes, fp16 planes of
 // qkv * s_qkv (csrc/h2.h) -> out fp32 [Nimg, heads, ntok] = softmax(q_0 k^T / 8) per (image, head)
 // (ntok <= 4352: 256 threads x 4 keys up to 1024 tokens, x 17 above)
+// the final norm of a tap of the residual stream X [Nimg, ntok, dim] without its normed tokens in HBM (csrc/vit_layers.hip): the normed CLS
+// row -> cls_out [Nimg, dim], mean | max | std over the normed patch rows -> pooled_out [Nimg, 3 dim] (either may be NULL, not both)
+int launch_vit_norm_token_stats(relax_handle* h, const float* X, const float* g, const float* b, float eps, float* cls_out, float* pooled_out,
+                                int Nimg, int ntok, int dim, hipStream_t s);
 int launch_vit_cls_attention(relax_handle* h, const void* qkv, bool planes, float s_qkv, float* out, int Nimg, int ntok, int heads, hipStream_t s);
 int launch_bn_relu_maxpool(relax_handle* h, const float* x, const float* scale, const float* shift, float* y,
                            int Nimg, int H, int W, int C, hipStream_t s);

@@ -392,8 +392,25 @@ int relax_load_vit_ex(relax_handle* h, const float* const* tensors, const char* 
 
 // frags: N images [Hc][Wc][3].  Hc = Wc = 224 is the loaded geometry: v.pos, the arena relax_reserve sized, the launches of always.
 // `what`: the entry point that was called, for the messages.
+// taps (relax_vit_intermediate_layers; NULL from every other entry point, whose launches are then the ones of always): after each of the
+// last n_last blocks the final norm of the residual stream - the whole normed rows into tokens[k] (launch_layernorm straight into the caller's
+// [n, N, ntok, dim]), the normed CLS row and the patch-token statistics into cls[k] / pooled[k] (vit_norm_token_stats, csrc/vit_layers.hip) -,
+// k = 0 for block depth - n_last.  The last tap IS the forward's final norm, which is then not launched again.
+struct VitTaps { int n_last; float *tokens, *cls, *pooled; };
+static int vit_tap(relax_handle* h, const VitTaps& t, int block, const float* X, int N, int ntok, hipStream_t s) {
+    const VitW& v = h->vit;
+    const int k = block - (v.depth - t.n_last);
+    if (k < 0) return RELAX_OK;
+    const size_t dim = (size_t)v.dim, per_tap = (size_t)N * dim;
+    if (t.tokens) RELAX_TRY(launch_layernorm(h, X, v.norm_g, v.norm_b, t.tokens + (size_t)k * per_tap * ntok, N * ntok, v.dim, kLnEps, s));
+    if (t.cls || t.pooled)
+        RELAX_TRY(launch_vit_norm_token_stats(h, X, v.norm_g, v.norm_b, kLnEps, t.cls ? t.cls + (size_t)k * per_tap : nullptr,
+                                              t.pooled ? t.pooled + (size_t)k * per_tap * 3 : nullptr, N, ntok, v.dim, s));
+    return RELAX_OK;
+}
+
 static int vit_forward(relax_handle* h, const char* what, const uint8_t* frags, int N, int Hc, int Wc, float* tokens, float* pooled,
-                       float* cls_attention, relax_stream stream) {
+                       float* cls_attention, relax_stream stream, const VitTaps* taps = nullptr) {
     if (!h) return RELAX_ERR_INVALID;
     RELAX_REQUIRE(h, h->vit.loaded, "%s: call relax_load_vit first", what);
     RELAX_REQUIRE(h, frags && N > 0, "%s: bad arguments", what);
@@ -480,7 +497,9 @@ static int vit_forward(relax_handle* h, const char* what, const uint8_t* frags, 
             RELAX_TRY(launch_layernorm_h2(h, Xx, b.ln2_g, b.ln2_b, Ys, b.s_ln2, rows, dim, kLnEps, s));
             RELAX_TRY(gemm(Ys, b.fc1, nullptr, nullptr, Hs, b.s_hid, rows, 2));              // GELU(erf) -> fp16 planes
             RELAX_TRY(gemm(Hs, b.fc2, Xx, Xx, nullptr, 0.f, rows, 0));                      // x += mlp
+            if (taps) RELAX_TRY(vit_tap(h, *taps, i, Xx, N, NTOK, s));
         }
+        if (taps) return RELAX_OK;
         RELAX_TRY(launch_layernorm(h, Xx, v.norm_g, v.norm_b, ATT, rows, dim, kLnEps, s));
         if (tokens) {
             const int64_t t = (int64_t)N * NPATCH * (dim / 4);
@@ -519,7 +538,9 @@ static int vit_forward(relax_handle* h, const char* what, const uint8_t* frags, 
             RELAX_TRY(launch_layernorm_sp3(h, Xx, b.ln2_g, b.ln2_b, Ys, rows, dim, kLnEps, s));
             RELAX_TRY(launch_gemm_x6(h, Ys, b.fc1.w_sp3, b.fc1.b, nullptr, nullptr, Hs, rows, 4 * dim, dim, 2, s)); // GELU(erf) -> sp3
             RELAX_TRY(launch_gemm_x6(h, Hs, b.fc2.w_sp3, b.fc2.b, Xx, Xx, nullptr, rows, dim, 4 * dim, 0, s));     // x += mlp
+            if (taps) RELAX_TRY(vit_tap(h, *taps, i, Xx, N, NTOK, s));
         }
+        if (taps) return RELAX_OK;
         RELAX_TRY(launch_layernorm(h, Xx, v.norm_g, v.norm_b, ATT, rows, dim, kLnEps, s));
         if (tokens) {
             const int64_t t = (int64_t)N * NPATCH * (dim / 4);
@@ -548,7 +569,9 @@ static int vit_forward(relax_handle* h, const char* what, const uint8_t* frags, 
         RELAX_TRY(launch_layernorm(h, X, b.ln2_g, b.ln2_b, Y, rows, dim, kLnEps, s));
         RELAX_TRY(launch_gemm(h, Y, b.fc1.w, b.fc1.b, nullptr, Hid, rows, 4 * dim, dim, 2, s));   // GELU(erf)
         RELAX_TRY(launch_gemm(h, Hid, b.fc2.w, b.fc2.b, X, X, rows, dim, 4 * dim, 0, s));   // x += mlp
+        if (taps) RELAX_TRY(vit_tap(h, *taps, i, X, N, NTOK, s));
     }
+    if (taps) return RELAX_OK;
     RELAX_TRY(launch_layernorm(h, X, v.norm_g, v.norm_b, Y, rows, dim, kLnEps, s));
     if (tokens) {
         const int64_t t = (int64_t)N * NPATCH * (dim / 4);
@@ -578,6 +601,17 @@ int relax_vit_features_canvas(relax_handle* h, const uint8_t* images, int N, int
     if (!h) return RELAX_ERR_INVALID;
     RELAX_REQUIRE(h, tokens || pooled || cls_attention, "relax_vit_features_canvas: no output requested");
     return vit_forward(h, "relax_vit_features_canvas", images, N, Hc, Wc, tokens, pooled, cls_attention, stream);
+}
+
+int relax_vit_intermediate_layers(relax_handle* h, const uint8_t* images, int N, int Hc, int Wc, int n_last, float* tokens, float* cls,
+                                  float* pooled, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, h->vit.loaded, "relax_vit_intermediate_layers: call relax_load_vit first");
+    RELAX_REQUIRE(h, n_last >= 1 && n_last <= h->vit.depth, "relax_vit_intermediate_layers: n_last=%d outside [1, %d] (the loaded model's depth)",
+                  n_last, h->vit.depth);
+    RELAX_REQUIRE(h, tokens || cls || pooled, "relax_vit_intermediate_layers: no output requested");
+    const VitTaps taps{n_last, tokens, cls, pooled};
+    return vit_forward(h, "relax_vit_intermediate_layers", images, N, Hc, Wc, nullptr, nullptr, nullptr, stream, &taps);
 }
 
 int relax_vit_canvas_geometry(relax_handle* h, int Hc, int Wc, int* gh, int* gw, int* ntok) {

@@ -579,6 +579,30 @@ class RelaxEngine:
                     "relax_vit_features_canvas")
         return at if with_cls else at[:, :, 1:]
 
+    def vit_intermediate_layers(self, frags, n=1, tokens=False, cls=True, pooled=True):
+        """VisionTransformer.get_intermediate_layers(x, n) (src/extractor/visualise_vit_layer.py:252-260): the final norm of the output of
+        each of the last n blocks, from ONE forward.  frags uint8 [N,Hc,Wc,3] BGR, any canvas (as vit_features) -> dict of the requested
+        'tokens' fp32 [n,N,ntok,dim] (row 0 the CLS token), 'cls' fp32 [n,N,dim], 'pooled' fp32 [n,N,3*dim] (mean | max | std over the
+        patch tokens); tap k is block depth - n + k, so the last one is vit_features' norm (tokens[-1][:, 1:] and pooled[-1] are its bits).
+        n outside [1, depth] is refused by the library (RuntimeError naming n)."""
+        frags, ntok = self._canvas(frags)
+        N, Hc, Wc, _ = frags.shape
+        n = int(n)
+        if not (tokens or cls or pooled):
+            raise ValueError("vit_intermediate_layers: no output requested")
+        rows = max(n, 0)   # (the library names a bad n; nothing is allocated for it)
+        dev, dim = self.device, self.vit_dim
+        out = {}
+        if tokens:
+            out["tokens"] = torch.empty((rows, N, ntok, dim), dtype=torch.float32, device=dev)
+        if cls:
+            out["cls"] = torch.empty((rows, N, dim), dtype=torch.float32, device=dev)
+        if pooled:
+            out["pooled"] = torch.empty((rows, N, 3 * dim), dtype=torch.float32, device=dev)
+        self._check(self.lib.relax_vit_intermediate_layers(self.h, _ptr(frags), N, Hc, Wc, n, _ptr(out.get("tokens")), _ptr(out.get("cls")),
+                                                           _ptr(out.get("pooled")), _stream()), "relax_vit_intermediate_layers")
+        return out
+
     def attention_overlay(self, frames, positions, counts, patch_values, lut=None, patch_size=16):
         """map_attention_to_original (src/demo_visual.py:12-25) on the GPU.
         frames uint8 [T,H,W,3] BGR (items may be strided, pixels packed); positions int32 [T,slots,2] / counts int32 [T] as
@@ -709,6 +733,18 @@ class RelaxEngine:
         T = fr["ori_frag"].shape[0]
         _, pooled = self.vit_features(torch.cat([fr["ori_frag"], fr["diff_frag"]], dim=0), tokens=False, pooled=True)
         return torch.cat([pooled[:T], pooled[T:]], dim=1)
+
+    def fragment_vit_layer_stack(self, frames, n=4, cls=False, patch_size=16, target_size=TARGET, top_n=None):
+        """frames uint8 [T,2,H,W,3] -> fp32 [T, 2*n*3*dim] (+ 2*n*dim columns with cls=True): fragment_vit_vectors with the last n blocks'
+        taps (vit_intermediate_layers) in place of the last block's pool.  Per fragment - the original, then the frame difference - the taps in
+        block order, each tap its pooled row, or its CLS row | its pooled row with cls=True (DINO's linear-probe features).  n=1, cls=False is
+        fragment_vit_vectors' row, bit for bit."""
+        fr = self.fragment_pairs(frames, top_n=top_n, patch_size=patch_size, target_size=target_size)
+        T = fr["ori_frag"].shape[0]
+        out = self.vit_intermediate_layers(torch.cat([fr["ori_frag"], fr["diff_frag"]], dim=0), n=n, tokens=False, cls=cls, pooled=True)
+        taps = torch.cat([out["cls"], out["pooled"]], dim=2) if cls else out["pooled"]       # [n, 2T, F]
+        rows = taps.permute(1, 0, 2).reshape(2 * T, -1)                                        # a fragment's taps side by side
+        return torch.cat([rows[:T], rows[T:]], dim=1)
 
     @staticmethod
     def _clip_geometry(patch_size, top_n, target_size):
@@ -1014,6 +1050,16 @@ class RelaxEngine:
         self._check(self.lib.relax_op_layernorm(self.h, _ptr(x), _ptr(g), _ptr(b), _ptr(y), rows, dim, eps, _stream()),
                     "relax_op_layernorm")
         return y
+
+    def op_vit_norm_token_stats(self, x, g, b, eps, cls=True, pooled=True):
+        """x fp32 [Nimg,ntok,dim] -> (the normed row 0 [Nimg,dim] | None, mean | max | std over the normed rows 1.. [Nimg,3*dim] | None): one
+        tap of vit_intermediate_layers, the bits of op_layernorm followed by op_token_stats"""
+        Nimg, ntok, dim = x.shape
+        c = torch.empty((Nimg, dim), dtype=torch.float32, device=self.device) if cls else None
+        p = torch.empty((Nimg, 3 * dim), dtype=torch.float32, device=self.device) if pooled else None
+        self._check(self.lib.relax_op_vit_norm_token_stats(self.h, _ptr(x), _ptr(g), _ptr(b), eps, _ptr(c), _ptr(p), Nimg, ntok, dim, _stream()),
+                    "relax_op_vit_norm_token_stats")
+        return c, p
 
     def op_attention(self, qkv, n_img, heads):
         out = torch.empty((qkv.shape[0], heads * 64), dtype=torch.float32, device=self.device)

@@ -40,6 +40,19 @@ class VitGenerator(object):
         return None, self.tokens(frag_bgr_u8)
 
 
+    def get_intermediate_layers(self, x, n=1):
+        """VisionTransformer.get_intermediate_layers (:252-260): x uint8 [N,Hc,Wc,3] BGR -> list of n tensors [N,ntok,dim], the final norm of
+        the output of each of the last n blocks (row 0 the CLS token), in block order; one forward."""
+        eng = runtime.ensure_vit(self.name_model, self.patch_size)
+        t = eng.vit_intermediate_layers(torch.from_numpy(np.ascontiguousarray(x)), n=n, tokens=True, cls=False, pooled=False)["tokens"]
+        return list(t.unbind(0))
+
+    def cls_token(self, x):
+        """forward's first output (:234-239, x[:, 0] after the final norm): x uint8 [N,Hc,Wc,3] BGR -> [N,dim]"""
+        eng = runtime.ensure_vit(self.name_model, self.patch_size)
+        return eng.vit_intermediate_layers(torch.from_numpy(np.ascontiguousarray(x)), n=1, tokens=False, cls=True, pooled=False)["cls"][0]
+
+
 def process_fragment_array(frag_bgr_u8, model):
     """frag_bgr_u8 uint8 [Hc,Wc,3] or [1,Hc,Wc,3], any canvas -> fp32 numpy [(Hc//p)*(Wc//p), dim]"""
     return model.tokens(frag_bgr_u8)[0].cpu().numpy()
