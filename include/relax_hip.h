@@ -107,9 +107,10 @@ int relax_reserve(relax_handle* h, int max_images);
  * "rn_h2_early" (default 1): with "rn_h2", the stem and the 3x3 convolutions of layer1 / layer2 run f16x2 as well; 0 = bf16x6 there.
  * "att_h2" (default 1): under "gemm_precision" 3 the ViT's attention runs on fp16 planes too (csrc/attention_h2.hip: the qkv GEMM writes planes,
  * three partial products, K / V by LDS-DMA into the fragment images); 0 = the bf16x6 attention kernel on an fp32 qkv output (A/B switch).
- * A patch-8 model (785 tokens) takes the "att_h2" = 0 route whatever the option says: csrc/attention_h2.hip holds all keys of an
- * (image, head) on the chip, which ends at 224; its qkv GEMM writes fp32 and the streaming bf16x6 kernel (csrc/attention_stream.hip)
- * writes the fp16 planes the projection reads.
+ * "att_h2_stream" (default 1): with "att_h2", a token count other than 197 (a patch-8 model's 785, any other canvas) runs attention on
+ * fp16 planes too (csrc/attention_stream_h2.hip: attention_h2's arithmetic with an online softmax over key tiles of 64; the qkv GEMM
+ * writes planes); 0 = that GEMM writes fp32 and the streaming bf16x6 kernel (csrc/attention_stream.hip) writes the fp16 planes the
+ * projection reads.  197 tokens run csrc/attention_h2.hip either way.  The option also picks relax_op_attention_ex's kernel under 3.
  * "rn_fuse" (default 1): with "rn_h2_early", the layer1 / layer2 blocks without a downsample branch run their 3x3 and their conv3 back to back in ONE
  * launch (csrc/gemm_x6.hip, B2B: the 3x3's output tile stays in registers as the A operand of the 1x1, conv3 on f16x2 with one scale
  * per pixel row); 0 = two launches, conv3 on bf16x6 (A/B switch).  "b2b_rows" (256 or 128): rows per tile of layer1's such launches, same bits.
@@ -541,7 +542,8 @@ int relax_op_attention(relax_handle* h, const float* qkv, float* out, int Nimg, 
 /* The streaming kernel (csrc/attention_stream.hip: key tiles of 32, online softmax) at ANY token count ntok >= 1 - also at 197,
  * where the forwards run the single-tile kernels (a test / benchmark entry point): qkv [Nimg*ntok, 3*heads*64] -> out
  * [Nimg*ntok, heads*64].  The arithmetic is the one the ViT forward's attention has under the current "gemm_precision": exact
- * fp32 MFMA under 0 (and 1), bf16x6 under 2 and 3. */
+ * fp32 MFMA under 0 (and 1), bf16x6 under 2, and under 3 the f16x2 kernel (csrc/attention_stream_h2.hip: key tiles of 64, one scale
+ * from the tensor's measured maximum) with "att_h2" and "att_h2_stream" on, bf16x6 otherwise. */
 int relax_op_attention_ex(relax_handle* h, const float* qkv, float* out, int Nimg, int ntok, int heads, relax_stream stream);
 /* relu(x*scale[c]+shift[c]) then 3x3/s2/p1 max-pool: [Nimg,H,W,C] -> [Nimg,H/2,W/2,C] */
 int relax_op_bn_relu_maxpool(relax_handle* h, const float* x, const float* scale, const float* shift, float* y,

@@ -299,6 +299,7 @@ int relax_set_option(relax_handle* h, const char* key, int value) {
         h->gemm.b2b_rows = value;
     }
     else if (k == "att_h2") h->gemm.att_h2 = value != 0;
+    else if (k == "att_h2_stream") h->gemm.att_h2_stream = value != 0;
     else if (k == "h2_form") {
         RELAX_REQUIRE(h, value >= 0 && value <= 2, "relax_set_option: h2_form must be 0, 1 or 2");
         h->gemm.h2_form = value;
@@ -344,6 +345,7 @@ int relax_get_option(relax_handle* h, const char* key, int* value) {
     else if (k == "rn_c1_h2") *value = h->gemm.rn_c1_h2;
     else if (k == "b2b_rows") *value = h->gemm.b2b_rows;
     else if (k == "att_h2") *value = h->gemm.att_h2;
+    else if (k == "att_h2_stream") *value = h->gemm.att_h2_stream;
     else if (k == "h2_stages") *value = h->gemm.h2_stages;
     else if (k == "h2_form") *value = h->gemm.h2_form;
     else if (k == "debug_poison") *value = h->gemm.debug_poison;

@@ -327,6 +327,19 @@ __global__ __launch_bounds__(256) void ah_from_h2(const char* __restrict__ y, fl
     *reinterpret_cast<ah_f32x4*>(dst + 4) = (ah_f32x4){o[4], o[5], o[6], o[7]};
 }
 
+// the two steps around the kernel, for the streaming operator entry too (attention_stream_h2.hip)
+int launch_ah_op_scalars(relax_handle* h, const unsigned* amax, float* tab, hipStream_t s) {
+    hipLaunchKernelGGL(ah_op_scalars, dim3(1), dim3(1), 0, s, amax, tab);
+    RELAX_HIP_CHECK(h, hipGetLastError());
+    return RELAX_OK;
+}
+int launch_ah_from_h2(relax_handle* h, const void* planes, float* out, int64_t rows, int dim, const float* inv, hipStream_t s) {
+    const int64_t total8 = rows * (dim / 8);
+    hipLaunchKernelGGL(ah_from_h2, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, s, static_cast<const char*>(planes), out, dim, total8, inv);
+    RELAX_HIP_CHECK(h, hipGetLastError());
+    return RELAX_OK;
+}
+
 // (operator level, tests: ONE scale from the maximum of the whole qkv tensor of the call - not batch-invariant, unlike the engine's ViT path,
 // which hands the kernel planes written with a static scale: csrc/h2.h)
 int launch_attention_h2_op(relax_handle* h, const float* qkv, float* out, int Nimg, int heads, hipStream_t s) {

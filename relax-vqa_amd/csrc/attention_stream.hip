@@ -309,7 +309,9 @@ extern "C" int relax_op_attention_ex(relax_handle* h, const float* qkv, float* o
     RELAX_REQUIRE(h, qkv && out, "relax_op_attention_ex: NULL operand");
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // the arithmetic the ViT forward's attention runs under this "gemm_precision": bf16x6 under 2 and 3, exact fp32 under 0 and 1
+    // the arithmetic the ViT forward's attention runs under this "gemm_precision": f16x2 planes under 3 with "att_h2" and "att_h2_stream",
+    // bf16x6 under 2 and otherwise under 3, exact fp32 under 0 and 1
+    if (h->gemm.precision == 3 && h->gemm.att_h2 && h->gemm.att_h2_stream) return launch_attention_stream_h2_op(h, qkv, out, Nimg, ntok, heads, s);
     if (h->gemm.precision >= 2) return launch_attention_stream_x6(h, qkv, out, nullptr, Nimg, ntok, heads, s, 0.f);
     return launch_attention_stream_f32(h, qkv, out, Nimg, ntok, heads, s);
 }

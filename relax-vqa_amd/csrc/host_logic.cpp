@@ -445,6 +445,34 @@ bool att_stream_plan(int Nimg, int heads, int ntok, int arith, AttStreamPlan* pl
     return true;
 }
 
+bool att_stream_h2_plan(int Nimg, int heads, int ntok, AttStreamH2Plan* plan, std::string& err) {
+    if (Nimg < 1 || heads < 1 || ntok < 1) {
+        err = "attention_stream_h2: Nimg=" + std::to_string(Nimg) + " heads=" + std::to_string(heads) + " ntok=" + std::to_string(ntok);
+        return false;
+    }
+    if (((int64_t)ntok + kAttStreamH2KeyTile) * heads * 64 * 3 * 4 > (int64_t)INT32_MAX) {   // (the last tile's padding rows are addressed too)
+        err = "attention_stream_h2: the plane rows of one image (" + std::to_string(ntok) + " tokens x " + std::to_string(heads) +
+              " heads) pass 2^31 bytes";
+        return false;
+    }
+    AttStreamH2Plan p;
+    p.key_tile = kAttStreamH2KeyTile;
+    p.qblock = kAttStreamH2QBlock;
+    p.qblocks = (ntok + p.qblock - 1) / p.qblock;
+    p.key_tiles = (ntok + p.key_tile - 1) / p.key_tile;
+    p.lds_bytes = kAttStreamH2Lds;
+    p.wgs_per_cu = kAttStreamH2WgsPerCu;
+    const int64_t items = (int64_t)Nimg * heads * p.qblocks;
+    if (items > (int64_t)INT32_MAX) {
+        err = "attention_stream_h2: " + std::to_string(items) + " work items (Nimg=" + std::to_string(Nimg) + " heads=" + std::to_string(heads) +
+              " query blocks=" + std::to_string(p.qblocks) + ")";
+        return false;
+    }
+    p.items = (int)items;
+    *plan = p;
+    return true;
+}
+
 }  // namespace host
 }  // namespace relax
 
@@ -611,6 +639,17 @@ int relax_host_att_stream_plan(int Nimg, int heads, int ntok, int arith, int* ou
     relax::host::AttStreamPlan p;
     std::string e;
     if (!relax::host::att_stream_plan(Nimg, heads, ntok, arith, &p, e)) {
+        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return -1;
+    }
+    std::memcpy(out, &p, sizeof(p));
+    return 0;
+}
+// f16x2 streaming-attention plan: out = key_tile, qblock, qblocks, key_tiles, lds_bytes, wgs_per_cu, items; 0, or -1 and a message
+int relax_host_att_stream_h2_plan(int Nimg, int heads, int ntok, int* out, char* err, int err_len) {
+    relax::host::AttStreamH2Plan p;
+    std::string e;
+    if (!relax::host::att_stream_h2_plan(Nimg, heads, ntok, &p, e)) {
         if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
         return -1;
     }

@@ -199,5 +199,27 @@ struct AttStreamPlan {
 // false and a message for Nimg / heads / ntok < 1, an image whose qkv rows pass 2^31 bytes (buffer-resource range) or more than 2^31 - 1 items
 bool att_stream_plan(int Nimg, int heads, int ntok, int arith, AttStreamPlan* plan, std::string& err);
 
+// attention_stream_h2.hip (f16x2): one workgroup = one (image, head, block of kAttStreamH2QBlock queries); it walks ceil(ntok / 64) key tiles,
+// the K and V rows of a tile as fp16-plane images of 256 bytes per key (attention_h2.hip's), two tiles resident (the next one lands by LDS-DMA
+// under the current one's math)
+constexpr int kAttStreamH2QBlock = 128;    // 4 waves x 32 queries
+constexpr int kAttStreamH2KeyTile = 64;
+constexpr int kAttStreamH2RowBytes = 256;  // one key of one image: 4 chunks of [16 hi][16 lo] fp16
+constexpr int kAttStreamH2Lds = 2 * 2 * kAttStreamH2KeyTile * kAttStreamH2RowBytes;   // (K image + V image) x two buffers = 65536
+constexpr int kAttStreamH2WgsPerCu = 2;    // what the kernel's registers (<= 256 a lane) and 2 x 64 KB of LDS allow
+static_assert(kAttStreamH2Lds * kAttStreamH2WgsPerCu <= kLdsBytesPerCu, "two workgroups of the f16x2 streaming attention share a CU's LDS");
+struct AttStreamH2Plan {
+    int key_tile;      // keys per tile
+    int qblock;        // queries per item
+    int qblocks;       // items per (image, head): query block b covers queries [b * qblock, min(ntok, (b + 1) * qblock))
+    int key_tiles;     // ceil(ntok / key_tile); the last one may hold padding keys (masked)
+    int lds_bytes;
+    int wgs_per_cu;    // resident workgroups per CU the LDS size is chosen for
+    int items;         // Nimg * heads * qblocks = workgroups of the launch
+};
+// false and a message for Nimg / heads / ntok < 1, an image whose plane rows (ntok + one tile, 3 * dim * 4 bytes each) pass 2^31 bytes
+// (buffer-resource range) or more than 2^31 - 1 items
+bool att_stream_h2_plan(int Nimg, int heads, int ntok, AttStreamH2Plan* plan, std::string& err);
+
 }  // namespace host
 }  // namespace relax

@@ -348,6 +348,8 @@ struct GemmOptions {
                            // per-image scales; 0 = the whole network on bf16x6 (the A/B switch of a test)
     int att_h2 = 1;        // "att_h2": under "gemm_precision" 3 the ViT's attention runs on fp16 planes too (attention_h2.hip: the qkv GEMM writes planes,
                            // three products, no conversion passes); 0 = attention_x6 on the fp32 qkv output (three bf16 planes, six products)
+    int att_h2_stream = 1;   // "att_h2_stream": with "att_h2", token counts other than 197 (patch-8 models, other canvases) run attention on fp16 planes too
+                           // (attention_stream_h2.hip: the streaming form of attention_h2); 0 = attention_stream's bf16x6 form on the fp32 qkv output
     int rn_h2_early = 1;   // "rn_h2_early": with "rn_h2", the stem and the 3x3 convolutions of layer1 / layer2 (the MFMA-bound launches in front of layer3) run f16x2 too,
                            // on the four-wave tiles of gemm_x6.hip (conv1 writes its output as fp16 planes with the image's Hoelder scale); 0 = bf16x6 there
     int rn_c1_h2 = 1;      // "rn_c1_h2": with "rn_h2_early", the conv1 (1x1) of the layer1 / layer2 blocks whose input travels as fp32 rows runs f16x2 too: the rows
@@ -457,6 +459,13 @@ int launch_attention_h2_op(relax_handle* h, const float* qkv, float* out, int Ni
 int launch_attention_stream_f32(relax_handle* h, const float* qkv, float* out, int Nimg, int ntok, int heads, hipStream_t s);
 int launch_attention_stream_x6(relax_handle* h, const float* qkv, float* out, void* out_planes, int Nimg, int ntok, int heads, hipStream_t s,
                                float out_h2_scale = 0.f);
+// the same on fp16 planes (attention_stream_h2.hip): attention_h2's arithmetic, operands and output layout at any token count
+int launch_attention_stream_h2(relax_handle* h, const void* qkv_planes, float s_qkv, void* out_planes, float out_scale, int Nimg, int ntok, int heads,
+                               hipStream_t s);
+int launch_attention_stream_h2_op(relax_handle* h, const float* qkv, float* out, int Nimg, int ntok, int heads, hipStream_t s);   // fp32 in / out (relax_op_attention_ex)
+// the operator entries' steps around the kernel (attention_h2.hip): tab = {s, 1 / s, alpha, out_mul} from the measured maximum; planes * inv[0] -> fp32
+int launch_ah_op_scalars(relax_handle* h, const unsigned* amax, float* tab, hipStream_t s);
+int launch_ah_from_h2(relax_handle* h, const void* planes, float* out, int64_t rows, int dim, const float* inv, hipStream_t s);
 // the last block's CLS attention row (vit_attention_map.hip): qkv as fp32 rows [Nimg*ntok][3*dim] or, with planes, fp16 planes of
 // qkv * s_qkv (csrc/h2.h) -> out fp32 [Nimg, heads, ntok] = softmax(q_0 k^T / 8) per (image, head)
 // (ntok <= 4352: 256 threads x 4 keys up to 1024 tokens, x 17 above)

@@ -482,11 +482,12 @@ static int vit_forward(relax_handle* h, const char* what, const uint8_t* frags, 
         for (int i = 0; i < v.depth; ++i) {
             const VitBlockW& b = v.blocks[i];
             RELAX_TRY(launch_layernorm_h2(h, Xx, b.ln1_g, b.ln1_b, Ys, b.s_ln1, rows, dim, kLnEps, s));
-            if (h->gemm.att_h2 && single_tile) {   // (attention_h2 is single-tile only: a patch-8 model takes the other branch whatever "att_h2" says)  q, k, v leave the GEMM as fp16 planes (the same 4 bytes per value) and attention reads them as they are
+            if (h->gemm.att_h2 && (single_tile || h->gemm.att_h2_stream)) {   // q, k, v leave the GEMM as fp16 planes (the same 4 bytes per value) and attention reads them as they are: attention_h2 at 197 tokens, its streaming form ("att_h2_stream") at any other count
                 RELAX_TRY(gemm(Ys, b.qkv, nullptr, nullptr, QKVx, b.s_qkv, rows, 0));
                 if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, true, b.s_qkv, cls_attention, N, NTOK, v.heads, s));
                 if (attention_only && i == last) return RELAX_OK;
-                RELAX_TRY(launch_attention_h2(h, QKVx, b.s_qkv, Ys, b.s_att, N, v.heads, s));
+                if (single_tile) RELAX_TRY(launch_attention_h2(h, QKVx, b.s_qkv, Ys, b.s_att, N, v.heads, s));
+                else RELAX_TRY(launch_attention_stream_h2(h, QKVx, b.s_qkv, Ys, b.s_att, N, NTOK, v.heads, s));
             } else {
                 RELAX_TRY(gemm(Ys, b.qkv, nullptr, QKVx, nullptr, 0.f, rows, 0));
                 if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, false, 0.f, cls_attention, N, NTOK, v.heads, s));

@@ -106,9 +106,9 @@ int launch_vit_cls_attention(relax_handle* h, const void* qkv, bool planes, floa
     const bool wide = ntok > 256 * AM_KPT;   // (197 and 785 tokens keep the instantiation they always ran)
     if (planes) {
         RELAX_REQUIRE(h, s_qkv > 0.f && s_qkv < 3.0e38f, "vit_cls_attention: bad qkv scale");
-        // (fp16 planes come from the single-tile forward alone: 197 tokens)
-        RELAX_REQUIRE(h, !wide, "vit_cls_attention: ntok=%d as fp16 planes (1 .. %d)", ntok, 256 * AM_KPT);
-        hipLaunchKernelGGL((vit_cls_attention<true, AM_KPT>), grid, dim3(256), 0, s, qkv, 1.f / s_qkv, out, heads, ntok);
+        // (fp16 planes come from the f16x2 forward: attention_h2 at 197 tokens, attention_stream_h2 at any other count)
+        if (wide) hipLaunchKernelGGL((vit_cls_attention<true, AM_KPT_WIDE>), grid, dim3(256), 0, s, qkv, 1.f / s_qkv, out, heads, ntok);
+        else hipLaunchKernelGGL((vit_cls_attention<true, AM_KPT>), grid, dim3(256), 0, s, qkv, 1.f / s_qkv, out, heads, ntok);
     } else {
         if (wide) hipLaunchKernelGGL((vit_cls_attention<false, AM_KPT_WIDE>), grid, dim3(256), 0, s, qkv, 1.f, out, heads, ntok);
         else hipLaunchKernelGGL((vit_cls_attention<false, AM_KPT>), grid, dim3(256), 0, s, qkv, 1.f, out, heads, ntok);

@@ -1069,7 +1069,8 @@ class RelaxEngine:
 
     def op_attention_ex(self, qkv, n_img, ntok, heads):
         """The streaming attention kernel (csrc/attention_stream.hip) at any token count: qkv fp32 [n_img*ntok, 3*heads*64] ->
-        fp32 [n_img*ntok, heads*64]; exact fp32 under "gemm_precision" 0 / 1, bf16x6 under 2 / 3 (relax_op_attention_ex)."""
+        fp32 [n_img*ntok, heads*64]; exact fp32 under "gemm_precision" 0 / 1, bf16x6 under 2, and under 3 the f16x2 streaming kernel
+        (csrc/attention_stream_h2.hip) with the options "att_h2" and "att_h2_stream" on, bf16x6 otherwise (relax_op_attention_ex)."""
         if qkv.dim() != 2 or tuple(qkv.shape) != (n_img * ntok, 3 * heads * 64) or qkv.dtype != torch.float32:
             raise ValueError(f"op_attention_ex: qkv must be fp32 [{n_img * ntok}, {3 * heads * 64}], got {qkv.dtype} {tuple(qkv.shape)}")
         qkv = qkv.to(self.device).contiguous()
