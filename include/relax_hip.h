@@ -653,6 +653,60 @@ int relax_png_encode_passes(const uint8_t* images, int64_t images_bytes, const i
                             int64_t out_bytes, uint8_t* scratch, int64_t scratch_bytes, int64_t* lengths, int32_t* status,
                             int passes, relax_stream stream);
 
+/* ---- raw YUV frames ---------------------------------------------------------------------------- */
+/* Headerless 8-bit YUV video -> uint8 HWC BGR: the frames the reference has ffmpeg cut out of raw files
+ * (`-s WxH -pix_fmt yuv420p -framerate r -i file.yuv`, src/video_frames_extract.py:29-49,76-100; the input path of the
+ * live_qualcomm dataset), converted on the device from the file's own bytes.
+ *
+ * Arithmetic, per pixel, integers throughout, >> an arithmetic shift, U' = U - 128, V' = V - 128:
+ *     y = cy*(Y - oy) + 32768
+ *     R = clip8((y + crv*V') >> 16)    G = clip8((y - cgu*U' - cgv*V') >> 16)    B = clip8((y + cbu*U') >> 16)
+ *                                  cy   oy     crv     cbu    cgu    cgv
+ *     BT.601 limited (yuv420p..)  76309  16  104597  132201  25675  53279   what swscale assumes for untagged raw input
+ *     BT.601 full    (yuvj*)      65536   0   91881  116130  22553  46801
+ *     BT.709 limited              76309  16  117489  138438  13975  34925   round(65536 * coefficient), Kr 0.2126, Kb 0.0722,
+ *     BT.709 full                 65536   0  103206  121609  12276  30679   limited: chroma * 255/224, cy = 255/219
+ * Within 1 code value of the float64 conversion on every (Y,U,V) triple.  Chroma is replicated, as swscale's unscaled
+ * yuv->rgb path does it: pixel (r, c) takes chroma sample (r>>1, c>>1) for 4:2:0 and NV12, (r, c>>1) for 4:2:2, (r, c) for
+ * 4:4:4; odd W or H have chroma planes of ceil(W/2) x ceil(H/2), ffmpeg's raw frame layout.  The output is pinned to this
+ * formula, not to any ffmpeg build (swscale's SIMD paths are not bit-exact with its own C path). */
+#define RELAX_YUV_420P 0   /* Y[H][W], U[ch][cw], V[ch][cw]; yuv420p / yuvj420p */
+#define RELAX_YUV_422P 1   /* Y[H][W], U[H][cw], V[H][cw] */
+#define RELAX_YUV_444P 2   /* Y[H][W], U[H][W], V[H][W] */
+#define RELAX_YUV_NV12 3   /* Y, then interleaved UV: what hardware decoders emit */
+#define RELAX_YUV_BT601 0
+#define RELAX_YUV_BT709 1
+#define RELAX_YUV_MAX_DIM 16384          /* W and H: 1..16384 */
+/* Per-item status words of relax_yuv_to_bgr. */
+#define RELAX_YUV_OK 0
+#define RELAX_YUV_OUT_OF_RANGE 1         /* the item's frame leaves src or its slot leaves out: nothing of it was written */
+
+/* Bytes of one frame; host arithmetic.  < 0: layout, H or W refused. */
+int64_t relax_yuv_frame_bytes(int layout, int H, int W);
+
+/* The table above, from the library: out[6] = cy, oy, crv, cbu, cgu, cgv (HOST memory; host arithmetic).  RELAX_ERR_INVALID for
+ * another matrix or range.  The Python layer reads its constants here, so host and device share one table. */
+int relax_yuv_coefficients(int matrix, int full_range, int32_t* out);
+
+/*   src     DEVICE bytes [src_bytes]: whole frames, anywhere in it (frame k of a raw file starts at k * frame_bytes)
+ *   items   DEVICE int64 [N][2]: source offset of the frame, output offset
+ *   out     DEVICE uint8 [out_bytes]: item n is written as [H][W][3] BGR at out + output offset - any slot of a clip tensor
+ *           [T,2,H,W,3]; a sampled frame and its successor are two items, so one launch fills a clip
+ *   status  DEVICE int32 [N]: RELAX_YUV_* per item, always written
+ * Every read of item n stays inside [offset, offset + frame_bytes) and every write inside its H*W*3 slot; an item whose
+ * ranges leave src or out writes nothing and gets RELAX_YUV_OUT_OF_RANGE, the other items of the call are unaffected.
+ * Each lane converts 16 pixels of the two rows that share a chroma row (one row for 4:2:2 and 4:4:4).  An item moves 16 bytes
+ * per access (Y 16, U and V 8 each - 16 for 4:4:4 and for NV12's interleaved row -, output 3 x 16) only when W is a multiple
+ * of 16 and both src + source offset and out + output offset are 16-byte-aligned addresses; any one of them off puts THAT
+ * item on the much slower bytewise path (frame_bytes of a raw file is often no multiple of 16: copy the frames to aligned
+ * slots, as sampling.GpuYuvLoader does).  Plain vector loads and stores, no inline assembly (csrc/yuv.hip; layout and
+ * bounds arithmetic in csrc/yuv_core.h, which the CPU tests run on the host).
+ * No handle and no library state, as relax_png_decode: loader threads call it at the same time on their own streams.
+ * Returns RELAX_ERR_INVALID, with the offending value in relax_last_error(NULL), for any other layout or matrix, full_range
+ * outside 0..1, W or H outside 1..RELAX_YUV_MAX_DIM, or bad buffers; RELAX_ERR_HIP if the launch fails. */
+int relax_yuv_to_bgr(const uint8_t* src, int64_t src_bytes, const int64_t* items, int N, int layout, int H, int W, int matrix,
+                     int full_range, uint8_t* out, int64_t out_bytes, int32_t* status, relax_stream stream);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* While enabled, every launch of the contraction kernel (GEMM / implicit-GEMM conv) and of the patch-score
  * kernel is bracketed by HIP events on the caller's stream.  relax_profile_read synchronises those events and

@@ -102,6 +102,9 @@ PROTOTYPES = {
     "relax_png_encode_bound": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "relax_png_encode": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, c_vp, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, c_vp]),
     "relax_png_encode_passes": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, c_vp, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, C.c_int, c_vp]),
+    "relax_yuv_frame_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "relax_yuv_coefficients": (C.c_int, [C.c_int, C.c_int, c_i32p]),
+    "relax_yuv_to_bgr": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, C.c_int64, c_vp, c_vp]),
     "relax_profile_enable": (C.c_int, [c_vp, C.c_int]),
     "relax_profile_read": (C.c_int, [c_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_int64)]),

@@ -114,6 +114,44 @@ class RelaxEngine:
         from . import pngencode
         pngencode.encoder_for(self.device).write(paths, images, filter=filter, stats=stats)
 
+    def yuv_to_bgr(self, planes_u8_device, H, W, pixfmt, matrix="bt601", out=None):
+        """Raw 8-bit YUV frames already on the device -> uint8 BGR [N,H,W,3] (relax_yuv_to_bgr; the arithmetic and the chroma
+        replication are stated in include/relax_hip.h and as numpy in sampling.yuv_frame_bgr).  planes_u8_device: uint8, N whole
+        frames back to back (any shape with N * frame_bytes elements; a host array is uploaded first).  pixfmt: yuv420p, yuvj420p,
+        yuv422p, yuvj422p, yuv444p, yuvj444p or nv12 (sampling.yuv_layout; others raise).  matrix: 'bt601' (what ffmpeg assumes
+        for untagged raw input) or 'bt709'.  out: a uint8 [N,H,W,3] view to fill (strided slots with packed rows allowed, e.g.
+        clip.view(-1,H,W,3)).  Runs on the current stream.  The kernel moves 16 bytes per access when W is a multiple of 16 and
+        frame and slot start at 16-byte-aligned addresses, else bytewise, per frame."""
+        from . import sampling
+        layout, full_range = sampling.yuv_layout(pixfmt)
+        if matrix not in sampling.YUV_MATRICES:
+            raise ValueError(f"matrix {matrix!r} is not one of {', '.join(sampling.YUV_MATRICES)}")
+        H, W = int(H), int(W)
+        fb = sampling.yuv_frame_bytes(layout, H, W)
+        src = self._dev_u8(planes_u8_device).view(-1)
+        if src.numel() % fb:
+            raise ValueError(f"{src.numel()} bytes is not a whole number of {W}x{H} {pixfmt} frames of {fb} bytes")
+        N = src.numel() // fb
+        slot = H * W * 3
+        if out is None:
+            out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=self.device)
+        else:
+            if out.dtype != torch.uint8 or out.device != self.device or tuple(out.shape) != (N, H, W, 3):
+                raise ValueError(f"out must be uint8 [{N},{H},{W},3] on {self.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+            if out.stride()[1:] != (W * 3, 3, 1) or (N > 1 and out.stride(0) < slot):
+                raise ValueError(f"out must hold each frame as contiguous rows in its own slot, strides {out.stride()}")
+        if N == 0:
+            return out
+        stride = out.stride(0) if N > 1 else slot
+        items = torch.stack([torch.arange(N, dtype=torch.int64) * fb, torch.arange(N, dtype=torch.int64) * stride], dim=1)
+        items = items.contiguous().to(self.device)
+        status = torch.empty(N, dtype=torch.int32, device=self.device)
+        rc = self.lib.relax_yuv_to_bgr(_ptr(src), src.numel(), _ptr(items), N, layout, H, W, sampling.YUV_MATRICES[matrix],
+                                       int(full_range), _ptr(out), (N - 1) * stride + slot, _ptr(status), _stream())
+        if rc != 0:
+            raise RuntimeError(f"relax_yuv_to_bgr failed ({rc}): {self.lib.relax_last_error(None).decode()}")
+        return out
+
     # ---- weights ------------------------------------------------------------------------------
     def _marshal_state_dict(self, sd):
         names, arrays = [], []

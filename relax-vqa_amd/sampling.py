@@ -7,6 +7,9 @@ decodes the video (or already holds the frames) and these helpers reproduce whic
                           index with zip truncation src/main_fragment_layerstack.py:283-293
   frame_pair_paths / load_clip_from_frames   src/main_fragment_layerstack.py:283-296: the sampled frames the reference's ffmpeg step left on disk
                           (`{video}_{n}.png`, `{video}_{n}_next.png`), paired by sorted index, read as cv2.imread reads them (uint8 BGR)
+  yuv_layout / yuv_frame_count / yuv_frame_bgr / load_clip_from_yuv / GpuYuvLoader   src/video_frames_extract.py:29-49,76-100: the frames
+                          ffmpeg cuts out of headerless raw video (`-s WxH -pix_fmt yuv420p -framerate r -i file.yuv`, the live_qualcomm
+                          input path), converted from the file's own bytes by the integer formula of include/relax_hip.h
   feature_file_name       src/main_fragment_layerstack.py:67-68,349-354  video_{i+1}_{network}_feature_map_original.npy
   features_matrix / save_mat  src/data_processing/extract_npy2mat.py:117-130, 79-84 (np.mean over frames; .mat key = dataset)
 """
@@ -127,6 +130,291 @@ class GpuFrameLoader:
         clip.record_stream(self.consumer)
         with self._lock:
             self.fallbacks += stats.get("fallback", 0)
+        return clip
+
+
+# ---- raw YUV video (src/video_frames_extract.py:29-49,76-100) ---------------------------------------------------------------
+YUV_420P, YUV_422P, YUV_444P, YUV_NV12 = 0, 1, 2, 3      # RELAX_YUV_* of include/relax_hip.h
+YUV_MAX_DIM = 16384
+YUV_MATRICES = {"bt601": 0, "bt709": 1}
+_yuv_coef_cache = {}
+
+
+def yuv_coefficients(matrix="bt601", full_range=False):
+    """(cy, oy, crv, cbu, cgu, cgv) of include/relax_hip.h's formula, read from the library (relax_yuv_coefficients: the one table
+    in csrc/yuv_core.h that the kernel uses), so host and device cannot drift apart."""
+    key = (matrix, bool(full_range))
+    if key not in _yuv_coef_cache:
+        import ctypes as C
+
+        from . import _lib
+        if matrix not in YUV_MATRICES:
+            raise ValueError(f"matrix {matrix!r} is not one of {', '.join(YUV_MATRICES)}")
+        out = (C.c_int32 * 6)()
+        if _lib.load().relax_yuv_coefficients(YUV_MATRICES[matrix], int(key[1]), out) != 0:
+            raise RuntimeError(f"relax_yuv_coefficients refused {key}")
+        _yuv_coef_cache[key] = tuple(out)
+    return _yuv_coef_cache[key]
+
+
+_YUV_PIXFMTS = {
+    "yuv420p": (YUV_420P, False), "yuvj420p": (YUV_420P, True),
+    "yuv422p": (YUV_422P, False), "yuvj422p": (YUV_422P, True),
+    "yuv444p": (YUV_444P, False), "yuvj444p": (YUV_444P, True),
+    "nv12": (YUV_NV12, False),
+}
+
+
+def yuv_layout(pixfmt):
+    """The reference's metadata `pixfmt` string -> (layout, full_range).  8-bit planar 4:2:0 / 4:2:2 / 4:4:4 (yuvj*: full range) and
+    nv12; everything else (10-bit and deeper, packed 4:2:2, palette, RGB, ...) raises a ValueError naming it."""
+    try:
+        return _YUV_PIXFMTS[str(pixfmt).strip()]
+    except KeyError:
+        raise ValueError(f"pixfmt {pixfmt!r} is not supported: raw input is read as one of {', '.join(_YUV_PIXFMTS)}") from None
+
+
+def yuv_plan(layout, H, W):
+    """The frame layout (csrc/yuv_core.h's Plan, restated): dict of cw, ch (chroma plane size: halves rounded up), u_off, v_off,
+    c_stride (bytes between chroma rows), c_step (bytes between chroma samples), frame_bytes."""
+    H, W = int(H), int(W)
+    if layout not in (YUV_420P, YUV_422P, YUV_444P, YUV_NV12):
+        raise ValueError(f"layout {layout!r} is not one of 0..3")
+    if not (1 <= H <= YUV_MAX_DIM and 1 <= W <= YUV_MAX_DIM):
+        raise ValueError(f"frame size {W}x{H} outside 1..{YUV_MAX_DIM}")
+    cw = W if layout == YUV_444P else (W + 1) // 2
+    ch = (H + 1) // 2 if layout in (YUV_420P, YUV_NV12) else H
+    nv12 = layout == YUV_NV12
+    return {"cw": cw, "ch": ch, "u_off": H * W, "v_off": H * W + (1 if nv12 else ch * cw), "c_stride": cw * (2 if nv12 else 1),
+            "c_step": 2 if nv12 else 1, "frame_bytes": H * W + 2 * ch * cw}
+
+
+def yuv_frame_bytes(layout, H, W):
+    return yuv_plan(layout, H, W)["frame_bytes"]
+
+
+def yuv_frame_count(path, W, H, pixfmt):
+    """Frames in a headerless raw file: size // frame bytes; a size that is no whole number of frames raises."""
+    fb = yuv_frame_bytes(yuv_layout(pixfmt)[0], H, W)
+    size = os.path.getsize(path)
+    if size % fb:
+        raise ValueError(f"{path}: {size} bytes is not a whole number of {W}x{H} {pixfmt} frames of {fb} bytes "
+                         f"({size // fb} frames and {size % fb} bytes over)")
+    return size // fb
+
+
+def yuv_planes(frame, layout, H, W):
+    """One frame's bytes (uint8 [frame_bytes]) -> (Y [H,W], U [ch,cw], V [ch,cw]) views."""
+    p = yuv_plan(layout, H, W)
+    frame = np.asarray(frame, np.uint8).reshape(-1)
+    if frame.size != p["frame_bytes"]:
+        raise ValueError(f"a {W}x{H} frame of layout {layout} has {p['frame_bytes']} bytes, got {frame.size}")
+    y = frame[:H * W].reshape(H, W)
+    if layout == YUV_NV12:
+        uv = frame[H * W:].reshape(p["ch"], p["cw"], 2)
+        return y, uv[..., 0], uv[..., 1]
+    n = p["ch"] * p["cw"]
+    return y, frame[H * W:H * W + n].reshape(p["ch"], p["cw"]), frame[H * W + n:].reshape(p["ch"], p["cw"])
+
+
+def yuv_frame_bgr(y, u, v, matrix="bt601", full_range=False, out=None):
+    """The numpy statement of relax_yuv_to_bgr's arithmetic (include/relax_hip.h): Y uint8 [H,W], U and V uint8 [ch,cw] with
+    ch in (H, ceil(H/2)) and cw in (W, ceil(W/2)) - chroma is replicated, pixel (r, c) takes sample (r >> 1, c >> 1) where the
+    plane is halved - -> uint8 [H,W,3] BGR.  int32 throughout; >> is numpy's arithmetic shift."""
+    cy, oy, crv, cbu, cgu, cgv = yuv_coefficients(matrix, full_range)
+    y = np.asarray(y)
+    H, W = y.shape
+
+    def full(c):
+        c = np.asarray(c)
+        if c.shape[0] != H:
+            if c.shape[0] != (H + 1) // 2:
+                raise ValueError(f"chroma plane of {c.shape[0]} rows under {H} luma rows")
+            c = np.repeat(c, 2, axis=0)[:H]
+        if c.shape[1] != W:
+            if c.shape[1] != (W + 1) // 2:
+                raise ValueError(f"chroma plane of {c.shape[1]} columns under {W} luma columns")
+            c = np.repeat(c, 2, axis=1)[:, :W]
+        return c.astype(np.int32) - 128
+
+    yy = cy * (y.astype(np.int32) - oy) + (1 << 15)
+    uu, vv = full(u), full(v)
+    out = np.empty((H, W, 3), np.uint8) if out is None else out
+    out[..., 2] = np.clip((yy + crv * vv) >> 16, 0, 255)
+    out[..., 1] = np.clip((yy - cgu * uu - cgv * vv) >> 16, 0, 255)
+    out[..., 0] = np.clip((yy + cbu * uu) >> 16, 0, 255)
+    return out
+
+
+def _yuv_pairs(path, W, H, pixfmt, framerate):
+    n = yuv_frame_count(path, W, H, pixfmt)
+    _, _, pairs = sampled_frame_indices(n, frame_interval(framerate))
+    if not pairs:
+        raise FileNotFoundError(f"{path}: {n} frames at framerate {framerate} hold no (frame, next frame) pair")
+    return pairs
+
+
+def load_clip_from_yuv(path, W, H, pixfmt, framerate, alloc=None, matrix="bt601"):
+    """A raw YUV video -> uint8 [T,2,H,W,3] BGR: pair_frames() of the converted video, reading only the sampled frames and their
+    successors (the PNGs the reference's two ffmpeg passes leave behind, src/video_frames_extract.py:76-100, without the PNGs).
+    The host twin of GpuYuvLoader; alloc as in load_clip_from_frames.  Raises FileNotFoundError if the file holds no pair."""
+    layout, full_range = yuv_layout(pixfmt)
+    pairs = _yuv_pairs(path, W, H, pixfmt, framerate)
+    fb = yuv_frame_bytes(layout, H, W)
+    shape = (len(pairs), 2, int(H), int(W), 3)
+    out = alloc(shape) if alloc is not None else np.empty(shape, dtype=np.uint8)
+    buf = np.empty(2 * fb, np.uint8)
+    with open(path, "rb", buffering=0) as f:
+        for t, (a, b) in enumerate(pairs):
+            span = b - a + 1                                   # 2: the successor, one read; 1: interval 1 pairs a frame with itself
+            f.seek(a * fb)
+            if span not in (1, 2) or f.readinto(memoryview(buf[:span * fb])) != span * fb:
+                raise OSError(f"{path}: short read at frame {a}")
+            for j, n in enumerate((a, b)):
+                yuv_frame_bgr(*yuv_planes(buf[(n - a) * fb:(n - a + 1) * fb], layout, H, W), matrix=matrix, full_range=full_range,
+                              out=out[t, j])
+    return out
+
+
+def load_frames_from_yuv(path, W, H, pixfmt, indices, matrix="bt601"):
+    """Frames `indices` of a raw YUV video -> uint8 [len(indices),H,W,3] BGR (host)."""
+    layout, full_range = yuv_layout(pixfmt)
+    n = yuv_frame_count(path, W, H, pixfmt)
+    fb = yuv_frame_bytes(layout, H, W)
+    out = np.empty((len(indices), int(H), int(W), 3), np.uint8)
+    buf = np.empty(fb, np.uint8)
+    with open(path, "rb", buffering=0) as f:
+        for k, i in enumerate(indices):
+            if not 0 <= i < n:
+                raise IndexError(f"{path}: frame {i} of {n}")
+            f.seek(i * fb)
+            if f.readinto(memoryview(buf)) != fb:
+                raise OSError(f"{path}: short read at frame {i}")
+            yuv_frame_bgr(*yuv_planes(buf, layout, H, W), matrix=matrix, full_range=full_range, out=out[k])
+    return out
+
+
+def read_yuv_frames(path, frames, frame_bytes, slot_bytes, host):
+    """Frames `frames` (ascending indices) of a raw file -> host[k * slot_bytes : k * slot_bytes + frame_bytes] for the k-th of
+    them (host: a writable uint8 array, the pinned staging buffer).  Each run of adjacent frames is one os.preadv with one
+    buffer per frame, so the slots may be padded to an alignment the file's frames do not have.  -> number of reads."""
+    reads = 0
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        k = 0
+        while k < len(frames):
+            e = k + 1
+            while e < len(frames) and frames[e] == frames[e - 1] + 1 and e - k < 512:      # (IOV_MAX is 1024)
+                e += 1
+            views = [memoryview(host[j * slot_bytes:j * slot_bytes + frame_bytes]) for j in range(k, e)]
+            want, at = (e - k) * frame_bytes, frames[k] * frame_bytes
+            got = os.preadv(fd, views, at)
+            reads += 1
+            while 0 < got < want:                                   # a short read (signals, network file systems): go on behind it
+                rest = [v[max(0, got - j * frame_bytes):] for j, v in enumerate(views) if got < (j + 1) * frame_bytes]
+                more = os.preadv(fd, rest, at + got)
+                if more <= 0:
+                    break
+                got += more
+            if got != want:
+                raise OSError(f"{path}: read {got} of {want} bytes at frame {frames[k]}")
+            k = e
+    finally:
+        os.close(fd)
+    return reads
+
+
+class _YuvThreadState:
+    """One loader thread's stream and pinned staging buffer."""
+
+    def __init__(self, device):
+        import torch
+        self.stream = torch.cuda.Stream(device)
+        self.pinned = None
+
+    def staging(self, n):
+        import torch
+        if self.pinned is None or self.pinned.numel() < n:
+            self.pinned = torch.empty(max(n, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
+        return self.pinned
+
+
+class GpuYuvLoader:
+    """load_clip_from_yuv on the GPU: clip i -> the uint8 BGR device tensor [T,2,H,W,3] that load_clip_from_yuv(paths[i],
+    widths[i], heights[i], pixfmts[i], framerates[i]) returns on the host, byte for byte.  Only the sampled frames and their
+    successors are read: each run of adjacent frames is one os.preadv into the calling thread's pinned buffer (every frame at a
+    16-byte-aligned slot, so the kernel's 16-byte path applies whenever W is a multiple of 16), followed by one host-to-device
+    copy and one relax_yuv_to_bgr launch on that thread's own stream; loader threads work at the same time.  Pass it as the
+    `clips` of dataset.extract_dataset_clips.  The clip is complete when __call__ returns and is recorded on `consumer_stream`
+    (default: the current stream of `device` when the loader is made).  A file with no pair raises FileNotFoundError."""
+
+    def __init__(self, paths, widths, heights, pixfmts, framerates, device=None, consumer_stream=None, matrix="bt601"):
+        import torch
+
+        from . import _lib
+        self.paths = list(paths)
+        n = len(self.paths)
+
+        def per_clip(v, what):
+            v = [v] * n if np.isscalar(v) or isinstance(v, str) else list(v)
+            if len(v) != n:
+                raise ValueError(f"{len(v)} {what} for {n} paths")
+            return v
+        self.widths, self.heights = per_clip(widths, "widths"), per_clip(heights, "heights")
+        self.pixfmts, self.framerates = per_clip(pixfmts, "pixfmts"), per_clip(framerates, "framerates")
+        if matrix not in YUV_MATRICES:
+            raise ValueError(f"matrix {matrix!r} is not one of {', '.join(YUV_MATRICES)}")
+        self.matrix = matrix
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.consumer = consumer_stream if consumer_stream is not None else torch.cuda.current_stream(self.device)
+        self.lib = _lib.load()
+        self._tls = threading.local()
+
+    def __len__(self):
+        return len(self.paths)
+
+    def _state(self):
+        st = getattr(self._tls, "state", None)
+        if st is None:
+            st = self._tls.state = _YuvThreadState(self.device)
+        return st
+
+    def __call__(self, i):
+        import ctypes as C
+
+        import torch
+        path, W, H = self.paths[i], int(self.widths[i]), int(self.heights[i])
+        layout, full_range = yuv_layout(self.pixfmts[i])
+        pairs = _yuv_pairs(path, W, H, self.pixfmts[i], self.framerates[i])
+        fb = yuv_frame_bytes(layout, H, W)
+        slot_bytes = (fb + 15) // 16 * 16
+        frames = sorted({n for ab in pairs for n in ab})
+        slot = {n: k for k, n in enumerate(frames)}
+        items_at = len(frames) * slot_bytes
+        total = items_at + 16 * 2 * len(pairs)
+        st = self._state()
+        pinned = st.staging(total)
+        host = pinned.numpy()
+        read_yuv_frames(path, frames, fb, slot_bytes, host)
+        items = np.empty((len(pairs) * 2, 2), np.int64)
+        slot_out = H * W * 3
+        for t, (a, b) in enumerate(pairs):
+            items[2 * t] = (slot[a] * slot_bytes, (2 * t) * slot_out)
+            items[2 * t + 1] = (slot[b] * slot_bytes, (2 * t + 1) * slot_out)
+        host[items_at:total] = items.view(np.uint8).reshape(-1)
+        with torch.cuda.stream(st.stream):
+            clip = torch.empty((len(pairs), 2, H, W, 3), dtype=torch.uint8, device=self.device)
+            dev = pinned[:total].to(self.device, non_blocking=True)
+            status = torch.empty(len(pairs) * 2, dtype=torch.int32, device=self.device)
+            rc = self.lib.relax_yuv_to_bgr(C.c_void_p(dev.data_ptr()), items_at, C.c_void_p(dev.data_ptr() + items_at), len(pairs) * 2,
+                                           layout, H, W, YUV_MATRICES[self.matrix], int(full_range), C.c_void_p(clip.data_ptr()),
+                                           clip.numel(), C.c_void_p(status.data_ptr()), C.c_void_p(st.stream.cuda_stream))
+            if rc != 0:
+                raise RuntimeError(f"relax_yuv_to_bgr failed ({rc}): {self.lib.relax_last_error(None).decode()}")
+            bad = status.cpu()                                      # waits for the conversion: the pinned buffer is free again
+        if bool(bad.any()):
+            raise RuntimeError(f"{path}: relax_yuv_to_bgr refused items {bad.nonzero().view(-1).tolist()} (out of range)")
+        clip.record_stream(self.consumer)
         return clip
 
 
