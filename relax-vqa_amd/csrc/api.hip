@@ -47,6 +47,13 @@ int ensure_buf(relax_handle* h, DevBuf& b, size_t bytes) {
     return poison_buf(h, b);
 }
 
+int allow_dynamic_lds(relax_handle* h, std::initializer_list<const void*> kernels, size_t bytes, std::atomic<bool>* done) {
+    if (done[h->device].load(std::memory_order_acquire)) return RELAX_OK;
+    for (const void* kernel : kernels) RELAX_HIP_CHECK(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done[h->device].store(true, std::memory_order_release);
+    return RELAX_OK;
+}
+
 void* DeviceOwner::keep(relax_handle* h, size_t bytes, const char* what) {
     void* p = nullptr;
     const hipError_t e = hipMalloc(&p, bytes);
@@ -214,13 +221,7 @@ int relax_create(int device, relax_handle** out) {
     }
     relax_handle* h = new relax_handle();
     h->device = device;
-    if (const char* e = getenv("RELAX_GEMM_SPLIT")) h->gemm.split_k = atoi(e);
-    if (const char* e = getenv("RELAX_GEMM_PRECISION")) h->gemm.precision = atoi(e) >= 0 && atoi(e) <= 3 ? atoi(e) : 0;
-    if (const char* e = getenv("RELAX_H2_FORM")) h->gemm.h2_form = atoi(e) >= 0 && atoi(e) <= 2 ? atoi(e) : 1;
-    if (const char* e = getenv("RELAX_GEMM_VARIANT")) h->gemm.variant = atoi(e);
-    if (const char* e = getenv("RELAX_GEMM_VARIANT_N64")) h->gemm.variant_n64 = atoi(e);
-    if (const char* e = getenv("RELAX_GEMM_GROUP_M")) h->gemm.group_m = atoi(e) > 0 ? atoi(e) : 1;
-    if (const char* e = getenv("RELAX_DEBUG_POISON")) h->gemm.debug_poison = atoi(e) != 0;
+    host::options_from_env(h->gemm, getenv);
     *out = h;
     return RELAX_OK;
 }
@@ -275,44 +276,8 @@ int relax_reserve(relax_handle* h, int max_images) {
 
 int relax_set_option(relax_handle* h, const char* key, int value) {
     if (!h) return RELAX_ERR_INVALID;
-    RELAX_REQUIRE(h, key, "relax_set_option: key is NULL");
-    const std::string k(key);
-    if (k == "gemm_split_k") h->gemm.split_k = value;
-    else if (k == "gemm_precision") {
-        RELAX_REQUIRE(h, value >= 0 && value <= 3, "relax_set_option: gemm_precision must be 0 (fp32), 1 (bf16x3), 2 (bf16x6) or 3 (f16x2)");
-        h->gemm.precision = value;
-    }
-    else if (k == "gemm_variant") h->gemm.variant = value;
-    else if (k == "gemm_variant_n64") h->gemm.variant_n64 = value;
-    else if (k == "gemm_group_m") h->gemm.group_m = value > 0 ? value : 1;
-    else if (k == "flow_max_pairs") h->gemm.flow_max_pairs = value > 0 ? value : 0;
-    else if (k == "flow_fused") h->gemm.flow_fused = value != 0;
-    else if (k == "flow_seg_rows") h->gemm.flow_seg_rows = value > 0 ? value : 0;
-    else if (k == "flow_pyramid_fused") h->gemm.flow_pyramid_fused = value != 0;
-    else if (k == "x6_fp32_rows") h->gemm.fp32_rows = value != 0;
-    else if (k == "rn_h2") h->gemm.rn_h2 = value != 0;
-    else if (k == "rn_h2_early") h->gemm.rn_h2_early = value != 0;
-    else if (k == "rn_fuse") h->gemm.rn_fuse = value != 0;
-    else if (k == "rn_c1_h2") h->gemm.rn_c1_h2 = value != 0;
-    else if (k == "b2b_rows") {
-        RELAX_REQUIRE(h, value == 128 || value == 256, "relax_set_option: b2b_rows must be 128 or 256");
-        h->gemm.b2b_rows = value;
-    }
-    else if (k == "att_h2") h->gemm.att_h2 = value != 0;
-    else if (k == "att_h2_stream") h->gemm.att_h2_stream = value != 0;
-    else if (k == "h2_form") {
-        RELAX_REQUIRE(h, value >= 0 && value <= 2, "relax_set_option: h2_form must be 0, 1 or 2");
-        h->gemm.h2_form = value;
-    }
-    else if (k == "h2_stages") {
-        RELAX_REQUIRE(h, value == 3 || value == 4, "relax_set_option: h2_stages must be 3 or 4");
-        h->gemm.h2_stages = value;
-    }
-    else if (k == "debug_poison") h->gemm.debug_poison = value != 0;
-    else {
-        set_error(h, "relax_set_option: unknown option '%s'", key);
-        return RELAX_ERR_INVALID;
-    }
+    std::string err;
+    RELAX_REQUIRE(h, host::option_set(h->gemm, key, value, err), "%s", err.c_str());
     return RELAX_OK;
 }
 
@@ -327,35 +292,14 @@ int relax_copy_bytes(relax_handle* h, const void* src, void* dst, int64_t n_byte
 
 int relax_get_option(relax_handle* h, const char* key, int* value) {
     if (!h) return RELAX_ERR_INVALID;
-    RELAX_REQUIRE(h, key && value, "relax_get_option: NULL argument");
-    const std::string k(key);
-    if (k == "gemm_split_k") *value = h->gemm.split_k;
-    else if (k == "gemm_precision") *value = h->gemm.precision;
-    else if (k == "gemm_variant") *value = h->gemm.variant;
-    else if (k == "gemm_variant_n64") *value = h->gemm.variant_n64;
-    else if (k == "gemm_group_m") *value = h->gemm.group_m;
-    else if (k == "flow_max_pairs") *value = h->gemm.flow_max_pairs;
-    else if (k == "flow_fused") *value = h->gemm.flow_fused;
-    else if (k == "flow_seg_rows") *value = h->gemm.flow_seg_rows;
-    else if (k == "flow_pyramid_fused") *value = h->gemm.flow_pyramid_fused;
-    else if (k == "x6_fp32_rows") *value = h->gemm.fp32_rows;
-    else if (k == "rn_h2") *value = h->gemm.rn_h2;
-    else if (k == "rn_h2_early") *value = h->gemm.rn_h2_early;
-    else if (k == "rn_fuse") *value = h->gemm.rn_fuse;
-    else if (k == "rn_c1_h2") *value = h->gemm.rn_c1_h2;
-    else if (k == "b2b_rows") *value = h->gemm.b2b_rows;
-    else if (k == "att_h2") *value = h->gemm.att_h2;
-    else if (k == "att_h2_stream") *value = h->gemm.att_h2_stream;
-    else if (k == "h2_stages") *value = h->gemm.h2_stages;
-    else if (k == "h2_form") *value = h->gemm.h2_form;
-    else if (k == "debug_poison") *value = h->gemm.debug_poison;
     // read-only counters (leak checks of a long pass): HIP events this handle owns (pooled + in spans), bytes of its workspaces in MiB
-    else if (k == "profile_events") *value = (int)(h->prof.pool.size() + 2 * h->prof.spans.size());
+    const std::string k(key && value ? key : "");
+    if (k == "profile_events") *value = (int)(h->prof.pool.size() + 2 * h->prof.spans.size());
     else if (k == "workspace_mib")
         *value = (int)((h->arena.bytes + h->scratch.bytes + h->splitk_ws.bytes + h->sp3_ws.bytes + h->resize_ws.bytes + h->flow_ws.bytes + h->head_ws.bytes) >> 20);
     else {
-        set_error(h, "relax_get_option: unknown option '%s'", key);
-        return RELAX_ERR_INVALID;
+        std::string err;
+        RELAX_REQUIRE(h, host::option_get(h->gemm, key, value, err), "%s", err.c_str());
     }
     return RELAX_OK;
 }

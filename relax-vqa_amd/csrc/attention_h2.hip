@@ -274,25 +274,26 @@ __global__ __launch_bounds__(AH_THREADS) void attention_h2(const char* __restric
 #endif
 }
 
+// one persistent workgroup (7 waves) per CU; the scalars as arguments, or - tab != null - read from tab[0 .. 1] = {alpha, out_mul} on the device
+static int launch_ah_kernel(relax_handle* h, const char* qkv_planes, char* out_planes, int Nimg, int heads, float alpha, float out_mul, const float* tab,
+                            hipStream_t s) {
+    static std::atomic<bool> lds_allowed[kMaxDevices];
+    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&attention_h2)}, AH_LDS, lds_allowed));
+    const int total = Nimg * heads;
+    hipLaunchKernelGGL(attention_h2, dim3(total < 256 ? total : 256), dim3(AH_THREADS), AH_LDS, s, qkv_planes, out_planes, heads, total, alpha, out_mul, tab);
+    RELAX_HIP_CHECK(h, hipGetLastError());
+    return RELAX_OK;
+}
+
 // qkv_planes: fp16 planes [Nimg * 197][3 * dim * 4 B] of qkv * s_qkv; out_planes: [Nimg * 197][dim * 4 B] of the attention output * out_scale
 int launch_attention_h2(relax_handle* h, const void* qkv_planes, float s_qkv, void* out_planes, float out_scale, int Nimg, int heads, hipStream_t s) {
     RELAX_REQUIRE(h, Nimg > 0 && heads > 0 && qkv_planes && out_planes, "attention_h2: Nimg=%d heads=%d", Nimg, heads);
     RELAX_REQUIRE(h, s_qkv > 0.f && s_qkv < 3.0e38f && out_scale > 0.f && out_scale < 3.0e38f, "attention_h2: bad scales");
     RELAX_REQUIRE(h, (int64_t)AH_NTOK * 3 * heads * 64 * 4 < 0x7ffffff0, "attention_h2: too many heads");
-    static bool attr_set[kMaxDevices] = {};
-    if (!attr_set[h->device]) {
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_h2), hipFuncAttributeMaxDynamicSharedMemorySize, AH_LDS));
-        attr_set[h->device] = true;
-    }
-    const int total = Nimg * heads;
-    const int grid = total < 256 ? total : 256;   // one persistent workgroup (7 waves) per CU
     // log2(e) / 8 and the two operand scales folded into the logits; the probabilities' 2^14, V's scale and the output scale into 1 / sum
     const float alpha = (float)(0.125 * 1.44269504088896341 / ((double)s_qkv * (double)s_qkv));
     const float out_mul = (float)((double)out_scale / ((double)s_qkv * 16384.0));
-    hipLaunchKernelGGL(attention_h2, dim3(grid), dim3(AH_THREADS), AH_LDS, s, static_cast<const char*>(qkv_planes), static_cast<char*>(out_planes),
-                       heads, total, alpha, out_mul, static_cast<const float*>(nullptr));
-    RELAX_HIP_CHECK(h, hipGetLastError());
-    return RELAX_OK;
+    return launch_ah_kernel(h, static_cast<const char*>(qkv_planes), static_cast<char*>(out_planes), Nimg, heads, alpha, out_mul, nullptr, s);
 }
 
 // ---- operator-level entry (relax_op_attention under "f16x2"): fp32 qkv in, fp32 out.  The planes are made here with ONE scale for the whole
@@ -327,25 +328,22 @@ __global__ __launch_bounds__(256) void ah_from_h2(const char* __restrict__ y, fl
     *reinterpret_cast<ah_f32x4*>(dst + 4) = (ah_f32x4){o[4], o[5], o[6], o[7]};
 }
 
-// the two steps around the kernel, for the streaming operator entry too (attention_stream_h2.hip)
-int launch_ah_op_scalars(relax_handle* h, const unsigned* amax, float* tab, hipStream_t s) {
+static int launch_ah_op_scalars(relax_handle* h, const unsigned* amax, float* tab, hipStream_t s) {
     hipLaunchKernelGGL(ah_op_scalars, dim3(1), dim3(1), 0, s, amax, tab);
     RELAX_HIP_CHECK(h, hipGetLastError());
     return RELAX_OK;
 }
-int launch_ah_from_h2(relax_handle* h, const void* planes, float* out, int64_t rows, int dim, const float* inv, hipStream_t s) {
+static int launch_ah_from_h2(relax_handle* h, const void* planes, float* out, int64_t rows, int dim, const float* inv, hipStream_t s) {
     const int64_t total8 = rows * (dim / 8);
     hipLaunchKernelGGL(ah_from_h2, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, s, static_cast<const char*>(planes), out, dim, total8, inv);
     RELAX_HIP_CHECK(h, hipGetLastError());
     return RELAX_OK;
 }
 
-// (operator level, tests: ONE scale from the maximum of the whole qkv tensor of the call - not batch-invariant, unlike the engine's ViT path,
-// which hands the kernel planes written with a static scale: csrc/h2.h)
-int launch_attention_h2_op(relax_handle* h, const float* qkv, float* out, int Nimg, int heads, hipStream_t s) {
-    RELAX_REQUIRE(h, Nimg > 0 && heads > 0 && qkv && out, "attention_h2 (operator): Nimg=%d heads=%d", Nimg, heads);
-    const int dim = heads * 64;
-    const int64_t rows = (int64_t)Nimg * AH_NTOK;
+// The steps of an operator entry around its kernel, for the streaming entry too (attention_stream_h2.hip): sp3_ws carved into the qkv planes, the
+// output planes, the maximum and the scalar table {s, 1 / s, alpha, out_mul}; the maximum of the whole qkv tensor; the scalars; the planes;
+// `kernel` (it reads alpha and out_mul from the pointer it is given); the output planes back to fp32
+int attention_h2_op_steps(relax_handle* h, const float* qkv, float* out, int64_t rows, int dim, hipStream_t s, const AttentionH2OpKernel& kernel) {
     const size_t q_bytes = ((size_t)rows * 3 * dim * 4 + 255) & ~(size_t)255, o_bytes = ((size_t)rows * dim * 4 + 255) & ~(size_t)255;
     RELAX_TRY(ensure_buf(h, h->sp3_ws, q_bytes + o_bytes + 512));
     char* Qp = static_cast<char*>(h->sp3_ws.p);
@@ -353,19 +351,19 @@ int launch_attention_h2_op(relax_handle* h, const float* qkv, float* out, int Ni
     unsigned* amax = reinterpret_cast<unsigned*>(Op + o_bytes);
     float* tab = reinterpret_cast<float*>(Op + o_bytes + 256);
     RELAX_TRY(launch_image_absmax(h, qkv, rows * 3 * dim, 1, amax, s));
-    hipLaunchKernelGGL(ah_op_scalars, dim3(1), dim3(1), 0, s, amax, tab);
+    RELAX_TRY(launch_ah_op_scalars(h, amax, tab, s));
     RELAX_TRY(launch_to_h2(h, qkv, 3 * dim, Qp, rows, 3 * dim, 1.f, tab, s, (int)rows));
-    static bool attr_set[kMaxDevices] = {};
-    if (!attr_set[h->device]) {
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_h2), hipFuncAttributeMaxDynamicSharedMemorySize, AH_LDS));
-        attr_set[h->device] = true;
-    }
-    const int total = Nimg * heads;
-    hipLaunchKernelGGL(attention_h2, dim3(total < 256 ? total : 256), dim3(AH_THREADS), AH_LDS, s, Qp, Op, heads, total, 0.f, 0.f, tab + 2);
-    const int64_t total8 = rows * (dim / 8);
-    hipLaunchKernelGGL(ah_from_h2, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, s, Op, out, dim, total8, tab + 1);
-    RELAX_HIP_CHECK(h, hipGetLastError());
-    return RELAX_OK;
+    RELAX_TRY(kernel(Qp, Op, tab + 2));
+    return launch_ah_from_h2(h, Op, out, rows, dim, tab + 1, s);
+}
+
+// (operator level, tests: ONE scale from the maximum of the whole qkv tensor of the call - not batch-invariant, unlike the engine's ViT path,
+// which hands the kernel planes written with a static scale: csrc/h2.h)
+int launch_attention_h2_op(relax_handle* h, const float* qkv, float* out, int Nimg, int heads, hipStream_t s) {
+    RELAX_REQUIRE(h, Nimg > 0 && heads > 0 && qkv && out, "attention_h2 (operator): Nimg=%d heads=%d", Nimg, heads);
+    return attention_h2_op_steps(h, qkv, out, (int64_t)Nimg * AH_NTOK, heads * 64, s, [&](const char* Qp, char* Op, const float* tab) -> int {
+        return launch_ah_kernel(h, Qp, Op, Nimg, heads, 0.f, 0.f, tab, s);
+    });
 }
 
 }  // namespace relax

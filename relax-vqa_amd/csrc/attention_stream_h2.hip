@@ -276,11 +276,8 @@ static int stream_h2_plan(relax_handle* h, int Nimg, int heads, int ntok, host::
         set_error(h, "%s", err.c_str());
         return RELAX_ERR_INVALID;
     }
-    static bool attr_set[kMaxDevices] = {};
-    if (!attr_set[h->device]) {
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_stream_h2), hipFuncAttributeMaxDynamicSharedMemorySize, SH_LDS));
-        attr_set[h->device] = true;
-    }
+    static std::atomic<bool> lds_allowed[kMaxDevices];
+    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&attention_stream_h2)}, SH_LDS, lds_allowed));
     return RELAX_OK;
 }
 
@@ -302,7 +299,7 @@ int launch_attention_stream_h2(relax_handle* h, const void* qkv_planes, float s_
 }
 
 // operator-level entry (relax_op_attention_ex under "f16x2" with "att_h2" and "att_h2_stream"): fp32 qkv in, fp32 out.  The planes are made
-// here with ONE scale for the whole tensor from its measured maximum, everything on the device (launch_attention_h2_op's steps)
+// here with ONE scale for the whole tensor from its measured maximum, everything on the device (attention_h2_op_steps)
 int launch_attention_stream_h2_op(relax_handle* h, const float* qkv, float* out, int Nimg, int ntok, int heads, hipStream_t s) {
     RELAX_REQUIRE(h, qkv && out, "attention_stream_h2 (operator): NULL operand");
     host::AttStreamH2Plan p;
@@ -310,19 +307,11 @@ int launch_attention_stream_h2_op(relax_handle* h, const float* qkv, float* out,
     const int dim = heads * 64;
     const int64_t rows = (int64_t)Nimg * ntok;
     RELAX_REQUIRE(h, rows <= (int64_t)INT32_MAX, "attention_stream_h2 (operator): %d images of %d tokens pass 2^31 - 1 rows", Nimg, ntok);
-    const size_t q_bytes = ((size_t)rows * 3 * dim * 4 + 255) & ~(size_t)255, o_bytes = ((size_t)rows * dim * 4 + 255) & ~(size_t)255;
-    RELAX_TRY(ensure_buf(h, h->sp3_ws, q_bytes + o_bytes + 512));
-    char* Qp = static_cast<char*>(h->sp3_ws.p);
-    char* Op = Qp + q_bytes;
-    unsigned* amax = reinterpret_cast<unsigned*>(Op + o_bytes);
-    float* tab = reinterpret_cast<float*>(Op + o_bytes + 256);
-    RELAX_TRY(launch_image_absmax(h, qkv, rows * 3 * dim, 1, amax, s));
-    RELAX_TRY(launch_ah_op_scalars(h, amax, tab, s));
-    RELAX_TRY(launch_to_h2(h, qkv, 3 * dim, Qp, rows, 3 * dim, 1.f, tab, s, (int)rows));
-    hipLaunchKernelGGL(attention_stream_h2, dim3((unsigned)p.items), dim3(SH_THREADS), SH_LDS, s, Qp, Op, ntok, heads, p.qblocks, p.key_tiles, 0.f, 0.f,
-                       tab + 2);
-    RELAX_HIP_CHECK(h, hipGetLastError());
-    return launch_ah_from_h2(h, Op, out, rows, dim, tab + 1, s);
+    return attention_h2_op_steps(h, qkv, out, rows, dim, s, [&](const char* Qp, char* Op, const float* tab) -> int {
+        hipLaunchKernelGGL(attention_stream_h2, dim3((unsigned)p.items), dim3(SH_THREADS), SH_LDS, s, Qp, Op, ntok, heads, p.qblocks, p.key_tiles, 0.f, 0.f, tab);
+        RELAX_HIP_CHECK(h, hipGetLastError());
+        return RELAX_OK;
+    });
 }
 
 }  // namespace relax

@@ -331,18 +331,10 @@ int launch_attention_x6(relax_handle* h, const float* qkv, float* out, void* out
                         float out_h2_scale) {
     RELAX_REQUIRE(h, Nimg > 0 && heads > 0 && (out || out_planes), "attention_x6: Nimg=%d heads=%d", Nimg, heads);
     RELAX_REQUIRE(h, !(out_h2_scale > 0.f) || (out_planes && !out), "attention_x6: the fp16-plane output goes alone");
-    static bool attr_set[kMaxDevices] = {};
-    if (!attr_set[h->device]) {
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_x6<1, false>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, A6_LDS_TOTAL));
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_x6<0, true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, A6_LDS_TOTAL));
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_x6<1, true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, A6_LDS_TOTAL));
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_x6<2, false>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, A6_LDS_TOTAL));
-        attr_set[h->device] = true;
-    }
+    static std::atomic<bool> lds_allowed[kMaxDevices];
+    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&attention_x6<1, false>), reinterpret_cast<const void*>(&attention_x6<0, true>),
+                                    reinterpret_cast<const void*>(&attention_x6<1, true>), reinterpret_cast<const void*>(&attention_x6<2, false>)},
+                                A6_LDS_TOTAL, lds_allowed));
     const int total = Nimg * heads;
     const int grid = total < 256 ? total : 256;   // one persistent workgroup (7 waves) per CU
     char* o6 = static_cast<char*>(out_planes);

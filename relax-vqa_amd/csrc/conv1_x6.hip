@@ -268,12 +268,8 @@ int make_conv1_h2_weights(relax_handle* h, const float* w_packed, int kpad, void
 // w_inv != null: `w` holds fp16 planes (make_conv1_h2_weights) and the kernel runs its f16x2 form
 int launch_conv1_x6(relax_handle* h, const uint8_t* frags, const void* w_sp3, float* out, float* gap_groups, int N, hipStream_t s, const float* w_inv) {
     RELAX_REQUIRE(h, frags && w_sp3 && out && N > 0, "conv1_x6: bad arguments");
-    static bool attr_set[kMaxDevices] = {};
-    if (!attr_set[h->device]) {
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1_x6<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1_LDS));
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1_x6<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1_LDS));
-        attr_set[h->device] = true;
-    }
+    static std::atomic<bool> lds_allowed[kMaxDevices];
+    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&conv1_x6<false>), reinterpret_cast<const void*>(&conv1_x6<true>)}, C1_LDS, lds_allowed));
     const int n_tiles = N * (C1_OPIX / C1_TILE);
     const double flops = 2.0 * N * (double)C1_OPIX * 64.0 * 147.0;
     const double bytes = (double)N * (C1_HW * C1_HW * 3 + (double)C1_OPIX * 64 * 4);

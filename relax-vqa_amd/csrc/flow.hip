@@ -1332,14 +1332,8 @@ static int flow_segment_rows(const relax_handle* h, int bands, int hh) {
 template <bool UP, bool MINMAX>
 static int launch_flow_iteration(relax_handle* h, const float* R, const float* flow_in, float* flow_out, int hh, int w, int P, const FlowUp& up,
                                  unsigned* mm, hipStream_t s) {
-    // per (instantiation, device); atomic: two handles of one device may launch from two threads (the call is idempotent, so the worst
-    // a lost race does is set the attribute twice)
-    static std::atomic<bool> attr_set[kMaxDevices];
-    if (!attr_set[h->device].load(std::memory_order_acquire)) {
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&flow_iteration<UP, MINMAX>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)IT_LDS));
-        attr_set[h->device].store(true, std::memory_order_release);
-    }
+    static std::atomic<bool> lds_allowed[kMaxDevices];
+    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&flow_iteration<UP, MINMAX>)}, IT_LDS, lds_allowed));
     const int bands = (w + IT_OUT - 1) / IT_OUT;
     const int seg = flow_segment_rows(h, bands, hh);
     hipLaunchKernelGGL((flow_iteration<UP, MINMAX>), dim3(bands, (hh + seg - 1) / seg, P), dim3(512), IT_LDS, s, R, flow_in, flow_out, hh, w,

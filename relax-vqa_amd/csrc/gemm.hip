@@ -506,31 +506,10 @@ __global__ __launch_bounds__(256) void splitk_finish(const GemmParams p) {
 template <int BM, int BN, int WM, int WN, int BK, int OCC, bool TAPS, int PREC>
 static int launch_variant(relax_handle* h, GemmParams& p, int blocks_per_cu, hipStream_t s) {
     constexpr int NT = WM * WN * 64;
-    p.tiles_n = p.N / BN;
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.ntiles = p.tiles_m * p.tiles_n;
-    p.group_m = h->gemm.group_m;
-    p.full_tiles = p.ntiles;
-    p.nsplit = 1;
-    p.partial = nullptr;
-    // Tail split-K: the last partial round of tiles would leave most CUs idle; cut those tiles along K so
-    // that the tail fills the chip once with short work units (partials summed in order by splitk_finish).  Cost model:
-    // host_logic.cpp (shared with gemm_x6.hip).
-    const host::TailSplit ts = host::choose_tail_split(p.ntiles, blocks_per_cu * 256, p.Kpad / BK, 4, h->gemm.split_k != 0);
-    if (ts.nsplit > 1) {
-        const size_t need = sizeof(float) * (size_t)(p.ntiles - ts.full_tiles) * ts.nsplit * BM * BN;
-        RELAX_TRY(ensure_buf(h, h->splitk_ws, need < (size_t)(64 << 20) ? (size_t)(64 << 20) : need));
-        p.partial = static_cast<float*>(h->splitk_ws.p);
-        p.full_tiles = ts.full_tiles;
-        p.nsplit = ts.nsplit;
-    }
+    RELAX_TRY(plan_tiles(h, p, BM, BN, blocks_per_cu * 256, p.Kpad / BK, 4, h->gemm.split_k != 0));
     constexpr size_t lds = sizeof(float) * 2 * (BM + BN) * (BK + 4);
-    static bool attr_set[kMaxDevices] = {};   // per (kernel instantiation, device): the attribute lives on the device's code object
-    if (!attr_set[h->device]) {
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_f32<BM, BN, WM, WN, BK, OCC, TAPS, PREC>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[h->device] = true;
-    }
+    static std::atomic<bool> lds_allowed[kMaxDevices];
+    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&conv_gemm_f32<BM, BN, WM, WN, BK, OCC, TAPS, PREC>)}, lds, lds_allowed));
     const int units = p.full_tiles + (p.ntiles - p.full_tiles) * p.nsplit;
     hipLaunchKernelGGL((conv_gemm_f32<BM, BN, WM, WN, BK, OCC, TAPS, PREC>), dim3(units), dim3(NT), lds, s, p);
     if (p.nsplit > 1)

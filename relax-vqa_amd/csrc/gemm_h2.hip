@@ -1097,22 +1097,9 @@ template <int FORM>
 static int launch_h2_variant(relax_handle* h, H2Params& p, hipStream_t s) {
     constexpr int BM = H2_BM, BN = H2_BN;
     constexpr bool BK32 = FORM >= 2;
-    p.tiles_n = p.N / BN;
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.ntiles = p.tiles_m * p.tiles_n;
-    p.group_m = h->gemm.group_m;
-    p.partial = nullptr;
-    // Tail split-K: the last, partial round of tiles is cut along K (cost model: host_logic.cpp, shared with the other kernels)
     // (splitk_finish_h2 knows neither the fused group sums nor a plane residual: those launches run unsplit)
-    const host::TailSplit ts = host::choose_tail_split(p.ntiles, 256, BK32 ? p.K / 32 : p.K / 16, BK32 ? 4 : 8,
-                                                       h->gemm.split_k && !p.no_split && !p.gap && !p.residual_h2);
-    p.full_tiles = ts.full_tiles;
-    p.nsplit = ts.nsplit;
-    if (p.nsplit > 1) {
-        const size_t need = sizeof(float) * (size_t)(p.ntiles - p.full_tiles) * p.nsplit * BM * BN;
-        RELAX_TRY(ensure_buf(h, h->splitk_ws, need < (size_t)(64 << 20) ? (size_t)(64 << 20) : need));
-        p.partial = static_cast<float*>(h->splitk_ws.p);
-    }
+    const bool can_split = h->gemm.split_k && !p.no_split && !p.gap && !p.residual_h2;
+    RELAX_TRY(plan_tiles(h, p, BM, BN, 256, BK32 ? p.K / 32 : p.K / 16, BK32 ? 4 : 8, can_split));
     constexpr size_t lds = BK32 ? (size_t)H3_NSTG * H3_STAGE : (size_t)(FORM == 1 ? 4 : 3) * H2_STAGE;
     auto kernel = [] {
         if constexpr (FORM == 0) return &gemm_h2<3>;
@@ -1122,11 +1109,8 @@ static int launch_h2_variant(relax_handle* h, H2Params& p, hipStream_t s) {
         else if constexpr (FORM == 4) return &gemm_h3<false, true, true>;
         else return &gemm_h3<false, false, true>;
     }();
-    static bool attr_set[kMaxDevices] = {};
-    if (!attr_set[h->device]) {
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[h->device] = true;
-    }
+    static std::atomic<bool> lds_allowed[kMaxDevices];
+    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(kernel)}, lds, lds_allowed));
     const int units = p.full_tiles + (p.ntiles - p.full_tiles) * p.nsplit;
     H2_STAMPS_BEFORE_LAUNCH(h, p, units);
     hipLaunchKernelGGL(kernel, dim3(units), dim3(512), lds, s, p);

@@ -1302,33 +1302,16 @@ template <int BM, int BN, int WM, int WN, bool TAPS, bool M16 = false, bool DUAL
 static int launch_x6_variant(relax_handle* h, X6Params& p, hipStream_t s) {
     constexpr int NT = WM * WN * 64;
     constexpr int WG_PER_CU = NT == 256 ? 2 : 1;
-    p.tiles_n = p.N / BN;
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.ntiles = p.tiles_m * p.tiles_n;
-    p.group_m = h->gemm.group_m;
-    p.partial = nullptr;
-    // Tail split-K: the last, partial round of tiles is cut along K (cost model: host_logic.cpp, shared with gemm.hip);
     // splitk_finish_x6 knows neither the fused group sums nor a split-plane residual, so those launches run unsplit
     const bool can_split = h->gemm.split_k && !p.gap && !p.residual_sp3 && !p.no_split && !p.out_h2 && !p.amax_out && !H2;
-    const host::TailSplit ts = host::choose_tail_split(p.ntiles, 256 * WG_PER_CU, p.K / 16, 8, can_split);
-    p.full_tiles = ts.full_tiles;
-    p.nsplit = ts.nsplit;
-    if (p.nsplit > 1) {
-        const size_t need = sizeof(float) * (size_t)(p.ntiles - p.full_tiles) * p.nsplit * BM * BN;
-        RELAX_TRY(ensure_buf(h, h->splitk_ws, need < (size_t)(64 << 20) ? (size_t)(64 << 20) : need));
-        p.partial = static_cast<float*>(h->splitk_ws.p);
-    }
+    RELAX_TRY(plan_tiles(h, p, BM, BN, 256 * WG_PER_CU, p.K / 16, 8, can_split));
     constexpr int CH = H2 ? kH2ChunkBytes : kChunkBytes;
     // (B2B: the waves' own staging rows of the conv3 passes, 64 x 68 floats each, + the row scales + two maxima: 70.7 KB, two workgroups per CU)
     constexpr size_t stages_lds = (((M16 && !TAPS && !DUAL) || (H2 && X6_H2_STAGES == 3)) ? 3 : 2) * (size_t)(BM * (AF32 ? 64 : CH) + BN * CH);
     constexpr size_t b2b_stg = (size_t)(WM * WN) * (BM / WM) * 68 * 4;     // the waves' own staging rows of the conv3 passes
     constexpr size_t lds = B2B ? (b2b_stg > stages_lds ? b2b_stg : stages_lds) + (size_t)WN * BM * 4 + 64 : stages_lds + 1024;
-    static bool attr_set[kMaxDevices] = {};
-    if (!attr_set[h->device]) {
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_x6<BM, BN, WM, WN, TAPS, M16, DUAL, AF32, H2, B2B>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[h->device] = true;
-    }
+    static std::atomic<bool> lds_allowed[kMaxDevices];
+    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&gemm_x6<BM, BN, WM, WN, TAPS, M16, DUAL, AF32, H2, B2B>)}, lds, lds_allowed));
     const int units = p.full_tiles + (p.ntiles - p.full_tiles) * p.nsplit;
     X6_STAMPS_BEFORE_LAUNCH(h, p, units);
     hipLaunchKernelGGL((gemm_x6<BM, BN, WM, WN, TAPS, M16, DUAL, AF32, H2, B2B>), dim3(units), dim3(NT), lds, s, p);

@@ -790,7 +790,7 @@ int relax_head_train_init(relax_handle* h, int input_features, int hidden_featur
     t.xb = static_cast<float*>(grab(sizeof(float) * (size_t)max_batch * t.Fpad));
     // the contraction's tail split-K workspace: it asks for max(64 MiB, tail tiles x splits x 128 x 128 floats), and the tail fills the
     // chip at most once (768 work units of 64 KiB = 48 MiB): sized here, a step never finds it too small and so never waits for the device
-    if (rc == RELAX_OK) rc = ensure_buf(h, h->splitk_ws, (size_t)(64 << 20));
+    if (rc == RELAX_OK) rc = ensure_buf(h, h->splitk_ws, kSplitKWsFloor);
     if (rc == RELAX_OK && hipDeviceSynchronize() != hipSuccess) {   // the zero fills above have completed before anything is enqueued on another stream
         set_error(h, "relax_head_train_init: hipDeviceSynchronize failed");
         rc = RELAX_ERR_HIP;

@@ -2,6 +2,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -473,6 +474,93 @@ bool att_stream_h2_plan(int Nimg, int heads, int ntok, AttStreamH2Plan* plan, st
     return true;
 }
 
+// ---- options table ---------------------------------------------------------------------------------------------------------------------
+#define OPT(key, member, rule, a, b, must_be, env, env_fallback) {key, &GemmOptions::member, rule, a, b, must_be, env, env_fallback}
+const OptionRow kOptions[] = {
+    OPT("gemm_split_k", split_k, kOptAsGiven, 0, 0, nullptr, "RELAX_GEMM_SPLIT", 0),
+    OPT("gemm_precision", precision, kOptRange, 0, 3, "0 (fp32), 1 (bf16x3), 2 (bf16x6) or 3 (f16x2)", "RELAX_GEMM_PRECISION", 0),
+    OPT("gemm_variant", variant, kOptAsGiven, 0, 0, nullptr, "RELAX_GEMM_VARIANT", 0),
+    OPT("gemm_variant_n64", variant_n64, kOptAsGiven, 0, 0, nullptr, "RELAX_GEMM_VARIANT_N64", 0),
+    OPT("gemm_group_m", group_m, kOptFloor, 1, 0, nullptr, "RELAX_GEMM_GROUP_M", 0),
+    OPT("flow_max_pairs", flow_max_pairs, kOptFloor, 0, 0, nullptr, nullptr, 0),
+    OPT("flow_fused", flow_fused, kOptBool, 0, 0, nullptr, nullptr, 0),
+    OPT("flow_seg_rows", flow_seg_rows, kOptFloor, 0, 0, nullptr, nullptr, 0),
+    OPT("flow_pyramid_fused", flow_pyramid_fused, kOptBool, 0, 0, nullptr, nullptr, 0),
+    OPT("x6_fp32_rows", fp32_rows, kOptBool, 0, 0, nullptr, nullptr, 0),
+    OPT("rn_h2", rn_h2, kOptBool, 0, 0, nullptr, nullptr, 0),
+    OPT("rn_h2_early", rn_h2_early, kOptBool, 0, 0, nullptr, nullptr, 0),
+    OPT("rn_fuse", rn_fuse, kOptBool, 0, 0, nullptr, nullptr, 0),
+    OPT("rn_c1_h2", rn_c1_h2, kOptBool, 0, 0, nullptr, nullptr, 0),
+    OPT("b2b_rows", b2b_rows, kOptOneOf, 128, 256, "128 or 256", nullptr, 0),
+    OPT("att_h2", att_h2, kOptBool, 0, 0, nullptr, nullptr, 0),
+    OPT("att_h2_stream", att_h2_stream, kOptBool, 0, 0, nullptr, nullptr, 0),
+    OPT("h2_form", h2_form, kOptRange, 0, 2, "0, 1 or 2", "RELAX_H2_FORM", 1),
+    OPT("h2_stages", h2_stages, kOptOneOf, 3, 4, "3 or 4", nullptr, 0),
+    OPT("debug_poison", debug_poison, kOptBool, 0, 0, nullptr, "RELAX_DEBUG_POISON", 0),
+};
+#undef OPT
+const int kNumOptions = (int)(sizeof(kOptions) / sizeof(kOptions[0]));
+
+static const OptionRow* find_option(const char* key) {
+    for (const OptionRow& r : kOptions)
+        if (std::strcmp(r.key, key) == 0) return &r;
+    return nullptr;
+}
+
+// the value as the row stores it; false where the row refuses it
+static bool option_take(const OptionRow& r, int value, int* stored) {
+    switch (r.rule) {
+        case kOptAsGiven: *stored = value; return true;
+        case kOptBool: *stored = value != 0; return true;
+        case kOptFloor: *stored = value > 0 ? value : r.a; return true;
+        case kOptOneOf: *stored = value; return value == r.a || value == r.b;
+        case kOptRange: *stored = value; return value >= r.a && value <= r.b;
+    }
+    return false;
+}
+
+bool option_set(GemmOptions& o, const char* key, int value, std::string& err) {
+    if (!key) {
+        err = "relax_set_option: key is NULL";
+        return false;
+    }
+    const OptionRow* r = find_option(key);
+    if (!r) {
+        err = std::string("relax_set_option: unknown option '") + key + "'";
+        return false;
+    }
+    int stored;
+    if (!option_take(*r, value, &stored)) {
+        err = std::string("relax_set_option: ") + r->key + " must be " + r->must_be;
+        return false;
+    }
+    o.*(r->member) = stored;
+    return true;
+}
+
+bool option_get(const GemmOptions& o, const char* key, int* value, std::string& err) {
+    if (!key || !value) {
+        err = "relax_get_option: NULL argument";
+        return false;
+    }
+    const OptionRow* r = find_option(key);
+    if (!r) {
+        err = std::string("relax_get_option: unknown option '") + key + "'";
+        return false;
+    }
+    *value = o.*(r->member);
+    return true;
+}
+
+void options_from_env(GemmOptions& o, const std::function<const char*(const char*)>& lookup) {
+    for (const OptionRow& r : kOptions) {
+        const char* e = r.env ? lookup(r.env) : nullptr;
+        if (!e) continue;
+        int stored;
+        o.*(r.member) = option_take(r, std::atoi(e), &stored) ? stored : r.env_fallback;
+    }
+}
+
 }  // namespace host
 }  // namespace relax
 
@@ -655,6 +743,31 @@ int relax_host_att_stream_h2_plan(int Nimg, int heads, int ntok, int* out, char*
     }
     std::memcpy(out, &p, sizeof(p));
     return 0;
+}
+
+// the options table.  The i-th key (NULL past the end); a GemmOptions with its defaults on the heap; set / get by key: 0, or -1 and the
+// message; the table's variables applied from n (name, value) pairs standing in for the environment
+const char* relax_host_option_key(int i) { return i >= 0 && i < relax::host::kNumOptions ? relax::host::kOptions[i].key : nullptr; }
+void* relax_host_options_new(void) { return new relax::GemmOptions(); }
+void relax_host_options_free(void* o) { delete static_cast<relax::GemmOptions*>(o); }
+int relax_host_option_set(void* o, const char* key, int value, char* err, int err_len) {
+    std::string e;
+    if (relax::host::option_set(*static_cast<relax::GemmOptions*>(o), key, value, e)) return 0;
+    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+    return -1;
+}
+int relax_host_option_get(const void* o, const char* key, int* value, char* err, int err_len) {
+    std::string e;
+    if (relax::host::option_get(*static_cast<const relax::GemmOptions*>(o), key, value, e)) return 0;
+    if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+    return -1;
+}
+void relax_host_options_from_env(void* o, const char* const* names, const char* const* values, int n) {
+    relax::host::options_from_env(*static_cast<relax::GemmOptions*>(o), [&](const char* name) -> const char* {
+        for (int i = 0; i < n; ++i)
+            if (std::strcmp(names[i], name) == 0) return values[i];
+        return nullptr;
+    });
 }
 
 }  // extern "C"

@@ -1,16 +1,58 @@
 // Pure-host half of librelax_hip.so: everything the model loaders and the launchers compute on the CPU before a byte goes
 // to the GPU - state-dict key matching, reading and folding a BatchNorm (read_bn), OIHW -> packed [Cout][K] weight layout, the Hoelder
-// constants of a folded convolution (conv_hoelder), the quality head's fc1 + BatchNorm1d fold, and the tail split-K cost model of the
-// contraction launchers.  No HIP type appears here, so the file
+// constants of a folded convolution (conv_hoelder), the quality head's fc1 + BatchNorm1d fold, the tail split-K cost model of the
+// contraction launchers, and the options of a handle (GemmOptions and the table relax_set_option / relax_get_option / relax_create go by).  No HIP type appears here, so the file
 // builds with plain g++ and runs under AddressSanitizer / UBSan on a CPU box (tests/test_host_logic_sanitized.py drives it with the
 // synthetic and the deliberately malformed state dicts; sanitizers are never run on the GPU).
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <string>
 #include <utility>
 
 namespace relax {
+
+// Tuning / reproducibility switches of the contraction kernel (relax_set_option; env defaults RELAX_GEMM_*): plain data, one
+// row of host::kOptions per field.
+struct GemmOptions {
+    int precision = 3; // "gemm_precision": 3 = f16x2 (default,  fp32-grade: two fp16 planes, four products in two MFMAs - gemm_h2.hip - for the
+                       // plain GEMMs with N % 256 == 0, i.e. the whole ViT; everything else as under 2), 2 = bf16x6 (fp32-grade), 0 = exact fp32
+                       // MFMA, 1 = bf16x3 split products (~1e-5 relative)
+    int h2_stages = 3; // "h2_stages": LDS stages of the 16-k form of the f16x2 kernel (3 or 4; same bits)
+    int h2_form = 1;   // "h2_form": 1 = 32-k steps, three products (al bl dropped) for K >= 256, four below; 0 = 16-k steps, four products;
+                       // 2 = 32-k steps, four products
+    int split_k = 1;   // "gemm_split_k": tail split-K on (1) / off (0: K sums are batch-invariant bit for bit)
+    int variant = -1;  // "gemm_variant": exact-fp32 kernel only: pin the tile variant for N % 128 == 0 problems, -1 = automatic
+    int variant_n64 = -1;  // "gemm_variant_n64": same for N % 128 != 0 (N = 64 layers)
+    int group_m = 8;   // "gemm_group_m": row-tiles per L2 group
+    int flow_max_pairs = 0;  // "flow_max_pairs": cap on the pairs per optical-flow chunk (0 = by workspace size only)
+    int flow_seg_rows = 0;       // "flow_seg_rows": rows per block of the Farneback iteration kernels, 0 = by the level's geometry (tests: the segmentation
+                                 // restarts the running column sums - the flow must not depend on it)
+    int flow_pyramid_fused = 1;  // "flow_pyramid_fused": 1 = the four pyramid-level inputs of a frame in one pass over its bytes (pyramid_fused; frames whose
+                                 // height and width are multiples of 8), 0 = gray plane + per-level blur / resize kernels (any size) - same bits
+    int flow_fused = 1;      // "flow_fused": 1 = one kernel per Farneback iteration (flow_iteration: M never leaves the chip); 0 = update_matrices_k +
+                             // box_solve_fused (M through HBM) - same bits, the A/B switch of a test
+    int rn_h2 = 1;         // "rn_h2": under "gemm_precision" 3, ResNet-50's layer3 / layer4 (the matrix-pipe-bound third of its time) run f16x2 with
+                           // per-image scales; 0 = the whole network on bf16x6 (the A/B switch of a test)
+    int att_h2 = 1;        // "att_h2": under "gemm_precision" 3 the ViT's attention runs on fp16 planes too (attention_h2.hip: the qkv GEMM writes planes,
+                           // three products, no conversion passes); 0 = attention_x6 on the fp32 qkv output (three bf16 planes, six products)
+    int att_h2_stream = 1;   // "att_h2_stream": with "att_h2", token counts other than 197 (patch-8 models, other canvases) run attention on fp16 planes too
+                           // (attention_stream_h2.hip: the streaming form of attention_h2); 0 = attention_stream's bf16x6 form on the fp32 qkv output
+    int rn_h2_early = 1;   // "rn_h2_early": with "rn_h2", the stem and the 3x3 convolutions of layer1 / layer2 (the MFMA-bound launches in front of layer3) run f16x2 too,
+                           // on the four-wave tiles of gemm_x6.hip (conv1 writes its output as fp16 planes with the image's Hoelder scale); 0 = bf16x6 there
+    int rn_c1_h2 = 1;      // "rn_c1_h2": with "rn_h2_early", the conv1 (1x1) of the layer1 / layer2 blocks whose input travels as fp32 rows runs f16x2 too: the rows
+                           // are split into two fp16 planes in the K loop with the image's scale (from its measured maximum); 0 = bf16x6 (three planes, six products)
+    int rn_fuse = 1;       // "rn_fuse": with "rn_h2_early", the blocks of layer1 / layer2 without a downsample branch run conv2 and conv3 back to back in ONE
+                           // launch (the 3x3's output tile stays in registers as the A operand of the 1x1: no write and re-read of it, conv3 on f16x2
+                           // with one scale per pixel row); 0 = two launches, conv3 on bf16x6 (the A/B switch of a test)
+    int b2b_rows = 256;    // "b2b_rows": rows per tile of the back-to-back launches: 256 (two workgroups of four waves per CU) or 128 (three: measured
+                           // slower, 2.49 against 2.13 ms per launch of layer1) - same bits
+    int fp32_rows = 1;     // "x6_fp32_rows": bf16x6 contractions onto 64 / 128 columns take fp32 activation rows and split them in the K loop
+                           // (ResNet-50 layer1 / layer2 block outputs travel as fp32); 0 = split planes everywhere (same bits, more bytes: the A/B switch of a test)
+    int debug_poison = 0;  // "debug_poison": fill every workspace with 0xFF bytes when it is requested (test mode: reads of unwritten workspace surface as NaN)
+};
+
 namespace host {
 
 // name -> (host pointer, element count) of a checkpoint as the C-ABI receives it (relax_load_resnet50 / _vit / _mlp_head)
@@ -56,6 +98,29 @@ struct TailSplit {
     int nsplit;       // slices per remaining tile (1 = no split)
 };
 TailSplit choose_tail_split(int ntiles, int slots, int nk, int min_steps, bool can_split);
+
+// ---- the options table: every relax_set_option / relax_get_option key once ------------------------------------------------------------------
+// How a row takes a value: as given; != 0; a non-positive value becomes `a`; one of {a, b}; the closed range [a, b].  The last two refuse
+// anything else with "relax_set_option: <key> must be <must_be>" and leave the stored value as it was.
+enum OptRule { kOptAsGiven = 0, kOptBool, kOptFloor, kOptOneOf, kOptRange };
+struct OptionRow {
+    const char* key;
+    int GemmOptions::*member;
+    OptRule rule;
+    int a, b;
+    const char* must_be;      // the refusal's text (kOptOneOf, kOptRange)
+    const char* env;          // the variable relax_create reads the initial value from, or nullptr
+    int env_fallback;         // what a variable's value that the rule refuses becomes
+};
+extern const OptionRow kOptions[];
+extern const int kNumOptions;
+// false and the message of relax_set_option (NULL key, unknown key, refused value); the stored value changes only on true
+bool option_set(GemmOptions& o, const char* key, int value, std::string& err);
+// false and the message of relax_get_option (NULL argument, unknown key)
+bool option_get(const GemmOptions& o, const char* key, int* value, std::string& err);
+// the variables of the table over `o`: lookup(name) is getenv's contract (nullptr = not set); a value is read with atoi (an unparsable one
+// is 0) and taken by the row's rule
+void options_from_env(GemmOptions& o, const std::function<const char*(const char*)>& lookup);
 
 // ---- VGG-16 (torchvision configuration D, no BatchNorm) -----------------------------------------------------------------------
 // The 13 convolutions features.{0,2,5,7,10,12,14,17,19,21,24,26,28} (3x3, pad 1) and the two classifier layers the features read

@@ -268,12 +268,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_197x64(const float* __r
 
 int launch_attention(relax_handle* h, const float* qkv, float* out, int Nimg, int heads, hipStream_t s) {
     RELAX_REQUIRE(h, Nimg > 0 && heads > 0, "attention: Nimg=%d heads=%d", Nimg, heads);
-    static bool attr_set[kMaxDevices] = {};
-    if (!attr_set[h->device]) {
-        RELAX_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_197x64),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_LDS));
-        attr_set[h->device] = true;
-    }
+    static std::atomic<bool> lds_allowed[kMaxDevices];
+    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&attention_197x64)}, ATT_LDS, lds_allowed));
     const int total = Nimg * heads;
     // one persistent workgroup (7 waves, ~250 VGPRs) per CU
     const int grid = total < 256 ? total : 256;

@@ -1,13 +1,16 @@
 // Internal declarations shared by the translation units of librelax_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
 
+#include "host_logic.h"
 #include "relax_hip.h"
 
 namespace relax {
@@ -324,47 +327,6 @@ struct Profiler {
 
 }  // namespace relax
 
-namespace relax {
-// Tuning / reproducibility switches of the contraction kernel (relax_set_option; env defaults RELAX_GEMM_*).
-struct GemmOptions {
-    int precision = 3; // "gemm_precision": 3 = f16x2 (default,  fp32-grade: two fp16 planes, four products in two MFMAs - gemm_h2.hip - for the
-                       // plain GEMMs with N % 256 == 0, i.e. the whole ViT; everything else as under 2), 2 = bf16x6 (fp32-grade), 0 = exact fp32
-                       // MFMA, 1 = bf16x3 split products (~1e-5 relative)
-    int h2_stages = 3; // "h2_stages": LDS stages of the 16-k form of the f16x2 kernel (3 or 4; same bits)
-    int h2_form = 1;   // "h2_form": 1 = 32-k steps, three products (al bl dropped) for K >= 256, four below; 0 = 16-k steps, four products;
-                       // 2 = 32-k steps, four products
-    int split_k = 1;   // "gemm_split_k": tail split-K on (1) / off (0: K sums are batch-invariant bit for bit)
-    int variant = -1;  // "gemm_variant": exact-fp32 kernel only: pin the tile variant for N % 128 == 0 problems, -1 = automatic
-    int variant_n64 = -1;  // "gemm_variant_n64": same for N % 128 != 0 (N = 64 layers)
-    int group_m = 8;   // "gemm_group_m": row-tiles per L2 group
-    int flow_max_pairs = 0;  // "flow_max_pairs": cap on the pairs per optical-flow chunk (0 = by workspace size only)
-    int flow_seg_rows = 0;       // "flow_seg_rows": rows per block of the Farneback iteration kernels, 0 = by the level's geometry (tests: the segmentation
-                                 // restarts the running column sums - the flow must not depend on it)
-    int flow_pyramid_fused = 1;  // "flow_pyramid_fused": 1 = the four pyramid-level inputs of a frame in one pass over its bytes (pyramid_fused; frames whose
-                                 // height and width are multiples of 8), 0 = gray plane + per-level blur / resize kernels (any size) - same bits
-    int flow_fused = 1;      // "flow_fused": 1 = one kernel per Farneback iteration (flow_iteration: M never leaves the chip); 0 = update_matrices_k +
-                             // box_solve_fused (M through HBM) - same bits, the A/B switch of a test
-    int rn_h2 = 1;         // "rn_h2": under "gemm_precision" 3, ResNet-50's layer3 / layer4 (the matrix-pipe-bound third of its time) run f16x2 with
-                           // per-image scales; 0 = the whole network on bf16x6 (the A/B switch of a test)
-    int att_h2 = 1;        // "att_h2": under "gemm_precision" 3 the ViT's attention runs on fp16 planes too (attention_h2.hip: the qkv GEMM writes planes,
-                           // three products, no conversion passes); 0 = attention_x6 on the fp32 qkv output (three bf16 planes, six products)
-    int att_h2_stream = 1;   // "att_h2_stream": with "att_h2", token counts other than 197 (patch-8 models, other canvases) run attention on fp16 planes too
-                           // (attention_stream_h2.hip: the streaming form of attention_h2); 0 = attention_stream's bf16x6 form on the fp32 qkv output
-    int rn_h2_early = 1;   // "rn_h2_early": with "rn_h2", the stem and the 3x3 convolutions of layer1 / layer2 (the MFMA-bound launches in front of layer3) run f16x2 too,
-                           // on the four-wave tiles of gemm_x6.hip (conv1 writes its output as fp16 planes with the image's Hoelder scale); 0 = bf16x6 there
-    int rn_c1_h2 = 1;      // "rn_c1_h2": with "rn_h2_early", the conv1 (1x1) of the layer1 / layer2 blocks whose input travels as fp32 rows runs f16x2 too: the rows
-                           // are split into two fp16 planes in the K loop with the image's scale (from its measured maximum); 0 = bf16x6 (three planes, six products)
-    int rn_fuse = 1;       // "rn_fuse": with "rn_h2_early", the blocks of layer1 / layer2 without a downsample branch run conv2 and conv3 back to back in ONE
-                           // launch (the 3x3's output tile stays in registers as the A operand of the 1x1: no write and re-read of it, conv3 on f16x2
-                           // with one scale per pixel row); 0 = two launches, conv3 on bf16x6 (the A/B switch of a test)
-    int b2b_rows = 256;    // "b2b_rows": rows per tile of the back-to-back launches: 256 (two workgroups of four waves per CU) or 128 (three: measured
-                           // slower, 2.49 against 2.13 ms per launch of layer1) - same bits
-    int fp32_rows = 1;     // "x6_fp32_rows": bf16x6 contractions onto 64 / 128 columns take fp32 activation rows and split them in the K loop
-                           // (ResNet-50 layer1 / layer2 block outputs travel as fp32); 0 = split planes everywhere (same bits, more bytes: the A/B switch of a test)
-    int debug_poison = 0;  // "debug_poison": fill every workspace with 0xFF bytes when it is requested (test mode: reads of unwritten workspace surface as NaN)
-};
-}  // namespace relax
-
 struct relax_handle {
     int device = 0;
     relax::GemmOptions gemm;
@@ -390,6 +352,37 @@ struct relax_handle {
 namespace relax {
 
 int ensure_buf(relax_handle* h, DevBuf& b, size_t bytes);
+
+// The opt-in of a launch site's kernel (or of the instantiations it chooses among) to `bytes` of dynamic LDS - more than the 64 KB a launch
+// gets unasked -, once per site and device (api.hip).  `done` is the site's own flags [kMaxDevices]: the attribute lives on the device's code
+// object, per kernel instantiation, so inside a templated launcher the array is a function-local static of that instantiation.  Atomic: two
+// handles of one device may launch from two threads (the call is idempotent, so the worst a lost race does is set the attribute twice); the
+// flag is stored only after every call has succeeded.
+int allow_dynamic_lds(relax_handle* h, std::initializer_list<const void*> kernels, size_t bytes, std::atomic<bool>* done);
+
+// The tile grid and the tail split-K of a contraction launch (gemm.hip, gemm_x6.hip, gemm_h2.hip: their parameter structs share the field
+// names): BM x BN tiles over `slots` resident workgroups, `nk` K steps of which a slice keeps at least `min_steps`.  The last, partial round of
+// tiles would leave most CUs idle; where the launch can be split, those tiles are cut along K so that the tail fills the chip once with short
+// work units (cost model: host::choose_tail_split; the launcher's finish kernel sums the partial tiles in order).  An unsplit launch is
+// {full_tiles = ntiles, nsplit = 1}, which is what choose_tail_split returns when it does not split.
+constexpr size_t kSplitKWsFloor = (size_t)(64 << 20);   // the least splitk_ws is requested at (head_train.hip too)
+template <class Params>
+int plan_tiles(relax_handle* h, Params& p, int BM, int BN, int slots, int nk, int min_steps, bool can_split) {
+    p.tiles_n = p.N / BN;
+    p.tiles_m = (p.M + BM - 1) / BM;
+    p.ntiles = p.tiles_m * p.tiles_n;
+    p.group_m = h->gemm.group_m;
+    const host::TailSplit ts = host::choose_tail_split(p.ntiles, slots, nk, min_steps, can_split);
+    p.full_tiles = ts.full_tiles;
+    p.nsplit = ts.nsplit;
+    p.partial = nullptr;
+    if (p.nsplit > 1) {
+        const size_t need = sizeof(float) * (size_t)(p.ntiles - p.full_tiles) * p.nsplit * BM * BN;
+        RELAX_TRY(ensure_buf(h, h->splitk_ws, need < kSplitKWsFloor ? kSplitKWsFloor : need));
+        p.partial = static_cast<float*>(h->splitk_ws.p);
+    }
+    return RELAX_OK;
+}
 
 // derived copies of a packed fp32 [rows][K] matrix on the device, kept by `mem` (weights.hip): split planes (sp3.h), and two fp16 planes with
 // one power-of-two scale per row + the inverse scales (h2.h).  The conversions are enqueued on the null stream; `what` names the matrix in an
@@ -463,9 +456,10 @@ int launch_attention_stream_x6(relax_handle* h, const float* qkv, float* out, vo
 int launch_attention_stream_h2(relax_handle* h, const void* qkv_planes, float s_qkv, void* out_planes, float out_scale, int Nimg, int ntok, int heads,
                                hipStream_t s);
 int launch_attention_stream_h2_op(relax_handle* h, const float* qkv, float* out, int Nimg, int ntok, int heads, hipStream_t s);   // fp32 in / out (relax_op_attention_ex)
-// the operator entries' steps around the kernel (attention_h2.hip): tab = {s, 1 / s, alpha, out_mul} from the measured maximum; planes * inv[0] -> fp32
-int launch_ah_op_scalars(relax_handle* h, const unsigned* amax, float* tab, hipStream_t s);
-int launch_ah_from_h2(relax_handle* h, const void* planes, float* out, int64_t rows, int dim, const float* inv, hipStream_t s);
+// the operator entries' steps around their kernel (attention_h2.hip): fp32 qkv [rows][3 dim] -> planes with one scale from the measured maximum ->
+// kernel(qkv planes, output planes, {alpha, out_mul} on the device) -> fp32 out [rows][dim]
+using AttentionH2OpKernel = std::function<int(const char* qkv_planes, char* out_planes, const float* tab)>;
+int attention_h2_op_steps(relax_handle* h, const float* qkv, float* out, int64_t rows, int dim, hipStream_t s, const AttentionH2OpKernel& kernel);
 // the last block's CLS attention row (vit_attention_map.hip): qkv as fp32 rows [Nimg*ntok][3*dim] or, with planes, fp16 planes of
 // qkv * s_qkv (csrc/h2.h) -> out fp32 [Nimg, heads, ntok] = softmax(q_0 k^T / 8) per (image, head)
 // (ntok <= 4352: 256 threads x 4 keys up to 1024 tokens, x 17 above)

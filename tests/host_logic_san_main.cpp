@@ -1,8 +1,9 @@
 // Stand-alone program (its own main) for AddressSanitizer + UBSan: csrc/host_logic.cpp's conv_hoelder and read_bn on the shapes of
-// tests/test_conv_hoelder_cpu.py and on malformed BatchNorm dicts.  Every input and output sits in a heap block of exactly its size, so a
-// read or write past an end is reported.  Built and run by tests/test_conv_hoelder_cpu.py; exit status 0 and "host_logic_san: OK" if all holds.
+// tests/test_conv_hoelder_cpu.py and on malformed BatchNorm dicts, and the options table's set / get with an empty key, a 1 KiB key and every
+// key of the table.  Every input and output sits in a heap block of exactly its size, so a read or write past an end is reported.  Built and run by tests/test_conv_hoelder_cpu.py; exit status 0 and "host_logic_san: OK" if all holds.
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -77,10 +78,55 @@ static void read_bn_cases() {
     }
 }
 
+// a key in a heap block of exactly its length + 1
+static std::vector<char> heap_key(const std::string& k) { return std::vector<char>(k.c_str(), k.c_str() + k.size() + 1); }
+
+static void option_cases() {
+    std::vector<relax::GemmOptions> heap(1);   // (the struct in a heap block of its size: a member pointer past its end is reported)
+    relax::GemmOptions& o = heap[0];
+    const relax::GemmOptions defaults;
+    std::string err;
+    int v = -7;
+    for (const std::string& bad : {std::string(), std::string(1024, 'k')}) {
+        const std::vector<char> key = heap_key(bad);
+        err.clear();
+        CHECK(!option_set(o, key.data(), 1, err) && err == "relax_set_option: unknown option '" + bad + "'");
+        err.clear();
+        CHECK(!option_get(o, key.data(), &v, err) && err == "relax_get_option: unknown option '" + bad + "'" && v == -7);
+    }
+    CHECK(!option_set(o, nullptr, 1, err) && err == "relax_set_option: key is NULL");
+    CHECK(!option_get(o, nullptr, &v, err) && err == "relax_get_option: NULL argument");
+    CHECK(!option_get(o, "gemm_split_k", nullptr, err) && err == "relax_get_option: NULL argument");
+    CHECK(std::memcmp(&o, &defaults, sizeof(o)) == 0);
+    CHECK(kNumOptions == 20);
+    for (int i = 0; i < kNumOptions; ++i) {
+        const std::vector<char> key = heap_key(kOptions[i].key);
+        int before = -7;
+        CHECK(option_get(o, key.data(), &before, err) && before == defaults.*(kOptions[i].member));
+        for (const int value : {INT32_MIN, -1, 0, 1, 2, 3, 4, 128, 256, INT32_MAX}) {   // accepted or refused: a refusal leaves the value
+            int stored = -7, now = -7;
+            CHECK(option_get(o, key.data(), &stored, err));
+            err.clear();
+            const bool ok = option_set(o, key.data(), value, err);
+            CHECK(ok == err.empty());
+            CHECK(option_get(o, key.data(), &now, err) && (ok || now == stored));
+        }
+        CHECK(option_set(o, key.data(), before, err));
+    }
+    CHECK(std::memcmp(&o, &defaults, sizeof(o)) == 0);
+    // the variables: none set, and every one set to a text atoi stops in
+    options_from_env(o, [](const char*) -> const char* { return nullptr; });
+    CHECK(std::memcmp(&o, &defaults, sizeof(o)) == 0);
+    const std::vector<char> text = heap_key("2x");
+    options_from_env(o, [&](const char*) -> const char* { return text.data(); });
+    CHECK(o.split_k == 2 && o.precision == 2 && o.h2_form == 2 && o.variant == 2 && o.variant_n64 == 2 && o.group_m == 2 && o.debug_poison == 1);
+}
+
 int main() {
     const int shapes[4][2] = {{1, 32}, {3, 64}, {64, 224}, {5, 4608}};
     for (const auto& sh : shapes) hoelder_cases(sh[0], sh[1]);
     read_bn_cases();
+    option_cases();
     if (failures) return 1;
     std::printf("host_logic_san: OK\n");
     return 0;

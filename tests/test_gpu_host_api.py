@@ -298,3 +298,38 @@ def test_checkpoint_files_go_through_the_loader_bit_for_bit(api, tmp_path, monke
     finally:
         eng.set_option("gemm_split_k", 1)
         runtime.set_weights(resnet50=rn, vit=vit, vit_name="vit_base")
+
+
+def test_every_option_reads_back_its_default_and_round_trips():
+    """relax_set_option / relax_get_option over the options table on a fresh handle: the key list of tests/test_options_cpu.py, each key's
+    default and one non-default value (no tensor moves)."""
+    from relax_vqa_amd.engine import RelaxEngine
+    from tests.test_options_cpu import ENV, OPTIONS
+    from_env = {key for var, key in ENV.items() if var in os.environ}    # (a poison-mode run of the suite: that key starts as its variable says)
+    other = {"given": 5, "floor": 3}
+    eng = RelaxEngine(0)
+    try:
+        for key, (default, rule) in OPTIONS.items():
+            initial = eng.get_option(key)
+            assert initial == default or key in from_env, key
+            kind = rule if isinstance(rule, str) else rule[0]
+            if kind == "bool":
+                value = 1 - initial
+            elif kind == "one_of":
+                value = rule[1] if initial == rule[2] else rule[2]
+            elif kind == "range":
+                value = rule[1] if initial != rule[1] else rule[2]
+            else:
+                value = other[kind] + (initial == other[kind])
+            eng.set_option(key, value)
+            assert eng.get_option(key) == value != initial, key
+            eng.set_option(key, initial)
+            assert eng.get_option(key) == initial, key
+        with pytest.raises(RuntimeError, match="relax_set_option: b2b_rows must be 128 or 256"):
+            eng.set_option("b2b_rows", 192)
+        with pytest.raises(RuntimeError, match="relax_get_option: unknown option 'no_such_option'"):
+            eng.get_option("no_such_option")
+        assert eng.get_option("profile_events") == 0 and eng.get_option("workspace_mib") == 0    # the two read-only counters, in front of the table
+        assert {k: eng.get_option(k) for k in OPTIONS if k not in from_env} == {k: d for k, (d, _) in OPTIONS.items() if k not in from_env}
+    finally:
+        eng.close()
