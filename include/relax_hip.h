@@ -291,6 +291,51 @@ int relax_resize_frames(relax_handle* h, const uint8_t* frames, int64_t item_str
 int relax_resize_residual(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
                           uint8_t* out_bilinear, uint8_t* out_lanczos, uint8_t* residual, relax_stream stream);
 
+/* ---- whole-frame front-end at ANY output size (the canvases relax_vit_features_canvas takes) --------- */
+/* The reference's resize size is an argument: transforms.Resize(img_size) (src/extractor/visualise_vit_layer.py:339-342, the
+ * reduced-size form left commented at :473; visualise_vit.py:339-342; demo_visual.py:27-28) and img.resize(..., LANCZOS) - in
+ * both cases Pillow's 8-bit resample.  The limits of these entries: */
+#define RELAX_RESIZE_BILINEAR 0
+#define RELAX_RESIZE_LANCZOS 1
+#define RELAX_RESIZE_MAX_OUT 2048     /* out_h, out_w: 1..2048 (a 4096-patch ViT canvas reaches 2048 pixels on a side: 2048 x 512 at patch 16) */
+#define RELAX_RESIZE_MAX_IN_W 8192    /* W: four input rows are staged in LDS (8192 * 3 * 4 B = 96 KiB; above 64 KiB by opt-in) */
+#define RELAX_RESIZE_MAX_IN_H 16384   /* H, and in_size of relax_resize_table */
+/* Everything outside them is refused (RELAX_ERR_INVALID) with the offending value named in relax_last_error. */
+
+/* The size transforms.Resize(size), size an int, gives a PIL image of H x W (torchvision's _compute_resized_output_size): the
+ * shorter side becomes `size`, the longer int(size * long / short); when W <= H - W == H included - W is the shorter side.
+ * Integer arithmetic: size * long < 2^26 inside the limits (H, W 1..RELAX_RESIZE_MAX_IN_H, size 1..RELAX_RESIZE_MAX_OUT), and
+ * Python's correctly rounded double quotient can reach the next integer from a fractional value only with quotient * short near
+ * 2^53, so floor division is int() of Python's expression.  A longer side above RELAX_RESIZE_MAX_OUT is refused.
+ * No handle, no GPU: host arithmetic; errors through relax_last_error(NULL). */
+int relax_resize_output_size(int H, int W, int size, int* out_h, int* out_w);
+
+/* The table of one resample pass, in_size -> out_size, filt RELAX_RESIZE_BILINEAR / _LANCZOS - Pillow's precompute_coeffs +
+ * normalize_coeffs_8bpc for the box (0, in_size), the table every resize kernel of this library reads:
+ *   bounds : int32 [out_size][2]  first tap, tap count
+ *   coeffs : int32 [out_size][*ksize]  the taps as 22-bit fixed point, zero behind the count
+ * bounds == NULL: only *ksize is written (the query before the buffers are made).  Host only, errors as above. */
+int relax_resize_table(int in_size, int out_size, int filt, int32_t* bounds, int32_t* coeffs, int* ksize);
+
+/* relax_resize_frames at a runtime output size: outputs uint8 [N,out_h,out_w,3], bit-identical to
+ * Image.resize((out_w,out_h), BILINEAR / LANCZOS) for downscaling, upscaling and mixed; either may be NULL, not both.
+ * Pillow's order and skips are kept (the uint8 intermediate makes them visible): the horizontal pass first, its result stored
+ * as uint8 [N,H,out_w,3] in the handle's workspace, then the vertical pass; a pass whose dimension already matches is skipped and
+ * the bytes are copied.  One read of each frame serves both filters.  Rows are staged 16 bytes per lane when W*3, item_stride and
+ * frames are multiples of 16, bytewise otherwise (decided per call).  The tables are cached on the handle per (input size, output
+ * size, filter), the least recently used of 16 replaced.  relax_resize_frames itself keeps its own 224-only kernels. */
+int relax_resize_frames_ex(relax_handle* h, const uint8_t* frames, int64_t item_stride, int N, int H, int W, int out_h, int out_w,
+                           uint8_t* out_bilinear, uint8_t* out_lanczos, relax_stream stream);
+
+/* relax_resize_residual at a runtime output size: out_bilinear / out_lanczos uint8 [T,out_h,out_w,3] = what
+ * relax_resize_frames_ex returns for the image |next - orig|, residual uint8 [T,H,W,3] contiguous.  Any of the three may be NULL,
+ * not all.  relax_resize_residual's contract holds unchanged: `residual` must not overlap `orig` or `next`, and rows move 16 bytes
+ * per lane only when W*3, pair_stride and all of orig, next and a non-NULL residual are multiples of 16 (an odd residual pointer
+ * alone puts the whole call on the bytewise path). */
+int relax_resize_residual_ex(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
+                             int out_h, int out_w, uint8_t* out_bilinear, uint8_t* out_lanczos, uint8_t* residual,
+                             relax_stream stream);
+
 /* ---- stage B: backbones ---------------------------------------------------------------------- */
 /* ResNet-50 on N fragments (uint8 [N,224,224,3] BGR).  One forward per image yields everything
  * the reference gets from 15 hooked forwards + 1 avgpool forward:

@@ -561,6 +561,83 @@ void options_from_env(GemmOptions& o, const std::function<const char*(const char
     }
 }
 
+// ---- Pillow's 8-bit resample tables ------------------------------------------------------------------------------------------------------
+static double filt_bilinear(double x) {
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+static double sinc(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return sin(x) / x;
+}
+static double filt_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? sinc(x) * sinc(x / 3) : 0.0; }
+
+constexpr int kResizePrecisionBits = 32 - 8 - 2;
+
+int resize_ksize(int in_size, int out_size, int filt) {
+    const double scale = (double)in_size / out_size;
+    const double support = (filt == 0 ? 1.0 : 3.0) * (scale < 1.0 ? 1.0 : scale);
+    return (int)ceil(support) * 2 + 1;
+}
+
+void resize_table(int in_size, int out_size, int filt, int32_t* bounds, int32_t* coeffs) {
+    double (*f)(double) = filt == 0 ? filt_bilinear : filt_lanczos;
+    const double support0 = filt == 0 ? 1.0 : 3.0;
+    const double scale = (double)in_size / out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = support0 * filterscale;
+    const int ksize = (int)ceil(support) * 2 + 1;
+    std::memset(coeffs, 0, sizeof(int32_t) * (size_t)out_size * ksize);
+    const double ss = 1.0 / filterscale;
+    std::vector<double> k((size_t)ksize);
+    for (int xx = 0; xx < out_size; ++xx) {
+        const double center = (xx + 0.5) * scale;
+        double ww = 0.0;
+        int xmin = (int)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int xmax = (int)(center + support + 0.5);
+        if (xmax > in_size) xmax = in_size;
+        xmax -= xmin;
+        for (int x = 0; x < xmax; ++x) {
+            const double w = f((x + xmin - center + 0.5) * ss);
+            k[x] = w;
+            ww += w;
+        }
+        for (int x = 0; x < xmax; ++x) {
+            if (ww != 0.0) k[x] /= ww;
+            const double v = k[x];
+            coeffs[(size_t)xx * ksize + x] = v < 0 ? (int)(-0.5 + v * (1 << kResizePrecisionBits)) : (int)(0.5 + v * (1 << kResizePrecisionBits));
+        }
+        bounds[xx * 2] = xmin;
+        bounds[xx * 2 + 1] = xmax;
+    }
+}
+
+bool resize_output_size(int H, int W, int size, int* out_h, int* out_w, std::string& err) {
+    char buf[160];
+    const char* bad = nullptr;
+    int v = 0, lim = kResizeMaxIn;
+    if (H < 1 || H > kResizeMaxIn) bad = "H", v = H;
+    else if (W < 1 || W > kResizeMaxIn) bad = "W", v = W;
+    else if (size < 1 || size > kResizeMaxOut) bad = "size", v = size, lim = kResizeMaxOut;
+    if (bad) {
+        std::snprintf(buf, sizeof buf, "%s=%d outside 1..%d", bad, v, lim);
+        err = buf;
+        return false;
+    }
+    const int64_t shorter = W <= H ? W : H, longer = W <= H ? H : W;
+    const int64_t new_long = (int64_t)size * longer / shorter;
+    if (new_long > kResizeMaxOut) {
+        std::snprintf(buf, sizeof buf, "size=%d makes the longer side %lld of %d x %d, above %d", size, (long long)new_long, H, W, kResizeMaxOut);
+        err = buf;
+        return false;
+    }
+    *out_h = W <= H ? (int)new_long : size;
+    *out_w = W <= H ? size : (int)new_long;
+    return true;
+}
+
 }  // namespace host
 }  // namespace relax
 

@@ -99,6 +99,21 @@ struct TailSplit {
 };
 TailSplit choose_tail_split(int ntiles, int slots, int nk, int min_steps, bool can_split);
 
+// ---- Pillow's 8-bit resample on the host (resize.hip, resize_any.hip; relax_resize_table, relax_resize_output_size) --------------------------
+// The table of one pass, in_size -> out_size samples under filter 0 (BILINEAR, support 1) or 1 (LANCZOS, support 3): libImaging/Resample.c's
+// precompute_coeffs for the box (0, in_size) + normalize_coeffs_8bpc, in the same double arithmetic - per output sample its first tap and tap
+// count (bounds [out_size][2]) and its taps as 22-bit fixed point (coeffs [out_size][ksize], zero behind the count).
+constexpr int kResizeMaxOut = 2048;    // output height / width (RELAX_RESIZE_MAX_OUT)
+constexpr int kResizeMaxIn = 16384;    // input height, and in_size of a table (RELAX_RESIZE_MAX_IN_H)
+int resize_ksize(int in_size, int out_size, int filt);
+void resize_table(int in_size, int out_size, int filt, int32_t* bounds, int32_t* coeffs);
+// The output size transforms.Resize(size) with an int gives a PIL image of H x W (torchvision's _compute_resized_output_size): the shorter
+// side becomes `size`, the longer int(size * long / short); W is the shorter side when W <= H.  size * long stays below 2^26 inside the
+// limits (H, W 1..kResizeMaxIn; size 1..kResizeMaxOut), so Python's correctly rounded true division cannot round a quotient with a
+// fraction (at least 1 / short away from the next integer) up to that integer - that takes quotient * short near 2^53 -, and the integer division
+// here is int() of Python's double.  false and a message naming the value: H, W or size outside the limits, or a longer side above kResizeMaxOut.
+bool resize_output_size(int H, int W, int size, int* out_h, int* out_w, std::string& err);
+
 // ---- the options table: every relax_set_option / relax_get_option key once ------------------------------------------------------------------
 // How a row takes a value: as given; != 0; a non-positive value becomes `a`; one of {a, b}; the closed range [a, b].  The last two refuse
 // anything else with "relax_set_option: <key> must be <must_be>" and leave the stored value as it was.

@@ -300,6 +300,16 @@ struct ResizeTable {
     int32_t* coeffs = nullptr;  // device [224][ksize]: 22-bit fixed point
 };
 
+// ... and of the any-size entries (resize_any.hip), per (input size, output size, filter): coeffs and bounds share one allocation; the
+// least recently used of the kResizeAnyCache entries is replaced (a call needs at most four)
+struct ResizeAnyTable {
+    int in_size = 0, out_size = 0, filt = 0, kstride = 0;
+    int32_t* coeffs = nullptr;  // device [out_size][kstride]: the table's rows padded with zeros to a multiple of four taps (16-byte rows)
+    int32_t* bounds = nullptr;  // device [out_size][2], behind coeffs
+    uint64_t used = 0;          // relax_handle::resize_any_clock of the last call that read it
+};
+constexpr int kResizeAnyCache = 16;
+
 // ---- event profiling ----------------------------------------------------------------------------
 struct ProfSpan {
     hipEvent_t start, stop;
@@ -343,6 +353,8 @@ struct relax_handle {
     relax::HeadW head;
     relax::HeadTrain head_train;
     std::vector<relax::ResizeTable> resize_tables;
+    relax::ResizeAnyTable resize_any_cache[relax::kResizeAnyCache];
+    uint64_t resize_any_clock = 0;
     relax::ResNet50W rn;
     relax::VitW vit;
     relax::VggW vgg;
@@ -487,7 +499,8 @@ int launch_nhwc_to_nchw(relax_handle* h, const float* x, float* y, int Nimg, int
 // model drivers
 void free_resnet(relax_handle* h);
 void free_vit(relax_handle* h);
-void free_resize(relax_handle* h);
+void free_resize(relax_handle* h);       // ... which calls
+void free_resize_any(relax_handle* h);   // (resize_any.hip: the any-size table cache)
 void free_head(relax_handle* h);
 void free_head_train(relax_handle* h);
 void free_vgg(relax_handle* h);

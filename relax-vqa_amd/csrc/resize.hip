@@ -5,13 +5,12 @@
 // Pillow (libImaging/Resample.c): separable, horizontal pass first; coefficients are computed in double, normalised,
 // and quantised to 22-bit fixed point; every output is clip8((2^21 + sum(pixel * k)) >> 22); the horizontal result is
 // stored as uint8 before the vertical pass.  The coefficient tables are built on the host with the same double
-// arithmetic and cached per (size, filter); the kernels are exact integer arithmetic, so the result is bit-identical.
+// arithmetic (host::resize_table, which resize_any.hip's any-size kernels share) and cached per (size, filter); the kernels are exact
+// integer arithmetic, so the result is bit-identical.
 // Each frame is read once (both filters share the horizontal read of a row through LDS).
 // relax_resize_residual is the same two passes on the frame difference |next - orig| of a pair (src/main_residual.py:223-231):
 // the difference is taken while the rows are staged, so a pair is read once and the residual image itself reaches HBM only when
 // the caller asks for it.
-#include <cmath>
-
 #include "relax_internal.h"
 
 namespace relax {
@@ -19,53 +18,6 @@ namespace relax {
 constexpr int OUT = RELAX_TARGET;  // 224
 constexpr int PRECISION_BITS = 32 - 8 - 2;
 constexpr int ROWS_PER_BLOCK = 4;
-
-static double filt_bilinear(double x) {
-    if (x < 0.0) x = -x;
-    return x < 1.0 ? 1.0 - x : 0.0;
-}
-static double sinc(double x) {
-    if (x == 0.0) return 1.0;
-    x = x * M_PI;
-    return sin(x) / x;
-}
-static double filt_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? sinc(x) * sinc(x / 3) : 0.0; }
-
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc for box (0, in_size)
-static void build_table(int in_size, int filt, std::vector<int32_t>& bounds, std::vector<int32_t>& coeffs, int* ksize_out) {
-    double (*f)(double) = filt == 0 ? filt_bilinear : filt_lanczos;
-    const double support0 = filt == 0 ? 1.0 : 3.0;
-    const double scale = (double)in_size / OUT;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = support0 * filterscale;
-    const int ksize = (int)ceil(support) * 2 + 1;
-    bounds.assign(OUT * 2, 0);
-    coeffs.assign((size_t)OUT * ksize, 0);
-    const double ss = 1.0 / filterscale;
-    std::vector<double> k(ksize);
-    for (int xx = 0; xx < OUT; ++xx) {
-        const double center = (xx + 0.5) * scale;
-        double ww = 0.0;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        for (int x = 0; x < xmax; ++x) {
-            const double w = f((x + xmin - center + 0.5) * ss);
-            k[x] = w;
-            ww += w;
-        }
-        for (int x = 0; x < xmax; ++x) {
-            if (ww != 0.0) k[x] /= ww;
-            const double v = k[x];
-            coeffs[(size_t)xx * ksize + x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS)) : (int)(0.5 + v * (1 << PRECISION_BITS));
-        }
-        bounds[xx * 2] = xmin;
-        bounds[xx * 2 + 1] = xmax;
-    }
-    *ksize_out = ksize;
-}
 
 __device__ inline uint8_t clip8(int v) {
     v >>= PRECISION_BITS;
@@ -170,11 +122,12 @@ static int get_table(relax_handle* h, int in_size, int filt, const ResizeTable**
             *out = &t;
             return RELAX_OK;
         }
-    std::vector<int32_t> bounds, coeffs;
     ResizeTable t;
     t.in_size = in_size;
     t.filt = filt;
-    build_table(in_size, filt, bounds, coeffs, &t.ksize);
+    t.ksize = host::resize_ksize(in_size, OUT, filt);   // Pillow's precompute_coeffs + normalize_coeffs_8bpc (host_logic.cpp)
+    std::vector<int32_t> bounds((size_t)OUT * 2), coeffs((size_t)OUT * t.ksize);
+    host::resize_table(in_size, OUT, filt, bounds.data(), coeffs.data());
     RELAX_HIP_CHECK(h, hipMalloc(reinterpret_cast<void**>(&t.bounds), bounds.size() * sizeof(int32_t)));
     RELAX_HIP_CHECK(h, hipMalloc(reinterpret_cast<void**>(&t.coeffs), coeffs.size() * sizeof(int32_t)));
     RELAX_HIP_CHECK(h, hipMemcpy(t.bounds, bounds.data(), bounds.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -190,6 +143,7 @@ void free_resize(relax_handle* h) {
         (void)hipFree(t.coeffs);
     }
     h->resize_tables.clear();
+    free_resize_any(h);
     if (h->resize_ws.p) (void)hipFree(h->resize_ws.p);
     h->resize_ws = DevBuf();
 }

@@ -480,16 +480,73 @@ class RelaxEngine:
                     "relax_resize_frames")
         return ob, ol
 
-    def residual_resize(self, frames, bilinear=True, lanczos=True, want_residual=False, out_bilinear=None, out_lanczos=None):
+    def resize_output_size(self, H, W, size):
+        """(out_h, out_w) that transforms.Resize(size), size an int, gives a PIL image of H x W: the shorter side becomes size, the
+        longer int(size * long / short) (torchvision's _compute_resized_output_size; relax_resize_output_size)."""
+        oh, ow = C.c_int(0), C.c_int(0)
+        rc = self.lib.relax_resize_output_size(int(H), int(W), int(size), C.byref(oh), C.byref(ow))
+        if rc != 0:
+            raise RuntimeError(f"relax_resize_output_size failed ({rc}): {self.lib.relax_last_error(None).decode()}")
+        return oh.value, ow.value
+
+    def _resize_target(self, H, W, size):
+        """size: an int (the shorter-side rule of resize_output_size) or an (h, w) pair -> (out_h, out_w)"""
+        if isinstance(size, (int, np.integer)):
+            return self.resize_output_size(H, W, size)
+        oh, ow = size
+        return int(oh), int(ow)
+
+    def _resize_outputs(self, what, n, oh, ow, bilinear, lanczos, out_bilinear, out_lanczos):
+        outs = []
+        for want, given in ((bilinear, out_bilinear), (lanczos, out_lanczos)):
+            o = (given if given is not None else torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=self.device)) if want else None
+            if o is not None and (o.dtype != torch.uint8 or tuple(o.shape) != (n, oh, ow, 3) or not o.is_contiguous() or not o.is_cuda):
+                raise ValueError(f"{what}: output buffers must be contiguous device uint8 [{n},{oh},{ow},3]")
+            outs.append(o)
+        return outs
+
+    def resize_frames_to(self, frames, size, bilinear=True, lanczos=True, out_bilinear=None, out_lanczos=None):
+        """frames uint8 [N,H,W,3] -> (bilinear, lanczos) uint8 [N,out_h,out_w,3] each (None if not requested), bit-identical to
+        PIL's Image.resize((out_w,out_h), BILINEAR / LANCZOS), down, up or mixed (relax_resize_frames_ex).  size: an int - the
+        shorter side becomes size, as transforms.Resize(size) does it (resize_output_size) - or an (h, w) pair.  Items may be
+        strided as in resize_frames."""
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        frames = frames.to(self.device, non_blocking=True)
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError(f"frames must be uint8 [N,H,W,3], got {frames.dtype} {tuple(frames.shape)}")
+        N, H, W, _ = frames.shape
+        oh, ow = self._resize_target(H, W, size)
+        if frames.stride()[1:] != (W * 3, 3, 1):      # items may be strided (e.g. clip[:, 0]); pixels must be packed
+            frames = frames.contiguous()
+        item_stride = frames.stride(0) if N > 1 else H * W * 3
+        ob, ol = self._resize_outputs("resize_frames_to", N, oh, ow, bilinear, lanczos, out_bilinear, out_lanczos)
+        self._check(self.lib.relax_resize_frames_ex(self.h, _ptr(frames), item_stride, N, H, W, oh, ow, _ptr(ob), _ptr(ol), _stream()),
+                    "relax_resize_frames_ex")
+        return ob, ol
+
+    def residual_resize(self, frames, bilinear=True, lanczos=True, want_residual=False, out_bilinear=None, out_lanczos=None, size=None):
         """frames uint8 [T,2,H,W,3] as fragment_pairs takes them -> (bilinear, lanczos, residual): the two uint8 [T,224,224,3]
         resizes of the WHOLE frame difference cv2.absdiff(next, orig) (src/main_residual.py:223-231), bit-identical to
         resize_frames on that image, and the uint8 [T,H,W,3] difference image itself; None for any output not requested.
-        One launch reads each pair once (relax_resize_residual); without want_residual the difference never reaches memory."""
+        One launch reads each pair once (relax_resize_residual); without want_residual the difference never reaches memory.
+        size (None: 224 x 224, the call above unchanged): an int or an (h, w) pair as resize_frames_to takes it -> outputs
+        [T,out_h,out_w,3] through relax_resize_residual_ex."""
         frames = self._dev_u8(frames)
         if frames.dim() != 5 or frames.shape[1] != 2 or frames.shape[4] != 3:
             raise ValueError(f"frames must be [T,2,H,W,3], got {tuple(frames.shape)}")
         T, _, H, W, _ = frames.shape
         dev = self.device
+        if size is not None:
+            oh, ow = self._resize_target(H, W, size)
+            ob, ol = self._resize_outputs("residual_resize", T, oh, ow, bilinear, lanczos, out_bilinear, out_lanczos)
+            res = torch.empty((T, H, W, 3), dtype=torch.uint8, device=dev) if want_residual else None
+            fb = H * W * 3
+            base = frames.data_ptr()
+            rc = self.lib.relax_resize_residual_ex(self.h, C.c_void_p(base), C.c_void_p(base + fb), 2 * fb, T, H, W, oh, ow, _ptr(ob),
+                                                   _ptr(ol), _ptr(res), _stream())
+            self._check(rc, "relax_resize_residual_ex")
+            return ob, ol, res
         ob = (out_bilinear if out_bilinear is not None else
               torch.empty((T, TARGET, TARGET, 3), dtype=torch.uint8, device=dev)) if bilinear else None
         ol = (out_lanczos if out_lanczos is not None else
@@ -857,6 +914,17 @@ class RelaxEngine:
         _, vp = self.vit_features(lan, tokens=False, pooled=True)
         return ls, vp
 
+    def whole_frame_vit_canvas(self, frames, size, tokens=False, pooled=True, attention=False):
+        """frames uint8 [N,H,W,3] BGR -> vit_features of the frames LANCZOS-resized to the canvas `size` (an int: the shorter side, as
+        transforms.Resize(size); or an (h, w) pair) on the GPU: the reference's whole-frame ViT input (img.resize(..., LANCZOS),
+        src/extractor/visualise_vit_layer.py:466-473) at a size of the caller's choosing, e.g. 1080 x 1920 -> 270 x 480 = 481 tokens.
+        size=(224, 224) is whole_frame_features' ViT half, through the same 224 kernels."""
+        if not isinstance(size, (int, np.integer)) and tuple(int(v) for v in size) == (TARGET, TARGET):
+            lan = self.resize_frames(frames, bilinear=False, lanczos=True)[1]
+        else:
+            lan = self.resize_frames_to(frames, size, bilinear=False, lanczos=True)[1]
+        return self.vit_features(lan, tokens=tokens, pooled=pooled, attention=attention)
+
     # ---- fragment-free ablation rows (src/main_residual.py, src/main_layer.py) ---------------------------------
     RESIDUAL_NAMES = ("frame_diff", "optical_flow")
 
@@ -890,15 +958,26 @@ class RelaxEngine:
             blocks.append(("vgg16", self.vgg16_features(bil, layer_stack=False, pool=True)[1]))
         return blocks
 
-    def whole_residual_features(self, frames, residual_name="frame_diff", resnet=True, vit=True, vgg16=False, flow_images=None):
+    def whole_residual_features(self, frames, residual_name="frame_diff", resnet=True, vit=True, vgg16=False, flow_images=None, vit_size=None):
         """frames uint8 [T,2,H,W,3] -> dict of per-frame fp32 device tensors, the rows src/main_residual.py:221-254 saves per
         video: the WHOLE residual image (residual_name 'frame_diff': cv2.absdiff(next, orig); 'optical_flow': the flow image,
         flow_images uint8 [T,H,W,3] or Farneback on the GPU) resized to 224 x 224 and pooled:
           'resnet' [T,2051] avgpool | mean, max, std      'vgg16' [T,4099] fc2 | mean, max, std      (BILINEAR bytes)
-          'vit'    [T,3*dim] token mean | max | std                                                  (LANCZOS bytes)"""
+          'vit'    [T,3*dim] token mean | max | std                                                  (LANCZOS bytes)
+        vit_size (None: 224 x 224, the calls above unchanged): the ViT's canvas, an int or an (h, w) pair as resize_frames_to takes it."""
         self._check_residual_name(residual_name)
         self._check_backbones(resnet, vit, vgg16)
-        bil, lan = self._whole_residual_inputs(frames, residual_name, resnet or vgg16, vit, flow_images)
+        if vit_size is None or not vit:
+            bil, lan = self._whole_residual_inputs(frames, residual_name, resnet or vgg16, vit, flow_images)
+            return dict(self._pool_blocks(bil, lan, resnet, vit, vgg16))
+        # the ViT's input on its own canvas (a second pass over the pairs); the BILINEAR 224 x 224 bytes of the other backbones as before
+        if residual_name == "optical_flow" and flow_images is None:
+            _, flow_images = self.optical_flow(frames)
+        bil = self._whole_residual_inputs(frames, residual_name, True, False, flow_images)[0] if resnet or vgg16 else None
+        if residual_name == "frame_diff":
+            lan = self.residual_resize(frames, bilinear=False, lanczos=True, size=vit_size)[1]
+        else:
+            lan = self.resize_frames_to(flow_images, vit_size, bilinear=False, lanczos=True)[1]
         return dict(self._pool_blocks(bil, lan, resnet, vit, vgg16))
 
     def whole_residual_vectors(self, clips, residual_name="frame_diff", resnet=True, vit=True, vgg16=False, flow_images=None,
