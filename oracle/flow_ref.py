@@ -27,16 +27,16 @@ def cv_round(x):
     return int(np.rint(x))   # round half to even, like cvRound (lrint)
 
 
-def gaussian_kernel(ksize, sigma):
+def gaussian_kernel(ksize, sigma, dtype=F32):
     """cv::getGaussianKernel(ksize, sigma, CV_32F)."""
     small = {1: [1.0], 3: [0.25, 0.5, 0.25], 5: [0.0625, 0.25, 0.375, 0.25, 0.0625],
              7: [0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125]}
     if ksize <= 7 and ksize % 2 == 1 and sigma <= 0:
-        return np.array(small[ksize], dtype=F32)
+        return np.array(small[ksize], dtype=dtype)
     s = sigma if sigma > 0 else ((ksize - 1) * 0.5 - 1) * 0.3 + 0.8
     x = np.arange(ksize, dtype=np.float64) - (ksize - 1) * 0.5
-    k = np.exp(-0.5 / (s * s) * x * x).astype(F32)
-    return (k * F32(1.0 / float(k.astype(np.float64).sum()))).astype(F32)
+    k = np.exp(-0.5 / (s * s) * x * x).astype(dtype)
+    return (k * dtype(1.0 / float(k.astype(np.float64).sum()))).astype(dtype)
 
 
 def _reflect101(idx, n):
@@ -44,9 +44,9 @@ def _reflect101(idx, n):
     return np.where(idx >= n, 2 * (n - 1) - idx, idx)
 
 
-def gaussian_blur(img, ksize, sigma):
+def gaussian_blur(img, ksize, sigma, dtype=F32):
     """Separable float32 Gaussian, BORDER_REFLECT_101 (cv::GaussianBlur default)."""
-    k = gaussian_kernel(ksize, sigma)
+    k = gaussian_kernel(ksize, sigma, dtype)
     r = ksize // 2
     h, w = img.shape
     cols = _reflect101(np.arange(-r, w + r), w)
@@ -62,7 +62,7 @@ def gaussian_blur(img, ksize, sigma):
     return out
 
 
-def resize_linear(img, out_h, out_w):
+def resize_linear(img, out_h, out_w, dtype=F32):
     """cv::resize(..., INTER_LINEAR) on float32 [H,W] or [H,W,C] (no antialiasing)."""
     h, w = img.shape[:2]
     if (h, w) == (out_h, out_w):
@@ -70,9 +70,9 @@ def resize_linear(img, out_h, out_w):
 
     def taps(n_in, n_out):
         scale = n_in / n_out
-        f = ((np.arange(n_out, dtype=np.float64) + 0.5) * scale - 0.5).astype(F32)   # OpenCV: (float)((dx+0.5)*scale-0.5)
+        f = ((np.arange(n_out, dtype=np.float64) + 0.5) * scale - 0.5).astype(dtype)   # OpenCV: (float)((dx+0.5)*scale-0.5)
         s = np.floor(f).astype(np.int64)
-        a = (f - s.astype(F32)).astype(F32)
+        a = (f - s.astype(dtype)).astype(dtype)
         lo = s < 0
         s[lo], a[lo] = 0, 0
         hi = s >= n_in - 1
@@ -85,20 +85,20 @@ def resize_linear(img, out_h, out_w):
         ax_, ay_ = ax[None, :, None], ay[:, None, None]
     else:
         ax_, ay_ = ax[None, :], ay[:, None]
-    hor = img[:, sx0] * (F32(1) - ax_) + img[:, sx1] * ax_
-    return (hor[sy0] * (F32(1) - ay_) + hor[sy1] * ay_).astype(F32)
+    hor = img[:, sx0] * (dtype(1) - ax_) + img[:, sx1] * ax_
+    return (hor[sy0] * (dtype(1) - ay_) + hor[sy1] * ay_).astype(dtype)
 
 
 # ---- Farneback ---------------------------------------------------------------------------------------------------
-def _prepare_gaussian(n, sigma):
+def _prepare_gaussian(n, sigma, dtype=F32):
     if sigma < np.finfo(np.float32).eps:
         sigma = n * 0.3
     x = np.arange(-n, n + 1, dtype=np.float64)
-    g = np.exp(-x * x / (2 * sigma * sigma)).astype(F32)
+    g = np.exp(-x * x / (2 * sigma * sigma)).astype(dtype)
     s = 1.0 / float(g.astype(np.float64).sum())
-    g = (g.astype(np.float64) * s).astype(F32)
-    xg = (x * g.astype(np.float64)).astype(F32)
-    xxg = (x * x * g.astype(np.float64)).astype(F32)
+    g = (g.astype(np.float64) * s).astype(dtype)
+    xg = (x * g.astype(np.float64)).astype(dtype)
+    xxg = (x * x * g.astype(np.float64)).astype(dtype)
     G = np.zeros((6, 6))
     gd = g.astype(np.float64)
     for yy in range(-n, n + 1):
@@ -115,9 +115,9 @@ def _prepare_gaussian(n, sigma):
     return g[n:], xg[n:], xxg[n:], inv[1, 1], inv[0, 3], inv[3, 3], inv[5, 5]
 
 
-def poly_exp(img, n=5, sigma=1.2):
+def poly_exp(img, n=5, sigma=1.2, dtype=F32):
     """FarnebackPolyExp: float32 [H,W] -> float32 [H,W,5] (r2..r6 in OpenCV's storage order)."""
-    g, xg, xxg, ig11, ig03, ig33, ig55 = _prepare_gaussian(n, sigma)
+    g, xg, xxg, ig11, ig03, ig33, ig55 = _prepare_gaussian(n, sigma, dtype)
     h, w = img.shape
     ys = np.arange(h)
     t0 = img * g[0]
@@ -148,7 +148,7 @@ def poly_exp(img, n=5, sigma=1.2):
         b3 += ((r1[:, p] + r1[:, m]) * g[k]).astype(np.float64)
         b6 += ((r1[:, p] - r1[:, m]) * xg[k]).astype(np.float64)
         b5 += ((r2[:, p] + r2[:, m]) * g[k]).astype(np.float64)
-    out = np.empty((h, w, 5), dtype=F32)
+    out = np.empty((h, w, 5), dtype=dtype)
     out[..., 1] = b2 * ig11
     out[..., 0] = b3 * ig11
     out[..., 3] = b1 * ig03 + b4 * ig33
@@ -157,43 +157,44 @@ def poly_exp(img, n=5, sigma=1.2):
     return out
 
 
-_BORDER = np.array([0.14, 0.14, 0.4472, 0.4472, 0.4472], dtype=F32)
+_BORDER = (0.14, 0.14, 0.4472, 0.4472, 0.4472)
 
 
-def update_matrices(R0, R1, flow):
-    """FarnebackUpdateMatrices over the whole image -> float32 [H,W,5]."""
+def update_matrices(R0, R1, flow, dtype=F32):
+    """FarnebackUpdateMatrices over the whole image -> dtype [H,W,5]."""
     h, w = flow.shape[:2]
-    xs = np.arange(w, dtype=F32)[None, :]
-    ys = np.arange(h, dtype=F32)[:, None]
+    border = np.array(_BORDER, dtype=dtype)
+    xs = np.arange(w, dtype=dtype)[None, :]
+    ys = np.arange(h, dtype=dtype)[:, None]
     dx, dy = flow[..., 0], flow[..., 1]
     fx, fy = xs + dx, ys + dy
     x1, y1 = np.floor(fx).astype(np.int64), np.floor(fy).astype(np.int64)
-    fx, fy = (fx - x1).astype(F32), (fy - y1).astype(F32)
+    fx, fy = (fx - x1).astype(dtype), (fy - y1).astype(dtype)
     ok = (x1 >= 0) & (x1 < w - 1) & (y1 >= 0) & (y1 < h - 1)
     xc, yc = np.clip(x1, 0, w - 2), np.clip(y1, 0, h - 2)
     a00, a01, a10, a11 = (1 - fx) * (1 - fy), fx * (1 - fy), (1 - fx) * fy, fx * fy
     samp = (a00[..., None] * R1[yc, xc] + a01[..., None] * R1[yc, xc + 1] +
-            a10[..., None] * R1[yc + 1, xc] + a11[..., None] * R1[yc + 1, xc + 1]).astype(F32)
-    r2 = np.where(ok, samp[..., 0], F32(0))
-    r3 = np.where(ok, samp[..., 1], F32(0))
-    r4 = np.where(ok, (R0[..., 2] + samp[..., 2]) * F32(0.5), R0[..., 2])
-    r5 = np.where(ok, (R0[..., 3] + samp[..., 3]) * F32(0.5), R0[..., 3])
-    r6 = np.where(ok, (R0[..., 4] + samp[..., 4]) * F32(0.25), R0[..., 4] * F32(0.5))
-    r2 = (R0[..., 0] - r2) * F32(0.5)
-    r3 = (R0[..., 1] - r3) * F32(0.5)
+            a10[..., None] * R1[yc + 1, xc] + a11[..., None] * R1[yc + 1, xc + 1]).astype(dtype)
+    r2 = np.where(ok, samp[..., 0], dtype(0))
+    r3 = np.where(ok, samp[..., 1], dtype(0))
+    r4 = np.where(ok, (R0[..., 2] + samp[..., 2]) * dtype(0.5), R0[..., 2])
+    r5 = np.where(ok, (R0[..., 3] + samp[..., 3]) * dtype(0.5), R0[..., 3])
+    r6 = np.where(ok, (R0[..., 4] + samp[..., 4]) * dtype(0.25), R0[..., 4] * dtype(0.5))
+    r2 = (R0[..., 0] - r2) * dtype(0.5)
+    r3 = (R0[..., 1] - r3) * dtype(0.5)
     r2 = r2 + r4 * dy + r6 * dx
     r3 = r3 + r6 * dy + r5 * dx
-    sx = np.ones(w, dtype=F32)
-    sy = np.ones(h, dtype=F32)
+    sx = np.ones(w, dtype=dtype)
+    sy = np.ones(h, dtype=dtype)
     for i in range(min(5, w)):
-        sx[i] *= _BORDER[i]
-        sx[w - 1 - i] *= _BORDER[i]
+        sx[i] *= border[i]
+        sx[w - 1 - i] *= border[i]
     for i in range(min(5, h)):
-        sy[i] *= _BORDER[i]
-        sy[h - 1 - i] *= _BORDER[i]
-    scale = (sy[:, None] * sx[None, :]).astype(F32)
+        sy[i] *= border[i]
+        sy[h - 1 - i] *= border[i]
+    scale = (sy[:, None] * sx[None, :]).astype(dtype)
     r2, r3, r4, r5, r6 = (v * scale for v in (r2, r3, r4, r5, r6))
-    M = np.empty((h, w, 5), dtype=F32)
+    M = np.empty((h, w, 5), dtype=dtype)
     M[..., 0] = r4 * r4 + r6 * r6
     M[..., 1] = (r4 + r5) * r6
     M[..., 2] = r5 * r5 + r6 * r6
@@ -202,7 +203,7 @@ def update_matrices(R0, R1, flow):
     return M
 
 
-def update_flow_blur(M, block_size=15):
+def update_flow_blur(M, block_size=15, dtype=F32):
     """FarnebackUpdateFlow_Blur: box filter (replicated border) of M in double, then the 2x2 solve -> flow [H,W,2]."""
     m = block_size // 2
     h, w = M.shape[:2]
@@ -214,23 +215,32 @@ def update_flow_blur(M, block_size=15):
     b = (cs[:, block_size:] - cs[:, :-block_size]) * (1.0 / (block_size * block_size))
     g11, g12, g22, h1, h2 = (b[..., i] for i in range(5))
     idet = 1.0 / (g11 * g22 - g12 * g12 + 1e-3)
-    flow = np.empty((h, w, 2), dtype=F32)
+    flow = np.empty((h, w, 2), dtype=dtype)
     flow[..., 0] = (g11 * h2 - g12 * h1) * idet
     flow[..., 1] = (g22 * h1 - g12 * h2) * idet
     return flow
 
 
-def farneback(prev_gray, next_gray, pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2):
-    """cv2.calcOpticalFlowFarneback(prev, next, None, .5, 3, 15, 3, 5, 1.2, 0) -> float32 [H,W,2]."""
-    h0, w0 = prev_gray.shape
+def pyramid_levels(h0, w0, pyr_scale=0.5, levels=3):
+    """How many levels below the full-size one calcOpticalFlowFarneback uses: it stops before a side falls under 32 pixels."""
     k, scale = 0, 1.0
     while k < levels:
         scale *= pyr_scale
         if w0 * scale < 32 or h0 * scale < 32:
             break
         k += 1
-    levels = k
-    imgs = [prev_gray.astype(F32), next_gray.astype(F32)]
+    return k
+
+
+def farneback(prev_gray, next_gray, pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2, dtype=F32,
+              update_matrices=update_matrices):
+    """cv2.calcOpticalFlowFarneback(prev, next, None, .5, 3, 15, 3, 5, 1.2, 0) -> float32 [H,W,2].
+    dtype: np.float32 restates OpenCV's float arithmetic; np.float64 runs every float32 step in double (the reference the GPU parity gates
+    measure against).  update_matrices: a replacement for this module's function, called as f(R0, R1, flow, dtype) - the tests' deliberately
+    wrong variants go in here."""
+    h0, w0 = prev_gray.shape
+    levels = pyramid_levels(h0, w0, pyr_scale, levels)
+    imgs = [prev_gray.astype(dtype), next_gray.astype(dtype)]
     prev_flow = None
     for k in range(levels, -1, -1):
         scale = pyr_scale ** k
@@ -238,15 +248,15 @@ def farneback(prev_gray, next_gray, pyr_scale=0.5, levels=3, winsize=15, iterati
         smooth = max(cv_round(sigma * 5) | 1, 3)
         w, h = cv_round(w0 * scale), cv_round(h0 * scale)
         if prev_flow is None:
-            flow = np.zeros((h, w, 2), dtype=F32)
+            flow = np.zeros((h, w, 2), dtype=dtype)
         else:
-            flow = resize_linear(prev_flow, h, w) * F32(1.0 / pyr_scale)
-        R = [poly_exp(resize_linear(gaussian_blur(im, smooth, sigma), h, w), poly_n, poly_sigma) for im in imgs]
-        M = update_matrices(R[0], R[1], flow)
+            flow = resize_linear(prev_flow, h, w, dtype) * dtype(1.0 / pyr_scale)
+        R = [poly_exp(resize_linear(gaussian_blur(im, smooth, sigma, dtype), h, w, dtype), poly_n, poly_sigma, dtype) for im in imgs]
+        M = update_matrices(R[0], R[1], flow, dtype)
         for i in range(iterations):
-            flow = update_flow_blur(M, winsize)
+            flow = update_flow_blur(M, winsize, dtype)
             if i < iterations - 1:
-                M = update_matrices(R[0], R[1], flow)
+                M = update_matrices(R[0], R[1], flow, dtype)
         prev_flow = flow
     return prev_flow
 

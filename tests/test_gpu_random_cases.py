@@ -87,7 +87,8 @@ def _smooth_pair(h, w, seed):
 @given(h=st.integers(16, 140), w=st.integers(16, 180), pairs=st.integers(1, 2), seed=st.integers(0, 2 ** 31 - 1))
 def test_flow_on_small_and_odd_frames(h, w, pairs, seed):
     """Frames from 16 pixels up: 1 to 3 pyramid levels instead of 4, rows shorter than a workgroup, odd sizes, blur / box windows wider
-    than the image (border replication everywhere)."""
+    than the image (border replication everywhere).  The content is smooth and moves 1 to 3 pixels; large motion, hard edges, noise,
+    saturated regions and every hue sector are in tests/test_gpu_flow_content.py."""
     ab = [_smooth_pair(h, w, seed + i) for i in range(pairs)]
     frames = np.stack([np.stack(p) for p in ab])
     flow, _ = engine().optical_flow(torch.from_numpy(frames).cuda(), want_flow=True, want_image=False)
