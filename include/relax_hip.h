@@ -752,6 +752,44 @@ int relax_yuv_coefficients(int matrix, int full_range, int32_t* out);
 int relax_yuv_to_bgr(const uint8_t* src, int64_t src_bytes, const int64_t* items, int N, int layout, int H, int W, int matrix,
                      int full_range, uint8_t* out, int64_t out_bytes, int32_t* status, relax_stream stream);
 
+/* ---- greyscale screen ----------------------------------------------------------------------------- */
+/* The pixel rule of the reference's src/data_processing/check_greyscale.py (is_greyscale_image, :25-35): a BGR frame is
+ * greyscale iff the largest b-g, b-r and g-r over its pixels are all <= 3 - where b, g and r are uint8, so each difference
+ * WRAPS modulo 256 before the maximum is taken (b - g = -1 counts as 255).  Both entries reduce every frame to one record of
+ * RELAX_GREYSCALE_RECORD_WORDS int32:
+ *     [0..2]  max over the pixels of (b-g) mod 256, (b-r) mod 256, (g-r) mod 256      the reference's rule
+ *     [3..5]  max over the pixels of |b-g|, |b-r|, |g-r|                              the rule without the wrap
+ *     [6]     status: RELAX_YUV_OK, or RELAX_YUV_OUT_OF_RANGE (relax_yuv_greyscale_scan only; the maxima are 0 then)
+ *     [7]     0
+ * so any threshold, under either rule, is a comparison on the record.  Every word of every record is defined by the call,
+ * whatever `out` held; maxima do not depend on the order of arrival, so the records are the same bits on every run.  No handle
+ * and no library state (as relax_yuv_to_bgr): loader threads call them at the same time on their own streams.  Plain vector
+ * loads, a wave and block maximum, one atomicMax per block and word; no inline assembly (csrc/greyscale.hip; the per-lane
+ * arithmetic in csrc/greyscale_core.h, which the CPU tests run on the host). */
+#define RELAX_GREYSCALE_RECORD_WORDS 8
+
+/*   frames  DEVICE uint8: frame n is [H][W][3] BGR with packed rows at frames + n * frame_stride (frame_stride >= H*W*3 bytes when
+ *           N > 1: the frames of a [N,H,W,3] tensor, the slots of a [T,2,H,W,3] clip, or a strided view of either)
+ *   out     DEVICE int32 [N][RELAX_GREYSCALE_RECORD_WORDS]
+ * A frame is read as H*W consecutive pixels, 16 to a lane: three 16-byte loads when the frame's first byte lies at a
+ * 16-byte-aligned address (any W: 48 bytes per lane keep every lane aligned), with the last H*W mod 16 pixels bytewise; a frame at
+ * any other address goes bytewise altogether.  N beyond 65535 is split over launches.
+ * Returns RELAX_ERR_INVALID, with the offending value in relax_last_error(NULL), for H or W outside 1..RELAX_YUV_MAX_DIM,
+ * N < 0, a frame_stride below H*W*3 with N > 1, or a NULL buffer with N > 0 - before anything is launched; RELAX_ERR_HIP if a
+ * launch fails. */
+int relax_greyscale_scan(const uint8_t* frames, int64_t frame_stride, int N, int H, int W, int32_t* out, relax_stream stream);
+
+/* The same records straight from raw YUV frames: each pixel is converted in registers by relax_yuv_to_bgr's arithmetic and goes
+ * into the maxima; no BGR is written.  For every frame the record equals relax_greyscale_scan's on relax_yuv_to_bgr's output
+ * for that frame (no shortcut on U == V == 128: the rule is on the converted BGR).
+ *   src      DEVICE bytes [src_bytes]; offsets  DEVICE int64 [N]: where frame n starts in src
+ *   layout, H, W, matrix, full_range: as relax_yuv_to_bgr, with its 16-byte path under its conditions (W a multiple of 16,
+ *   src + offset 16-byte aligned) and its bytewise path otherwise, per frame
+ * A frame whose range leaves src gets status RELAX_YUV_OUT_OF_RANGE and zero maxima, and is not read; the other frames of the
+ * call are unaffected.  Refusals as relax_yuv_to_bgr's. */
+int relax_yuv_greyscale_scan(const uint8_t* src, int64_t src_bytes, const int64_t* offsets, int N, int layout, int H, int W,
+                             int matrix, int full_range, int32_t* out, relax_stream stream);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* While enabled, every launch of the contraction kernel (GEMM / implicit-GEMM conv) and of the patch-score
  * kernel is bracketed by HIP events on the caller's stream.  relax_profile_read synchronises those events and

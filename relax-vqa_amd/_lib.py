@@ -109,6 +109,8 @@ PROTOTYPES = {
     "relax_yuv_frame_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "relax_yuv_coefficients": (C.c_int, [C.c_int, C.c_int, c_i32p]),
     "relax_yuv_to_bgr": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, C.c_int64, c_vp, c_vp]),
+    "relax_greyscale_scan": (C.c_int, [c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, c_vp, c_vp]),
+    "relax_yuv_greyscale_scan": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp]),
     "relax_profile_enable": (C.c_int, [c_vp, C.c_int]),
     "relax_profile_read": (C.c_int, [c_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_int64)]),

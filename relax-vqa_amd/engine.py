@@ -152,6 +152,24 @@ class RelaxEngine:
             raise RuntimeError(f"relax_yuv_to_bgr failed ({rc}): {self.lib.relax_last_error(None).decode()}")
         return out
 
+    # ---- greyscale screen (data_processing/check_greyscale.py, csrc/greyscale.hip) -------------------------------
+    def greyscale_scan(self, frames):
+        """The reference's is_greyscale_image (src/data_processing/check_greyscale.py:25-35) for many frames at once
+        (relax_greyscale_scan): frames uint8 [N,H,W,3], [T,2,H,W,3], a strided view of either, or [N,H,W] (greyscale by the
+        reference's first branch, nothing launched); a host array is uploaded first.  -> a dict of device tensors - 'records' int32
+        [N,8], 'wrapped' [N,3] (maxima of (b-g, b-r, g-r) mod 256: the reference's rule), 'abs' [N,3] (maxima of the absolute
+        differences), 'status' [N] - with is_greyscale(threshold=3, mode='reference') -> bool [N]."""
+        from .data_processing import check_greyscale
+        if isinstance(frames, np.ndarray):
+            frames = self._dev_u8(frames)
+        return check_greyscale.scan_frames(frames)
+
+    def yuv_greyscale_scan(self, planes, H, W, pixfmt, matrix="bt601"):
+        """greyscale_scan(yuv_to_bgr(planes, H, W, pixfmt, matrix)) in one pass that writes no BGR (relax_yuv_greyscale_scan):
+        each pixel is converted in registers and goes straight into the maxima.  Arguments as yuv_to_bgr's."""
+        from .data_processing import check_greyscale
+        return check_greyscale.scan_yuv_frames(self._dev_u8(planes), H, W, pixfmt, matrix)
+
     # ---- weights ------------------------------------------------------------------------------
     def _marshal_state_dict(self, sd):
         names, arrays = [], []
@@ -303,10 +321,11 @@ class RelaxEngine:
         from . import metrics
         return metrics.evaluate_head(self, features_train, mos_train, features_test, mos_test, config)
 
-    def holdout_protocol(self, features, mos, config=None, n_repeats=21, test_size=0.2, groups=None):
-        """The repeated 80/20 hold-out with medians and the median model; see metrics.holdout_protocol."""
+    def holdout_protocol(self, features, mos, config=None, n_repeats=21, test_size=0.2, groups=None, drop_indices=None):
+        """The repeated 80/20 hold-out with medians and the median model; drop_indices: the rows of a greyscale report, dropped
+        first (metrics.drop_rows).  See metrics.holdout_protocol."""
         from . import metrics
-        return metrics.holdout_protocol(self, features, mos, config, n_repeats, test_size, groups)
+        return metrics.holdout_protocol(self, features, mos, config, n_repeats, test_size, groups, drop_indices)
 
     def load_fitted_head(self, result):
         """load_mlp_head on what fit_head / fine_tune_head returned."""

@@ -6,8 +6,11 @@ Follows the reference's src/model_regression.py:
   main()'s body for one split (:572-613)                                       evaluate_head
   main()'s repeat loop, nan_to_num, medians, median model (:548-697)           holdout_protocol
   split_train_test.process_other's train_test_split of the unique ids          holdout_split
+  the greyscale rows dropped before any of it (split_train_test.py:15-21,49-50, :114-117,144;
+  fine_tune.py:72-75,94; recover_median_train_test.py:23-27,50)                 drop_rows, holdout_protocol(drop_indices=...)
 
-Out of scope, as before: plots, .mat / .csv / log writing, the per-dataset file handling of split_train_test.
+Out of scope, as before: plots, .mat / log writing, and the per-dataset file handling of split_train_test other than the greyscale
+drop (the reports themselves are read and written by data_processing.check_greyscale).
 The pure host rules (split, seeds, median model, summary) have no GPU in them and are tested on the CPU.
 """
 import ctypes as C
@@ -55,6 +58,34 @@ def group_split(groups, test_size=0.2, random_state=0):
     is_test = np.zeros(ids.size, dtype=bool)
     is_test[test_g] = True
     return np.flatnonzero(~is_test[row_gid]), np.flatnonzero(is_test[row_gid]), ids[test_g]
+
+
+def drop_rows(indices, features, mos, groups=None):
+    """The reference's greyscale drop: `df.drop(index=indices).reset_index(drop=True)` on the metadata rows (mos, groups) and
+    `np.delete(features, indices, axis=0)` on the feature matrix, as one rule -> (features, mos, groups) without those rows, order
+    kept.  A row listed twice is dropped once (both of the reference's calls do that).  An index outside 0..n-1 raises IndexError
+    naming it: df.drop raises for a label that is not there, and np.delete for an index past the end; a negative index, which
+    np.delete alone would count from the end, is refused with them.  Device tensors stay on their device (index_select with the
+    kept rows; no host round trip); arrays stay arrays."""
+    n = int(features.shape[0])
+    for name, v in (("mos", mos), ("groups", groups)):
+        if v is not None and int(np.prod(tuple(v.shape))) != n:
+            raise ValueError(f"drop_rows: {int(np.prod(tuple(v.shape)))} {name} values against {n} feature rows")
+    idx = np.unique(np.asarray(list(indices) if not isinstance(indices, np.ndarray) else indices, dtype=np.int64).reshape(-1))
+    bad = idx[(idx < 0) | (idx >= n)]
+    if bad.size:
+        raise IndexError(f"drop_rows: index {int(bad[0])} outside 0..{n - 1}")
+    keep = np.ones(n, dtype=bool)
+    keep[idx] = False
+    rows = np.flatnonzero(keep)
+
+    def take(v):
+        if v is None:
+            return None
+        if isinstance(v, torch.Tensor):
+            return v.reshape(n, *v.shape[1:]).index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=v.device))
+        return np.asarray(v).reshape(n, *np.asarray(v).shape[1:])[rows]
+    return take(features), take(mos), take(groups)
 
 
 def median_model_index(values):
@@ -206,17 +237,24 @@ def evaluate_head(engine, features_train, mos_train, features_test, mos_test, co
             "state_dict": state_dict, "scaler": scaler, "test_scaler": test_scaler, "history": history}
 
 
-def holdout_protocol(engine, features, mos, config=None, n_repeats=21, test_size=0.2, groups=None):
+def holdout_protocol(engine, features, mos, config=None, n_repeats=21, test_size=0.2, groups=None, drop_indices=None):
     """main()'s repeated 80/20 hold-out (model_regression.py:548-697).  Repeat i = 1..n_repeats splits the unique ids of
     `groups` (default: one per row) with random_state = ceil(8.8 i) as train_test_split does, runs evaluate_head, and after
     nan_to_num takes the median and the standard deviation of each metric over the repeats.  The median model is the first
     repeat whose test-set selection metric (RMSE under select_criteria 'byrmse', KRCC otherwise) equals the median.
+    drop_indices: rows dropped first by drop_rows - the Index column of a greyscale report (check_greyscale.greyscale_indices), as
+    the reference's scripts drop them before they split; every row number in the result then counts in the shortened set.
 
     Returns a dict keyed like the reference's .mat: 'SRCC_train' ... 'RMSE_test' (float64 [n_repeats]), 'Median_KRCC' or
     'Median_RMSE', 'Test_Videos_list', 'Test_videos_Median_model'; plus 'summary' {key: (median, std)}, 'median_index',
     'median_state_dict', 'median_scaler', 'median_test_scaler', 'median_predictions' {'MOS', 'y_test_pred',
     'y_test_pred_logistic'} (the reference's score table), and 'repeats', the evaluate_head result of every repeat without its
     training history."""
+    if drop_indices is not None:
+        if not isinstance(features, torch.Tensor):
+            features = np.asarray(features)
+        features, mos, groups = drop_rows(drop_indices, features, mos if isinstance(mos, torch.Tensor) else np.asarray(mos).reshape(-1),
+                                          None if groups is None else np.asarray(groups).reshape(-1))
     mos = np.asarray(mos.detach().cpu() if isinstance(mos, torch.Tensor) else mos, dtype=np.float64).reshape(-1)
     n = mos.size
     if not isinstance(features, torch.Tensor):

@@ -12,10 +12,15 @@ from . import sampling
 RAW_VIDEO_TYPES = ("live_qualcomm",)
 
 
+def container_error(video_type, video_name):
+    """What every entry that meets a container raises (data_processing.check_greyscale too)."""
+    return NotImplementedError(f"video_type {video_type!r} ({video_name}): container formats need a demuxer and a video decoder; "
+                               f"only raw YUV input ({', '.join(RAW_VIDEO_TYPES)}) is read here")
+
+
 def _clip(video_type, video_name, frame_interval, video_path, video_width, video_height, pixfmt, framerate, device):
     if video_type not in RAW_VIDEO_TYPES:
-        raise NotImplementedError(f"video_type {video_type!r} ({video_name}): container formats need a demuxer and a video decoder; "
-                                  f"only raw YUV input ({', '.join(RAW_VIDEO_TYPES)}) is read here")
+        raise container_error(video_type, video_name)
     if frame_interval is not None and int(frame_interval) != sampling.frame_interval(framerate):
         raise ValueError(f"{video_name}: frame_interval {frame_interval} is not the interval of framerate {framerate} "
                          f"({sampling.frame_interval(framerate)})")
