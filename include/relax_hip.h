@@ -266,6 +266,40 @@ int relax_attention_overlay_ex(relax_handle* h, const uint8_t* frames, int64_t f
  * OpenCV's algorithm restated (not ported); parity is by tolerance against the reference's example flow PNGs. */
 int relax_optical_flow(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
                        float* flow, uint8_t* flow_bgr, relax_stream stream);
+/* cv2.calcOpticalFlowFarneback(gray(orig), gray(next), None, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags)
+ * + flow_to_rgb: relax_optical_flow with OpenCV's parameters as arguments.  Buffers, chunking, workspace and visualisation as there.
+ * Formula source: OpenCV's optflowgf.cpp as restated by oracle/flow_ref.py (farneback(prev, next, pyr_scale, levels, winsize,
+ * iterations, poly_n, poly_sigma)): the pyramid of relax_flow_plan below, FarnebackPrepareGaussian(poly_n, poly_sigma), the box
+ * window winsize, `iterations` updates per level, the coarser flow resized and multiplied by (float)(1 / pyr_scale).
+ * With the reference's literals (0.5, 3, 15, 3, 5, 1.2, 0) it runs relax_optical_flow's launches: the same bits at the same speed.
+ * Accepted: */
+#define RELAX_FLOW_PYR_SCALE_MIN 0.5
+#define RELAX_FLOW_PYR_SCALE_MAX 0.95
+#define RELAX_FLOW_MAX_LEVELS 8        /* levels 0..8, as long as the coarsest level USED (relax_flow_plan) has scale >= 1/32 */
+#define RELAX_FLOW_MIN_SCALE (1.0 / 32) /* 79 smoothing taps */
+#define RELAX_FLOW_MIN_WINSIZE 3
+#define RELAX_FLOW_MAX_WINSIZE 63      /* odd values only */
+#define RELAX_FLOW_MAX_ITERATIONS 10   /* 1..10 */
+/* poly_n 5 or 7; poly_sigma finite and > 0; flags 0.
+ * Refused (RELAX_ERR_INVALID, the offending value named in relax_last_error, before anything is launched - and before the handle is
+ * looked at: with h NULL the refusal is in relax_last_error(NULL), so the rules can be asked on a machine without a GPU):
+ *   - anything outside the limits above;
+ *   - an even winsize: OpenCV's box pass sums 2 * (winsize / 2) + 1 rows and columns but scales by 1 / winsize^2, the oracle sums
+ *     exactly winsize; without OpenCV at hand nothing pins which of the two an even window means;
+ *   - flags with OPTFLOW_FARNEBACK_GAUSSIAN (256) or OPTFLOW_USE_INITIAL_FLOW (4), each by name: the oracle restates neither. */
+int relax_optical_flow_ex(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
+                          double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                          float* flow, uint8_t* flow_bgr, relax_stream stream);
+/* The pyramid calcOpticalFlowFarneback builds for H x W frames (H, W >= 16), OpenCV's own loop: scale = pyr_scale multiplied k
+ * times in double; level k and every coarser one is dropped when W * scale < 32 or H * scale < 32; sigma = (1 / scale - 1) / 2,
+ * smoothing kernel max(cvRound(5 sigma) | 1, 3) taps, level size cvRound(side * scale) (round half to even).
+ *   n_levels       : the levels used below the full-size one (0..levels)
+ *   level_hw_ksize : int32 [n_levels + 1][3] = (h, w, smoothing taps) per level, COARSEST FIRST, the full-size level last
+ *                    (room for levels + 1 rows; may be NULL)
+ *   level_sigma    : double [n_levels + 1], the smoothing sigma per level (may be NULL)
+ * pyr_scale and levels within the limits above; refused too: a coarsest used scale under RELAX_FLOW_MIN_SCALE.
+ * No handle, no GPU: host arithmetic; errors through relax_last_error(NULL). */
+int relax_flow_plan(int H, int W, double pyr_scale, int levels, int* n_levels, int32_t* level_hw_ksize, double* level_sigma);
 /* flow_to_rgb alone: fp32 [T,H,W,2] -> uint8 [T,H,W,3] (BGR, despite the reference's name). */
 int relax_flow_to_rgb(relax_handle* h, const float* flow, int T, int H, int W, uint8_t* flow_bgr, relax_stream stream);
 

@@ -14,6 +14,9 @@
 //   blur in double + 2x2 solve in one kernel; the first one takes the x2 linear upsampling of the coarser level's flow on the fly, the
 //   last one of the finest level the magnitude range)   [flow_fused = 0: update_matrices_k + box_solve_fused, the matrix plane through HBM]
 //   flow_visualise: fastAtan2, normalisation, 8-bit HSV -> BGR (float formula, truncated).
+// relax_optical_flow_ex takes OpenCV's six parameters (FlowParams below): the literals run exactly the launches above; other values take
+// poly_expansion<7>, the per-level pyramid kernels (wide instantiations down to scale 1/32), resize_linear_f32<2> for the pyramid step and,
+// for windows other than 15, update_matrices_k + box_solve_any.  DESIGN.md has the band / halo / segment arithmetic.
 // LAB_NOTES.md section 3.3 has the measurements and what was tried and not kept.
 #include <cfloat>
 #include <cmath>
@@ -37,20 +40,27 @@ namespace relax {
         __builtin_amdgcn_s_barrier();                         \
     } while (0)
 
-constexpr int POLY_N = 5;
+// The reference's literals (relax_optical_flow, and relax_optical_flow_ex when it is given them).  WINSIZE is also the window of the
+// register-ring kernels below (box_solve_fused, flow_iteration); every other odd window goes through box_solve_any.
 constexpr int WINSIZE = 15;
 constexpr int ITERS = 3;
-constexpr int MAX_GAUSS = 32;
+constexpr int POLY_N_LITERAL = 5;
+constexpr double POLY_SIGMA_LITERAL = 1.2;
+constexpr int MAX_GAUSS = 32;        // taps of the literal pyramid's kernels (scales down to 1/8: 19)
+constexpr int MAX_GAUSS_WIDE = 80;   // relax_optical_flow_ex: scales down to 1/32, 79 taps
 typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector: 16-byte loads / stores of the 4-pixel kernels
 
-struct PolyConsts {
-    float g[POLY_N + 1], xg[POLY_N + 1], xxg[POLY_N + 1];
+template <int N>
+struct PolyConstsT {
+    float g[N + 1], xg[N + 1], xxg[N + 1];
     double ig11, ig03, ig33, ig55;
 };
-struct GaussKernel {
-    float k[MAX_GAUSS];
+template <int MAXG>
+struct GaussTaps {
+    float k[MAXG];
     int ksize;
 };
+typedef GaussTaps<MAX_GAUSS> GaussKernel;
 
 __device__ inline int reflect101(int i, int n) {
     if (i < 0) i = -i;
@@ -90,15 +100,16 @@ __global__ __launch_bounds__(256) void flow_gray_v4(const uint8_t* __restrict__ 
 
 // The taps arrive by value in the kernel argument; indexing that with a loop counter costs one dependent scalar load per tap,
 // so every block first copies them into LDS (and the common 3-tap blur of the two finest levels is unrolled from registers).
-__device__ inline void stage_taps(const GaussKernel& gk, float* sk) {
-    if (threadIdx.x < MAX_GAUSS) sk[threadIdx.x] = gk.k[threadIdx.x];
+template <int MAXG>
+__device__ inline void stage_taps(const GaussTaps<MAXG>& gk, float* sk) {
+    if (threadIdx.x < MAXG) sk[threadIdx.x] = gk.k[threadIdx.x];
     __syncthreads();
 }
 
-template <bool VERTICAL>
+template <bool VERTICAL, int MAXG = MAX_GAUSS>
 __global__ __launch_bounds__(256) void gauss_pass(const float* __restrict__ src, float* __restrict__ dst, int H, int W,
-                                                  GaussKernel gk) {
-    __shared__ float sk[MAX_GAUSS];
+                                                  GaussTaps<MAXG> gk) {
+    __shared__ float sk[MAXG];
     stage_taps(gk, sk);
     const int x = blockIdx.x * 256 + threadIdx.x;         // grid (W / 256, H, images)
     if (x >= W) return;
@@ -165,10 +176,12 @@ __device__ inline void linear_tap(int d, double scale, int n_in, int* s0, int* s
 // the stretch of the source row its 256 outputs tap (reflected at the borders while copying) into LDS with coalesced loads;
 // the 9 / 19 taps per output then come from LDS instead of strided global loads.
 constexpr int GH_SEG = 1280;   // floats of source row per block: 128 output columns x scale <= 8, plus the taps
+constexpr int GH_SEG_WIDE = 4352;   // relax_optical_flow_ex: 128 output columns x scale <= 32 (x 1.016: a 32-pixel level rounded down), plus 79 taps
+template <int MAXG = MAX_GAUSS, int SEG = GH_SEG>
 __global__ __launch_bounds__(256) void gauss_h_sampled(const float* __restrict__ src, float* __restrict__ tmp, int H, int W,
-                                                       int w, double scale_x, GaussKernel gk) {
-    __shared__ float sk[MAX_GAUSS];
-    __shared__ float seg[GH_SEG];
+                                                       int w, double scale_x, GaussTaps<MAXG> gk) {
+    __shared__ float sk[MAXG];
+    __shared__ float seg[SEG];
     const int e0 = blockIdx.x * 256;                      // grid (2w / 256, H, images): e = dx * 2 + j
     const int64_t row = (int64_t)blockIdx.z * H + blockIdx.y;            // b*H + y
     const float* r_ = src + row * W;
@@ -179,8 +192,8 @@ __global__ __launch_bounds__(256) void gauss_h_sampled(const float* __restrict__
     const int dx_last = (e0 + 255) >> 1 < w ? (e0 + 255) >> 1 : w - 1;
     linear_tap(dx_last, scale_x, W, &b0, &b1, &f);
     const int xlo = a0 - r;
-    const int n = b1 + r - xlo + 1;                       // <= GH_SEG (checked by the launcher)
-    if (threadIdx.x < MAX_GAUSS) sk[threadIdx.x] = gk.k[threadIdx.x];
+    const int n = b1 + r - xlo + 1;                       // <= SEG (checked by the launcher)
+    if (threadIdx.x < MAXG) sk[threadIdx.x] = gk.k[threadIdx.x];
     for (int i = threadIdx.x; i < n; i += 256) seg[i] = r_[reflect101(xlo + i, W)];
     __syncthreads();
     const int e = e0 + threadIdx.x;
@@ -194,10 +207,11 @@ __global__ __launch_bounds__(256) void gauss_h_sampled(const float* __restrict__
 }
 
 // vertical blur at the two sample rows + the bilinear combine: tmp [B][H][w][2] -> dst [B][h][w]
+template <int MAXG = MAX_GAUSS>
 __global__ __launch_bounds__(256) void gauss_v_sampled_resize(const float* __restrict__ tmp, float* __restrict__ dst, int H,
                                                               int W, int h, int w, double scale_y, double scale_x,
-                                                              GaussKernel gk) {
-    __shared__ float sk[MAX_GAUSS];
+                                                              GaussTaps<MAXG> gk) {
+    __shared__ float sk[MAXG];
     stage_taps(gk, sk);
     const int dx = blockIdx.x * 256 + threadIdx.x;       // grid (w / 256, h, images)
     if (dx >= w) return;
@@ -422,11 +436,14 @@ __global__ __launch_bounds__(256) void pyramid_fused(const uint8_t* __restrict__
 //   * the three vertical results go through LDS (double-buffered: one barrier per row), and the horizontal 11-tap part (double
 //     accumulators, as OpenCV) reads its neighbours there.
 // The intermediate [h][w][3] plane never goes to HBM: 4 + 20 bytes per pixel.
-constexpr int POLY_OUT = 256 - 2 * POLY_N;   // 246 (224-pixel bands, whose rows start on 128-byte lines, measured the same: profiles/r04_write_bw.txt has the pattern alone)
-constexpr int POLY_RING = 2 * POLY_N + 1;    // 11
-constexpr int POLY_SLOTS = 16;               // the window + 5 rows in flight
+// poly_n is the template parameter N (5: the numbers above; 7: bands of 242 columns, a 15-row window in a ring of 20 slots, 15-tap loops).
+template <int N>
 __global__ __launch_bounds__(256) void poly_expansion(const float* __restrict__ I, float* __restrict__ R, int h, int w, int seg,
-                                                      PolyConsts pc) {
+                                                      PolyConstsT<N> pc) {
+    constexpr int POLY_N = N;
+    constexpr int POLY_OUT = 256 - 2 * N;        // 246 (224-pixel bands, whose rows start on 128-byte lines, measured the same: profiles/r04_write_bw.txt has the pattern alone)
+    constexpr int POLY_RING = 2 * N + 1;         // 11
+    constexpr int POLY_SLOTS = POLY_RING + 5;    // 16: the window + 5 rows in flight
     __shared__ f32x4 lt[2][256];                           // (t0, t1, t2, -) of a column side by side: one 16-byte read per neighbour
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const int tid = threadIdx.x;
@@ -843,6 +860,119 @@ __global__ __launch_bounds__(256) void box_solve_fused(const float* __restrict__
     }
 }
 
+// ---- the box blur and the solve for ANY odd window (relax_optical_flow_ex; 3 .. 63, 15 has the register-ring kernels) --------------------
+// box_solve_fused with the window as an argument.  A band is 256 - 2 m columns of which (256 - 2 m) & ~3 are outputs (m = winsize / 2: 252 at
+// winsize 3, 224 at 33, 192 at 63), a thread owns a column and keeps the five running column sums in double - but a register ring of 63 rows x 5
+// planes does not exist, so the row that LEAVES the window is read again from M (the row entered winsize rows earlier: an L2 hit while a
+// band's window, winsize x 256 x 20 bytes <= 323 KB, stays resident; at worst 40 instead of 20 bytes of M per pixel).  Same sums in the same
+// order as box_solve_fused: the window of a segment's first row added up top to bottom, then `s += entering - leaving` per row; four rows of
+// column sums per barrier pair go through LDS in double, strips of 4 adjacent outputs add up their first window left to right and slide it.
+// The 1 / winsize^2 of the box filter is folded into the regulariser as in solve_flow: reg = 1e-3 * winsize^4.
+constexpr int ANY_ROWS = 4;
+__device__ __forceinline__ float2 solve_flow_reg(double A0, double A1, double A2, double A3, double A4, double reg) {
+    const double det = __fma_rn(A0, A2, __fma_rn(-A1, A1, reg));
+    double r = __builtin_amdgcn_rcp(det);
+    r = __fma_rn(__fma_rn(-det, r, 1.0), r, r);
+    r = __fma_rn(__fma_rn(-det, r, 1.0), r, r);
+    const double nx = __fma_rn(A0, A4, -__dmul_rn(A1, A3));
+    const double ny = __fma_rn(A2, A3, -__dmul_rn(A1, A4));
+    return make_float2((float)__dmul_rn(nx, r), (float)__dmul_rn(ny, r));
+}
+template <bool MINMAX>
+__global__ __launch_bounds__(256) void box_solve_any(const float* __restrict__ M, float* __restrict__ flow, int h, int w, int seg,
+                                                     int winsize, int out_cols, double reg, unsigned* __restrict__ mm) {
+    __shared__ __attribute__((aligned(16))) double lds[ANY_ROWS][5][256];
+    const int m = winsize >> 1;
+    const int tid = threadIdx.x;
+    const int c0 = blockIdx.x * out_cols;                     // first output column of the band
+    const int xc = clampi(c0 - m + tid, 0, w - 1);            // this thread's column (clamped = replicated border)
+    const bool vert = tid < out_cols + 2 * m;                 // (<= 256: out_cols <= 256 - 2 m)
+    const int y0 = blockIdx.y * seg;
+    const int y1 = y0 + seg < h ? y0 + seg : h;
+    const int64_t hw = (int64_t)h * w;
+    const int64_t pair = blockIdx.z;
+    const float* col = M + pair * 5 * hw + xc;
+    // strip role: out_cols / 4 <= 63 strips per row, ANY_ROWS rows
+    const int strips = out_cols >> 2;
+    const int sr = tid / strips, sq = tid - sr * strips;
+    const int x0 = c0 + 4 * sq;
+    const bool strip = sr < ANY_ROWS && x0 < w;
+
+    [[maybe_unused]] unsigned mag_lo = 0xffffffffu, mag_hi = 0u;
+    double s[5] = {0, 0, 0, 0, 0};
+    if (vert)
+        for (int k = 0; k < winsize; ++k) {                   // rows y0 - m .. y0 + m in order
+            const int64_t ro = (int64_t)clampi(y0 - m + k, 0, h - 1) * w;
+#pragma unroll
+            for (int c = 0; c < 5; ++c) s[c] += col[c * hw + ro];
+        }
+    for (int yg = y0; yg < y1; yg += ANY_ROWS) {              // uniform over the block
+        float ent[ANY_ROWS][5], lea[ANY_ROWS][5];
+#pragma unroll
+        for (int r = 0; r < ANY_ROWS; ++r) {
+            const int y = yg + r;
+            const bool move = vert && y > y0 && y < y1;
+            const int64_t re = (int64_t)clampi(y + m, 0, h - 1) * w, rl = (int64_t)clampi(y - m - 1, 0, h - 1) * w;
+#pragma unroll
+            for (int c = 0; c < 5; ++c) {
+                ent[r][c] = move ? col[c * hw + re] : 0.f;
+                lea[r][c] = move ? col[c * hw + rl] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < ANY_ROWS; ++r)
+#pragma unroll
+            for (int c = 0; c < 5; ++c) {
+                s[c] += (double)ent[r][c] - (double)lea[r][c];   // (+ 0 at a segment's first row and past its last)
+                lds[r][c][tid] = s[c];
+            }
+        __syncthreads();
+        const int y = yg + sr;
+        if (strip && y < y1) {
+            double acc[5][4];
+#pragma unroll
+            for (int c = 0; c < 5; ++c) {
+                const double* v = &lds[sr][c][4 * sq];        // column sums at band columns 4 sq .. 4 sq + winsize + 2 (< out_cols + 2 m)
+                double a = 0;
+                for (int j = 0; j < winsize; ++j) a += v[j];
+                acc[c][0] = a;
+#pragma unroll
+                for (int e = 1; e < 4; ++e) {
+                    a += v[winsize - 1 + e] - v[e - 1];
+                    acc[c][e] = a;
+                }
+            }
+            float* dst = flow + (pair * hw + (int64_t)y * w + x0) * 2;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (x0 + e < w) {
+                    const float2 f = solve_flow_reg(acc[0][e], acc[1][e], acc[2][e], acc[3][e], acc[4][e], reg);
+                    dst[2 * e] = f.x;
+                    dst[2 * e + 1] = f.y;
+                    if constexpr (MINMAX) {
+                        const unsigned u = __float_as_uint(flow_magnitude(f.x, f.y));
+                        mag_lo = u < mag_lo ? u : mag_lo;
+                        mag_hi = u > mag_hi ? u : mag_hi;
+                    }
+                }
+            }
+        }
+        __syncthreads();   // the next group overwrites the rows
+    }
+    if constexpr (MINMAX) {   // wave minimum / maximum, one atomic pair per wave
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const unsigned a = __shfl_xor(mag_lo, o), b = __shfl_xor(mag_hi, o);
+            mag_lo = a < mag_lo ? a : mag_lo;
+            mag_hi = b > mag_hi ? b : mag_hi;
+        }
+        if ((tid & 63) == 0) {
+            atomicMin(&mm[pair], mag_lo);                 // mins [0,P), maxs [P,2P)
+            atomicMax(&mm[gridDim.z + pair], mag_hi);
+        }
+    }
+}
+
 // ---- one Farneback iteration in ONE kernel ----------------------------------------------------------------------------
 // FarnebackUpdateMatrices + the 15x15 box blur + the 2x2 solve, without the matrix plane M ever going to HBM: per pixel and
 // iteration the memory system sees R0 (20 B), R1 at the displaced position (20 B), the flow in (8 B) and out (8 B) = 56 bytes
@@ -1236,9 +1366,12 @@ __global__ __launch_bounds__(256) void flow_visualise_v4(const float* __restrict
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------
-static void prepare_poly(PolyConsts* pc) {
-    const int n = POLY_N;
-    const double sigma = 1.2;
+// FarnebackPrepareGaussian for poly_n = N and any sigma (below FLT_EPSILON: 0.3 N, as OpenCV)
+template <int N>
+static void prepare_poly(double sigma, PolyConstsT<N>* pc) {
+    const int n = N;
+    constexpr int POLY_N = N;
+    if (sigma < FLT_EPSILON) sigma = n * 0.3;
     float g[2 * POLY_N + 1];
     double s = 0.;
     for (int x = -n; x <= n; ++x) {
@@ -1275,7 +1408,8 @@ static void prepare_poly(PolyConsts* pc) {
     }
 }
 
-static void make_gauss(int ksize, double sigma, GaussKernel* gk) {
+template <int MAXG>
+static void make_gauss(int ksize, double sigma, GaussTaps<MAXG>* gk) {
     gk->ksize = ksize;
     if (ksize == 3 && sigma <= 0) {
         gk->k[0] = 0.25f; gk->k[1] = 0.5f; gk->k[2] = 0.25f;
@@ -1322,11 +1456,53 @@ static int visualise(relax_handle* h, const float* flow, int P, int HW, uint8_t*
 // the level is small, so that a clip's 32 pairs still give every CU work.  The choice depends on the level's geometry only - never on
 // the number of pairs in the launch: the running column sums restart at a segment's first row, so the segmentation is part of what
 // fixes the last bits of the flow, and a pair's flow must not depend on its batch.
-static int flow_segment_rows(const relax_handle* h, int bands, int hh) {
-    if (h->gemm.flow_seg_rows > 0) return (h->gemm.flow_seg_rows + 14) / 15 * 15;   // tests: force a segmentation (multiples of the ring period)
-    for (const int cand : {270, 135, 90, 60, 45})
-        if (bands * ((hh + cand - 1) / cand) >= 16) return cand;
-    return 30;
+// A segment is a multiple of the window (15: the ring period of the register-ring kernels; 270, 135, 90, 60, 45 or 30 rows).
+static int flow_segment_rows(const relax_handle* h, int bands, int hh, int winsize = WINSIZE) {
+    if (h->gemm.flow_seg_rows > 0) return (h->gemm.flow_seg_rows + winsize - 1) / winsize * winsize;   // tests: force a segmentation
+    for (const int mult : {18, 9, 6, 4, 3})
+        if (bands * ((hh + mult * winsize - 1) / (mult * winsize)) >= 16) return mult * winsize;
+    return 2 * winsize;
+}
+
+// What calcOpticalFlowFarneback takes besides the frames (flags: 0 only).  The literal set runs the launches relax_optical_flow has always
+// run; what another value changes: pyr_scale / levels - the per-level pyramid kernels instead of pyramid_fused, and the coarser flow resized by
+// resize_linear_f32<2> (x 1 / pyr_scale) where the x 2 written into flow_up_value does not apply; winsize - update_matrices_k + box_solve_any;
+// poly_n / poly_sigma - poly_expansion<7>, other constants; iterations - the loop count.
+struct FlowParams {
+    double pyr_scale;
+    int levels, winsize, iterations, poly_n;
+    double poly_sigma;
+};
+static const FlowParams kFlowLiteral = {0.5, 3, WINSIZE, ITERS, POLY_N_LITERAL, POLY_SIGMA_LITERAL};
+
+template <int N>
+static void launch_poly_expansion(const float* I, float* R, int hh, int w, int P, double sigma, hipStream_t s) {
+    PolyConstsT<N> pc;
+    prepare_poly<N>(sigma, &pc);
+    int seg = 64;   // rows per block (a ring of rows to fill before the first one); shorter segments when the level is small (enough blocks for 256 CUs)
+    const int bands = (w + (256 - 2 * N) - 1) / (256 - 2 * N);
+    while (seg > 16 && (int64_t)bands * ((hh + seg - 1) / seg) * P * 2 < 2048) seg -= 16;
+    hipLaunchKernelGGL(poly_expansion<N>, dim3(bands, (hh + seg - 1) / seg, P * 2), dim3(256), 0, s, I, R, hh, w, seg, pc);
+}
+
+// box_solve_fused (winsize 15) or box_solve_any over M, in place on `flow`; minmax: the magnitude range rides on this launch
+static void launch_box_solve(const relax_handle* h, const float* M, float* flow, int hh, int w, int P, int winsize, bool minmax, unsigned* mm,
+                             hipStream_t s) {
+    if (winsize == WINSIZE) {
+        const int bands = (w + FUSE_OUT - 1) / FUSE_OUT;
+        const int seg = flow_segment_rows(h, bands, hh);   // multiples of the 15-row ring period; the same segments as flow_iteration
+        const dim3 gf(bands, (hh + seg - 1) / seg, P);
+        if (minmax) hipLaunchKernelGGL(box_solve_fused<true>, gf, dim3(256), 0, s, M, flow, hh, w, seg, mm);
+        else hipLaunchKernelGGL(box_solve_fused<false>, gf, dim3(256), 0, s, M, flow, hh, w, seg, nullptr);
+        return;
+    }
+    const int out_cols = (256 - 2 * (winsize / 2)) & ~3;
+    const int bands = (w + out_cols - 1) / out_cols;
+    const int seg = flow_segment_rows(h, bands, hh, winsize);
+    const dim3 gf(bands, (hh + seg - 1) / seg, P);
+    const double reg = 1e-3 * ((double)winsize * winsize) * ((double)winsize * winsize);
+    if (minmax) hipLaunchKernelGGL(box_solve_any<true>, gf, dim3(256), 0, s, M, flow, hh, w, seg, winsize, out_cols, reg, mm);
+    else hipLaunchKernelGGL(box_solve_any<false>, gf, dim3(256), 0, s, M, flow, hh, w, seg, winsize, out_cols, reg, nullptr);
 }
 
 template <bool UP, bool MINMAX>
@@ -1343,7 +1519,7 @@ static int launch_flow_iteration(relax_handle* h, const float* R, const float* f
 }
 
 static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int P, int H, int W,
-                      float* flow_out, uint8_t* bgr_out, hipStream_t s) {
+                      const FlowParams& fp, float* flow_out, uint8_t* bgr_out, hipStream_t s) {
     const int64_t HW = (int64_t)H * W;
     // the matrix kernels address a pair's two coefficient images through ONE buffer resource with 32-bit byte offsets
     RELAX_REQUIRE(h, HW * 40 < (int64_t)0x7fffffff, "optical flow: frames of %d x %d exceed the 2 GB a buffer resource addresses (40 bytes per pixel)", W, H);
@@ -1360,23 +1536,20 @@ static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next,
     float* flowB = flowA + (size_t)P * 2 * HW;
     unsigned* mm = reinterpret_cast<unsigned*>(flowB + (size_t)P * 2 * HW);
 
-    PolyConsts pc;
-    prepare_poly(&pc);
     // measurement (relax_profile_read kind 6): the whole stage, first launch to last; its algorithmic bytes are added up launch by launch
     double stage_bytes = 0;
     int stage_span;
     RELAX_TRY(prof_begin(h, s, 4, 0.0, &stage_span));
+    // the levels used and their sizes, smoothing kernels and sigmas: OpenCV's loop, in host_logic.cpp (what relax_flow_plan returns)
     int levels = 0;
+    host::FlowLevel plan[host::kFlowMaxLevels + 1];
     {
-        double sc = 1.0;
-        for (; levels < 3; ++levels) {
-            sc *= 0.5;
-            if (W * sc < 32 || H * sc < 32) break;
-        }
+        std::string err;
+        RELAX_REQUIRE(h, host::flow_plan(H, W, fp.pyr_scale, fp.levels, &levels, plan, err), "optical flow: %s", err.c_str());
     }
     // the four level inputs in one pass over the frames (pyramid_fused) when the scales are exact: blur -> level 0, I -> level 1,
     // tmp -> levels 2 and 3; otherwise the gray plane and the per-level blur / resize kernels below
-    const bool pyr = h->gemm.flow_pyramid_fused && levels == 3 && H % 8 == 0 && W % 8 == 0 && pair_stride % 4 == 0 &&
+    const bool pyr = h->gemm.flow_pyramid_fused && levels == 3 && fp.pyr_scale == 0.5 && H % 8 == 0 && W % 8 == 0 && pair_stride % 4 == 0 &&
                      ((reinterpret_cast<uintptr_t>(orig) | reinterpret_cast<uintptr_t>(next)) & 3) == 0;
     float* lvl_in[4] = {blur, I, tmp, tmp + (size_t)P * 2 * (HW / 16)};
     if (pyr) {
@@ -1406,28 +1579,45 @@ static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next,
     int ph = 0, pw = 0;
     float* cur = flowA;
     for (int k = levels; k >= 0; --k) {
-        double scale = 1.0;
-        for (int i = 0; i < k; ++i) scale *= 0.5;
-        const double sigma = (1. / scale - 1) * 0.5;
-        int smooth = (int)lrint(sigma * 5) | 1;
-        if (smooth < 3) smooth = 3;
-        RELAX_REQUIRE(h, smooth <= MAX_GAUSS, "optical flow: smoothing kernel %d too large", smooth);
-        RELAX_REQUIRE(h, k < 2 || 129.0 / scale + smooth + 4 <= GH_SEG, "optical flow: pyramid scale %g too coarse for the row stage", scale);
-        const int w = (int)lrint(W * scale), hh = (int)lrint(H * scale);
+        const host::FlowLevel& lv = plan[levels - k];
+        const double scale = lv.scale, sigma = lv.sigma;
+        const int smooth = lv.ksize, w = lv.w, hh = lv.h;
+        // coarse levels (scale < 1/2: levels 2 and 3 of the literal pyramid) blur only where the resize samples; past 32 taps, or a row stage
+        // past GH_SEG floats (scales under 1/8), the wide instantiations of the same kernels
+        const bool sampled = scale < 0.5;
+        const bool wide = smooth > MAX_GAUSS || (sampled && 129.0 * W / w + smooth + 4 > GH_SEG);
+        RELAX_REQUIRE(h, smooth < MAX_GAUSS_WIDE, "optical flow: smoothing kernel %d too large", smooth);
+        RELAX_REQUIRE(h, !sampled || 129.0 * W / w + smooth + 4 <= GH_SEG_WIDE, "optical flow: pyramid scale %g too coarse for the row stage", scale);
+        RELAX_REQUIRE(h, !wide || sampled, "optical flow: %d smoothing taps at scale %g", smooth, scale);   // (scale >= 1/2 has 3 taps)
         const int64_t hw = (int64_t)w * hh;
         if (!prev_flow) RELAX_HIP_CHECK(h, hipMemsetAsync(cur, 0, sizeof(float) * P * 2 * hw, s));
-        // (finer levels: the first matrix update resizes the coarser flow where it reads it - no resized plane)
+        // finer levels: the first matrix update resizes the coarser flow where it reads it - no resized plane - when the pyramid step doubles
+        // it (x 2 is written into flow_up_value); any other pyr_scale: resize_linear_f32<2>, the same operations, x (float)(1 / pyr_scale)
+        const bool up_fused = prev_flow && fp.pyr_scale == 0.5;
+        if (prev_flow && !up_fused) {
+            hipLaunchKernelGGL(resize_linear_f32<2>, dim3(nblocks(2 * w), hh, P), dim3(256), 0, s, prev_flow, cur, ph, pw, hh, w, (double)ph / hh,
+                               (double)pw / w, (float)(1.0 / fp.pyr_scale));
+            stage_bytes += 8.0 * P * ((double)ph * pw + (double)hw);
+        }
         GaussKernel gk;
-        make_gauss(smooth, sigma, &gk);
+        GaussTaps<MAX_GAUSS_WIDE> gkw;
+        if (wide) make_gauss(smooth, sigma, &gkw);
+        else make_gauss(smooth, sigma, &gk);
         const float* Isrc;
         const dim3 g_full(nblocks(W), H, P * 2), g_lvl2(nblocks(w), hh, P * 2), g_um(nblocks(w), 8 * ((hh + 7) / 8), P);
         if (!pyr)   // per-level blur (+ resize): the gray frame read once, the level input written once (+ the full-size blur written and read at level 1)
-            stage_bytes += 2.0 * P * (4.0 * HW + 4.0 * hw + (k == 1 ? 8.0 * HW : 0.0));
+            stage_bytes += 2.0 * P * (4.0 * HW + 4.0 * hw + (k >= 1 && !sampled ? 8.0 * HW : 0.0));
         if (pyr) {
             Isrc = lvl_in[k];
-        } else if (k >= 2) {   // coarse levels: blur only where the resize samples
-            hipLaunchKernelGGL(gauss_h_sampled, dim3(nblocks(2 * w), H, P * 2), dim3(256), 0, s, gray, tmp, H, W, w, (double)W / w, gk);
-            hipLaunchKernelGGL(gauss_v_sampled_resize, g_lvl2, dim3(256), 0, s, tmp, I, H, W, hh, w, (double)H / hh,
+        } else if (sampled && wide) {
+            hipLaunchKernelGGL((gauss_h_sampled<MAX_GAUSS_WIDE, GH_SEG_WIDE>), dim3(nblocks(2 * w), H, P * 2), dim3(256), 0, s, gray, tmp, H, W, w,
+                               (double)W / w, gkw);
+            hipLaunchKernelGGL(gauss_v_sampled_resize<MAX_GAUSS_WIDE>, g_lvl2, dim3(256), 0, s, tmp, I, H, W, hh, w, (double)H / hh,
+                               (double)W / w, gkw);
+            Isrc = I;
+        } else if (sampled) {   // coarse levels: blur only where the resize samples
+            hipLaunchKernelGGL((gauss_h_sampled<>), dim3(nblocks(2 * w), H, P * 2), dim3(256), 0, s, gray, tmp, H, W, w, (double)W / w, gk);
+            hipLaunchKernelGGL(gauss_v_sampled_resize<>, g_lvl2, dim3(256), 0, s, tmp, I, H, W, hh, w, (double)H / hh,
                                (double)W / w, gk);
             Isrc = I;
         } else {
@@ -1445,32 +1635,33 @@ static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next,
                 Isrc = I;
             }
         }
-        {
-            int seg = 64;   // rows per block (16 to fill the ring before the first one); shorter segments when the level is small (enough blocks for 256 CUs)
-            const int bands = (w + POLY_OUT - 1) / POLY_OUT;
-            while (seg > 16 && (int64_t)bands * ((hh + seg - 1) / seg) * P * 2 < 2048) seg -= 16;
-            hipLaunchKernelGGL(poly_expansion, dim3(bands, (hh + seg - 1) / seg, P * 2), dim3(256), 0, s, Isrc, R, hh, w, seg, pc);
-            stage_bytes += 2.0 * P * hw * 24;      // 4 bytes in, 5 coefficients out per pixel and frame
-        }
-        if (h->gemm.flow_fused) {
+        if (fp.poly_n == 7) launch_poly_expansion<7>(Isrc, R, hh, w, P, fp.poly_sigma, s);
+        else launch_poly_expansion<5>(Isrc, R, hh, w, P, fp.poly_sigma, s);
+        stage_bytes += 2.0 * P * hw * 24;      // 4 bytes in, 5 coefficients out per pixel and frame
+        const int iters = fp.iterations;
+        // the fused iteration kernel is written for the 15-pixel window (its ring, its fill steps); every other window takes the two kernels
+        if (h->gemm.flow_fused && fp.winsize == WINSIZE) {
             // one kernel per iteration (flow_iteration): M stays on the chip.  The iterations ping-pong between the two flow buffers:
             // a block reads flow rows its neighbours may already have rewritten otherwise.
             // measurement (relax_profile_read kind 5): algorithmic bytes per pixel = 2 x 5 floats of R at the pixel and at the displaced
             // position (counted once: neighbours share the lines) + the flow in and out = 56 bytes
             const double it_bytes = 56.0 * (double)hw * P;
-            stage_bytes += ITERS * it_bytes;
+            stage_bytes += iters * it_bytes;
             float* other = (cur == flowA) ? flowB : flowA;
             const float* in = cur;                // coarsest level: zeros
             float* out = other;
-            const FlowUp up = prev_flow ? FlowUp{prev_flow, ph, pw, (double)ph / hh, (double)pw / w} : FlowUp{};
-            if (prev_flow) out = cur;             // finer levels: the first iteration interpolates the coarser flow (in `other`)
-            for (int it = 0; it < ITERS; ++it) {
+            const FlowUp up = up_fused ? FlowUp{prev_flow, ph, pw, (double)ph / hh, (double)pw / w} : FlowUp{};
+            if (up_fused) out = cur;              // finer levels: the first iteration interpolates the coarser flow (in `other`)
+            for (int it = 0; it < iters; ++it) {
                 int span;
                 RELAX_TRY(prof_begin(h, s, 3, it_bytes, &span));
-                if (it == 0 && prev_flow) {
+                const bool last = k == 0 && it == iters - 1 && bgr_out;   // the final flow: its magnitude range is taken on the way out
+                if (last) RELAX_TRY(minmax_reset(h, P, mm, s));
+                if (it == 0 && up_fused && last) {                        // (one iteration per level)
+                    RELAX_TRY((launch_flow_iteration<true, true>(h, R, nullptr, out, hh, w, P, up, mm, s)));
+                } else if (it == 0 && up_fused) {
                     RELAX_TRY((launch_flow_iteration<true, false>(h, R, nullptr, out, hh, w, P, up, nullptr, s)));
-                } else if (k == 0 && it == ITERS - 1 && bgr_out) {   // the final flow: its magnitude range is taken on the way out
-                    RELAX_TRY(minmax_reset(h, P, mm, s));
+                } else if (last) {
                     RELAX_TRY((launch_flow_iteration<false, true>(h, R, in, out, hh, w, P, FlowUp{}, mm, s)));
                 } else {
                     RELAX_TRY((launch_flow_iteration<false, false>(h, R, in, out, hh, w, P, FlowUp{}, nullptr, s)));
@@ -1485,32 +1676,24 @@ static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next,
             // 2 x 5 floats of R at the pixel + 5 floats of R1 gathered at the displaced position (counted once: neighbours share
             // the lines) ... = 40 + 8 (flow) + 20 (M written) = 68 bytes
             const double um_bytes = 68.0 * (double)hw * P;
-            stage_bytes += ITERS * (um_bytes + 28.0 * (double)hw * P);      // + box_solve_fused: M read, flow written
+            stage_bytes += iters * (um_bytes + 28.0 * (double)hw * P);      // + box_solve_fused: M read, flow written
             int um_span;
             RELAX_TRY(prof_begin(h, s, 3, um_bytes, &um_span));
-            if (prev_flow) {
+            if (up_fused) {
                 const FlowUp up{prev_flow, ph, pw, (double)ph / hh, (double)pw / w};
                 hipLaunchKernelGGL(update_matrices_k<true>, g_um, dim3(256), 0, s, R, cur, M, hh, w, (hh + 7) / 8, up);
             } else {
                 hipLaunchKernelGGL(update_matrices_k<false>, g_um, dim3(256), 0, s, R, cur, M, hh, w, (hh + 7) / 8, FlowUp{});
             }
             RELAX_TRY(prof_end(h, s, um_span));
-            {
-                const int bands = (w + FUSE_OUT - 1) / FUSE_OUT;
-                const int seg = flow_segment_rows(h, bands, hh);   // multiples of the 15-row ring period; the same segments as flow_iteration
-                const dim3 gf(bands, (hh + seg - 1) / seg, P);
-                for (int it = 0; it < ITERS; ++it) {
-                    if (k == 0 && it == ITERS - 1 && bgr_out) {   // the final flow: its magnitude range is taken on the way out
-                        RELAX_TRY(minmax_reset(h, P, mm, s));
-                        hipLaunchKernelGGL(box_solve_fused<true>, gf, dim3(256), 0, s, M, cur, hh, w, seg, mm);
-                    } else {
-                        hipLaunchKernelGGL(box_solve_fused<false>, gf, dim3(256), 0, s, M, cur, hh, w, seg, nullptr);
-                    }
-                    if (it < ITERS - 1) {
-                        RELAX_TRY(prof_begin(h, s, 3, um_bytes, &um_span));
-                        hipLaunchKernelGGL(update_matrices_k<false>, g_um, dim3(256), 0, s, R, cur, M, hh, w, (hh + 7) / 8, FlowUp{});
-                        RELAX_TRY(prof_end(h, s, um_span));
-                    }
+            for (int it = 0; it < iters; ++it) {
+                const bool last = k == 0 && it == iters - 1 && bgr_out;   // the final flow: its magnitude range is taken on the way out
+                if (last) RELAX_TRY(minmax_reset(h, P, mm, s));
+                launch_box_solve(h, M, cur, hh, w, P, fp.winsize, last, mm, s);
+                if (it < iters - 1) {
+                    RELAX_TRY(prof_begin(h, s, 3, um_bytes, &um_span));
+                    hipLaunchKernelGGL(update_matrices_k<false>, g_um, dim3(256), 0, s, R, cur, M, hh, w, (hh + 7) / 8, FlowUp{});
+                    RELAX_TRY(prof_end(h, s, um_span));
                 }
             }
         }
@@ -1537,12 +1720,12 @@ using namespace relax;
 
 extern "C" {
 
-int relax_optical_flow(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
-                       float* flow, uint8_t* flow_bgr, relax_stream stream) {
-    if (!h) return RELAX_ERR_INVALID;
-    RELAX_REQUIRE(h, orig && next && T > 0 && H >= 16 && W >= 16, "relax_optical_flow: bad arguments");
-    RELAX_REQUIRE(h, flow || flow_bgr, "relax_optical_flow: no output requested");
-    RELAX_REQUIRE(h, pair_stride >= (int64_t)H * W * 3 || T == 1, "relax_optical_flow: pair stride smaller than a frame");
+// both entries: the argument checks, then the pairs in chunks that the workspace bounds
+static int optical_flow_run(relax_handle* h, const char* who, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
+                            const FlowParams& fp, float* flow, uint8_t* flow_bgr, relax_stream stream) {
+    RELAX_REQUIRE(h, orig && next && T > 0 && H >= 16 && W >= 16, "%s: bad arguments", who);
+    RELAX_REQUIRE(h, flow || flow_bgr, "%s: no output requested", who);
+    RELAX_REQUIRE(h, pair_stride >= (int64_t)H * W * 3 || T == 1, "%s: pair stride smaller than a frame", who);
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     // bound the workspace: 108 B per pixel per pair; chunks of up to RELAX_FLOW_WS_GB (default 32) GB - 288 GB of HBM make
@@ -1556,8 +1739,59 @@ int relax_optical_flow(relax_handle* h, const uint8_t* orig, const uint8_t* next
     if (chunk > T) chunk = T;
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int P = T - t0 < chunk ? T - t0 : chunk;
-        RELAX_TRY(flow_chunk(h, orig + t0 * pair_stride, next + t0 * pair_stride, pair_stride, P, H, W,
+        RELAX_TRY(flow_chunk(h, orig + t0 * pair_stride, next + t0 * pair_stride, pair_stride, P, H, W, fp,
                              flow ? flow + (int64_t)t0 * HW * 2 : nullptr, flow_bgr ? flow_bgr + (int64_t)t0 * HW * 3 : nullptr, s));
+    }
+    return RELAX_OK;
+}
+
+int relax_optical_flow(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
+                       float* flow, uint8_t* flow_bgr, relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    return optical_flow_run(h, "relax_optical_flow", orig, next, pair_stride, T, H, W, kFlowLiteral, flow, flow_bgr, stream);
+}
+
+int relax_optical_flow_ex(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
+                          double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                          float* flow, uint8_t* flow_bgr, relax_stream stream) {
+    // the parameters first, before the handle is looked at and before anything is launched (a NULL handle gets the refusal through
+    // relax_last_error(NULL): the rules can be asked without a GPU)
+    std::string err;
+    if (!host::flow_check_params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, err)) {
+        set_error(h, "relax_optical_flow_ex: %s", err.c_str());
+        return RELAX_ERR_INVALID;
+    }
+    if (!h) {
+        set_error(nullptr, "relax_optical_flow_ex: the handle is NULL");
+        return RELAX_ERR_INVALID;
+    }
+    {   // (frames under 16 x 16, and a pyramid whose coarsest used level lies under scale 1/32)
+        int n;
+        host::FlowLevel plan[host::kFlowMaxLevels + 1];
+        RELAX_REQUIRE(h, host::flow_plan(H, W, pyr_scale, levels, &n, plan, err), "relax_optical_flow_ex: %s", err.c_str());
+    }
+    const FlowParams fp = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma};
+    return optical_flow_run(h, "relax_optical_flow_ex", orig, next, pair_stride, T, H, W, fp, flow, flow_bgr, stream);
+}
+
+int relax_flow_plan(int H, int W, double pyr_scale, int levels, int* n_levels, int32_t* level_hw_ksize, double* level_sigma) {
+    if (!n_levels) {
+        set_error(nullptr, "relax_flow_plan: n_levels is NULL");
+        return RELAX_ERR_INVALID;
+    }
+    std::string err;
+    host::FlowLevel plan[host::kFlowMaxLevels + 1];
+    if (!host::flow_plan(H, W, pyr_scale, levels, n_levels, plan, err)) {
+        set_error(nullptr, "relax_flow_plan: %s", err.c_str());
+        return RELAX_ERR_INVALID;
+    }
+    for (int i = 0; i <= *n_levels; ++i) {
+        if (level_hw_ksize) {
+            level_hw_ksize[3 * i] = plan[i].h;
+            level_hw_ksize[3 * i + 1] = plan[i].w;
+            level_hw_ksize[3 * i + 2] = plan[i].ksize;
+        }
+        if (level_sigma) level_sigma[i] = plan[i].sigma;
     }
     return RELAX_OK;
 }

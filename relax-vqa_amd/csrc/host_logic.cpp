@@ -638,8 +638,121 @@ bool resize_output_size(int H, int W, int size, int* out_h, int* out_w, std::str
     return true;
 }
 
+bool flow_check_params(double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags, std::string& err) {
+    char buf[320];
+    buf[0] = 0;
+    if (!(pyr_scale >= kFlowMinPyrScale && pyr_scale <= kFlowMaxPyrScale))
+        std::snprintf(buf, sizeof buf, "pyr_scale=%g outside %g..%g", pyr_scale, kFlowMinPyrScale, kFlowMaxPyrScale);
+    else if (levels < 0 || levels > kFlowMaxLevels)
+        std::snprintf(buf, sizeof buf, "levels=%d outside 0..%d", levels, kFlowMaxLevels);
+    else if (winsize < kFlowMinWinsize || winsize > kFlowMaxWinsize)
+        std::snprintf(buf, sizeof buf, "winsize=%d outside %d..%d", winsize, kFlowMinWinsize, kFlowMaxWinsize);
+    else if (winsize % 2 == 0)
+        std::snprintf(buf, sizeof buf, "winsize=%d is even: OpenCV's box pass sums 2 * (winsize / 2) + 1 rows and scales by 1 / winsize^2, the "
+                      "oracle sums winsize rows, and nothing here can pin which an even window means - odd windows only", winsize);
+    else if (iterations < 1 || iterations > kFlowMaxIterations)
+        std::snprintf(buf, sizeof buf, "iterations=%d outside 1..%d", iterations, kFlowMaxIterations);
+    else if (poly_n != 5 && poly_n != 7)
+        std::snprintf(buf, sizeof buf, "poly_n=%d is neither 5 nor 7", poly_n);
+    else if (!(std::isfinite(poly_sigma) && poly_sigma > 0))
+        std::snprintf(buf, sizeof buf, "poly_sigma=%g is not a finite positive number", poly_sigma);
+    else if (flags & 256)
+        std::snprintf(buf, sizeof buf, "flags=%d asks for OPTFLOW_FARNEBACK_GAUSSIAN (256): the Gaussian window has no oracle here", flags);
+    else if (flags & 4)
+        std::snprintf(buf, sizeof buf, "flags=%d asks for OPTFLOW_USE_INITIAL_FLOW (4): an initial flow has no oracle here", flags);
+    else if (flags != 0)
+        std::snprintf(buf, sizeof buf, "flags=%d: only 0 is accepted", flags);
+    if (!buf[0]) return true;
+    err = buf;
+    return false;
+}
+
+bool flow_plan(int H, int W, double pyr_scale, int levels, int* n_levels, FlowLevel* lv, std::string& err) {
+    char buf[200];
+    buf[0] = 0;
+    if (H < 16) std::snprintf(buf, sizeof buf, "H=%d under 16", H);
+    else if (W < 16) std::snprintf(buf, sizeof buf, "W=%d under 16", W);
+    else if (!(pyr_scale >= kFlowMinPyrScale && pyr_scale <= kFlowMaxPyrScale))
+        std::snprintf(buf, sizeof buf, "pyr_scale=%g outside %g..%g", pyr_scale, kFlowMinPyrScale, kFlowMaxPyrScale);
+    else if (levels < 0 || levels > kFlowMaxLevels)
+        std::snprintf(buf, sizeof buf, "levels=%d outside 0..%d", levels, kFlowMaxLevels);
+    if (buf[0]) {
+        err = buf;
+        return false;
+    }
+    int used = 0;
+    {
+        double scale = 1.0;
+        for (; used < levels; ++used) {
+            scale *= pyr_scale;
+            if (W * scale < 32 || H * scale < 32) break;
+        }
+    }
+    for (int k = used; k >= 0; --k) {
+        double scale = 1.0;
+        for (int i = 0; i < k; ++i) scale *= pyr_scale;
+        if (scale < kFlowMinScale) {
+            std::snprintf(buf, sizeof buf, "levels=%d at pyr_scale=%g uses scale %g of %d x %d, under 1/32", levels, pyr_scale, scale, H, W);
+            err = buf;
+            return false;
+        }
+        FlowLevel& l = lv[used - k];
+        l.scale = scale;
+        l.sigma = (1. / scale - 1) * 0.5;
+        l.ksize = (int)std::lrint(l.sigma * 5) | 1;
+        if (l.ksize < 3) l.ksize = 3;
+        l.w = (int)std::lrint(W * scale);
+        l.h = (int)std::lrint(H * scale);
+    }
+    *n_levels = used;
+    return true;
+}
+
 }  // namespace host
 }  // namespace relax
+
+#ifdef RELAX_FLOW_PLAN_MAIN
+// ---- stand-alone program (make flow_plan_san: AddressSanitizer + UBSan, CPU only): every plan of a grid of sizes, scales and depths into a heap
+// array of exactly kFlowMaxLevels + 1 entries, its invariants checked; every refusal of flow_check_params once ---------------------------------
+int main() {
+    using namespace relax::host;
+    const double scales[] = {0.5, 0.6, 0.7, 0.75, 0.8, 0.9, 0.95};
+    long plans = 0, refused = 0;
+    std::string err;
+    for (int H = 16; H <= 2200; H += 37)
+        for (int W = 16; W <= 4200; W += 211)
+            for (double ps : scales)
+                for (int levels = 0; levels <= kFlowMaxLevels; ++levels) {
+                    std::vector<FlowLevel> lv((size_t)kFlowMaxLevels + 1);
+                    int n = -1;
+                    if (!flow_plan(H, W, ps, levels, &n, lv.data(), err)) {
+                        ++refused;
+                        continue;
+                    }
+                    ++plans;
+                    bool ok = n >= 0 && n <= levels && lv[n].h == H && lv[n].w == W && lv[n].ksize == 3 && lv[n].sigma == 0;
+                    for (int i = 0; i <= n && ok; ++i)
+                        ok = lv[i].ksize >= 3 && lv[i].ksize <= kFlowMaxTaps && lv[i].ksize % 2 == 1 && lv[i].scale >= kFlowMinScale &&
+                             (i == n || (lv[i].h >= 32 && lv[i].w >= 32 && lv[i].h <= lv[i + 1].h && lv[i].w <= lv[i + 1].w));
+                    if (!ok) {
+                        std::printf("bad plan for %d x %d, pyr_scale %g, levels %d\n", H, W, ps, levels);
+                        return 1;
+                    }
+                }
+    const struct { double ps; int lv, ws, it, pn; double sg; int fl; } bad[] = {
+        {0.49, 3, 15, 3, 5, 1.2, 0}, {1.0, 3, 15, 3, 5, 1.2, 0}, {0.5, 9, 15, 3, 5, 1.2, 0}, {0.5, 3, 14, 3, 5, 1.2, 0}, {0.5, 3, 65, 3, 5, 1.2, 0},
+        {0.5, 3, 15, 0, 5, 1.2, 0}, {0.5, 3, 15, 3, 6, 1.2, 0}, {0.5, 3, 15, 3, 5, 0.0, 0}, {0.5, 3, 15, 3, 5, NAN, 0}, {0.5, 3, 15, 3, 5, 1.2, 4},
+        {0.5, 3, 15, 3, 5, 1.2, 256}, {0.5, 3, 15, 3, 5, 1.2, 1}};
+    for (const auto& b : bad)
+        if (flow_check_params(b.ps, b.lv, b.ws, b.it, b.pn, b.sg, b.fl, err) || err.empty()) {
+            std::printf("not refused: %g %d %d %d %d %g %d\n", b.ps, b.lv, b.ws, b.it, b.pn, b.sg, b.fl);
+            return 1;
+        }
+    if (!flow_check_params(0.5, 3, 15, 3, 5, 1.2, 0, err) || !flow_check_params(0.95, 8, 63, 10, 7, 0.1, 0, err)) return 1;
+    std::printf("flow_plan ok: %ld plans, %ld refused\n", plans, refused);
+    return 0;
+}
+#endif
 
 #ifdef RELAX_HOST_TEST_API
 // ---- C entry points of the host half alone (librelax_host_san.so of tests/test_host_logic_sanitized.py; compiled only

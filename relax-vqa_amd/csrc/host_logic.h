@@ -114,6 +114,28 @@ void resize_table(int in_size, int out_size, int filt, int32_t* bounds, int32_t*
 // here is int() of Python's double.  false and a message naming the value: H, W or size outside the limits, or a longer side above kResizeMaxOut.
 bool resize_output_size(int H, int W, int size, int* out_h, int* out_w, std::string& err);
 
+// ---- Farneback's parameters and pyramid on the host (flow.hip; relax_optical_flow_ex, relax_flow_plan) -----------------------------------
+// The limits of relax_optical_flow_ex (RELAX_FLOW_* of relax_hip.h) and what calcOpticalFlowFarneback derives from (H, W, pyr_scale, levels):
+// OpenCV's own loop - `scale` by repeated multiplication in double, a level is dropped (and every coarser one) when a side times the scale
+// falls under 32 pixels, sigma = (1 / scale - 1) / 2, smoothing kernel max(cvRound(5 sigma) | 1, 3) taps, level size cvRound(side * scale).
+constexpr double kFlowMinPyrScale = 0.5, kFlowMaxPyrScale = 0.95;
+constexpr int kFlowMaxLevels = 8;
+constexpr double kFlowMinScale = 1.0 / 32;     // coarsest scale a call may use: 79 smoothing taps
+constexpr int kFlowMaxTaps = 79;
+constexpr int kFlowMinWinsize = 3, kFlowMaxWinsize = 63;
+constexpr int kFlowMaxIterations = 10;
+struct FlowLevel {
+    int h, w, ksize;
+    double scale, sigma;
+};
+// false and a message that names the offending value: anything outside the limits, an even winsize, flags other than 0 (the Gaussian
+// window, 256, and the initial flow, 4, by name)
+bool flow_check_params(double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags, std::string& err);
+// the levels used below the full-size one (*n_levels, 0..levels) and lv[0 .. *n_levels], COARSEST FIRST (lv[*n_levels] is the full-size
+// level: scale 1, sigma 0, 3 taps); lv must hold kFlowMaxLevels + 1 entries.  false and a message: H or W under 16, pyr_scale or levels
+// outside the limits, or a coarsest used scale under kFlowMinScale.
+bool flow_plan(int H, int W, double pyr_scale, int levels, int* n_levels, FlowLevel* lv, std::string& err);
+
 // ---- the options table: every relax_set_option / relax_get_option key once ------------------------------------------------------------------
 // How a row takes a value: as given; != 0; a non-positive value becomes `a`; one of {a, b}; the closed range [a, b].  The last two refuse
 // anything else with "relax_set_option: <key> must be <must_be>" and leave the stored value as it was.

@@ -455,9 +455,41 @@ class RelaxEngine:
                     "relax_merge_fragments")
         return out
 
-    def optical_flow(self, frames, want_flow=False, want_image=True):
+    FLOW_DEFAULTS = dict(pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2, flags=0)
+
+    def optical_flow(self, frames, want_flow=False, want_image=True, *, pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5,
+                     poly_sigma=1.2, flags=0):
         """frames uint8 [T,2,H,W,3] BGR -> (flow fp32 [T,H,W,2] | None, flow image uint8 [T,H,W,3] | None): Farneback flow
-        with the reference's parameters and its flow_to_rgb visualisation (src/main_fragment_layerstack.py:313-316)."""
+        and the reference's flow_to_rgb visualisation (src/main_fragment_layerstack.py:313-316).  The keywords are
+        cv2.calcOpticalFlowFarneback's parameters; their defaults are the reference's literals, and with all of them at the default the
+        call is relax_optical_flow as ever.  Anything else goes through relax_optical_flow_ex (include/relax_hip.h has the limits:
+        pyr_scale 0.5..0.95, levels 0..8 down to scale 1/32, odd winsize 3..63, iterations 1..10, poly_n 5 or 7, flags 0); the literals
+        passed explicitly through it give the same bits."""
+        given = dict(pyr_scale=pyr_scale, levels=levels, winsize=winsize, iterations=iterations, poly_n=poly_n, poly_sigma=poly_sigma,
+                     flags=flags)
+        return self._optical_flow(frames, want_flow, want_image, None if given == self.FLOW_DEFAULTS else given)
+
+    def optical_flow_ex(self, frames, want_flow=False, want_image=True, **params):
+        """optical_flow through relax_optical_flow_ex whatever the parameters are (missing ones: the literals) - what a test of the
+        literal route calls."""
+        unknown = set(params) - set(self.FLOW_DEFAULTS)
+        if unknown:
+            raise TypeError(f"optical_flow_ex: unknown parameters {sorted(unknown)}")
+        return self._optical_flow(frames, want_flow, want_image, {**self.FLOW_DEFAULTS, **params})
+
+    def flow_plan(self, H, W, pyr_scale=0.5, levels=3):
+        """The pyramid calcOpticalFlowFarneback builds for H x W frames (relax_flow_plan; no GPU work) -> list of dict(h, w, ksize,
+        sigma), coarsest level first, the full-size level last: len - 1 is the number of levels used below it (OpenCV stops before a
+        side falls under 32 pixels)."""
+        n = C.c_int(0)
+        hwk = (C.c_int32 * (3 * 9))()
+        sig = (C.c_double * 9)()
+        rc = self.lib.relax_flow_plan(int(H), int(W), float(pyr_scale), int(levels), C.byref(n), C.cast(hwk, C.c_void_p), C.cast(sig, C.c_void_p))
+        if rc != 0:
+            raise RuntimeError(f"relax_flow_plan failed ({rc}): {self.lib.relax_last_error(None).decode()}")
+        return [dict(h=hwk[3 * i], w=hwk[3 * i + 1], ksize=hwk[3 * i + 2], sigma=sig[i]) for i in range(n.value + 1)]
+
+    def _optical_flow(self, frames, want_flow, want_image, params):
         frames = self._dev_u8(frames)
         if frames.dim() != 5 or frames.shape[1] != 2 or frames.shape[4] != 3:
             raise ValueError(f"frames must be [T,2,H,W,3], got {tuple(frames.shape)}")
@@ -466,9 +498,15 @@ class RelaxEngine:
         im = torch.empty((T, H, W, 3), dtype=torch.uint8, device=self.device) if want_image else None
         fb = H * W * 3
         base = frames.data_ptr()
-        rc = self.lib.relax_optical_flow(self.h, C.c_void_p(base), C.c_void_p(base + fb), 2 * fb, T, H, W, _ptr(fl), _ptr(im),
-                                         _stream())
-        self._check(rc, "relax_optical_flow")
+        if params is None:
+            rc = self.lib.relax_optical_flow(self.h, C.c_void_p(base), C.c_void_p(base + fb), 2 * fb, T, H, W, _ptr(fl), _ptr(im),
+                                             _stream())
+            self._check(rc, "relax_optical_flow")
+            return fl, im
+        rc = self.lib.relax_optical_flow_ex(self.h, C.c_void_p(base), C.c_void_p(base + fb), 2 * fb, T, H, W, float(params["pyr_scale"]),
+                                            int(params["levels"]), int(params["winsize"]), int(params["iterations"]), int(params["poly_n"]),
+                                            float(params["poly_sigma"]), int(params["flags"]), _ptr(fl), _ptr(im), _stream())
+        self._check(rc, "relax_optical_flow_ex")
         return fl, im
 
     def flow_to_rgb(self, flow):
@@ -768,13 +806,15 @@ class RelaxEngine:
 
     OVERLAY_FRAGMENTS = ("residual_imp", "residual_of_imp", "ori_frag", "residual_merged_frag")
 
-    def attention_overlays(self, frames, fragment="ori_frag", flow_images=None, lut=None, patch_size=16, top_n=None, target_size=None):
+    def attention_overlays(self, frames, fragment="ori_frag", flow_images=None, lut=None, patch_size=16, top_n=None, target_size=None,
+                           flow_params=None):
         """The __main__ of src/demo_visual.py (:86-128) for a whole clip: frames uint8 [T,2,H,W,3] as fragment_pairs takes them;
         fragment one of OVERLAY_FRAGMENTS:
           residual_imp          the frame-difference fragment, frame-difference positions
           ori_frag              the original fragment, frame-difference positions
           residual_merged_frag  merge_fragments(difference fragment, flow fragment), frame-difference positions
-          residual_of_imp       the flow fragment, flow positions (flow_images, or Farneback on the GPU when None)
+          residual_of_imp       the flow fragment, flow positions (flow_images, or Farneback on the GPU when None; flow_params: a dict
+                                of optical_flow's keywords for it, None = the reference's literals)
         patch_size / top_n: the fragment's geometry on the 224 x 224 canvas (slots = (224 / patch_size)^2: 784 / 196 / 49; top_n=None
         = all).  patch_size must go with the loaded ViT (fragment_geometry.overlay_slot_rule): equal to its patch size - a patch-8
         model with patch_size=8 paints its 784 tokens one to one -, or 32, where a slot takes the mean of the head-mean attention
@@ -793,7 +833,7 @@ class RelaxEngine:
         positions, counts = fr["positions"], fr["counts"]
         if fragment in ("residual_of_imp", "residual_merged_frag"):
             if flow_images is None:
-                _, flow_images = self.optical_flow(frames)
+                _, flow_images = self.optical_flow(frames, **(flow_params or {}))
             fl = self.fragment_image(flow_images, **kw)
         if fragment == "residual_imp":
             image = fr["diff_frag"]
@@ -812,19 +852,21 @@ class RelaxEngine:
         return dict(overlay=overlay, patch_means=patch_means, attention=attention, positions=positions, counts=counts)
 
     # ---- whole clip ---------------------------------------------------------------------------
-    def extract_clip(self, frames, resnet=True, vit=True, flow_images=None, flow=False, patch_size=16, top_n=None, target_size=None):
+    def extract_clip(self, frames, resnet=True, vit=True, flow_images=None, flow=False, patch_size=16, top_n=None, target_size=None,
+                     flow_params=None):
         """frames uint8 [T,2,H,W,3] on the device -> per-frame features (all fp32, on the device):
              resnet: [T,15171] = layer-stack of the original fragment | pool of the residual fragment
              vit:    [T,4608]  = pool of the original fragment | pool of the residual fragment
         The residual fragment is the frame-difference fragment, merged 50/50 with the optical-flow
         fragment when flow_images (uint8 [T,H,W,3]) are supplied (src/main_fragment_layerstack.py:313-325).
         patch_size / top_n: the fragments' geometry on the 224 x 224 canvas (8 / 16 / 32; top_n=None = all (224 / patch_size)^2 slots;
-        positions come back as [T,slots,2]); target_size is refused: the backbones take 224 (fragment_geometry.backbone_geometry)."""
+        positions come back as [T,slots,2]); target_size is refused: the backbones take 224 (fragment_geometry.backbone_geometry).
+        flow_params: a dict of optical_flow's keywords for the flow computed here (flow=True without flow_images); None = the literals."""
         kw = self._clip_geometry(patch_size, top_n, target_size)
         fr = self.fragment_pairs(frames, **kw)
         resid = fr["diff_frag"]
         if flow and flow_images is None:
-            _, flow_images = self.optical_flow(frames)     # full ReLaX: Farneback + flow_to_rgb on the GPU
+            _, flow_images = self.optical_flow(frames, **(flow_params or {}))     # full ReLaX: Farneback + flow_to_rgb on the GPU
         if flow_images is not None:
             fl = self.fragment_image(flow_images, **kw)
             resid = self.merge_fragments(resid, fl["frag"])
@@ -947,14 +989,15 @@ class RelaxEngine:
     # ---- fragment-free ablation rows (src/main_residual.py, src/main_layer.py) ---------------------------------
     RESIDUAL_NAMES = ("frame_diff", "optical_flow")
 
-    def _whole_residual_inputs(self, frames, residual_name, bilinear, lanczos, flow_images=None, out_bilinear=None, out_lanczos=None):
+    def _whole_residual_inputs(self, frames, residual_name, bilinear, lanczos, flow_images=None, out_bilinear=None, out_lanczos=None,
+                               flow_params=None):
         """The two backbone inputs of one clip's whole residual images: the frame difference through the fused
         difference + resize, the flow image (given, or Farneback on the GPU) through resize_frames."""
         if residual_name == "frame_diff":
             return self.residual_resize(frames, bilinear=bilinear, lanczos=lanczos, out_bilinear=out_bilinear,
                                         out_lanczos=out_lanczos)[:2]
         if flow_images is None:
-            _, flow_images = self.optical_flow(frames)
+            _, flow_images = self.optical_flow(frames, **(flow_params or {}))
         return self.resize_frames(flow_images, bilinear=bilinear, lanczos=lanczos, out_bilinear=out_bilinear, out_lanczos=out_lanczos)
 
     def _check_residual_name(self, residual_name):
@@ -977,21 +1020,23 @@ class RelaxEngine:
             blocks.append(("vgg16", self.vgg16_features(bil, layer_stack=False, pool=True)[1]))
         return blocks
 
-    def whole_residual_features(self, frames, residual_name="frame_diff", resnet=True, vit=True, vgg16=False, flow_images=None, vit_size=None):
+    def whole_residual_features(self, frames, residual_name="frame_diff", resnet=True, vit=True, vgg16=False, flow_images=None, vit_size=None,
+                                flow_params=None):
         """frames uint8 [T,2,H,W,3] -> dict of per-frame fp32 device tensors, the rows src/main_residual.py:221-254 saves per
         video: the WHOLE residual image (residual_name 'frame_diff': cv2.absdiff(next, orig); 'optical_flow': the flow image,
         flow_images uint8 [T,H,W,3] or Farneback on the GPU) resized to 224 x 224 and pooled:
           'resnet' [T,2051] avgpool | mean, max, std      'vgg16' [T,4099] fc2 | mean, max, std      (BILINEAR bytes)
           'vit'    [T,3*dim] token mean | max | std                                                  (LANCZOS bytes)
-        vit_size (None: 224 x 224, the calls above unchanged): the ViT's canvas, an int or an (h, w) pair as resize_frames_to takes it."""
+        vit_size (None: 224 x 224, the calls above unchanged): the ViT's canvas, an int or an (h, w) pair as resize_frames_to takes it.
+        flow_params: a dict of optical_flow's keywords for the flow computed here ('optical_flow' without flow_images); None = the literals."""
         self._check_residual_name(residual_name)
         self._check_backbones(resnet, vit, vgg16)
         if vit_size is None or not vit:
-            bil, lan = self._whole_residual_inputs(frames, residual_name, resnet or vgg16, vit, flow_images)
+            bil, lan = self._whole_residual_inputs(frames, residual_name, resnet or vgg16, vit, flow_images, flow_params=flow_params)
             return dict(self._pool_blocks(bil, lan, resnet, vit, vgg16))
         # the ViT's input on its own canvas (a second pass over the pairs); the BILINEAR 224 x 224 bytes of the other backbones as before
         if residual_name == "optical_flow" and flow_images is None:
-            _, flow_images = self.optical_flow(frames)
+            _, flow_images = self.optical_flow(frames, **(flow_params or {}))
         bil = self._whole_residual_inputs(frames, residual_name, True, False, flow_images)[0] if resnet or vgg16 else None
         if residual_name == "frame_diff":
             lan = self.residual_resize(frames, bilinear=False, lanczos=True, size=vit_size)[1]
@@ -1000,10 +1045,10 @@ class RelaxEngine:
         return dict(self._pool_blocks(bil, lan, resnet, vit, vgg16))
 
     def whole_residual_vectors(self, clips, residual_name="frame_diff", resnet=True, vit=True, vgg16=False, flow_images=None,
-                               per_frame=False):
+                               per_frame=False, flow_params=None):
         """Several clips (list of uint8 [T_i,2,H_i,W_i,3], any mix of resolutions; flow_images: optional list of uint8
         [T_i,H_i,W_i,3]) in ONE batched pass per backbone -> fp32 [len(clips), F] per-clip means of the whole_residual_features
-        rows, columns resnet | vit | vgg16 of those requested.  per_frame=True as in clip_vectors."""
+        rows, columns resnet | vit | vgg16 of those requested.  per_frame=True as in clip_vectors; flow_params as in whole_residual_features."""
         self._check_residual_name(residual_name)
         self._check_backbones(resnet, vit, vgg16)
         counts = [int(c.shape[0]) for c in clips]
@@ -1014,7 +1059,7 @@ class RelaxEngine:
         for i, (c, t) in enumerate(zip(clips, counts)):
             self._whole_residual_inputs(c, residual_name, bil is not None, lan is not None,
                                         None if flow_images is None else flow_images[i],
-                                        None if bil is None else bil[at:at + t], None if lan is None else lan[at:at + t])
+                                        None if bil is None else bil[at:at + t], None if lan is None else lan[at:at + t], flow_params=flow_params)
             at += t
         blocks, col = [], 0
         for _, rows in self._pool_blocks(bil, lan, resnet, vit, vgg16):
@@ -1039,21 +1084,23 @@ class RelaxEngine:
             out["vgg16"] = out["vgg16"][:, :VGG16_POOL_DIM - 3]
         return out
 
-    def full_clip_vector(self, frames, flow_images=None, flow=False, whole_frames=None, patch_size=16, top_n=None, target_size=None):
+    def full_clip_vector(self, frames, flow_images=None, flow=False, whole_frames=None, patch_size=16, top_n=None, target_size=None,
+                         flow_params=None):
         """frames uint8 [T,2,H,W,3] -> fp32 [35203]: the vector src/demo_test.py:171-175 assembles
         (whole-frame ResNet-50 LS | whole-frame ViT | fragment ResNet-50 LS+pool | fragment ViT x2), each part averaged
         over the sampled frames.  Without flow_images the residual fragment is the frame-difference fragment alone.
         whole_frames uint8 [Ts,H,W,3]: all sampled frames when the last one has no pair (see full_clip_vectors).
         With self.demo_write_png set, the pairs' files are written too (src/demo_test.py:120,135; at the reference's 16 / 196
-        geometry whatever patch_size says); the vector is the same.  patch_size / top_n / target_size as in extract_clip."""
+        geometry whatever patch_size says); the vector is the same.  patch_size / top_n / target_size / flow_params as in extract_clip."""
         if self.demo_write_png is not None:
             from . import visualisation
             visualisation.write_for_driver(self, frames, self.demo_write_png, flow=flow or flow_images is not None)
         return self.full_clip_vectors([frames], flow=flow, flow_images=None if flow_images is None else [flow_images],
                                       whole_frames=None if whole_frames is None else [whole_frames], patch_size=patch_size, top_n=top_n,
-                                      target_size=target_size)[0]
+                                      target_size=target_size, flow_params=flow_params)[0]
 
-    def full_clip_vectors(self, clips, flow=True, flow_images=None, whole_frames=None, patch_size=16, top_n=None, target_size=None):
+    def full_clip_vectors(self, clips, flow=True, flow_images=None, whole_frames=None, patch_size=16, top_n=None, target_size=None,
+                          flow_params=None):
         """Several clips -> fp32 [len(clips), 35203] in ONE batched pass of each backbone (3*T fragments / frames per
         clip: original fragment, residual fragment, whole frame).  Same layout as full_clip_vector.  Batch-invariant to
         fp32 rounding; bit for bit only with set_option("gemm_split_k", 0) (see clip_vectors).
@@ -1063,11 +1110,12 @@ class RelaxEngine:
         = full_features(full_prepare(...)): full_prepare is the byte / HBM work (fragments, Farneback flow, resizes), full_features
         the contractions.  Running the two halves of consecutive batches on two streams was measured at 1.01 x
         (tools/flow_overlap_try.py) and is not done in the product; the split stays because the dataset driver stages on it.
-        patch_size / top_n / target_size as in extract_clip."""
+        patch_size / top_n / target_size / flow_params as in extract_clip."""
         return self.full_features(self.full_prepare(clips, flow=flow, flow_images=flow_images, whole_frames=whole_frames,
-                                                    patch_size=patch_size, top_n=top_n, target_size=target_size))
+                                                    patch_size=patch_size, top_n=top_n, target_size=target_size, flow_params=flow_params))
 
-    def full_prepare(self, clips, flow=True, flow_images=None, whole_frames=None, patch_size=16, top_n=None, target_size=None):
+    def full_prepare(self, clips, flow=True, flow_images=None, whole_frames=None, patch_size=16, top_n=None, target_size=None,
+                     flow_params=None):
         """The input half of full_clip_vectors: fragments (difference + flow, merged), whole-frame resizes -> the two backbone
         input batches.  Everything is enqueued on the current stream."""
         kw = self._clip_geometry(patch_size, top_n, target_size)
@@ -1085,7 +1133,7 @@ class RelaxEngine:
             self.fragment_pairs(c, out_ori=vit_in[at:at + t], out_diff=res, **kw)
             fimg = None if flow_images is None else flow_images[i]
             if flow and fimg is None:
-                _, fimg = self.optical_flow(c)
+                _, fimg = self.optical_flow(c, **(flow_params or {}))
             if fimg is not None:
                 self.merge_fragments(res, self.fragment_image(fimg, **kw)["frag"], out=res)
             tw = wcounts[i]

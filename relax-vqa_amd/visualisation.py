@@ -7,15 +7,16 @@ import os
 NAMES = ("residual", "residual_imp", "ori_frag", "residual_of", "residual_of_imp", "residual_merged_frag")
 
 
-def example_set_arrays(engine, frames, flow=True, overlays=None):
-    """frames uint8 [T,2,H,W,3] -> {suffix: uint8 [T,h,w,3] device tensor} of the files write_example_set writes."""
+def example_set_arrays(engine, frames, flow=True, overlays=None, flow_params=None):
+    """frames uint8 [T,2,H,W,3] -> {suffix: uint8 [T,h,w,3] device tensor} of the files write_example_set writes.
+    flow_params: a dict of RelaxEngine.optical_flow's keywords (None = the reference's literals)."""
     frames = engine._dev_u8(frames)
     fr = engine.fragment_pairs(frames)
     out = {"residual": engine.residual_resize(frames, bilinear=False, lanczos=False, want_residual=True)[2],
            "residual_imp": fr["diff_frag"], "ori_frag": fr["ori_frag"]}
     flow_images = None
     if flow:
-        _, flow_images = engine.optical_flow(frames)
+        _, flow_images = engine.optical_flow(frames, **(flow_params or {}))
         fl = engine.fragment_image(flow_images)
         out["residual_of"] = flow_images
         out["residual_of_imp"] = fl["frag"]
@@ -23,7 +24,7 @@ def example_set_arrays(engine, frames, flow=True, overlays=None):
     if overlays is not None:
         if overlays not in engine.OVERLAY_FRAGMENTS:
             raise ValueError(f"overlays must be one of {engine.OVERLAY_FRAGMENTS}, got {overlays!r}")
-        out[f"{overlays}_overlay"] = engine.attention_overlays(frames, overlays, flow_images=flow_images)["overlay"]
+        out[f"{overlays}_overlay"] = engine.attention_overlays(frames, overlays, flow_images=flow_images, flow_params=flow_params)["overlay"]
     return out
 
 
