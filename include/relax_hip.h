@@ -308,7 +308,16 @@ int relax_flow_to_rgb(relax_handle* h, const float* flow, int T, int H, int W, u
  *   out_bilinear : what transforms.Resize((224,224)) gives a PIL image (src/extractor/visualise_resnet.py:40-47)
  *   out_lanczos  : img.resize((224,224), Image.Resampling.LANCZOS)     (src/extractor/visualise_vit_layer.py:466-469)
  * frames uint8 [H,W,3] per item (item n at frames + n*item_stride; channel order is irrelevant), outputs
- * uint8 [N,224,224,3]; either output may be NULL.  One read of each frame serves both filters. */
+ * uint8 [N,224,224,3]; either output may be NULL.  One read of each frame serves both filters.
+ * This is relax_resize_frames_ex (below) at out_h = out_w = 224, on the same kernels, with these consequences:
+ *   - a pass whose dimension is already 224 is skipped and the bytes are copied, as Pillow does it (the 224 -> 224 table is one
+ *     coefficient 2^22 per sample for both filters, so an identity pass would give the same bytes);
+ *   - W above RELAX_RESIZE_224_MAX_IN_W (5461) is refused, as it always was on this entry, although the kernels stage rows up to
+ *     RELAX_RESIZE_MAX_IN_W; W = 5457..5461 stage 4 * 16384 + 32 bytes of LDS, more than 64 KiB, and take the dynamic-LDS opt-in;
+ *   - N above 65535 (the launch grid; once a failed launch) and H above RELAX_RESIZE_MAX_IN_H (once computed: the table builder
+ *     itself has no limit) are refused with RELAX_ERR_INVALID and the value named;
+ *   - the tables come from the handle's cache of 16 (least recently used replaced; a call needs at most four), and a table with
+ *     a coefficient outside 24 bits would be refused - for out = 224 none is (the largest over the input sizes tested is 5 386 769). */
 int relax_resize_frames(relax_handle* h, const uint8_t* frames, int64_t item_stride, int N, int H, int W,
                         uint8_t* out_bilinear, uint8_t* out_lanczos, relax_stream stream);
 
@@ -321,19 +330,23 @@ int relax_resize_frames(relax_handle* h, const uint8_t* frames, int64_t item_str
  * once, and the residual image is written only when asked for.
  * `residual` must not overlap `orig` or `next` (the kernel treats the three as distinct memory).
  * Rows move 16 bytes per lane only when W*3, pair_stride and all of orig, next and a non-NULL residual are multiples of
- * 16; any one of them off (an odd residual pointer alone included) puts the whole call on the much slower bytewise path. */
+ * 16; any one of them off (an odd residual pointer alone included) puts the whole call on the much slower bytewise path.
+ * This is relax_resize_residual_ex at out_h = out_w = 224: the limits and consequences listed at relax_resize_frames hold here
+ * too (T in the place of N).  With W == 224 and H != 224 the difference image goes through the handle's workspace once and serves
+ * both filters. */
 int relax_resize_residual(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
                           uint8_t* out_bilinear, uint8_t* out_lanczos, uint8_t* residual, relax_stream stream);
 
 /* ---- whole-frame front-end at ANY output size (the canvases relax_vit_features_canvas takes) --------- */
 /* The reference's resize size is an argument: transforms.Resize(img_size) (src/extractor/visualise_vit_layer.py:339-342, the
  * reduced-size form left commented at :473; visualise_vit.py:339-342; demo_visual.py:27-28) and img.resize(..., LANCZOS) - in
- * both cases Pillow's 8-bit resample.  The limits of these entries: */
+ * both cases Pillow's 8-bit resample.  The limits of the resize entries: */
 #define RELAX_RESIZE_BILINEAR 0
 #define RELAX_RESIZE_LANCZOS 1
 #define RELAX_RESIZE_MAX_OUT 2048     /* out_h, out_w: 1..2048 (a 4096-patch ViT canvas reaches 2048 pixels on a side: 2048 x 512 at patch 16) */
 #define RELAX_RESIZE_MAX_IN_W 8192    /* W: four input rows are staged in LDS (8192 * 3 * 4 B = 96 KiB; above 64 KiB by opt-in) */
 #define RELAX_RESIZE_MAX_IN_H 16384   /* H, and in_size of relax_resize_table */
+#define RELAX_RESIZE_224_MAX_IN_W 5461   /* W of relax_resize_frames / relax_resize_residual: four rows of it are the 64 KiB their first kernels staged */
 /* Everything outside them is refused (RELAX_ERR_INVALID) with the offending value named in relax_last_error. */
 
 /* The size transforms.Resize(size), size an int, gives a PIL image of H x W (torchvision's _compute_resized_output_size): the
@@ -357,7 +370,7 @@ int relax_resize_table(int in_size, int out_size, int filt, int32_t* bounds, int
  * as uint8 [N,H,out_w,3] in the handle's workspace, then the vertical pass; a pass whose dimension already matches is skipped and
  * the bytes are copied.  One read of each frame serves both filters.  Rows are staged 16 bytes per lane when W*3, item_stride and
  * frames are multiples of 16, bytewise otherwise (decided per call).  The tables are cached on the handle per (input size, output
- * size, filter), the least recently used of 16 replaced.  relax_resize_frames itself keeps its own 224-only kernels. */
+ * size, filter), the least recently used of 16 replaced.  relax_resize_frames is this entry at 224 x 224 with its own width limit. */
 int relax_resize_frames_ex(relax_handle* h, const uint8_t* frames, int64_t item_stride, int N, int H, int W, int out_h, int out_w,
                            uint8_t* out_bilinear, uint8_t* out_lanczos, relax_stream stream);
 

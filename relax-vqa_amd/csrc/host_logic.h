@@ -99,7 +99,7 @@ struct TailSplit {
 };
 TailSplit choose_tail_split(int ntiles, int slots, int nk, int min_steps, bool can_split);
 
-// ---- Pillow's 8-bit resample on the host (resize.hip, resize_any.hip; relax_resize_table, relax_resize_output_size) --------------------------
+// ---- Pillow's 8-bit resample on the host (resize.hip; relax_resize_table, relax_resize_output_size) ------------------------------------------
 // The table of one pass, in_size -> out_size samples under filter 0 (BILINEAR, support 1) or 1 (LANCZOS, support 3): libImaging/Resample.c's
 // precompute_coeffs for the box (0, in_size) + normalize_coeffs_8bpc, in the same double arithmetic - per output sample its first tap and tap
 // count (bounds [out_size][2]) and its taps as 22-bit fixed point (coeffs [out_size][ksize], zero behind the count).

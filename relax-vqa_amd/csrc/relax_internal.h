@@ -293,15 +293,8 @@ struct HeadTrain {
     DeviceOwner mem;
 };
 
-// ---- resize coefficient tables (Pillow-exact), cached per (input size, filter) ------------------------------
-struct ResizeTable {
-    int in_size = 0, filt = 0, ksize = 0;
-    int32_t* bounds = nullptr;  // device [224][2]: first tap, tap count
-    int32_t* coeffs = nullptr;  // device [224][ksize]: 22-bit fixed point
-};
-
-// ... and of the any-size entries (resize_any.hip), per (input size, output size, filter): coeffs and bounds share one allocation; the
-// least recently used of the kResizeAnyCache entries is replaced (a call needs at most four)
+// ---- resize coefficient tables (Pillow-exact; resize.hip), cached per (input size, output size, filter): coeffs and bounds share one
+// allocation; the least recently used of the kResizeAnyCache entries is replaced (a call needs at most four)
 struct ResizeAnyTable {
     int in_size = 0, out_size = 0, filt = 0, kstride = 0;
     int32_t* coeffs = nullptr;  // device [out_size][kstride]: the table's rows padded with zeros to a multiple of four taps (16-byte rows)
@@ -352,7 +345,6 @@ struct relax_handle {
     relax::DevBuf metrics_ws;   // pair counters and results of the correlation metrics (metrics.hip)
     relax::HeadW head;
     relax::HeadTrain head_train;
-    std::vector<relax::ResizeTable> resize_tables;
     relax::ResizeAnyTable resize_any_cache[relax::kResizeAnyCache];
     uint64_t resize_any_clock = 0;
     relax::ResNet50W rn;
@@ -499,8 +491,7 @@ int launch_nhwc_to_nchw(relax_handle* h, const float* x, float* y, int Nimg, int
 // model drivers
 void free_resnet(relax_handle* h);
 void free_vit(relax_handle* h);
-void free_resize(relax_handle* h);       // ... which calls
-void free_resize_any(relax_handle* h);   // (resize_any.hip: the any-size table cache)
+void free_resize(relax_handle* h);       // the table cache and resize_ws
 void free_head(relax_handle* h);
 void free_head_train(relax_handle* h);
 void free_vgg(relax_handle* h);

@@ -519,23 +519,8 @@ class RelaxEngine:
 
     def resize_frames(self, frames, bilinear=True, lanczos=True, out_bilinear=None, out_lanczos=None):
         """frames uint8 [N,H,W,3] -> (bilinear, lanczos) uint8 [N,224,224,3] each (None if not requested), bit-identical
-        to PIL's Image.resize((224,224), BILINEAR / LANCZOS) (the reference's whole-frame inputs)."""
-        if isinstance(frames, np.ndarray):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        frames = frames.to(self.device, non_blocking=True)
-        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError(f"frames must be uint8 [N,H,W,3], got {frames.dtype} {tuple(frames.shape)}")
-        N, H, W, _ = frames.shape
-        if frames.stride()[1:] != (W * 3, 3, 1):      # items may be strided (e.g. clip[:, 0]); pixels must be packed
-            frames = frames.contiguous()
-        item_stride = frames.stride(0) if N > 1 else H * W * 3
-        ob = (out_bilinear if out_bilinear is not None else
-              torch.empty((N, TARGET, TARGET, 3), dtype=torch.uint8, device=self.device)) if bilinear else None
-        ol = (out_lanczos if out_lanczos is not None else
-              torch.empty((N, TARGET, TARGET, 3), dtype=torch.uint8, device=self.device)) if lanczos else None
-        self._check(self.lib.relax_resize_frames(self.h, _ptr(frames), item_stride, N, H, W, _ptr(ob), _ptr(ol), _stream()),
-                    "relax_resize_frames")
-        return ob, ol
+        to PIL's Image.resize((224,224), BILINEAR / LANCZOS) (the reference's whole-frame inputs; relax_resize_frames)."""
+        return self._resize_frames("resize_frames", frames, None, bilinear, lanczos, out_bilinear, out_lanczos)
 
     def resize_output_size(self, H, W, size):
         """(out_h, out_w) that transforms.Resize(size), size an int, gives a PIL image of H x W: the shorter side becomes size, the
@@ -567,19 +552,26 @@ class RelaxEngine:
         PIL's Image.resize((out_w,out_h), BILINEAR / LANCZOS), down, up or mixed (relax_resize_frames_ex).  size: an int - the
         shorter side becomes size, as transforms.Resize(size) does it (resize_output_size) - or an (h, w) pair.  Items may be
         strided as in resize_frames."""
+        return self._resize_frames("resize_frames_to", frames, size, bilinear, lanczos, out_bilinear, out_lanczos)
+
+    def _resize_frames(self, what, frames, size, bilinear, lanczos, out_bilinear, out_lanczos):
+        """size None: 224 x 224 through relax_resize_frames (its width limit and message), otherwise relax_resize_frames_ex"""
         if isinstance(frames, np.ndarray):
             frames = torch.from_numpy(np.ascontiguousarray(frames))
         frames = frames.to(self.device, non_blocking=True)
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError(f"frames must be uint8 [N,H,W,3], got {frames.dtype} {tuple(frames.shape)}")
         N, H, W, _ = frames.shape
-        oh, ow = self._resize_target(H, W, size)
+        oh, ow = (TARGET, TARGET) if size is None else self._resize_target(H, W, size)
         if frames.stride()[1:] != (W * 3, 3, 1):      # items may be strided (e.g. clip[:, 0]); pixels must be packed
             frames = frames.contiguous()
         item_stride = frames.stride(0) if N > 1 else H * W * 3
-        ob, ol = self._resize_outputs("resize_frames_to", N, oh, ow, bilinear, lanczos, out_bilinear, out_lanczos)
-        self._check(self.lib.relax_resize_frames_ex(self.h, _ptr(frames), item_stride, N, H, W, oh, ow, _ptr(ob), _ptr(ol), _stream()),
-                    "relax_resize_frames_ex")
+        ob, ol = self._resize_outputs(what, N, oh, ow, bilinear, lanczos, out_bilinear, out_lanczos)
+        src, outs = (self.h, _ptr(frames), item_stride, N, H, W), (_ptr(ob), _ptr(ol), _stream())
+        if size is None:
+            self._check(self.lib.relax_resize_frames(*src, *outs), "relax_resize_frames")
+        else:
+            self._check(self.lib.relax_resize_frames_ex(*src, oh, ow, *outs), "relax_resize_frames_ex")
         return ob, ol
 
     def residual_resize(self, frames, bilinear=True, lanczos=True, want_residual=False, out_bilinear=None, out_lanczos=None, size=None):
@@ -587,36 +579,22 @@ class RelaxEngine:
         resizes of the WHOLE frame difference cv2.absdiff(next, orig) (src/main_residual.py:223-231), bit-identical to
         resize_frames on that image, and the uint8 [T,H,W,3] difference image itself; None for any output not requested.
         One launch reads each pair once (relax_resize_residual); without want_residual the difference never reaches memory.
-        size (None: 224 x 224, the call above unchanged): an int or an (h, w) pair as resize_frames_to takes it -> outputs
-        [T,out_h,out_w,3] through relax_resize_residual_ex."""
+        size (None: 224 x 224 through relax_resize_residual, its width limit and message): an int or an (h, w) pair as
+        resize_frames_to takes it -> outputs [T,out_h,out_w,3] through relax_resize_residual_ex."""
         frames = self._dev_u8(frames)
         if frames.dim() != 5 or frames.shape[1] != 2 or frames.shape[4] != 3:
             raise ValueError(f"frames must be [T,2,H,W,3], got {tuple(frames.shape)}")
         T, _, H, W, _ = frames.shape
-        dev = self.device
-        if size is not None:
-            oh, ow = self._resize_target(H, W, size)
-            ob, ol = self._resize_outputs("residual_resize", T, oh, ow, bilinear, lanczos, out_bilinear, out_lanczos)
-            res = torch.empty((T, H, W, 3), dtype=torch.uint8, device=dev) if want_residual else None
-            fb = H * W * 3
-            base = frames.data_ptr()
-            rc = self.lib.relax_resize_residual_ex(self.h, C.c_void_p(base), C.c_void_p(base + fb), 2 * fb, T, H, W, oh, ow, _ptr(ob),
-                                                   _ptr(ol), _ptr(res), _stream())
-            self._check(rc, "relax_resize_residual_ex")
-            return ob, ol, res
-        ob = (out_bilinear if out_bilinear is not None else
-              torch.empty((T, TARGET, TARGET, 3), dtype=torch.uint8, device=dev)) if bilinear else None
-        ol = (out_lanczos if out_lanczos is not None else
-              torch.empty((T, TARGET, TARGET, 3), dtype=torch.uint8, device=dev)) if lanczos else None
-        for o in (ob, ol):
-            if o is not None and (o.dtype != torch.uint8 or tuple(o.shape) != (T, TARGET, TARGET, 3) or not o.is_contiguous()):
-                raise ValueError("residual_resize: output buffers must be contiguous uint8 [T,224,224,3]")
-        res = torch.empty((T, H, W, 3), dtype=torch.uint8, device=dev) if want_residual else None
+        oh, ow = (TARGET, TARGET) if size is None else self._resize_target(H, W, size)
+        ob, ol = self._resize_outputs("residual_resize", T, oh, ow, bilinear, lanczos, out_bilinear, out_lanczos)
+        res = torch.empty((T, H, W, 3), dtype=torch.uint8, device=self.device) if want_residual else None
         fb = H * W * 3
         base = frames.data_ptr()
-        rc = self.lib.relax_resize_residual(self.h, C.c_void_p(base), C.c_void_p(base + fb), 2 * fb, T, H, W, _ptr(ob), _ptr(ol),
-                                            _ptr(res), _stream())
-        self._check(rc, "relax_resize_residual")
+        src, outs = (self.h, C.c_void_p(base), C.c_void_p(base + fb), 2 * fb, T, H, W), (_ptr(ob), _ptr(ol), _ptr(res), _stream())
+        if size is None:
+            self._check(self.lib.relax_resize_residual(*src, *outs), "relax_resize_residual")
+        else:
+            self._check(self.lib.relax_resize_residual_ex(*src, oh, ow, *outs), "relax_resize_residual_ex")
         return ob, ol, res
 
     # ---- stage B ------------------------------------------------------------------------------

@@ -19,6 +19,10 @@ CASES = [
     ((1080, 1920), (270, 480), 2),   # a real size
     ((3, 8192), (2, 100), 1),     # the widest row: the row stage above 64 KiB of LDS
 ]
+# the 224 entries (relax_resize_frames / relax_resize_residual) on the same kernels: the widest rows they take (H = 5), and the input sizes
+# whose -> 224 tables are checked for coefficients inside 24 bits
+WIDEST_224 = [5456, 5461]
+IN_SIZES_224 = [1, 2, 3, 100, 223, 224, 225, 448, 1080, 1920, 2160, 3840, 5456, 5457, 5461, 8192, 16384]
 TABLE_PAIRS = [(53, 30), (37, 16), (34, 80), (18, 48), (240, 120), (1080, 270), (1920, 480), (2160, 224), (7, 1), (1, 5), (64, 63)]
 
 _frames, _refs = {}, {}

@@ -57,6 +57,21 @@ def test_matches_pillow_on_the_host_made_difference(h, w):
         _same(gl[i], lan[i], f"lanczos pair {i}")
 
 
+@pytest.mark.parametrize("h,w", [(224, 300), (301, 224), (224, 224)])
+def test_skipped_passes_at_224(h, w):
+    """A side that is already 224 has no pass, as in Pillow: H == 224 - the horizontal pass writes the outputs; W == 224 - the difference
+    goes through the workspace once and serves both filters' vertical passes; both - the outputs are the difference image."""
+    t = 2
+    frames = np.random.default_rng(7 * h + w).integers(0, 256, (t, 2, h, w, 3), dtype=np.uint8)
+    d = fragment_ref.absdiff(frames[:, 1], frames[:, 0])
+    gb, gl, gr = engine().residual_resize(torch.from_numpy(frames).cuda(), want_residual=True)
+    _same(gr, d, "residual image")
+    for i in range(t):
+        img = Image.fromarray(d[i])
+        _same(gb[i], np.asarray(img.resize((224, 224), Image.BILINEAR)), f"bilinear pair {i}")
+        _same(gl[i], np.asarray(img.resize((224, 224), Image.LANCZOS)), f"lanczos pair {i}")
+
+
 @pytest.mark.parametrize("h,w", [(250, 333), (270, 480)])
 def test_separate_orig_and_next_tensors(h, w):
     """pair_stride = one frame: orig and next are two [T,H,W,3] tensors, not the interleaved [T,2,H,W,3] one."""

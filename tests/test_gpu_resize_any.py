@@ -1,13 +1,14 @@
-"""relax_resize_frames_ex / relax_resize_residual_ex (csrc/resize_any.hip) and the engine methods on them: the resize to any output size,
+"""relax_resize_frames_ex / relax_resize_residual_ex (csrc/resize.hip) and the engine methods on them: the resize to any output size,
 bit for bit against oracle/resize_ref.resize (pinned to Pillow at the same cases in tests/test_resize_any_cpu.py) - down, up, mixed, with
-either pass or both skipped, on the 16-byte and the bytewise row path, into guarded buffers, from strided items -, against the 224-only
-kernels at 224 x 224, the residual form against the plain one on the torch-made difference, the refusals, and whole_frame_vit_canvas."""
+either pass or both skipped, on the 16-byte and the bytewise row path, into guarded buffers, from strided items -, the 224 entries on the
+same kernels (both entries against the oracle at 224 x 224, their widest rows, the table cache turning over under them), the residual form
+against the plain one on the torch-made difference, the refusals, and whole_frame_vit_canvas."""
 import numpy as np
 import pytest
 import torch
 from PIL import Image
 
-from oracle import resize_ref
+from oracle import fragment_ref, resize_ref
 from relax_vqa_amd.engine import _ptr, _stream
 from tests import resize_any_cases as cases
 from tests.gpu_common import engine, rn50_weights, vit_weights
@@ -90,11 +91,49 @@ def test_the_shorter_side_rule():
 
 @pytest.mark.parametrize("hw", [(20, 16), (270, 480)], ids=["20x16", "270x480"])
 def test_equals_the_224_kernels_at_224(hw):
+    """resize_frames and resize_frames_to(..., (224, 224)) reach the same kernels through two entries: each equals the oracle, and
+    they equal each other."""
     frames = _strided(cases.frames(hw, 2))
     eng = engine()
     wb, wl = eng.resize_frames(frames)
     gb, gl = eng.resize_frames_to(frames, (224, 224))
+    for filt, name, w, g in ((resize_ref.BILINEAR, "bilinear", wb, gb), (resize_ref.LANCZOS, "lanczos", wl, gl)):
+        want = cases.reference(hw, (224, 224), 2, filt)
+        _same(w, want, f"resize_frames {name}")
+        _same(g, want, f"resize_frames_to {name}")
     assert torch.equal(gb, wb) and torch.equal(gl, wl)
+
+
+@pytest.mark.parametrize("w", cases.WIDEST_224, ids=["5456-16-byte-rows", "5461-bytewise-lds-opt-in"])
+def test_widest_rows_of_the_224_entries(w):
+    """The last widths relax_resize_frames / relax_resize_residual take: 5456 (16-byte rows, 4 * 16368 + 32 bytes of LDS, the last
+    width under 64 KiB) and 5461 (bytewise rows, 4 * 16384 + 32 bytes: the dynamic-LDS opt-in).  H = 5: two workgroups, the second
+    with one row."""
+    hw, n = (5, w), 2
+    assert (w * 3 % 16 == 0) == (w == 5456)
+    orig = cases.frames(hw, n)
+    nxt = np.random.default_rng(w).integers(0, 256, orig.shape, dtype=np.uint8)
+    diff = fragment_ref.absdiff(nxt, orig)
+    pairs = torch.from_numpy(np.stack([orig, nxt], axis=1)).cuda()
+    eng = engine()
+    bufs = [_guarded(n, 224, 224) for _ in range(4)]
+    eng.resize_frames(pairs[:, 0], out_bilinear=bufs[0][1], out_lanczos=bufs[1][1])
+    _, _, gr = eng.residual_resize(pairs, want_residual=True, out_bilinear=bufs[2][1], out_lanczos=bufs[3][1])
+    for k, filt in enumerate((resize_ref.BILINEAR, resize_ref.LANCZOS)):
+        _same(bufs[k][1], cases.reference(hw, (224, 224), n, filt), f"resize_frames filter {filt}")
+        _same(bufs[2 + k][1], np.stack([resize_ref.resize(d, 224, 224, filt) for d in diff]), f"residual_resize filter {filt}")
+    _same(gr, diff, "residual image")
+    assert all(_guards_intact(b) for b, _ in bufs), "bytes outside an output were written"
+
+
+def test_table_eviction_under_the_224_entries():
+    """Nine shapes ask for 36 tables of the 16 the handle caches; the first shape, whose tables have gone by then, comes back right."""
+    eng = engine()
+    shapes = [(10 + i, 20 + i) for i in range(9)]
+    for hw in shapes + shapes[:1]:
+        gb, gl = eng.resize_frames(_dev(cases.frames(hw, 1)))
+        _same(gb, cases.reference(hw, (224, 224), 1, resize_ref.BILINEAR), f"bilinear {hw}")
+        _same(gl, cases.reference(hw, (224, 224), 1, resize_ref.LANCZOS), f"lanczos {hw}")
 
 
 # down | vertical skipped | horizontal skipped (the difference goes through the workspace) | copy | 16-byte rows | several workgroups

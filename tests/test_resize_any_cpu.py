@@ -1,6 +1,7 @@
 """The host half of the any-size resize (include/relax_hip.h: relax_resize_table, relax_resize_output_size; csrc/host_logic.cpp) and its
-yardstick: the tables against oracle/resize_ref.precompute_coeffs, the output size against the rule transforms.Resize(int) applies to a
-PIL image, and oracle/resize_ref.resize against PIL.Image.resize at every case the GPU tests use."""
+yardstick: the tables against oracle/resize_ref.precompute_coeffs, the tables the 224 entries read inside the 24 bits the kernels multiply
+in, the output size against the rule transforms.Resize(int) applies to a PIL image, and oracle/resize_ref.resize against PIL.Image.resize
+at every case the GPU tests use."""
 import ctypes as C
 
 import numpy as np
@@ -34,6 +35,22 @@ def test_table_equals_the_oracle(in_size, out_size, filt):
     assert coeffs.shape == want_c.shape, "ksize"
     assert np.array_equal(bounds, want_b)
     assert np.array_equal(coeffs, want_c)
+
+
+@pytest.mark.parametrize("filt", [resize_ref.BILINEAR, resize_ref.LANCZOS], ids=["bilinear", "lanczos"])
+def test_tables_to_224_stay_inside_24_bits(filt):
+    """The kernels multiply on the 24-bit multiplier and the device table refuses a coefficient outside it: for the 224 entries it never
+    does.  224 -> 224 is the identity (one 2^22 per sample), which is why a skipped pass and an identity pass give the same bytes."""
+    lib = _lib.load()
+    for in_size in cases.IN_SIZES_224:
+        _, coeffs = _table(lib, in_size, 224, filt)
+        assert int(np.abs(coeffs.astype(np.int64)).max()) < 1 << 23, in_size
+    bounds, coeffs = _table(lib, 224, 224, filt)
+    for i in range(224):
+        assert bounds[i, 0] <= i < bounds[i, 0] + bounds[i, 1], i      # the 2^22 sits on sample i itself
+        row = np.zeros(coeffs.shape[1], np.int32)
+        row[i - bounds[i, 0]] = 1 << 22
+        assert np.array_equal(coeffs[i], row), i
 
 
 def test_table_refusals_name_the_value():
@@ -90,7 +107,8 @@ def test_output_size_refusals_name_the_value():
     assert lib.relax_resize_output_size(5, 5, 5, None, None) != 0
 
 
-@pytest.mark.parametrize("hw,out,n", cases.CASES + [((20, 16), (224, 224), 1), ((270, 480), (224, 224), 1)],
+@pytest.mark.parametrize("hw,out,n", cases.CASES + [((20, 16), (224, 224), 1), ((270, 480), (224, 224), 1)]
+                         + [((5, w), (224, 224), 2) for w in cases.WIDEST_224],
                          ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
 def test_oracle_is_pillow_at_the_gpu_cases(hw, out, n):
     f = cases.frames(hw, n)[0]
