@@ -1,7 +1,13 @@
 """Parameter sets, inputs and references of the optical-flow checks with OpenCV's parameters as arguments (relax_optical_flow_ex,
 csrc/flow.hip), shared by tests/test_flow_params_cpu.py, tests/test_gpu_flow_params.py, tools/flow_params_parity.py and
 tools/flow_params_bench.py.  Inputs are tests/flow_cases.make_pair's; the reference is oracle/flow_ref.farneback with the same six
-parameters, in float64 and in float32 (computed once per case)."""
+parameters, in float64 and in float32 (computed once per case).
+
+The sets below move ONE parameter at a time away from the literal set.  tests/flow_param_space.py holds the parameters in combination
+(every pyr_scale with windows under, at and over 15; poly_n 7 and pyr_scale != 0.5 with box_solve_any; pyramid_fused with box_solve_any; the
+sampled pyramid kernels at 0.6, 0.7 and 0.8; nine levels at 0.95; ten iterations; widths and heights at the band and segment edges) and uses
+this module's contents, references, parity terms and gate.  Neither covers the 39- and 79-tap wide kernels in combination (deep4 / deep5
+here run them with the literal window and poly_n), 2160p frames, or poly_sigma outside 1.1 .. 2.0."""
 import functools
 import json
 import os
