@@ -505,14 +505,43 @@ __global__ __launch_bounds__(512, 2) void gemm_h2(const H2Params p) {
 // 2.83e-7 / 2.84e-7 at K = 768, 5.47e-7 / 5.47e-7 at K = 3072 - the fp32 accumulator's own rounding is what is left - and both below the
 // fp32 FMA chain's 4.4e-7 / 8.8e-7); FOUR = true adds A[lo] . B[lo] in front (short K: at K = 32 the three-product error, 9.7e-8, would
 // sit above the chain's 9.0e-8).  48 MFMAs per wave and 16 k (v1 above: 64, bf16x6: 96), 12 ds_read_b128 (16, 32), half the barriers.
-// LDS: two stages of [hi image: 512 rows x 64 B][lo image: the same] = 64 KB; unit u (8 k) of row r sits in slot u ^ f((r >> 2) & 3),
+// LDS rows are 64 B (the 32 k of one plane); unit u (8 k) of row r sits in slot u ^ f((r >> 2) & 3),
 // f = {0, 3, 2, 1}: conflict-free ds_read_b128 (a 16-lane group holds rows {0-3, 12-15} at one parity of g and {4-11} at the other);
 // the permutation is applied on the SOURCE offset of the DMA.  The global format keeps its 16-k chunks ([16 hi][16 lo]): unit u of the
-// 32-k step = chunk u >> 1, half u & 1.  Eight DMA pieces per wave and step, one in front of each MFMA group of the region; the pieces of
-// step k+2 go into the stage step k has just left and have the rest of the region to land (two stages: nothing stays in flight across a
-// barrier).
-constexpr int H3_STAGE = (H2_BM + H2_BN) * 128;   // 64 KB
-constexpr int H3_NSTG = 2;
+// 32-k step = chunk u >> 1, half u & 1.  Eight DMA pieces per wave and step (four per operand), one in front of each MFMA group of a region.
+// LDS (dynamic, nothing static): every operand has its own ring of 32 KB stages, [hi image: 256 rows x 64 B][lo image: the same]; the
+// activation ring (ASTG stages) first, the weight ring (BSTG stages) behind it.  2 + 2 stages = 128 KB is the schedule in which nothing
+// stays in flight across a barrier: region k issues both operands of step k+2 into the stages step k has just left, and its head waits
+// for vmcnt(0).  The part has 160 KB: ONE operand can have a third stage (3 + 2 or 2 + 3 = 163840 B, the most a gfx950 workgroup can
+// ask for).  That operand (the "late" one) is requested a step further ahead - region k issues its pieces of step k+3 into the stage
+// step k has left, BEHIND the pieces of the other operand for step k+2 - so the newest DMAs of a wave at a region's head are always pieces
+// that are not needed yet: the head waits with a counted vmcnt and the late operand's pieces have a whole further region to land.
+// Which form runs with which rings: h3_rings below (measured per form: profiles/h3_a_stages.json).
+constexpr int H3_OPSTAGE = H2_BM * 128;   // 32 KB: one stage of one operand (H2_BM == H2_BN)
+static_assert(H2_BM == H2_BN, "gemm_h3: the operand rings share their stage size");
+// Ring sizes per form (plain GEMMs: the ViT; 1x1 and tap convolutions: ResNet-50 layer3 / layer4) and the issue order of a 3 + 2 / 2 + 3
+// region (0: the four pieces of the early operand, then the four of the late one; 1: early, early, late, late by plane).  Compile-time
+// switches so that a variant library can be measured against this one (tools/build_ablations.sh h3stg:<plain>:<1x1>:<taps>, three digits each).
+// Measured (profiles/h3_a_stages.json), a ViT pass over 1024 fragments: 2 + 2 101.1 ms, 3 + 2 98.4, 2 + 3 98.7, with order 1 100.7 / 100.3; a
+// ResNet-50 pass: 35.3 ms with the convolution forms on 2 + 2, 35.4 with the 1x1 form on 3 + 2, 36.6 with the tap form on 3 + 2 (spills).
+#ifndef H3_PLAIN_STAGES
+#define H3_PLAIN_STAGES 3, 2, 0
+#endif
+#ifndef H3_CONV1_STAGES
+#define H3_CONV1_STAGES 2, 2, 0
+#endif
+#ifndef H3_TAPS_STAGES
+#define H3_TAPS_STAGES 2, 2, 0
+#endif
+struct H3Rings { int a, b, order; };
+constexpr H3Rings h3_rings(bool taps, bool perimg) { return taps ? H3Rings{H3_TAPS_STAGES} : perimg ? H3Rings{H3_CONV1_STAGES} : H3Rings{H3_PLAIN_STAGES}; }
+constexpr size_t h3_lds_bytes(bool taps, bool perimg) { return (size_t)(h3_rings(taps, perimg).a + h3_rings(taps, perimg).b) * H3_OPSTAGE; }
+// Stamp 1 of the diagnostic build is taken where the K loop starts, with DMAs in flight that the loop counts: a store there would be one
+// more entry on the wave's VM counter.  The stamp is latched in a register and stored behind the loop.
+#ifndef H2_STAMP_LATCH
+#define H2_STAMP_LATCH(v_)
+#define H2_STAMP_PUT(i_, v_)
+#endif
 
 // the maximum over the 16 lanes of a DPP row, in every lane of the row (quad swaps, then the two mirrors)
 __device__ inline float dpp_row_max(float v) {
@@ -527,10 +556,14 @@ __device__ inline float dpp_row_max(float v) {
 
 // PERIMG: the per-image features of the convolution launches (per-image scales, plane residual, fused means, maxima, out_rows): the
 // plain GEMMs of the ViT keep the lean epilogue
-template <bool FOUR, bool TAPS = false, bool PERIMG = false>
-__global__ __launch_bounds__(512, 2) void gemm_h3(const H2Params p) {
+// ASTG / BSTG: the stages of the activation / weight ring (2 + 2, 3 + 2 or 2 + 3), ORDER: the issue order of a region with a late operand
 #if __HIP_DEVICE_COMPILE__   // the host pass only needs the launch stub (no __amdgpu_buffer_rsrc_t there)
-    constexpr int BM = H2_BM, BN = H2_BN, STAGE = H3_STAGE, NSTG = H3_NSTG, IMG = STAGE / 2;
+template <bool FOUR, bool TAPS, bool PERIMG, int ASTG, int BSTG, int ORDER>
+__device__ __forceinline__ void gemm_h3_body(const H2Params& p) {
+    constexpr int BM = H2_BM, BN = H2_BN, OPSTG = H3_OPSTAGE, IMG = OPSTG / 2, B0 = ASTG * OPSTG;
+    constexpr int LA = ASTG - 2, LB = BSTG - 2;   // how many steps further ahead than k+2 an operand is requested
+    static_assert(LA >= 0 && LB >= 0 && LA + LB <= 1 && (ORDER == 0 || ORDER == 1), "gemm_h3: 2 + 2, 3 + 2 or 2 + 3 stages");
+    constexpr int WAITN = ORDER == 0 ? 4 : 2;     // the pieces of the late operand a wave has issued behind its last early piece
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -575,10 +608,10 @@ __global__ __launch_bounds__(512, 2) void gemm_h3(const H2Params p) {
 #endif
     H2_STAMP(0);
 
-    // ---- DMA descriptors.  A piece = 1 KiB = 16 rows x 64 B of one image; the images hold 32 pieces each (activation rows: 0 .. 15,
-    // weight rows: 16 .. 31).  Piece j of this wave: image j >> 2 (hi, lo), piece wave + 8 (j & 3) of it; lane l fills slot l & 3 of row
-    // 16 * piece + (l >> 2), which holds unit slot ^ f(row) = chunk (unit >> 1), half (unit & 1) of the step.  The hi and the lo piece
-    // of the same rows share the per-lane offset (the plane is + 32 B in the scalar offset): four offsets.
+    // ---- DMA descriptors.  A piece = 1 KiB = 16 rows x 64 B of one image; an operand's images hold 16 pieces each.  Piece i of this wave
+    // and operand: image i >> 1 (hi, lo), piece wave + 8 (i & 1) of it; lane l fills slot l & 3 of row 16 * piece + (l >> 2), which
+    // holds unit slot ^ f(row) = chunk (unit >> 1), half (unit & 1) of the step.  The hi and the lo piece of the same rows share the
+    // per-lane offset (the plane is + 32 B in the scalar offset): four offsets (q = 0, 1: activation rows, 2, 3: weight rows).
     // Convolutions (p.pixels): an activation row is an output pixel; its offset is the input pixel it reads at tap (0, 0), the step's
     // tap adds (dy W + dx) pixels, a tap outside the image (bit mask per piece) or a row past M an out-of-range offset: the DMA
     // writes zeros.  K order: 32-channel groups outermost, the KH*KW taps of a group innermost (they re-read neighbouring pixels: L2).
@@ -623,46 +656,88 @@ __global__ __launch_bounds__(512, 2) void gemm_h3(const H2Params p) {
             voff[q] = (unsigned)(trow * (int)arow_bytes + off);
         }
     }
-    // the next 32-k step to issue (steps are issued in order): plain = a byte offset; taps = (32-channel group, dy, dx)
-    int d_kt = kt_begin;
-    [[maybe_unused]] int d_cc = 0, d_tap = 0, d_dy = 0, d_dx = 0;
+    // the next 32-k step to issue, per operand (steps are issued in order; the late operand runs one step ahead of the other): plain = a byte
+    // offset; taps = (32-channel group, tap, dy, dx)
+    int dA_kt = kt_begin;
+    [[maybe_unused]] int dA_cc = 0, dA_tap = 0, dA_dy = 0, dA_dx = 0;
     [[maybe_unused]] const int cin_chunks = p.Cin >> 4;
     if (TAPS) {
-        d_cc = kt_begin / ntaps;
-        d_tap = kt_begin - d_cc * ntaps;
-        d_dy = d_tap / p.KW;
-        d_dx = d_tap - d_dy * p.KW;
+        dA_cc = kt_begin / ntaps;
+        dA_tap = kt_begin - dA_cc * ntaps;
+        dA_dy = dA_tap / p.KW;
+        dA_dx = dA_tap - dA_dy * p.KW;
     }
-#define H3_ISSUE_PIECE(st_, j_)                                                                                         \
+    // (2 + 2: both operands are always at the same step - the weights go by the activations' counters)
+    [[maybe_unused]] int dW_kt_own = dA_kt, dW_cc_own = dA_cc, dW_tap_own = dA_tap;
+    int &dW_kt = LA + LB > 0 ? dW_kt_own : dA_kt, &dW_cc = LA + LB > 0 ? dW_cc_own : dA_cc, &dW_tap = LA + LB > 0 ? dW_tap_own : dA_tap;
+#define H3_ISSUE_A(st_, i_)                                                                                             \
     {                                                                                                                   \
-        const int dst_ = (st_) * STAGE + ((j_) >> 2) * IMG + (wave + 8 * ((j_) & 3)) * 1024;                             \
-        if (((j_) & 3) < 2) {                                                                                           \
-            if (TAPS) {                                                                                                 \
-                const bool ok_ = (a_taps[(j_) & 1] >> d_tap) & 1u;                                                      \
-                const int tapoff_ = (d_dy * p.W + d_dx) * (int)arow_bytes + d_cc * (2 * kH2ChunkBytes) + ((j_) >> 2) * 32; \
-                H2_DMA(rsrc_a, dst_, ok_ ? voff[(j_) & 3] + (unsigned)tapoff_ : kH2OutOfRange, 0);                      \
-            } else {                                                                                                    \
-                H2_DMA(rsrc_a, dst_, voff[(j_) & 3], H3_KSTEP(d_kt) * (2 * kH2ChunkBytes) + ((j_) >> 2) * 32);          \
-            }                                                                                                           \
-        } else {                                                                                                        \
-            const int wk_ = TAPS ? (d_tap * cin_chunks + 2 * d_cc) * kH2ChunkBytes : H3_KSTEP(d_kt) * (2 * kH2ChunkBytes); \
-            H2_DMA(rsrc_w, dst_, voff[(j_) & 3], wk_ + ((j_) >> 2) * 32);                                                \
-        }                                                                                                               \
-    }
-#define H3_ISSUE_ADVANCE()                                                                                              \
-    {                                                                                                                   \
-        ++d_kt;                                                                                                         \
+        const int dst_ = (st_) * OPSTG + ((i_) >> 1) * IMG + (wave + 8 * ((i_) & 1)) * 1024;                             \
         if (TAPS) {                                                                                                     \
-            ++d_tap;                                                                                                    \
-            ++d_dx;                                                                                                     \
-            const bool wx_ = d_dx == p.KW;                                                                              \
-            d_dx = wx_ ? 0 : d_dx;                                                                                      \
-            d_dy += wx_ ? 1 : 0;                                                                                        \
-            const bool wt_ = d_tap == ntaps;                                                                            \
-            d_tap = wt_ ? 0 : d_tap;                                                                                    \
-            d_dy = wt_ ? 0 : d_dy;                                                                                      \
-            d_cc += wt_ ? 1 : 0;                                                                                        \
+            const bool ok_ = (a_taps[(i_) & 1] >> dA_tap) & 1u;                                                         \
+            const int tapoff_ = (dA_dy * p.W + dA_dx) * (int)arow_bytes + dA_cc * (2 * kH2ChunkBytes) + ((i_) >> 1) * 32; \
+            H2_DMA(rsrc_a, dst_, ok_ ? voff[(i_) & 1] + (unsigned)tapoff_ : kH2OutOfRange, 0);                          \
+        } else {                                                                                                        \
+            H2_DMA(rsrc_a, dst_, voff[(i_) & 1], H3_KSTEP(dA_kt) * (2 * kH2ChunkBytes) + ((i_) >> 1) * 32);             \
         }                                                                                                               \
+    }
+#define H3_ISSUE_W(st_, i_)                                                                                             \
+    {                                                                                                                   \
+        const int dst_ = B0 + (st_) * OPSTG + ((i_) >> 1) * IMG + (wave + 8 * ((i_) & 1)) * 1024;                        \
+        const int wk_ = TAPS ? (dW_tap * cin_chunks + 2 * dW_cc) * kH2ChunkBytes : H3_KSTEP(dW_kt) * (2 * kH2ChunkBytes); \
+        H2_DMA(rsrc_w, dst_, voff[2 + ((i_) & 1)], wk_ + ((i_) >> 1) * 32);                                              \
+    }
+#define H3_ADVANCE_A()                                                                                                  \
+    {                                                                                                                   \
+        ++dA_kt;                                                                                                        \
+        if (TAPS) {                                                                                                     \
+            ++dA_tap;                                                                                                   \
+            ++dA_dx;                                                                                                    \
+            const bool wx_ = dA_dx == p.KW;                                                                             \
+            dA_dx = wx_ ? 0 : dA_dx;                                                                                    \
+            dA_dy += wx_ ? 1 : 0;                                                                                       \
+            const bool wt_ = dA_tap == ntaps;                                                                           \
+            dA_tap = wt_ ? 0 : dA_tap;                                                                                  \
+            dA_dy = wt_ ? 0 : dA_dy;                                                                                    \
+            dA_cc += wt_ ? 1 : 0;                                                                                       \
+        }                                                                                                               \
+    }
+#define H3_ADVANCE_W()                                                                                                  \
+    if (LA + LB > 0) {                                                                                                  \
+        ++dW_kt;                                                                                                        \
+        if (TAPS) {                                                                                                     \
+            ++dW_tap;                                                                                                   \
+            const bool wt_ = dW_tap == ntaps;                                                                           \
+            dW_tap = wt_ ? 0 : dW_tap;                                                                                  \
+            dW_cc += wt_ ? 1 : 0;                                                                                       \
+        }                                                                                                               \
+    }
+    // the piece in front of MFMA group s_ of a region (s_ = 0 .. 7), into stage sa_ / sb_ of its operand's ring.  2 + 2: activation and
+    // weight pieces interleaved (A, A, W, W of the hi planes, then of the lo planes).  Measured on that form, cycles per 16 k of the qkv /
+    // fc2 loops: this order 1767 / 1956, all four activation pieces first 1836 / 2070, all four weight pieces first 1943 / 2116
+    // (profiles/r05_h3_group_m_and_dma_placement.txt).  With a late operand: ORDER 0 = the early operand's four pieces (hi, hi, lo, lo),
+    // then the late operand's; ORDER 1 = early, early, late, late of the hi planes, then of the lo planes.
+#define H3_ISSUE_SLOT(sa_, sb_, s_, has_a_, has_b_)                                                                     \
+    {                                                                                                                   \
+        const bool grouped_ = LA + LB > 0 && ORDER == 0;                                                                \
+        const bool second_ = grouped_ ? (s_) >= 4 : ((s_) & 3) >= 2;        /* the second operand of the order */        \
+        const bool is_a_ = LA + LB == 0 ? !second_ : second_ == (LA == 1);  /* (the late operand is the second one) */    \
+        const int i_ = grouped_ ? (s_) & 3 : ((s_) >> 2) * 2 + ((s_) & 1);                                              \
+        if (is_a_) {                                                                                                    \
+            if (has_a_) H3_ISSUE_A(sa_, i_);                                                                            \
+        } else {                                                                                                        \
+            if (has_b_) H3_ISSUE_W(sb_, i_);                                                                            \
+        }                                                                                                               \
+    }
+#define H3_ISSUE_STEP_A(step_)                                                                                          \
+    {                                                                                                                   \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) H3_ISSUE_A((step_) % ASTG, i);                                    \
+        H3_ADVANCE_A();                                                                                                 \
+    }
+#define H3_ISSUE_STEP_W(step_)                                                                                          \
+    {                                                                                                                   \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) H3_ISSUE_W((step_) % BSTG, i);                                    \
+        H3_ADVANCE_W();                                                                                                 \
     }
 
     floatx4 acc[8][4];   // 16-row A fragments x 16-column B fragments of the wave's 128 x 64
@@ -676,8 +751,8 @@ __global__ __launch_bounds__(512, 2) void gemm_h3(const H2Params p) {
     // fragment read offsets: lane (r, g) reads unit g (k = 8g .. 8g+7 of the 32-k step) of its row, hi image; lo image: + IMG
     const int r16 = lane & 15, g16 = lane >> 4;
     const int f16 = (4 - ((r16 >> 2) & 3)) & 3;
-    const int a_h = (wm * 128 + r16) * 64 + ((g16 ^ f16) << 4);
-    const int b_h = (BM + wn * 64 + r16) * 64 + ((g16 ^ f16) << 4);
+    const int a_h = (wm * 128 + r16) * 64 + ((g16 ^ f16) << 4);   // (inside a stage of the activation ring)
+    const int b_h = (wn * 64 + r16) * 64 + ((g16 ^ f16) << 4);    // (inside a stage of the weight ring)
     h2k_f16x8 xb[2][4][2], ya[2][2];   // [set][fragment][hi, lo], [buffer][hi, lo]
 #define H3_READ_XB(set_, sp_)                                                                                           \
     _Pragma("unroll") for (int y = 0; y < 4; ++y) {                                                                     \
@@ -704,76 +779,118 @@ __global__ __launch_bounds__(512, 2) void gemm_h3(const H2Params p) {
             acc[e_][y] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ya[buf_][0], xb[set_][y][0], acc[e_][y], 0, 0, 0);      \
         __builtin_amdgcn_sched_barrier(0);   /* nothing moves across: the software pipeline below is the schedule */     \
     }
-    // region k: [wait for step k+1 (every piece of this wave: two stages), barrier, B forms and A fragment 0 of step k+1, piece 0 of step
-    // k+2 into the stage step k has left, MFMAs of fragment 7 of step k, then fragments 0..6 of step k+1 each behind the read of the next
-    // one and one more piece]; xs_ = k & 1 = the register set of B = the LDS stage of step k.
-    // the order the eight pieces of a step are issued in: activation and weight pieces interleaved (A, A, W, W of the hi planes, then of
-    // the lo planes).  Measured, cycles per 16 k of the qkv / fc2 loops: this order 1767 / 1956, all four activation pieces first 1836 /
-    // 2070, all four weight pieces first 1943 / 2116 (profiles/r05_h3_group_m_and_dma_placement.txt)
-#define H3_ORDER(i_) (i_)
-#define H3_REGION(xs_, has_next_, has_d_)                                                                               \
+    // region k: [wait for step k+1, barrier, B forms and A fragment 0 of step k+1, MFMAs of fragment 7 of step k, then fragments 0..6 of
+    // step k+1 each behind the read of the next one and one DMA piece].  k6_ = k % PERIOD (a literal): k6_ & 1 = the register set of B for step k,
+    // k6_ % ASTG / k6_ % BSTG = the stages of step k, which every wave has left at this region's barrier (its last ds_read was retired by the
+    // lgkmcnt(0) in front of it): the pieces of step k+2, or of step k+3 for the late operand, go into them.  Reads of a stage stay one
+    // barrier behind the wait that retires its DMAs.
+    // At the head, a wave's outstanding pieces are, oldest first: the early operand's of step k+1 (issued in region k-1; the late operand's
+    // of step k+1 are older: region k-2) and behind them the late operand's of step k+2 - WAITN pieces that may stay in flight.
+    // has_next_ = step k+1 exists, has_e_ = step k+2 exists, has_l_ = step k+3 exists; literal `true` in the steady state.
+#define H3_REGION(k6_, has_next_, has_e_, has_l_)                                                                       \
     {                                                                                                                   \
-        const char* sn_ = smem + ((xs_) ^ 1) * STAGE;                                                                   \
+        const char* sa_ = smem + (((k6_) + 1) % ASTG) * OPSTG;                                                          \
+        const char* sb_ = smem + B0 + (((k6_) + 1) % BSTG) * OPSTG;                                                     \
+        const bool has_a_ = LA ? (has_l_) : (has_e_), has_b_ = LB ? (has_l_) : (has_e_);                                \
         if (has_next_) {                                                                                                \
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                 \
+            if (LA + LB > 0 && (has_e_)) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WAITN) : "memory");        \
+            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                            \
             __builtin_amdgcn_s_barrier();                                                                               \
-            H3_READ_XB((xs_) ^ 1, sn_);                                                                                 \
-            H3_READ_A(0, 0, sn_);                                                                                       \
-            if (has_d_) H3_ISSUE_PIECE(xs_, H3_ORDER(0));                                                               \
+            H3_READ_XB(((k6_) + 1) & 1, sb_);                                                                           \
+            H3_READ_A(0, 0, sa_);                                                                                       \
+            H3_ISSUE_SLOT(((k6_) + 2 + LA) % ASTG, ((k6_) + 2 + LB) % BSTG, 0, has_a_, has_b_);                         \
         }                                                                                                               \
-        H3_MFMAS(xs_, 1, 7);                                                                                            \
+        H3_MFMAS((k6_) & 1, 1, 7);                                                                                      \
         if (has_next_) {                                                                                                \
             _Pragma("unroll") for (int e = 0; e < 7; ++e) {                                                             \
-                H3_READ_A((e + 1) & 1, e + 1, sn_);                                                                     \
-                if (has_d_) H3_ISSUE_PIECE(xs_, H3_ORDER(e + 1));                                                       \
-                H3_MFMAS((xs_) ^ 1, e & 1, e);                                                                          \
+                H3_READ_A((e + 1) & 1, e + 1, sa_);                                                                     \
+                H3_ISSUE_SLOT(((k6_) + 2 + LA) % ASTG, ((k6_) + 2 + LB) % BSTG, e + 1, has_a_, has_b_);                 \
+                H3_MFMAS(((k6_) + 1) & 1, e & 1, e);                                                                    \
             }                                                                                                           \
-            if (has_d_) H3_ISSUE_ADVANCE();                                                                             \
+            if (has_a_) H3_ADVANCE_A();                                                                                 \
+            if (has_b_) H3_ADVANCE_W();                                                                                 \
         }                                                                                                               \
     }
 
     const int nk = kt_end - kt_begin;
-    {
+    // prologue: 2 + 2 = steps 0 and 1 (step 0 has to have landed, step 1 stays in flight); with a late operand L and an early one E:
+    // E(0), L(0), E(1), L(1), L(2), as many as exist - everything behind L(0) stays in flight
+    if (LA + LB == 0) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) H3_ISSUE_PIECE(0, j);
-        H3_ISSUE_ADVANCE();
+        for (int j = 0; j < 8; ++j) H3_ISSUE_SLOT(0, 0, j, true, true);
+        H3_ADVANCE_A();
+        H3_ADVANCE_W();
         if (nk > 1) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) H3_ISSUE_PIECE(1, j);
-            H3_ISSUE_ADVANCE();
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // step 0 has landed; step 1 stays in flight
+            for (int j = 0; j < 8; ++j) H3_ISSUE_SLOT(1, 1, j, true, true);
+            H3_ADVANCE_A();
+            H3_ADVANCE_W();
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    } else {
+        if (LA) {
+            H3_ISSUE_STEP_W(0);
+            H3_ISSUE_STEP_A(0);
+        } else {
+            H3_ISSUE_STEP_A(0);
+            H3_ISSUE_STEP_W(0);
+        }
+        if (nk > 1) {
+            if (LA) {
+                H3_ISSUE_STEP_W(1);
+                H3_ISSUE_STEP_A(1);
+            } else {
+                H3_ISSUE_STEP_A(1);
+                H3_ISSUE_STEP_W(1);
+            }
+        }
+        if (nk > 2) {
+            if (LA) H3_ISSUE_STEP_A(2) else H3_ISSUE_STEP_W(2)
+            asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+        } else if (nk > 1) {
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
     }
     __builtin_amdgcn_s_barrier();
-    H3_READ_XB(0, smem);
+    H3_READ_XB(0, smem + B0);
     H3_READ_A(0, 0, smem);
-    H2_STAMP(1);
+    H2_STAMP_LATCH(stamp1);
 #pragma unroll
     for (int e = 0; e < 7; ++e) {
         H3_READ_A((e + 1) & 1, e + 1, smem);
         H3_MFMAS(0, e & 1, e);
     }
     {
-        // has_next = step k+1 exists; has_d = step k+2 exists (its DMA is issued in region k); literal `true` in the steady state
+        // One period of (register set, activation stage, weight stage) - two regions, six with a ring of three - is spelled out so that
+        // every index is a constant.  The last region of the steady state issues step k + PERIOD + 1, or + 2 for the late operand.
+        constexpr int PERIOD = LA + LB > 0 ? 6 : 2;
         int k = 0;
-        for (; k + 3 < nk; k += 2) {
-            H3_REGION(0, true, true);
-            H3_REGION(1, true, true);
+        for (; k + PERIOD + 1 + LA + LB < nk; k += PERIOD) {
+#pragma unroll
+            for (int i = 0; i < PERIOD; ++i) H3_REGION(i, true, true, true);
         }
-        for (; k < nk; k += 2) {
-            H3_REGION(0, k + 1 < nk, k + 2 < nk);
-            if (k + 1 < nk) H3_REGION(1, k + 2 < nk, k + 3 < nk);
+        for (; k < nk; k += PERIOD) {
+#pragma unroll
+            for (int i = 0; i < PERIOD; ++i)
+                if (k + i < nk) H3_REGION(i, k + i + 1 < nk, k + i + 2 < nk, k + i + 3 < nk);
         }
     }
 #undef H3_REGION
-#undef H3_ORDER
+#undef H3_ISSUE_STEP_W
+#undef H3_ISSUE_STEP_A
+#undef H3_ISSUE_SLOT
+#undef H3_ADVANCE_W
+#undef H3_ADVANCE_A
+#undef H3_ISSUE_W
+#undef H3_ISSUE_A
 #undef H3_MFMAS
 #undef H3_READ_A
 #undef H3_READ_XB
-#undef H3_ISSUE_PIECE
-#undef H3_ISSUE_ADVANCE
+    H2_STAMP_PUT(1, stamp1);
     H2_STAMP(2);
     __syncthreads();   // no DMA is in flight and every fragment is in registers: the stages become the epilogue staging
     H2_STAMP(7);
@@ -786,7 +903,7 @@ __global__ __launch_bounds__(512, 2) void gemm_h3(const H2Params p) {
     constexpr int EP_ROWS = 64;
     constexpr int C8 = BN / 8;
     constexpr int NT = 512;
-    static_assert(EP_ROWS * LDC * 4 <= NSTG * STAGE, "epilogue pass must fit the staging LDS");
+    static_assert(EP_ROWS * LDC * 4 <= 96 * 1024 && 96 * 1024 + 64 <= (ASTG + BSTG) * OPSTG, "epilogue pass must fit the staging LDS");
     constexpr int EP_STEP = NT / C8;
     constexpr int EP_ITERS = EP_ROWS / EP_STEP;
     const bool planes = p.out_h2 != nullptr || (PERIMG && p.residual_h2 != nullptr);   // workgroup-uniform
@@ -1014,6 +1131,15 @@ __global__ __launch_bounds__(512, 2) void gemm_h3(const H2Params p) {
         if (tid < 16 && simg[tid] != 0u) atomicMax(p.amax_out + img_first + tid, simg[tid]);
     }
     H2_STAMP(3);
+}
+#endif
+
+// (the kernel keeps its three parameters - its name is what profiles and tools match on; the rings are a property of the form)
+template <bool FOUR, bool TAPS = false, bool PERIMG = false>
+__global__ __launch_bounds__(512, 2) void gemm_h3(const H2Params p) {
+#if __HIP_DEVICE_COMPILE__
+    constexpr H3Rings R = h3_rings(TAPS, PERIMG);
+    gemm_h3_body<FOUR, TAPS, PERIMG, R.a, R.b, R.order>(p);
 #endif
 }
 
@@ -1100,7 +1226,7 @@ static int launch_h2_variant(relax_handle* h, H2Params& p, hipStream_t s) {
     // (splitk_finish_h2 knows neither the fused group sums nor a plane residual: those launches run unsplit)
     const bool can_split = h->gemm.split_k && !p.no_split && !p.gap && !p.residual_h2;
     RELAX_TRY(plan_tiles(h, p, BM, BN, 256, BK32 ? p.K / 32 : p.K / 16, BK32 ? 4 : 8, can_split));
-    constexpr size_t lds = BK32 ? (size_t)H3_NSTG * H3_STAGE : (size_t)(FORM == 1 ? 4 : 3) * H2_STAGE;
+    constexpr size_t lds = BK32 ? h3_lds_bytes(FORM == 4, FORM >= 4) : (size_t)(FORM == 1 ? 4 : 3) * H2_STAGE;
     auto kernel = [] {
         if constexpr (FORM == 0) return &gemm_h2<3>;
         else if constexpr (FORM == 1) return &gemm_h2<4>;

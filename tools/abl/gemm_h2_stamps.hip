@@ -5,7 +5,10 @@
 #include <vector>
 
 #define H2_STAMP(i_) if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 8 + (i_)] = __builtin_amdgcn_s_memtime()
-#define H2_STAMPS_BEFORE_LAUNCH(h_, p_, units_)                                                          \
+// gemm_h3 counts its DMAs on the VM counter across the start of the K loop: stamp 1 is read there and stored behind the loop
+#define H2_STAMP_LATCH(v_) const unsigned long long v_ = __builtin_amdgcn_s_memtime()
+#define H2_STAMP_PUT(i_, v_) if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 8 + (i_)] = (v_)
+#define H2_STAMPS_BEFORE_LAUNCH(h_, p_, units_)                                                       \
     RELAX_TRY(ensure_buf(h_, (h_)->scratch, sizeof(unsigned long long) * 8 * (size_t)(units_)));        \
     (p_).stamps = static_cast<unsigned long long*>((h_)->scratch.p)
 #define H2_STAMPS_AFTER_LAUNCH(h_, p_, units_, s_) RELAX_TRY((h2_report_stamps(h_, p_, units_, s_)))

@@ -10,7 +10,10 @@
 #                                           WRONG results, timing only); b2bpf:<0|1|2> / x6stg2: same-bits variants (B-fragment prefetch mode; two LDS stages)
 #   tools/build_ablations.sh h3b2b          the f16x2 kernel with the conv3 launches of ResNet-50's layer3 / layer4 never fetching their A operand and the 3x3
 #                                           launches never storing their planes (WRONG results: the most a conv2 -> conv3 fusion there could return)
-#   tools/build_ablations.sh flowstamps     fused Farneback iteration with tick stamps per phase of a step (tools/flow_stamps.py prints them)
+#   tools/build_ablations.sh h3stg:<plain>[:<1x1>[:<taps>]]   gemm_h3 with other LDS rings per form (same bits): three digits each, activation stages, weight
+#                                           stages, issue order - 220 two + two, 320 a third activation stage, 230 a third weight stage, 321 / 231 the
+#                                           interleaved order; h3stg_stamps:... the same with the cycle stamps
+#   tools/build_ablations.sh flowstamps    fused Farneback iteration with tick stamps per phase of a step (tools/flow_stamps.py prints them)
 #   tools/build_ablations.sh a6stamps       bf16x6 attention kernel with ticks per phase of an item (tools/attn_stamps.py prints them;
 #                                           overwrites the first floats of the fp32 output: timing only)
 # The loop ablations of rounds 1 - 4 (RELAX_X3_ABLATE, RELAX_F32_ABLATE, RELAX_X6_ABLATE, RELAX_FLOW_ABLATE: WRONG results, timing only)
@@ -24,7 +27,7 @@ make -s
 mkdir -p ../../tools/abl
 CC="/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -Wno-unused-function"
 FLOWCC="$CC -fno-slp-vectorize -ffp-contract=off"   # as the Makefile builds flow.hip
-OBJS="api.o fragment.o flow.o resize.o gemm.o gemm_x6.o gemm_h2.o conv1_x6.o attention_x6.o attention_h2.o layers.o resnet50.o vit.o head.o host_logic.o"
+OBJS="$(sed -n 's/^SRCS := //p' Makefile | sed 's/\.hip/.o/g') host_logic.o"   # the objects of the product library, as the Makefile lists them
 link() {  # link <replaced object> <new object> <output name>
   /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 ${OBJS/$1/$2} -o ../../tools/abl/librelax_$3.so
 }
@@ -39,6 +42,13 @@ for n in "$@"; do
     h3ahead) $CC -I. -DH3_EP_FETCH_AHEAD=1 -c gemm_h2.hip -o /tmp/gemm_h2_ahead.o; link gemm_h2.o /tmp/gemm_h2_ahead.o h3ahead ;;
     h3ahead_stamps) $CC -I. -DH3_EP_FETCH_AHEAD=1 -c ../../tools/abl/gemm_h2_stamps.hip -o /tmp/gemm_h2_ahead_st.o; link gemm_h2.o /tmp/gemm_h2_ahead_st.o h3ahead_stamps ;;
     h3stagger:*) $CC -I. -DH3_STAGGER=${n#h3stagger:} -c gemm_h2.hip -o /tmp/gemm_h2_stg.o; link gemm_h2.o /tmp/gemm_h2_stg.o h3stagger${n#h3stagger:} ;;
+    h3stg:*|h3stg_stamps:*)   # h3stg:<plain>[:<1x1>[:<taps>]], each three digits <activation stages><weight stages><issue order>, e.g. h3stg:320:220:220
+      spec=${n#*:}; IFS=: read -r s_plain s_c1 s_taps <<< "$spec"; s_c1=${s_c1:-220}; s_taps=${s_taps:-220}
+      d() { echo "${1:0:1},${1:1:1},${1:2:1}"; }
+      src=gemm_h2.hip; [ "${n%%:*}" = h3stg_stamps ] && src=../../tools/abl/gemm_h2_stamps.hip
+      name=${n%%:*}${s_plain}_${s_c1}_${s_taps}
+      $CC -I. -DH3_PLAIN_STAGES=$(d $s_plain) -DH3_CONV1_STAGES=$(d $s_c1) -DH3_TAPS_STAGES=$(d $s_taps) -c $src -o /tmp/gemm_h2_$name.o
+      link gemm_h2.o /tmp/gemm_h2_$name.o $name ;;
     h2l2hit) $CC -I. -DH3_L2HIT -c ../../tools/abl/gemm_h2_stamps.hip -o /tmp/gemm_h2_l2hit.o; link gemm_h2.o /tmp/gemm_h2_l2hit.o h2l2hit ;;
     flowstamps) $FLOWCC -I. -c ../../tools/abl/flow_stamps.hip -o /tmp/flow_stamps.o; link flow.o /tmp/flow_stamps.o flowstamps ;;
     a6stamps) $CC -I. -c ../../tools/abl/attention_x6_stamps.hip -o /tmp/attention_x6_stamps.o; link attention_x6.o /tmp/attention_x6_stamps.o a6stamps ;;
