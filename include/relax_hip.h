@@ -799,6 +799,78 @@ int relax_yuv_coefficients(int matrix, int full_range, int32_t* out);
 int relax_yuv_to_bgr(const uint8_t* src, int64_t src_bytes, const int64_t* items, int N, int layout, int H, int W, int matrix,
                      int full_range, uint8_t* out, int64_t out_bytes, int32_t* status, relax_stream stream);
 
+/* ---- raw YUV frames: 10 / 12-bit, packed 4:2:2, 4:1:1, 4:1:0 and NV21 -------------------------------- */
+/* The pixel formats that `ffmpeg -f rawvideo` leaves behind for the reference's datasets (metadata column `pixfmt`; the frames
+ * of src/video_frames_extract.py:29-49,76-100): the `_ex` entries take a FORMAT where relax_yuv_to_bgr takes a layout.
+ * Formats 0..3 are RELAX_YUV_420P/422P/444P/NV12 and run relax_yuv_to_bgr's own kernels: the same bytes.  A frame, as
+ * ffmpeg writes it raw (cw = ceil(W / 2^hshift), ch = ceil(H / 2^vshift)):
+ *     NV21                as NV12 with V first
+ *     YUYV422, UYVY422    one plane: rows of ceil(W/2) four-byte groups Y0 U Y1 V / U Y0 V Y1; for odd W the last group's second
+ *                         luma is padding - present in the file, never shown
+ *     411P                Y[H][W], U and V [H][ceil(W/4)]
+ *     410P                Y[H][W], U and V [ceil(H/4)][ceil(W/4)]
+ *     4xxP10LE, 4xxP12LE  the 8-bit planar layouts with 2-byte little-endian samples; the value sits in the low `depth` bits,
+ *                         HIGHER BITS ARE MASKED OFF
+ *     P010LE              NV12's layout with 2-byte samples; the value is the HIGH 10 bits (word >> 6), the low 6 are ignored
+ * Chroma is replicated: pixel (r, c) takes sample (r >> vshift, c >> hshift), no interpolation.
+ *
+ * Arithmetic, one formula for every depth, s = depth - 8, the coefficient table of relax_yuv_to_bgr unchanged:
+ *     y = cy*(Y - (oy << s))      u = U - (128 << s)      v = V - (128 << s)
+ *     channel = clamp(sum + (1 << (15+s)), 0, 2^(24+s) - 1) >> (16+s)        sum = y + crv*v | y - cgu*u - cgv*v | y + cbu*u
+ * At s = 0 this is relax_yuv_to_bgr's formula bit for bit.  depth <= 12 keeps every sum inside int32.  Within 1 code value of
+ * the float64 BT.601 / BT.709 conversion rounded to 8 bits.  The output is pinned to this formula and to float64 BT.601 /
+ * BT.709, not to any ffmpeg build; for sources deeper than 8 bits ffmpeg's PNG path goes through 16-bit RGB and OpenCV
+ * reduces that to 8 bits - that rounding is NOT pinned here. */
+#define RELAX_YUVF_420P 0
+#define RELAX_YUVF_422P 1
+#define RELAX_YUVF_444P 2
+#define RELAX_YUVF_NV12 3
+#define RELAX_YUVF_NV21 4
+#define RELAX_YUVF_YUYV422 5
+#define RELAX_YUVF_UYVY422 6
+#define RELAX_YUVF_411P 7
+#define RELAX_YUVF_410P 8
+#define RELAX_YUVF_420P10LE 9
+#define RELAX_YUVF_422P10LE 10
+#define RELAX_YUVF_444P10LE 11
+#define RELAX_YUVF_420P12LE 12
+#define RELAX_YUVF_422P12LE 13
+#define RELAX_YUVF_444P12LE 14
+#define RELAX_YUVF_P010LE 15
+#define RELAX_YUVF_COUNT 16
+#define RELAX_YUV_PACKING_PLANAR 0
+#define RELAX_YUV_PACKING_SEMIPLANAR 1
+#define RELAX_YUV_PACKING_PACKED 2
+#define RELAX_YUV_FORMAT_INFO_WORDS 8
+
+/* Bytes of one frame (src/video_frames_extract.py:29-49,76-100: what one `-s WxH -pix_fmt F` frame occupies in the raw file);
+ * host arithmetic, answers without a GPU.  -1: format, H or W refused. */
+int64_t relax_yuv_frame_bytes_ex(int format, int H, int W);
+
+/* The one format table (csrc/yuv_core.h), for the layers that restate the layout of src/video_frames_extract.py:29-49,76-100's
+ * input: out[RELAX_YUV_FORMAT_INFO_WORDS] (HOST memory) = bytes per sample, depth, shift (sample = (word >> shift) & (2^depth - 1)),
+ * hshift, vshift, packing (RELAX_YUV_PACKING_*), swap (semi-planar: 1 = V first; packed: 1 = chroma first), 0.
+ * RELAX_ERR_INVALID, naming the value, for a format outside 0..RELAX_YUVF_COUNT-1 or a NULL out. */
+int relax_yuv_format_info(int format, int32_t* out);
+
+/* relax_yuv_to_bgr (the frames of src/video_frames_extract.py:29-49,76-100) for every RELAX_YUVF_* format: the same arguments,
+ * item rule, status words and refusals, `format` in place of `layout`.  One lane takes 16 pixels of the 1, 2 or 4 rows that share
+ * a chroma row; all of its loads are in flight before its first store; each row leaves as three 16-byte stores.  The 16-byte path
+ * under relax_yuv_to_bgr's conditions (W a multiple of 16, frame and slot at 16-byte-aligned addresses): per lane and row two
+ * 16-byte loads of 16-bit luma or of a packed row (which holds its chroma), per lane one 16-byte load per plane of 16-bit 4:2:0 /
+ * 4:2:2 chroma, two of 16-bit 4:4:4 chroma and of P010's interleaved pairs, one dword per plane of 4:1:1 / 4:1:0 chroma;
+ * everything else bytewise with every index under its bound.  Kernels specialised on sample bytes, packing, hshift and vshift
+ * (csrc/yuv.hip); offsets, widths and arithmetic in csrc/yuv_core.h, which csrc/yuv_ex_host.cpp walks on the host. */
+int relax_yuv_to_bgr_ex(const uint8_t* src, int64_t src_bytes, const int64_t* items, int N, int format, int H, int W, int matrix,
+                        int full_range, uint8_t* out, int64_t out_bytes, int32_t* status, relax_stream stream);
+
+/* relax_yuv_greyscale_scan (the screen of the frames of src/video_frames_extract.py:29-49,76-100) for every RELAX_YUVF_* format:
+ * each pixel converted in registers by the arithmetic above and folded into the record, no BGR written, no shortcut on neutral
+ * chroma.  For every frame the record equals relax_greyscale_scan's on relax_yuv_to_bgr_ex's output.  Arguments, status and
+ * refusals as relax_yuv_greyscale_scan, `format` in place of `layout`. */
+int relax_yuv_greyscale_scan_ex(const uint8_t* src, int64_t src_bytes, const int64_t* offsets, int N, int format, int H, int W,
+                                int matrix, int full_range, int32_t* out, relax_stream stream);
+
 /* ---- greyscale screen ----------------------------------------------------------------------------- */
 /* The pixel rule of the reference's src/data_processing/check_greyscale.py (is_greyscale_image, :25-35): a BGR frame is
  * greyscale iff the largest b-g, b-r and g-r over its pixels are all <= 3 - where b, g and r are uint8, so each difference

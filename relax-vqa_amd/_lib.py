@@ -112,6 +112,10 @@ PROTOTYPES = {
     "relax_yuv_frame_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "relax_yuv_coefficients": (C.c_int, [C.c_int, C.c_int, c_i32p]),
     "relax_yuv_to_bgr": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, C.c_int64, c_vp, c_vp]),
+    "relax_yuv_frame_bytes_ex": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "relax_yuv_format_info": (C.c_int, [C.c_int, c_i32p]),
+    "relax_yuv_to_bgr_ex": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, C.c_int64, c_vp, c_vp]),
+    "relax_yuv_greyscale_scan_ex": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp]),
     "relax_greyscale_scan": (C.c_int, [c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, c_vp, c_vp]),
     "relax_yuv_greyscale_scan": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp]),
     "relax_profile_enable": (C.c_int, [c_vp, C.c_int]),

@@ -4,10 +4,12 @@
 // step and all twelve loads of a lane are in flight before its arithmetic starts; then a wave maximum, a block maximum
 // through LDS and one atomicMax per block and word on the frame's record (zeroed on the stream before the launch).
 // What a lane does with its pixels, and the geometry: greyscale_core.h (the same text the CPU tests run).
+// relax_yuv_greyscale_scan_ex: the YUV scan for the RELAX_YUVF_* formats, one kernel per kind as in yuv.hip.
 #include <hip/hip_runtime.h>
 
 #include "greyscale_core.h"
 #include "relax_internal.h"
+#include "yuv_load.h"
 
 namespace {
 
@@ -146,6 +148,63 @@ __global__ __launch_bounds__(kBlock) void yuv_greyscale_scan_kernel(const uint8_
     commit(a, rec);
 }
 
+// the RELAX_YUVF_* formats: yuv.hip's lane (the segments of yuv::fast_unit_ex, loaded whole before the arithmetic), one unit
+// per step, kLaneUnits steps
+template <int SB, int PACK, int HS, int VS>
+__global__ __launch_bounds__(kBlock) void yuv_greyscale_scan_ex_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                                       const int64_t* __restrict__ offsets, int format, int H, int W,
+                                                                       int matrix, int full_range, int32_t* __restrict__ out) {
+    using K = yuv::Kind<SB, PACK, HS, VS>;
+    const int n = blockIdx.y;
+    int32_t* rec = out + static_cast<int64_t>(n) * grey::kRecordWords;
+    yuv::Plan p;
+    yuv::Coef k;
+    if (yuv::plan_ex(format, H, W, &p) != 0 || !K::matches(p) || !yuv::coef(matrix, full_range, &k)) return;   // refused on the host already
+    const int64_t src_off = offsets[n];
+    const bool ok = grey::yuv_frame_in_range(p, src_off, src_bytes);
+    if (!ok) {                                                                              // uniform over the block: nothing is read
+        if (blockIdx.x == 0 && threadIdx.x == 0) rec[grey::kStatusWord] = RELAX_YUV_OUT_OF_RANGE;
+        return;
+    }
+    const uint8_t* f = src + src_off;
+    const int64_t nunits = yuv::units_ex(p);
+    grey::Acc a;
+    grey::init(&a);
+    if (grey::yuv_fast_path(p, reinterpret_cast<uint64_t>(f))) {                           // uniform over the block
+#pragma unroll
+        for (int j = 0; j < kLaneUnits; ++j) {
+            const int64_t unit = grey::unit_of(blockIdx.x, threadIdx.x, j);
+            if (unit < nunits) {
+                const yuv::FastUnitEx u = yuv::fast_unit_ex(p, unit);
+                uint32_t lw[K::kRows][K::kYWords], cw[2][K::kCWords];
+                if constexpr (K::kCPlanes >= 1) yuv::load_segment<K::kCBytes>(f + u.c[0], cw[0]);
+                if constexpr (K::kCPlanes == 2) yuv::load_segment<K::kCBytes>(f + u.c[1], cw[1]);
+#pragma unroll
+                for (int i = 0; i < K::kRows; ++i)
+                    if (i < u.rows) yuv::load_segment<K::kYWords * 4>(f + u.y[i], lw[i]);
+                const uint32_t* cu = K::kCPlanes == 0 ? lw[0] : cw[0];
+                const uint32_t* cv = K::kCPlanes == 0 ? lw[0] : cw[K::kCPlanes == 2 ? 1 : 0];
+#pragma unroll
+                for (int i = 0; i < K::kRows; ++i)
+                    if (i < u.rows) grey::yuv_row16_ex<K>(&a, p, k, lw[i], cu, cv);
+            }
+        }
+    } else {
+#pragma unroll 1
+        for (int j = 0; j < kLaneUnits; ++j) {
+            const int64_t unit = grey::unit_of(blockIdx.x, threadIdx.x, j);
+            if (unit < nunits) grey::yuv_unit_bytewise_ex(&a, p, k, f, unit);
+        }
+    }
+    commit(a, rec);
+}
+
+using ExScanKernel = void (*)(const uint8_t*, int64_t, const int64_t*, int, int, int, int, int, int32_t*);
+template <int SB, int PACK, int HS, int VS>
+struct ExScanKernelOf {
+    static ExScanKernel get() { return yuv_greyscale_scan_ex_kernel<SB, PACK, HS, VS>; }
+};
+
 int zero_records(const char* who, int32_t* out, int N, hipStream_t stream) {
     const hipError_t e = hipMemsetAsync(out, 0, static_cast<size_t>(N) * grey::kRecordWords * sizeof(int32_t), stream);
     if (e != hipSuccess) {
@@ -233,6 +292,57 @@ extern "C" int relax_yuv_greyscale_scan(const uint8_t* src, int64_t src_bytes, c
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             relax::set_error(nullptr, "relax_yuv_greyscale_scan: launch failed: %s", hipGetErrorString(e));
+            return RELAX_ERR_HIP;
+        }
+    }
+    return RELAX_OK;
+}
+
+extern "C" int relax_yuv_greyscale_scan_ex(const uint8_t* src, int64_t src_bytes, const int64_t* offsets, int N, int format, int H,
+                                           int W, int matrix, int full_range, int32_t* out, relax_stream stream) {
+    yuv::Plan p;
+    yuv::Coef k;
+    const int bad = yuv::plan_ex(format, H, W, &p);
+    if (bad == 1) {
+        relax::set_error(nullptr, "relax_yuv_greyscale_scan_ex: format %d is not one of RELAX_YUVF_* (0..%d)", format, RELAX_YUVF_COUNT - 1);
+        return RELAX_ERR_INVALID;
+    }
+    if (bad) {
+        relax::set_error(nullptr, "relax_yuv_greyscale_scan_ex: %s = %d outside 1..%d", bad == 2 ? "H" : "W", bad == 2 ? H : W,
+                         yuv::kMaxDim);
+        return RELAX_ERR_INVALID;
+    }
+    if (format <= RELAX_YUVF_NV12)                                 // the 8-bit layouts: relax_yuv_greyscale_scan's kernel, its checks
+        return relax_yuv_greyscale_scan(src, src_bytes, offsets, N, format, H, W, matrix, full_range, out, stream);
+    if (!yuv::coef(matrix, full_range, &k)) {
+        relax::set_error(nullptr, "relax_yuv_greyscale_scan_ex: matrix %d is not RELAX_YUV_BT601 (0) or RELAX_YUV_BT709 (1)", matrix);
+        return RELAX_ERR_INVALID;
+    }
+    if (full_range != 0 && full_range != 1) {
+        relax::set_error(nullptr, "relax_yuv_greyscale_scan_ex: full_range %d is not 0 or 1", full_range);
+        return RELAX_ERR_INVALID;
+    }
+    if (N < 0 || src_bytes < 0 || (N > 0 && (!offsets || !out || !src))) {
+        relax::set_error(nullptr, "relax_yuv_greyscale_scan_ex: bad arguments (N %d, src_bytes %lld, or a NULL buffer)", N,
+                         static_cast<long long>(src_bytes));
+        return RELAX_ERR_INVALID;
+    }
+    if (N == 0) return RELAX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RELAX_TRY(zero_records("relax_yuv_greyscale_scan_ex", out, N, s));
+    const unsigned blocks = static_cast<unsigned>(grey::blocks(yuv::units_ex(p)));
+    const ExScanKernel kernel = yuv::for_kind<ExScanKernelOf, false>(p);
+    if (!kernel) {
+        relax::set_error(nullptr, "relax_yuv_greyscale_scan_ex: no kernel for format %d", format);
+        return RELAX_ERR_INVALID;
+    }
+    for (int n0 = 0; n0 < N; n0 += 65535) {
+        const int nn = N - n0 < 65535 ? N - n0 : 65535;
+        kernel<<<dim3(blocks, nn), kBlock, 0, s>>>(src, src_bytes, offsets + n0, format, H, W, matrix, full_range,
+                                                   out + static_cast<int64_t>(n0) * grey::kRecordWords);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            relax::set_error(nullptr, "relax_yuv_greyscale_scan_ex: launch failed: %s", hipGetErrorString(e));
             return RELAX_ERR_HIP;
         }
     }

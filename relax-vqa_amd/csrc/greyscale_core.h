@@ -137,6 +137,28 @@ GREY_HD void split_nv12(const uint32_t* in, uint32_t* u, uint32_t* v) {
     }
 }
 
+// ---- the RELAX_YUVF_* formats: yuv_core.h's plan_ex, units, accesses and pixel_ex ---------------------------------------------------
+GREY_HD void yuv_unit_bytewise_ex(Acc* a, const yuv::Plan& p, const yuv::Coef& k, const uint8_t* f, int64_t unit) {
+    const yuv::Unit u = yuv::unit_at_ex(p, unit);
+    for (int r = u.r0; r < u.r0 + u.rows; ++r)
+        for (int c = u.c0; c < u.c0 + u.cols; ++c) {
+            int b, g, rr;
+            yuv::pixel_bytewise_ex(p, k, f, r, c, &b, &g, &rr);
+            add(a, b, g, rr);
+        }
+}
+
+// 16 pixels of one row from the words of a lane's segments (K: yuv::Kind)
+template <class K>
+GREY_HD void yuv_row16_ex(Acc* a, const yuv::Plan& p, const yuv::Coef& k, const uint32_t* lw, const uint32_t* cu, const uint32_t* cv) {
+    GREY_UNROLL
+    for (int px = 0; px < kLanePixels; ++px) {
+        int b, g, r;
+        K::pixel(p, k, lw, cu, cv, px, &b, &g, &r);
+        add(a, b, g, r);
+    }
+}
+
 // a frame may be read iff it lies inside src (yuv::item_in_range with a slot that always fits)
 GREY_HD bool yuv_frame_in_range(const yuv::Plan& p, int64_t src_off, int64_t src_bytes) {
     return yuv::item_in_range(p, src_off, src_bytes, 0, p.out_bytes);

@@ -109,18 +109,24 @@ def scan_frames(frames):
     return GreyscaleScan(records)
 
 
-def scan_yuv_frames(planes, H, W, pixfmt, matrix="bt601", offsets=None, out=None):
+def _yuv_scan_entry(lib, extended):
+    return (lib.relax_yuv_greyscale_scan_ex, "relax_yuv_greyscale_scan_ex") if extended else (lib.relax_yuv_greyscale_scan, "relax_yuv_greyscale_scan")
+
+
+def scan_yuv_frames(planes, H, W, pixfmt, matrix="bt601", offsets=None, out=None, extended=False):
     """Raw 8-bit YUV frames on the device -> GreyscaleScan, without writing BGR (relax_yuv_greyscale_scan): frame by frame the
     records of scan_frames(engine.yuv_to_bgr(...)).  planes: uint8 device tensor holding N whole frames back to back, or any
-    bytes with `offsets` (int64 [N], host or device: where each frame starts).  out: an int32 [N,8] device tensor to fill."""
+    bytes with `offsets` (int64 [N], host or device: where each frame starts).  out: an int32 [N,8] device tensor to fill.
+    extended=True: pixfmt is one of sampling.yuv_format's names (10 / 12-bit, packed 4:2:2, 4:1:1, 4:1:0, NV21 too) and the scan is
+    relax_yuv_greyscale_scan_ex."""
     import torch
 
     from .. import _lib
-    layout, full_range = sampling.yuv_layout(pixfmt)
+    layout, full_range, frame_bytes, _ = sampling._yuv_source(pixfmt, extended)
     if matrix not in sampling.YUV_MATRICES:
         raise ValueError(f"matrix {matrix!r} is not one of {', '.join(sampling.YUV_MATRICES)}")
     H, W = int(H), int(W)
-    fb = sampling.yuv_frame_bytes(layout, H, W)
+    fb = frame_bytes(H, W)
     if not isinstance(planes, torch.Tensor) or not planes.is_cuda or planes.dtype != torch.uint8:
         raise TypeError("scan_yuv_frames: expected a uint8 device tensor")
     src = planes.contiguous().view(-1)
@@ -131,15 +137,16 @@ def scan_yuv_frames(planes, H, W, pixfmt, matrix="bt601", offsets=None, out=None
     offsets = torch.as_tensor(offsets, dtype=torch.int64).reshape(-1).to(src.device).contiguous()
     N = offsets.numel()
     lib = _lib.load()
+    scan, name = _yuv_scan_entry(lib, extended)
     with torch.cuda.device(src.device):
         if out is None:
             out = torch.empty((N, RECORD_WORDS), dtype=torch.int32, device=src.device)
         elif out.dtype != torch.int32 or tuple(out.shape) != (N, RECORD_WORDS) or not out.is_contiguous() or out.device != src.device:
             raise ValueError(f"out must be a contiguous int32 [{N},{RECORD_WORDS}] tensor on {src.device}")
-        rc = lib.relax_yuv_greyscale_scan(C.c_void_p(src.data_ptr()), src.numel(), C.c_void_p(offsets.data_ptr()), N, layout, H, W,
-                                          sampling.YUV_MATRICES[matrix], int(full_range), C.c_void_p(out.data_ptr()), _stream_ptr())
+        rc = scan(C.c_void_p(src.data_ptr()), src.numel(), C.c_void_p(offsets.data_ptr()), N, layout, H, W,
+                  sampling.YUV_MATRICES[matrix], int(full_range), C.c_void_p(out.data_ptr()), _stream_ptr())
     if rc != 0:
-        raise RuntimeError(f"relax_yuv_greyscale_scan failed ({rc}): {lib.relax_last_error(None).decode()}")
+        raise RuntimeError(f"{name} failed ({rc}): {lib.relax_last_error(None).decode()}")
     return GreyscaleScan(out)
 
 
@@ -157,8 +164,9 @@ def is_greyscale_image(image, threshold=3, mode="reference"):
 
 
 def scan_yuv_file(video_path, width, height, pixfmt, chunk_frames=None, matrix="bt601", device=None, threshold=3, mode="reference",
-                  stop_at_colour=True):
-    """Every frame of a raw YUV file through relax_yuv_greyscale_scan, in file order.
+                  stop_at_colour=True, extended=False):
+    """Every frame of a raw YUV file through relax_yuv_greyscale_scan (extended=True: relax_yuv_greyscale_scan_ex, pixfmt one of
+    sampling.yuv_format's names), in file order.
 
     The frames are read in chunks of `chunk_frames` (default and upper limit: what fits 64 MiB, one frame at least) with
     sampling.read_yuv_frames into one of two pinned staging buffers, every frame at a 16-byte-aligned slot as in GpuYuvLoader;
@@ -172,18 +180,19 @@ def scan_yuv_file(video_path, width, height, pixfmt, chunk_frames=None, matrix="
 
     from .. import _lib
     lo = _mode(mode)
-    layout, full_range = sampling.yuv_layout(pixfmt)
+    layout, full_range, frame_bytes, _ = sampling._yuv_source(pixfmt, extended)
     if matrix not in sampling.YUV_MATRICES:
         raise ValueError(f"matrix {matrix!r} is not one of {', '.join(sampling.YUV_MATRICES)}")
     H, W = int(height), int(width)
-    n = sampling.yuv_frame_count(video_path, W, H, pixfmt)
-    fb = sampling.yuv_frame_bytes(layout, H, W)
+    n = sampling.yuv_frame_count(video_path, W, H, pixfmt, extended)
+    fb = frame_bytes(H, W)
     slot = (fb + 15) // 16 * 16
     limit = max(1, STAGING_BYTES // slot)
     chunk = limit if chunk_frames is None else max(1, min(int(chunk_frames), limit))
     chunk = max(1, min(chunk, n))
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     lib = _lib.load()
+    scan, name = _yuv_scan_entry(lib, extended)
     t_start = time.perf_counter()
     result = {"first_colour_frame": None, "frames_scanned": 0, "n_frames": n, "chunk_frames": chunk, "read_seconds": 0.0}
     parts = []
@@ -213,11 +222,11 @@ def scan_yuv_file(video_path, width, height, pixfmt, chunk_frames=None, matrix="
             with torch.cuda.stream(stream):
                 staged[c % 2][:count * slot].copy_(pinned[c % 2][:count * slot], non_blocking=True)
                 records = torch.empty((count, RECORD_WORDS), dtype=torch.int32, device=dev)
-                rc = lib.relax_yuv_greyscale_scan(C.c_void_p(staged[c % 2].data_ptr()), count * slot, C.c_void_p(offsets.data_ptr()),
-                                                  count, layout, H, W, sampling.YUV_MATRICES[matrix], int(full_range),
-                                                  C.c_void_p(records.data_ptr()), C.c_void_p(stream.cuda_stream))
+                rc = scan(C.c_void_p(staged[c % 2].data_ptr()), count * slot, C.c_void_p(offsets.data_ptr()),
+                          count, layout, H, W, sampling.YUV_MATRICES[matrix], int(full_range),
+                          C.c_void_p(records.data_ptr()), C.c_void_p(stream.cuda_stream))
                 if rc != 0:
-                    raise RuntimeError(f"relax_yuv_greyscale_scan failed ({rc}): {lib.relax_last_error(None).decode()}")
+                    raise RuntimeError(f"{name} failed ({rc}): {lib.relax_last_error(None).decode()}")
             if pending is not None:
                 collect(pending)                                   # the chunk before this one; this one is in flight meanwhile
             pending = (first, count, records)
@@ -227,7 +236,7 @@ def scan_yuv_file(video_path, width, height, pixfmt, chunk_frames=None, matrix="
         stream.synchronize()
     result["records"] = np.concatenate(parts) if parts else np.zeros((0, RECORD_WORDS), np.int32)
     if (result["records"][:, 6] != 0).any():
-        raise RuntimeError(f"{video_path}: relax_yuv_greyscale_scan refused frames {np.flatnonzero(result['records'][:, 6]).tolist()}")
+        raise RuntimeError(f"{video_path}: {name} refused frames {np.flatnonzero(result['records'][:, 6]).tolist()}")
     result["seconds"] = time.perf_counter() - t_start
     return result
 
@@ -237,7 +246,7 @@ def _png_frames(directory):
 
 
 def check_video_greyscale(video_path, width=None, height=None, pixfmt=None, chunk_frames=None, device=None, threshold=3,
-                          mode="reference"):
+                          mode="reference", extended=False):
     """check_video_greyscale (:37-55) -> (is_greyscale, frame_read): (False, True) at the first colour frame, (True, True) if
     every frame passed and at least one was read, (False, False) if no frame could be read - a missing file, a file shorter than
     one frame, a directory without PNG files.
@@ -245,7 +254,8 @@ def check_video_greyscale(video_path, width=None, height=None, pixfmt=None, chun
     video_path: a raw .yuv file (width and height as the metadata give them - required, a raw file has no header; pixfmt default
     yuv420p, what the reference assumes for live_qualcomm) scanned by scan_yuv_file; or a directory of PNG frames, decoded on the GPU (pngdecode) in sorted
     order, chunk_frames at a time.  Containers (mp4, mkv, avi, ...) need a demuxer and a decoder and raise NotImplementedError as
-    video_frames_extract does: decode them to raw frames or PNGs first."""
+    video_frames_extract does: decode them to raw frames or PNGs first.  extended=True: a raw file's pixfmt may be any of
+    sampling.yuv_format's names."""
     _mode(mode)
     video_path = os.fspath(video_path)
     if os.path.isdir(video_path):
@@ -269,10 +279,11 @@ def check_video_greyscale(video_path, width=None, height=None, pixfmt=None, chun
     if width is None or height is None:
         raise ValueError(f"{video_path}: a raw file has no header - width and height must be given (the metadata's columns)")
     W, H, pixfmt = int(width), int(height), pixfmt or "yuv420p"
-    fb = sampling.yuv_frame_bytes(sampling.yuv_layout(pixfmt)[0], H, W)
+    fb = sampling._yuv_source(pixfmt, extended)[2](H, W)
     if os.path.getsize(video_path) < fb:
         return False, False
-    res = scan_yuv_file(video_path, W, H, pixfmt, chunk_frames=chunk_frames, device=device, threshold=threshold, mode=mode)
+    res = scan_yuv_file(video_path, W, H, pixfmt, chunk_frames=chunk_frames, device=device, threshold=threshold, mode=mode,
+                        extended=extended)
     return res["first_colour_frame"] is None and res["frames_scanned"] > 0, res["frames_scanned"] > 0
 
 
@@ -316,16 +327,16 @@ def video_path_for(data_name, video_dir, row):
 
 
 def process_videos_from_csv(metadata_path, output_csv, data_name, video_dir, chunk_frames=None, device=None, threshold=3,
-                            mode="reference"):
+                            mode="reference", extended=False):
     """process_videos_from_csv (:57-95): every row of the metadata file is screened (raw files with the row's width, height and
     pixfmt), and the rows of the greyscale videos alone go to output_csv as `Index,vid,Is Greyscale`, Index being the row number in
-    the metadata file.  No file is written when no video is greyscale.  -> the report rows."""
+    the metadata file (extended: as check_video_greyscale).  No file is written when no video is greyscale.  -> the report rows."""
     with open(metadata_path, newline="") as f:
         meta = list(csv.DictReader(f))
     rows = []
     for i, row in enumerate(meta):
         grey, _ = check_video_greyscale(video_path_for(data_name, video_dir, row), row.get("width"), row.get("height"), row.get("pixfmt"),
-                                        chunk_frames=chunk_frames, device=device, threshold=threshold, mode=mode)
+                                        chunk_frames=chunk_frames, device=device, threshold=threshold, mode=mode, extended=extended)
         if grey:
             rows.append((i, row["vid"], True))
     if rows:

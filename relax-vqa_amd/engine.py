@@ -122,12 +122,22 @@ class RelaxEngine:
         for untagged raw input) or 'bt709'.  out: a uint8 [N,H,W,3] view to fill (strided slots with packed rows allowed, e.g.
         clip.view(-1,H,W,3)).  Runs on the current stream.  The kernel moves 16 bytes per access when W is a multiple of 16 and
         frame and slot start at 16-byte-aligned addresses, else bytewise, per frame."""
+        return self._yuv_to_bgr(planes_u8_device, H, W, pixfmt, matrix, out, False)
+
+    def yuv_to_bgr_ex(self, planes_u8_device, H, W, pixfmt, matrix="bt601", out=None):
+        """yuv_to_bgr for every pixfmt of sampling.yuv_format (relax_yuv_to_bgr_ex): 10 / 12-bit planar, p010le, yuyv422, uyvy422,
+        yuv411p, yuv410p and nv21 beside the 8-bit names, which give yuv_to_bgr's bytes.  The same arguments and the same checks;
+        the numpy statement is sampling.yuv_frame_bgr_ex on sampling.yuv_samples."""
+        return self._yuv_to_bgr(planes_u8_device, H, W, pixfmt, matrix, out, True)
+
+    def _yuv_to_bgr(self, planes_u8_device, H, W, pixfmt, matrix, out, extended):
         from . import sampling
-        layout, full_range = sampling.yuv_layout(pixfmt)
+        layout, full_range, frame_bytes, _ = sampling._yuv_source(pixfmt, extended)
+        convert, name = (self.lib.relax_yuv_to_bgr_ex, "relax_yuv_to_bgr_ex") if extended else (self.lib.relax_yuv_to_bgr, "relax_yuv_to_bgr")
         if matrix not in sampling.YUV_MATRICES:
             raise ValueError(f"matrix {matrix!r} is not one of {', '.join(sampling.YUV_MATRICES)}")
         H, W = int(H), int(W)
-        fb = sampling.yuv_frame_bytes(layout, H, W)
+        fb = frame_bytes(H, W)
         src = self._dev_u8(planes_u8_device).view(-1)
         if src.numel() % fb:
             raise ValueError(f"{src.numel()} bytes is not a whole number of {W}x{H} {pixfmt} frames of {fb} bytes")
@@ -146,10 +156,10 @@ class RelaxEngine:
         items = torch.stack([torch.arange(N, dtype=torch.int64) * fb, torch.arange(N, dtype=torch.int64) * stride], dim=1)
         items = items.contiguous().to(self.device)
         status = torch.empty(N, dtype=torch.int32, device=self.device)
-        rc = self.lib.relax_yuv_to_bgr(_ptr(src), src.numel(), _ptr(items), N, layout, H, W, sampling.YUV_MATRICES[matrix],
-                                       int(full_range), _ptr(out), (N - 1) * stride + slot, _ptr(status), _stream())
+        rc = convert(_ptr(src), src.numel(), _ptr(items), N, layout, H, W, sampling.YUV_MATRICES[matrix],
+                     int(full_range), _ptr(out), (N - 1) * stride + slot, _ptr(status), _stream())
         if rc != 0:
-            raise RuntimeError(f"relax_yuv_to_bgr failed ({rc}): {self.lib.relax_last_error(None).decode()}")
+            raise RuntimeError(f"{name} failed ({rc}): {self.lib.relax_last_error(None).decode()}")
         return out
 
     # ---- greyscale screen (data_processing/check_greyscale.py, csrc/greyscale.hip) -------------------------------
@@ -169,6 +179,12 @@ class RelaxEngine:
         each pixel is converted in registers and goes straight into the maxima.  Arguments as yuv_to_bgr's."""
         from .data_processing import check_greyscale
         return check_greyscale.scan_yuv_frames(self._dev_u8(planes), H, W, pixfmt, matrix)
+
+    def yuv_greyscale_scan_ex(self, planes, H, W, pixfmt, matrix="bt601"):
+        """greyscale_scan(yuv_to_bgr_ex(planes, H, W, pixfmt, matrix)) in one pass that writes no BGR
+        (relax_yuv_greyscale_scan_ex), for every pixfmt of sampling.yuv_format.  Arguments and checks as yuv_greyscale_scan's."""
+        from .data_processing import check_greyscale
+        return check_greyscale.scan_yuv_frames(self._dev_u8(planes), H, W, pixfmt, matrix, extended=True)
 
     # ---- weights ------------------------------------------------------------------------------
     def _marshal_state_dict(self, sd):

@@ -7,6 +7,7 @@ decodes the video (or already holds the frames) and these helpers reproduce whic
                           index with zip truncation src/main_fragment_layerstack.py:283-293
   frame_pair_paths / load_clip_from_frames   src/main_fragment_layerstack.py:283-296: the sampled frames the reference's ffmpeg step left on disk
                           (`{video}_{n}.png`, `{video}_{n}_next.png`), paired by sorted index, read as cv2.imread reads them (uint8 BGR)
+  yuv_format / yuv_samples / yuv_frame_bgr_ex   the same for 10 / 12-bit, packed 4:2:2, 4:1:1, 4:1:0 and NV21 input (extended=True)
   yuv_layout / yuv_frame_count / yuv_frame_bgr / load_clip_from_yuv / GpuYuvLoader   src/video_frames_extract.py:29-49,76-100: the frames
                           ffmpeg cuts out of headerless raw video (`-s WxH -pix_fmt yuv420p -framerate r -i file.yuv`, the live_qualcomm
                           input path), converted from the file's own bytes by the integer formula of include/relax_hip.h
@@ -193,9 +194,10 @@ def yuv_frame_bytes(layout, H, W):
     return yuv_plan(layout, H, W)["frame_bytes"]
 
 
-def yuv_frame_count(path, W, H, pixfmt):
-    """Frames in a headerless raw file: size // frame bytes; a size that is no whole number of frames raises."""
-    fb = yuv_frame_bytes(yuv_layout(pixfmt)[0], H, W)
+def yuv_frame_count(path, W, H, pixfmt, extended=False):
+    """Frames in a headerless raw file: size // frame bytes; a size that is no whole number of frames raises.  extended: pixfmt is one
+    of yuv_format's names."""
+    fb = _yuv_source(pixfmt, extended)[2](H, W)
     size = os.path.getsize(path)
     if size % fb:
         raise ValueError(f"{path}: {size} bytes is not a whole number of {W}x{H} {pixfmt} frames of {fb} bytes "
@@ -246,21 +248,158 @@ def yuv_frame_bgr(y, u, v, matrix="bt601", full_range=False, out=None):
     return out
 
 
-def _yuv_pairs(path, W, H, pixfmt, framerate):
-    n = yuv_frame_count(path, W, H, pixfmt)
+# ---- the RELAX_YUVF_* formats: 10 / 12-bit, packed 4:2:2, 4:1:1, 4:1:0, NV21 (include/relax_hip.h; opt-in: extended=True) ----------
+(YUVF_420P, YUVF_422P, YUVF_444P, YUVF_NV12, YUVF_NV21, YUVF_YUYV422, YUVF_UYVY422, YUVF_411P, YUVF_410P, YUVF_420P10LE, YUVF_422P10LE,
+ YUVF_444P10LE, YUVF_420P12LE, YUVF_422P12LE, YUVF_444P12LE, YUVF_P010LE) = range(16)
+YUV_PLANAR, YUV_SEMIPLANAR, YUV_PACKED = 0, 1, 2
+_YUV_FORMATS = dict(_YUV_PIXFMTS)
+_YUV_FORMATS.update({
+    "nv21": (YUVF_NV21, False), "yuyv422": (YUVF_YUYV422, False), "uyvy422": (YUVF_UYVY422, False),
+    "yuv411p": (YUVF_411P, False), "yuv410p": (YUVF_410P, False),
+    "yuv420p10le": (YUVF_420P10LE, False), "yuv422p10le": (YUVF_422P10LE, False), "yuv444p10le": (YUVF_444P10LE, False),
+    "yuv420p12le": (YUVF_420P12LE, False), "yuv422p12le": (YUVF_422P12LE, False), "yuv444p12le": (YUVF_444P12LE, False),
+    "p010le": (YUVF_P010LE, False),
+})
+_yuv_info_cache = {}
+
+
+def yuv_format(pixfmt):
+    """The reference's metadata `pixfmt` string -> (format, full_range) for the `_ex` entries: yuv_layout's seven names (formats
+    0..3) and nv21, yuyv422, uyvy422, yuv411p, yuv410p, yuv4{20,22,44}p1{0,2}le, p010le.  Everything else (pal8, RGB, alpha,
+    big-endian, 14 / 16-bit, gray, ...) raises a ValueError naming it."""
+    try:
+        return _YUV_FORMATS[str(pixfmt).strip()]
+    except KeyError:
+        raise ValueError(f"pixfmt {pixfmt!r} is not supported: raw input is read as one of {', '.join(_YUV_FORMATS)}") from None
+
+
+def yuv_format_info(format):
+    """The library's format table (relax_yuv_format_info: csrc/yuv_core.h's, the one the kernels use): dict of sample_bytes, depth,
+    shift (sample = (word >> shift) & (2^depth - 1)), hshift, vshift, packing (YUV_PLANAR / YUV_SEMIPLANAR / YUV_PACKED), swap
+    (semi-planar: V first; packed: chroma first)."""
+    if isinstance(format, bool) or not isinstance(format, (int, np.integer)):
+        raise ValueError(f"format {format!r} is not one of RELAX_YUVF_* (0..15)")
+    format = int(format)
+    if format not in _yuv_info_cache:
+        import ctypes as C
+
+        from . import _lib
+        out = (C.c_int32 * 8)()
+        if _lib.load().relax_yuv_format_info(format, out) != 0:
+            raise ValueError(f"format {format!r} is not one of RELAX_YUVF_* (0..15)")
+        _yuv_info_cache[format] = dict(zip(("sample_bytes", "depth", "shift", "hshift", "vshift", "packing", "swap"), out))
+    return _yuv_info_cache[format]
+
+
+def yuv_plan_ex(format, H, W):
+    """The frame layout of a format, from yuv_format_info's table (csrc/yuv_core.h's plan_ex, restated): dict of cw, ch (chroma plane
+    size: W >> hshift and H >> vshift, rounded up), frame_bytes, and the byte offsets / steps / strides of the luma and chroma samples
+    (y_off, y_step, y_stride, u_off, v_off, c_step, c_stride)."""
+    t = yuv_format_info(format)
+    H, W = int(H), int(W)
+    if not (1 <= H <= YUV_MAX_DIM and 1 <= W <= YUV_MAX_DIM):
+        raise ValueError(f"frame size {W}x{H} outside 1..{YUV_MAX_DIM}")
+    sb = t["sample_bytes"]
+    cw, ch = -(-W // (1 << t["hshift"])), -(-H // (1 << t["vshift"]))
+    if t["packing"] == YUV_PACKED:
+        u = 0 if t["swap"] else 1
+        return {"cw": cw, "ch": ch, "y_off": 1 if t["swap"] else 0, "y_step": 2, "y_stride": 4 * cw, "u_off": u, "v_off": u + 2, "c_step": 4,
+                "c_stride": 4 * cw, "frame_bytes": 4 * cw * H}
+    yb, cb = H * W * sb, ch * cw * sb
+    p = {"cw": cw, "ch": ch, "y_off": 0, "y_step": sb, "y_stride": W * sb, "frame_bytes": yb + 2 * cb}
+    if t["packing"] == YUV_SEMIPLANAR:
+        p.update(u_off=yb + (sb if t["swap"] else 0), v_off=yb + (0 if t["swap"] else sb), c_step=2 * sb, c_stride=2 * cw * sb)
+    else:
+        p.update(u_off=yb, v_off=yb + cb, c_step=sb, c_stride=cw * sb)
+    return p
+
+
+def yuv_frame_bytes_ex(format, H, W):
+    return yuv_plan_ex(format, H, W)["frame_bytes"]
+
+
+def yuv_samples(frame, format, H, W):
+    """One frame's bytes (uint8 [frame_bytes]) -> (Y [H,W], U [ch,cw], V [ch,cw], depth): integer arrays at the format's native depth
+    (uint8 views for 8-bit planes, uint16 otherwise; shift and mask applied: garbage above a 10-bit value or below a P010 value is gone)."""
+    t, p = yuv_format_info(format), yuv_plan_ex(format, H, W)
+    H, W = int(H), int(W)
+    frame = np.asarray(frame, np.uint8).reshape(-1)
+    if frame.size != p["frame_bytes"]:
+        raise ValueError(f"a {W}x{H} frame of format {format} has {p['frame_bytes']} bytes, got {frame.size}")
+    sb, cw, ch = t["sample_bytes"], p["cw"], p["ch"]
+
+    def plane(off, rows, cols, stride, step):
+        at = off + np.arange(rows, dtype=np.int64)[:, None] * stride + np.arange(cols, dtype=np.int64)[None, :] * step
+        if sb == 1:
+            return frame[at]
+        word = frame[at].astype(np.uint16) | (frame[at + 1].astype(np.uint16) << 8)
+        return (word >> t["shift"]) & ((1 << t["depth"]) - 1)
+    return (plane(p["y_off"], H, W, p["y_stride"], p["y_step"]), plane(p["u_off"], ch, cw, p["c_stride"], p["c_step"]),
+            plane(p["v_off"], ch, cw, p["c_stride"], p["c_step"]), t["depth"])
+
+
+def yuv_frame_bgr_ex(y, u, v, depth=8, matrix="bt601", full_range=False, out=None):
+    """The numpy statement of relax_yuv_to_bgr_ex's arithmetic (include/relax_hip.h), s = depth - 8: Y [H,W], U and V [ch,cw] integer
+    arrays at `depth` bits with ch in (H, ceil(H/2), ceil(H/4)) and cw in (W, ceil(W/2), ceil(W/4)) - chroma is replicated - -> uint8
+    [H,W,3] BGR.  int32 throughout (depth <= 12 keeps every sum inside it).  At depth 8 this is yuv_frame_bgr bit for bit."""
+    if depth not in (8, 10, 12):
+        raise ValueError(f"depth {depth!r} is not 8, 10 or 12")
+    s = depth - 8
+    cy, oy, crv, cbu, cgu, cgv = yuv_coefficients(matrix, full_range)
+    y = np.asarray(y)
+    H, W = y.shape
+
+    def full(c):
+        c = np.asarray(c)
+        for axis, n in ((0, H), (1, W)):
+            if c.shape[axis] != n:
+                k = next((k for k in (2, 4) if c.shape[axis] == -(-n // k)), None)
+                if k is None:
+                    raise ValueError(f"chroma plane of {c.shape[axis]} {'rows' if axis == 0 else 'columns'} under {n} of luma")
+                c = np.repeat(c, k, axis=axis)[:H] if axis == 0 else np.repeat(c, k, axis=axis)[:, :W]
+        return c.astype(np.int32) - (128 << s)
+
+    yy = cy * (y.astype(np.int32) - (oy << s)) + (1 << (15 + s))
+    uu, vv = full(u), full(v)
+    out = np.empty((H, W, 3), np.uint8) if out is None else out
+    top = (1 << (24 + s)) - 1
+    out[..., 2] = np.clip(yy + crv * vv, 0, top) >> (16 + s)
+    out[..., 1] = np.clip(yy - cgu * uu - cgv * vv, 0, top) >> (16 + s)
+    out[..., 0] = np.clip(yy + cbu * uu, 0, top) >> (16 + s)
+    return out
+
+
+def _yuv_source(pixfmt, extended):
+    """-> (layout or format, full_range, frame_bytes(H, W), frame_bgr(bytes, H, W, matrix, out)) of a pixfmt: the 8-bit surface
+    (yuv_layout, relax_yuv_to_bgr), or with extended=True the RELAX_YUVF_* one (yuv_format, the `_ex` entries)."""
+    if not extended:
+        layout, full_range = yuv_layout(pixfmt)
+        return (layout, full_range, lambda H, W: yuv_frame_bytes(layout, H, W),
+                lambda buf, H, W, matrix, out: yuv_frame_bgr(*yuv_planes(buf, layout, H, W), matrix=matrix, full_range=full_range, out=out))
+    fmt, full_range = yuv_format(pixfmt)
+
+    def frame_bgr(buf, H, W, matrix, out):
+        y, u, v, depth = yuv_samples(buf, fmt, H, W)
+        return yuv_frame_bgr_ex(y, u, v, depth, matrix=matrix, full_range=full_range, out=out)
+    return fmt, full_range, lambda H, W: yuv_frame_bytes_ex(fmt, H, W), frame_bgr
+
+
+def _yuv_pairs(path, W, H, pixfmt, framerate, extended=False):
+    n = yuv_frame_count(path, W, H, pixfmt, extended)
     _, _, pairs = sampled_frame_indices(n, frame_interval(framerate))
     if not pairs:
         raise FileNotFoundError(f"{path}: {n} frames at framerate {framerate} hold no (frame, next frame) pair")
     return pairs
 
 
-def load_clip_from_yuv(path, W, H, pixfmt, framerate, alloc=None, matrix="bt601"):
+def load_clip_from_yuv(path, W, H, pixfmt, framerate, alloc=None, matrix="bt601", extended=False):
     """A raw YUV video -> uint8 [T,2,H,W,3] BGR: pair_frames() of the converted video, reading only the sampled frames and their
     successors (the PNGs the reference's two ffmpeg passes leave behind, src/video_frames_extract.py:76-100, without the PNGs).
-    The host twin of GpuYuvLoader; alloc as in load_clip_from_frames.  Raises FileNotFoundError if the file holds no pair."""
-    layout, full_range = yuv_layout(pixfmt)
-    pairs = _yuv_pairs(path, W, H, pixfmt, framerate)
-    fb = yuv_frame_bytes(layout, H, W)
+    The host twin of GpuYuvLoader; alloc as in load_clip_from_frames.  Raises FileNotFoundError if the file holds no pair.
+    extended=True: pixfmt is one of yuv_format's names and the frames go through yuv_samples / yuv_frame_bgr_ex."""
+    _, _, frame_bytes, frame_bgr = _yuv_source(pixfmt, extended)
+    pairs = _yuv_pairs(path, W, H, pixfmt, framerate, extended)
+    fb = frame_bytes(H, W)
     shape = (len(pairs), 2, int(H), int(W), 3)
     out = alloc(shape) if alloc is not None else np.empty(shape, dtype=np.uint8)
     buf = np.empty(2 * fb, np.uint8)
@@ -271,16 +410,15 @@ def load_clip_from_yuv(path, W, H, pixfmt, framerate, alloc=None, matrix="bt601"
             if span not in (1, 2) or f.readinto(memoryview(buf[:span * fb])) != span * fb:
                 raise OSError(f"{path}: short read at frame {a}")
             for j, n in enumerate((a, b)):
-                yuv_frame_bgr(*yuv_planes(buf[(n - a) * fb:(n - a + 1) * fb], layout, H, W), matrix=matrix, full_range=full_range,
-                              out=out[t, j])
+                frame_bgr(buf[(n - a) * fb:(n - a + 1) * fb], H, W, matrix, out[t, j])
     return out
 
 
-def load_frames_from_yuv(path, W, H, pixfmt, indices, matrix="bt601"):
-    """Frames `indices` of a raw YUV video -> uint8 [len(indices),H,W,3] BGR (host)."""
-    layout, full_range = yuv_layout(pixfmt)
-    n = yuv_frame_count(path, W, H, pixfmt)
-    fb = yuv_frame_bytes(layout, H, W)
+def load_frames_from_yuv(path, W, H, pixfmt, indices, matrix="bt601", extended=False):
+    """Frames `indices` of a raw YUV video -> uint8 [len(indices),H,W,3] BGR (host).  extended: as load_clip_from_yuv."""
+    _, _, frame_bytes, frame_bgr = _yuv_source(pixfmt, extended)
+    n = yuv_frame_count(path, W, H, pixfmt, extended)
+    fb = frame_bytes(H, W)
     out = np.empty((len(indices), int(H), int(W), 3), np.uint8)
     buf = np.empty(fb, np.uint8)
     with open(path, "rb", buffering=0) as f:
@@ -290,7 +428,7 @@ def load_frames_from_yuv(path, W, H, pixfmt, indices, matrix="bt601"):
             f.seek(i * fb)
             if f.readinto(memoryview(buf)) != fb:
                 raise OSError(f"{path}: short read at frame {i}")
-            yuv_frame_bgr(*yuv_planes(buf, layout, H, W), matrix=matrix, full_range=full_range, out=out[k])
+            frame_bgr(buf, H, W, matrix, out[k])
     return out
 
 
@@ -346,9 +484,11 @@ class GpuYuvLoader:
     16-byte-aligned slot, so the kernel's 16-byte path applies whenever W is a multiple of 16), followed by one host-to-device
     copy and one relax_yuv_to_bgr launch on that thread's own stream; loader threads work at the same time.  Pass it as the
     `clips` of dataset.extract_dataset_clips.  The clip is complete when __call__ returns and is recorded on `consumer_stream`
-    (default: the current stream of `device` when the loader is made).  A file with no pair raises FileNotFoundError."""
+    (default: the current stream of `device` when the loader is made).  A file with no pair raises FileNotFoundError.
+    extended=True: the pixfmts are yuv_format's names and the launch is relax_yuv_to_bgr_ex; the host twin is
+    load_clip_from_yuv(..., extended=True)."""
 
-    def __init__(self, paths, widths, heights, pixfmts, framerates, device=None, consumer_stream=None, matrix="bt601"):
+    def __init__(self, paths, widths, heights, pixfmts, framerates, device=None, consumer_stream=None, matrix="bt601", extended=False):
         import torch
 
         from . import _lib
@@ -365,6 +505,7 @@ class GpuYuvLoader:
         if matrix not in YUV_MATRICES:
             raise ValueError(f"matrix {matrix!r} is not one of {', '.join(YUV_MATRICES)}")
         self.matrix = matrix
+        self.extended = bool(extended)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.consumer = consumer_stream if consumer_stream is not None else torch.cuda.current_stream(self.device)
         self.lib = _lib.load()
@@ -384,9 +525,10 @@ class GpuYuvLoader:
 
         import torch
         path, W, H = self.paths[i], int(self.widths[i]), int(self.heights[i])
-        layout, full_range = yuv_layout(self.pixfmts[i])
-        pairs = _yuv_pairs(path, W, H, self.pixfmts[i], self.framerates[i])
-        fb = yuv_frame_bytes(layout, H, W)
+        layout, full_range, frame_bytes, _ = _yuv_source(self.pixfmts[i], self.extended)
+        pairs = _yuv_pairs(path, W, H, self.pixfmts[i], self.framerates[i], self.extended)
+        fb = frame_bytes(H, W)
+        convert, name = (self.lib.relax_yuv_to_bgr_ex, "relax_yuv_to_bgr_ex") if self.extended else (self.lib.relax_yuv_to_bgr, "relax_yuv_to_bgr")
         slot_bytes = (fb + 15) // 16 * 16
         frames = sorted({n for ab in pairs for n in ab})
         slot = {n: k for k, n in enumerate(frames)}
@@ -406,14 +548,14 @@ class GpuYuvLoader:
             clip = torch.empty((len(pairs), 2, H, W, 3), dtype=torch.uint8, device=self.device)
             dev = pinned[:total].to(self.device, non_blocking=True)
             status = torch.empty(len(pairs) * 2, dtype=torch.int32, device=self.device)
-            rc = self.lib.relax_yuv_to_bgr(C.c_void_p(dev.data_ptr()), items_at, C.c_void_p(dev.data_ptr() + items_at), len(pairs) * 2,
-                                           layout, H, W, YUV_MATRICES[self.matrix], int(full_range), C.c_void_p(clip.data_ptr()),
-                                           clip.numel(), C.c_void_p(status.data_ptr()), C.c_void_p(st.stream.cuda_stream))
+            rc = convert(C.c_void_p(dev.data_ptr()), items_at, C.c_void_p(dev.data_ptr() + items_at), len(pairs) * 2,
+                         layout, H, W, YUV_MATRICES[self.matrix], int(full_range), C.c_void_p(clip.data_ptr()),
+                         clip.numel(), C.c_void_p(status.data_ptr()), C.c_void_p(st.stream.cuda_stream))
             if rc != 0:
-                raise RuntimeError(f"relax_yuv_to_bgr failed ({rc}): {self.lib.relax_last_error(None).decode()}")
+                raise RuntimeError(f"{name} failed ({rc}): {self.lib.relax_last_error(None).decode()}")
             bad = status.cpu()                                      # waits for the conversion: the pinned buffer is free again
         if bool(bad.any()):
-            raise RuntimeError(f"{path}: relax_yuv_to_bgr refused items {bad.nonzero().view(-1).tolist()} (out of range)")
+            raise RuntimeError(f"{path}: {name} refused items {bad.nonzero().view(-1).tolist()} (out of range)")
         clip.record_stream(self.consumer)
         return clip
 
