@@ -300,6 +300,45 @@ int relax_optical_flow_ex(relax_handle* h, const uint8_t* orig, const uint8_t* n
  * pyr_scale and levels within the limits above; refused too: a coarsest used scale under RELAX_FLOW_MIN_SCALE.
  * No handle, no GPU: host arithmetic; errors through relax_last_error(NULL). */
 int relax_flow_plan(int H, int W, double pyr_scale, int levels, int* n_levels, int32_t* level_hw_ksize, double* level_sigma);
+/* relax_optical_flow_ex with the two flag bits it refuses: flags in {0, 4, 256, 260}.  The six parameters: relax_optical_flow_ex's rules and
+ * wording (the rules answer with h == NULL through relax_last_error(NULL) here too); any other flags bit is refused with the value named.
+ * With flags 0 (init_flow NULL) it makes relax_optical_flow_ex's launches: the same bits.
+ * BOTH MODES ARE PINNED TO THE FORMULAS STATED HERE, restated in float64 by tests/flow_flag_ref.py, AND NOT TO AN OPENCV BUILD: nothing here can
+ * run OpenCV, and its output on these modes has not been compared.
+ * RELAX_FLOW_GAUSSIAN (OPTFLOW_FARNEBACK_GAUSSIAN, 256): the box window of the flow update becomes a separable Gaussian window of the same
+ *   2 m + 1 taps, m = winsize / 2, sigma = 0.3 m: k[0] = 1, k[i] = (float)exp(-i^2 / (2 sigma^2)), s = 1 / (1 + 2 sum k[1..m]) in double,
+ *   k[i] = (float)(k[i] s).  Over each of the five planes of the matrix image M, rows then columns, replicated borders:
+ *   v = M[y] k[0] + sum_i (M[min(y + i, h - 1)] + M[max(y - i, 0)]) k[i], the same along x on v.  All 2 m + 1 taps are used (the outermost is
+ *   3.9e-3 of the centre).  The 2 x 2 solve is the box window's, in double, regulariser 1e-3, without a 1 / winsize^2 (the taps sum to 1).
+ *   It takes update_matrices_k + gauss_solve_any at every window, 15 included; results do not depend on batch, chunk or "flow_seg_rows".
+ * RELAX_FLOW_USE_INITIAL (OPTFLOW_USE_INITIAL_FLOW, 4): at the coarsest level USED (relax_flow_plan's first row, h_c x w_c at scale_c) the zero
+ *   field becomes resize_area(init_flow, h_c, w_c) * (float)scale_c; finer levels are unchanged.  resize_area is cv::resize(INTER_AREA)'s
+ *   separable table (relax_flow_area_table below), accumulated in double.
+ *   init_flow : fp32 [T,H,W,2]; required with bit 4 and NULL without it - both mistakes are refused by name.  init_flow == flow is allowed
+ *               (OpenCV's in/out use: a chunk of pairs reads its initial field before it writes its flow); any other overlap is refused.
+ *               The call waits for the stream once per chunk (the host tables of the resize). */
+#define RELAX_FLOW_USE_INITIAL 4
+#define RELAX_FLOW_GAUSSIAN 256
+int relax_optical_flow_flags(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
+                             double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                             const float* init_flow, float* flow, uint8_t* flow_bgr, relax_stream stream);
+/* The Gaussian window above, one half of it: half_taps[0 .. winsize / 2] (room for winsize / 2 + 1 floats), odd winsize in
+ * RELAX_FLOW_MIN_WINSIZE .. RELAX_FLOW_MAX_WINSIZE.  No handle, no GPU; errors through relax_last_error(NULL). */
+int relax_flow_gauss_window(int winsize, float* half_taps);
+/* cv::resize(INTER_AREA)'s table for one axis, src >= dst >= 1.  S = src / dst in double; cell d covers [d S, d S + S), cw = min(S, src - d S):
+ *   - full source pixels s1 = ceil(d S) up to but not including s2 = min(floor(d S + S), src - 1), with s1 = min(s1, s2), at 1 / cw each;
+ *   - the left partial pixel s1 - 1 at (s1 - d S) / cw if that overlap exceeds 1e-3;
+ *   - the right partial pixel s2 at min(d S + S - s2, 1, cw) / cw if that overlap exceeds 1e-3
+ *     (an overlap of at most 1e-3 pixel is dropped, as in OpenCV: such a row sums to a little under 1; it takes dst / gcd(src, dst) >= 1000).
+ *   first, count : int32 [dst] - source pixels first[d] .. first[d] + count[d] - 1
+ *   weights      : double [dst][RELAX_FLOW_AREA_TAPS(src, dst)], count[d] of each row written, in source order
+ * With dst == src it is a copy.  No handle, no GPU; errors through relax_last_error(NULL). */
+#define RELAX_FLOW_AREA_TAPS(src, dst) ((src) / (dst) + 2)
+int relax_flow_area_table(int src, int dst, int32_t* first, int32_t* count, double* weights);
+/* The starting field of relax_optical_flow_flags' coarsest level alone: out fp32 [T,h_c,w_c,2] = resize_area(init_flow [T,H,W,2]) *
+ * (float)scale_c with (h_c, w_c) relax_flow_plan(H, W, pyr_scale, levels)'s first row; levels 0: a copy, bit for bit.  Waits for the stream. */
+int relax_flow_initial_level(relax_handle* h, const float* init_flow, int T, int H, int W, double pyr_scale, int levels, float* out,
+                             relax_stream stream);
 /* flow_to_rgb alone: fp32 [T,H,W,2] -> uint8 [T,H,W,3] (BGR, despite the reference's name). */
 int relax_flow_to_rgb(relax_handle* h, const float* flow, int T, int H, int W, uint8_t* flow_bgr, relax_stream stream);
 

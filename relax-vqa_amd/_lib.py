@@ -46,7 +46,12 @@ PROTOTYPES = {
     "relax_optical_flow_ex": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_double, C.c_int, c_vp, c_vp, c_vp]),
     "relax_flow_plan": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int), c_vp, c_vp]),
-    "relax_flow_to_rgb": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp, c_vp]),
+    "relax_optical_flow_flags": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_double, C.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "relax_flow_gauss_window": (C.c_int, [C.c_int, c_vp]),
+    "relax_flow_area_table": (C.c_int, [C.c_int, C.c_int, c_vp, c_vp, c_vp]),
+    "relax_flow_initial_level": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, c_vp, c_vp]),
+    "relax_flow_to_rgb":(C.c_int, [c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp, c_vp]),
     "relax_resize_frames": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp]),
     "relax_resize_residual": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp]),
     "relax_resize_output_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -17,6 +17,9 @@
 // relax_optical_flow_ex takes OpenCV's six parameters (FlowParams below): the literals run exactly the launches above; other values take
 // poly_expansion<7>, the per-level pyramid kernels (wide instantiations down to scale 1/32), resize_linear_f32<2> for the pyramid step and,
 // for windows other than 15, update_matrices_k + box_solve_any.  DESIGN.md has the band / halo / segment arithmetic.
+// relax_optical_flow_flags adds the two flag bits: OPTFLOW_FARNEBACK_GAUSSIAN - update_matrices_k + gauss_solve_any at every window - and
+// OPTFLOW_USE_INITIAL_FLOW - resize_area_f32x2 of the caller's field in place of the coarsest level's zeros.  Both follow the formulas stated in
+// include/relax_hip.h (restated in float64 by tests/flow_flag_ref.py), not an OpenCV build.
 // LAB_NOTES.md section 3.3 has the measurements and what was tried and not kept.
 #include <cfloat>
 #include <cmath>
@@ -973,6 +976,126 @@ __global__ __launch_bounds__(256) void box_solve_any(const float* __restrict__ M
     }
 }
 
+// ---- the Gaussian window and the solve for any odd window (relax_optical_flow_flags, OPTFLOW_FARNEBACK_GAUSSIAN) ----------------------------
+// box_solve_any's counterpart: the separable window of host::flow_gauss_window (half taps as a kernel argument) over the five planes of M with
+// replicated borders, then the same 2 x 2 solve with the regulariser 1e-3 (the taps sum to 1: no 1 / winsize^2).  No running sums - every output
+// adds up its own 2 m + 1 taps - so there is no segmentation to depend on: a block is a tile of GS_TH x GS_TW outputs of one pair, one plane at a
+// time: (GS_TH + 2 m) x (GS_TW + 2 m) floats of M staged in LDS with clamped coordinates (47 KB at m = 31), the vertical pass into a second LDS
+// tile of GS_TH x (GS_TW + 2 m) floats (accumulated in double in the order of the definition - centre, then (below + above) x k[i], i = 1 .. m -
+// and rounded to float once), the horizontal pass in double into registers: a thread owns 8 outputs (one column, every 4th row) and keeps their
+// five blurred values across the planes.  LDS addresses of a wave are consecutive in both passes.  63.5 KB of dynamic LDS at most.
+constexpr int GS_TH = 32, GS_TW = 64, GS_PER = GS_TH * GS_TW / 256;
+struct GaussHalfTaps {
+    float k[host::kFlowMaxHalfWindow + 1];
+};
+static inline size_t gauss_solve_lds(int m) { return sizeof(float) * (size_t)(GS_TH + 2 * m + GS_TH) * (GS_TW + 2 * m); }
+template <bool MINMAX>
+__global__ __launch_bounds__(256) void gauss_solve_any(const float* __restrict__ M, float* __restrict__ flow, int h, int w, int m,
+                                                       GaussHalfTaps taps, unsigned* __restrict__ mm) {
+    extern __shared__ __attribute__((aligned(16))) float gs_lds[];
+    const int cw = GS_TW + 2 * m, rows_in = GS_TH + 2 * m;
+    float* tin = gs_lds;                       // [rows_in][cw]
+    float* tv = gs_lds + rows_in * cw;         // [GS_TH][cw]
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * GS_TW, y0 = blockIdx.y * GS_TH;
+    const int64_t hw = (int64_t)h * w;
+    const int64_t pair = blockIdx.z;
+    const int ox = tid & (GS_TW - 1), oy = tid >> 6;          // outputs (oy + 4 e, ox), e < GS_PER
+    double acc[5][GS_PER];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+        const float* plane = M + (pair * 5 + c) * hw;
+        if (c) __syncthreads();                               // the previous plane's horizontal pass has read tv
+        {   // stage: element (row, col) of the tile = M at the clamped (y0 - m + row, x0 - m + col)
+            int row = 0, col = tid;
+            while (col >= cw) { col -= cw; ++row; }
+            while (row < rows_in) {
+                tin[row * cw + col] = plane[(int64_t)clampi(y0 - m + row, 0, h - 1) * w + clampi(x0 - m + col, 0, w - 1)];
+                col += 256;
+                while (col >= cw) { col -= cw; ++row; }
+            }
+        }
+        __syncthreads();
+        for (int idx = tid; idx < GS_TH * cw; idx += 256) {   // vertical: output row r, column q at idx = r cw + q; its centre row is r + m
+            const float* p = tin + idx + m * cw;
+            double a = __dmul_rn((double)p[0], (double)taps.k[0]);
+            for (int i = 1; i <= m; ++i) a = __fma_rn(__dadd_rn((double)p[i * cw], (double)p[-i * cw]), (double)taps.k[i], a);
+            tv[idx] = (float)a;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < GS_PER; ++e) {                    // horizontal: output column ox has its centre at column ox + m
+            const float* p = tv + (oy + 4 * e) * cw + ox + m;
+            double a = __dmul_rn((double)p[0], (double)taps.k[0]);
+            for (int i = 1; i <= m; ++i) a = __fma_rn(__dadd_rn((double)p[i], (double)p[-i]), (double)taps.k[i], a);
+            acc[c][e] = a;
+        }
+    }
+    [[maybe_unused]] unsigned mag_lo = 0xffffffffu, mag_hi = 0u;
+    const int x = x0 + ox;
+#pragma unroll
+    for (int e = 0; e < GS_PER; ++e) {
+        const int y = y0 + oy + 4 * e;
+        if (x < w && y < h) {
+            const float2 f = solve_flow_reg(acc[0][e], acc[1][e], acc[2][e], acc[3][e], acc[4][e], 1e-3);
+            float* dst = flow + (pair * hw + (int64_t)y * w + x) * 2;
+            dst[0] = f.x;
+            dst[1] = f.y;
+            if constexpr (MINMAX) {
+                const unsigned u = __float_as_uint(flow_magnitude(f.x, f.y));
+                mag_lo = u < mag_lo ? u : mag_lo;
+                mag_hi = u > mag_hi ? u : mag_hi;
+            }
+        }
+    }
+    if constexpr (MINMAX) {   // wave minimum / maximum, one atomic pair per wave (integer min / max: the order of arrival does not matter)
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const unsigned a = __shfl_xor(mag_lo, o), b = __shfl_xor(mag_hi, o);
+            mag_lo = a < mag_lo ? a : mag_lo;
+            mag_hi = b > mag_hi ? b : mag_hi;
+        }
+        if ((tid & 63) == 0) {
+            atomicMin(&mm[pair], mag_lo);                 // mins [0,P), maxs [P,2P)
+            atomicMax(&mm[gridDim.z + pair], mag_hi);
+        }
+    }
+}
+
+// ---- the initial flow at the coarsest level (relax_optical_flow_flags, OPTFLOW_USE_INITIAL_FLOW; relax_flow_initial_level) --------------------
+// cv::resize(INTER_AREA) of a flow field [P][H][W][2] -> [P][h][w][2], times (float)scale: the two tables of host::flow_area_table (first, count,
+// weights in double, `taps` weights per cell), a thread per output pixel, both components: rows in order, within a row the columns in order,
+// accumulated in double, rounded to float once, then one float multiply.  With h == H and w == W and scale 1: a copy, bit for bit.
+struct AreaAxis {
+    const int32_t* first;
+    const int32_t* count;
+    const double* weights;
+    int taps;
+};
+__global__ __launch_bounds__(256) void resize_area_f32x2(const float* __restrict__ src, float* __restrict__ dst, int H, int W, int h, int w,
+                                                         AreaAxis ay, AreaAxis ax, float scale) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;      // grid (w / 256, h, pairs)
+    if (x >= w) return;
+    const int64_t pair = blockIdx.z;
+    const int fy = ay.first[y], ny = ay.count[y], fx = ax.first[x], nx = ax.count[x];
+    const double* wy = ay.weights + (int64_t)y * ay.taps;
+    const double* wx = ax.weights + (int64_t)x * ax.taps;
+    double sx = 0, sy = 0;
+    for (int j = 0; j < ny; ++j) {          // (every count is at least 1; the first term is a product, not 0 + product: -0 stays -0 in a copy)
+        const float* row = src + ((pair * H + fy + j) * W + fx) * 2;
+        double rx = __dmul_rn((double)row[0], wx[0]), ry = __dmul_rn((double)row[1], wx[0]);
+        for (int i = 1; i < nx; ++i) {
+            rx = __fma_rn((double)row[2 * i], wx[i], rx);
+            ry = __fma_rn((double)row[2 * i + 1], wx[i], ry);
+        }
+        sx = j ? __fma_rn(rx, wy[j], sx) : __dmul_rn(rx, wy[0]);
+        sy = j ? __fma_rn(ry, wy[j], sy) : __dmul_rn(ry, wy[0]);
+    }
+    float* o = dst + ((pair * h + y) * w + x) * 2;
+    o[0] = __fmul_rn((float)sx, scale);
+    o[1] = __fmul_rn((float)sy, scale);
+}
+
 // ---- one Farneback iteration in ONE kernel ----------------------------------------------------------------------------
 // FarnebackUpdateMatrices + the 15x15 box blur + the 2x2 solve, without the matrix plane M ever going to HBM: per pixel and
 // iteration the memory system sees R0 (20 B), R1 at the displaced position (20 B), the flow in (8 B) and out (8 B) = 56 bytes
@@ -1468,10 +1591,14 @@ static int flow_segment_rows(const relax_handle* h, int bands, int hh, int winsi
 // run; what another value changes: pyr_scale / levels - the per-level pyramid kernels instead of pyramid_fused, and the coarser flow resized by
 // resize_linear_f32<2> (x 1 / pyr_scale) where the x 2 written into flow_up_value does not apply; winsize - update_matrices_k + box_solve_any;
 // poly_n / poly_sigma - poly_expansion<7>, other constants; iterations - the loop count.
+// flags (relax_optical_flow_flags alone; 0 everywhere else, and then no launch differs): OPTFLOW_FARNEBACK_GAUSSIAN - update_matrices_k +
+// gauss_solve_any at every window, 15 too (the fused iteration is the box window's); OPTFLOW_USE_INITIAL_FLOW - the coarsest level starts from
+// resize_area_f32x2 of the caller's field instead of zeros.
 struct FlowParams {
     double pyr_scale;
     int levels, winsize, iterations, poly_n;
     double poly_sigma;
+    int flags;
 };
 static const FlowParams kFlowLiteral = {0.5, 3, WINSIZE, ITERS, POLY_N_LITERAL, POLY_SIGMA_LITERAL};
 
@@ -1505,6 +1632,41 @@ static void launch_box_solve(const relax_handle* h, const float* M, float* flow,
     else hipLaunchKernelGGL(box_solve_any<false>, gf, dim3(256), 0, s, M, flow, hh, w, seg, winsize, out_cols, reg, nullptr);
 }
 
+// gauss_solve_any over M, in place on `flow`
+static int launch_gauss_solve(relax_handle* h, const float* M, float* flow, int hh, int w, int P, int winsize, bool minmax, unsigned* mm,
+                              hipStream_t s) {
+    GaussHalfTaps taps = {};
+    RELAX_REQUIRE(h, host::flow_gauss_window(winsize, taps.k), "optical flow: no Gaussian window of %d", winsize);
+    const int m = winsize / 2;
+    const dim3 g((w + GS_TW - 1) / GS_TW, (hh + GS_TH - 1) / GS_TH, P);
+    if (minmax) hipLaunchKernelGGL(gauss_solve_any<true>, g, dim3(256), gauss_solve_lds(m), s, M, flow, hh, w, m, taps, mm);
+    else hipLaunchKernelGGL(gauss_solve_any<false>, g, dim3(256), gauss_solve_lds(m), s, M, flow, hh, w, m, taps, nullptr);
+    RELAX_HIP_CHECK(h, hipGetLastError());
+    return RELAX_OK;
+}
+
+// resize_area_f32x2: src [P][H][W][2] -> dst [P][hh][w][2] x scale.  The two tables go through h->scratch; the call waits for the stream before
+// it returns (the host tables, and the next call's upload into the same scratch, must not overtake the kernel).
+static int launch_resize_area(relax_handle* h, const float* src, int P, int H, int W, int hh, int w, float scale, float* dst, hipStream_t s) {
+    const int ty = host::flow_area_taps(H, hh), tx = host::flow_area_taps(W, w);
+    std::vector<int32_t> idx(2 * ((size_t)hh + w));                     // first_y | count_y | first_x | count_x
+    std::vector<double> wts((size_t)hh * ty + (size_t)w * tx);            // weights_y | weights_x
+    RELAX_REQUIRE(h, host::flow_area_table(H, hh, idx.data(), idx.data() + hh, wts.data()) &&
+                         host::flow_area_table(W, w, idx.data() + 2 * hh, idx.data() + 2 * hh + w, wts.data() + (size_t)hh * ty),
+                  "optical flow: no area table for %d x %d -> %d x %d", H, W, hh, w);
+    const size_t wbytes = sizeof(double) * wts.size(), ibytes = sizeof(int32_t) * idx.size();
+    RELAX_TRY(ensure_buf(h, h->scratch, wbytes + ibytes));
+    double* d_w = static_cast<double*>(h->scratch.p);
+    int32_t* d_i = reinterpret_cast<int32_t*>(d_w + wts.size());
+    RELAX_HIP_CHECK(h, hipMemcpyAsync(d_w, wts.data(), wbytes, hipMemcpyHostToDevice, s));
+    RELAX_HIP_CHECK(h, hipMemcpyAsync(d_i, idx.data(), ibytes, hipMemcpyHostToDevice, s));
+    const AreaAxis ay{d_i, d_i + hh, d_w, ty}, ax{d_i + 2 * hh, d_i + 2 * hh + w, d_w + (size_t)hh * ty, tx};
+    hipLaunchKernelGGL(resize_area_f32x2, dim3(nblocks(w), hh, P), dim3(256), 0, s, src, dst, H, W, hh, w, ay, ax, scale);
+    RELAX_HIP_CHECK(h, hipGetLastError());
+    RELAX_HIP_CHECK(h, hipStreamSynchronize(s));
+    return RELAX_OK;
+}
+
 template <bool UP, bool MINMAX>
 static int launch_flow_iteration(relax_handle* h, const float* R, const float* flow_in, float* flow_out, int hh, int w, int P, const FlowUp& up,
                                  unsigned* mm, hipStream_t s) {
@@ -1519,8 +1681,9 @@ static int launch_flow_iteration(relax_handle* h, const float* R, const float* f
 }
 
 static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int P, int H, int W,
-                      const FlowParams& fp, float* flow_out, uint8_t* bgr_out, hipStream_t s) {
+                      const FlowParams& fp, const float* init, float* flow_out, uint8_t* bgr_out, hipStream_t s) {
     const int64_t HW = (int64_t)H * W;
+    const bool gaussian = (fp.flags & host::kFlowFlagGaussian) != 0;
     // the matrix kernels address a pair's two coefficient images through ONE buffer resource with 32-bit byte offsets
     RELAX_REQUIRE(h, HW * 40 < (int64_t)0x7fffffff, "optical flow: frames of %d x %d exceed the 2 GB a buffer resource addresses (40 bytes per pixel)", W, H);
     // workspace carve (floats unless noted), all sized for level 0
@@ -1590,7 +1753,12 @@ static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next,
         RELAX_REQUIRE(h, !sampled || 129.0 * W / w + smooth + 4 <= GH_SEG_WIDE, "optical flow: pyramid scale %g too coarse for the row stage", scale);
         RELAX_REQUIRE(h, !wide || sampled, "optical flow: %d smoothing taps at scale %g", smooth, scale);   // (scale >= 1/2 has 3 taps)
         const int64_t hw = (int64_t)w * hh;
-        if (!prev_flow) RELAX_HIP_CHECK(h, hipMemsetAsync(cur, 0, sizeof(float) * P * 2 * hw, s));
+        if (!prev_flow && init) {          // OPTFLOW_USE_INITIAL_FLOW: the caller's field, area-resized to the coarsest level, x (float)scale
+            RELAX_TRY(launch_resize_area(h, init, P, H, W, hh, w, (float)scale, cur, s));
+            stage_bytes += 8.0 * P * ((double)HW + (double)hw);
+        } else if (!prev_flow) {
+            RELAX_HIP_CHECK(h, hipMemsetAsync(cur, 0, sizeof(float) * P * 2 * hw, s));
+        }
         // finer levels: the first matrix update resizes the coarser flow where it reads it - no resized plane - when the pyramid step doubles
         // it (x 2 is written into flow_up_value); any other pyr_scale: resize_linear_f32<2>, the same operations, x (float)(1 / pyr_scale)
         const bool up_fused = prev_flow && fp.pyr_scale == 0.5;
@@ -1640,7 +1808,7 @@ static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next,
         stage_bytes += 2.0 * P * hw * 24;      // 4 bytes in, 5 coefficients out per pixel and frame
         const int iters = fp.iterations;
         // the fused iteration kernel is written for the 15-pixel window (its ring, its fill steps); every other window takes the two kernels
-        if (h->gemm.flow_fused && fp.winsize == WINSIZE) {
+        if (h->gemm.flow_fused && fp.winsize == WINSIZE && !gaussian) {
             // one kernel per iteration (flow_iteration): M stays on the chip.  The iterations ping-pong between the two flow buffers:
             // a block reads flow rows its neighbours may already have rewritten otherwise.
             // measurement (relax_profile_read kind 5): algorithmic bytes per pixel = 2 x 5 floats of R at the pixel and at the displaced
@@ -1689,7 +1857,8 @@ static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next,
             for (int it = 0; it < iters; ++it) {
                 const bool last = k == 0 && it == iters - 1 && bgr_out;   // the final flow: its magnitude range is taken on the way out
                 if (last) RELAX_TRY(minmax_reset(h, P, mm, s));
-                launch_box_solve(h, M, cur, hh, w, P, fp.winsize, last, mm, s);
+                if (gaussian) RELAX_TRY(launch_gauss_solve(h, M, cur, hh, w, P, fp.winsize, last, mm, s));
+                else launch_box_solve(h, M, cur, hh, w, P, fp.winsize, last, mm, s);
                 if (it < iters - 1) {
                     RELAX_TRY(prof_begin(h, s, 3, um_bytes, &um_span));
                     hipLaunchKernelGGL(update_matrices_k<false>, g_um, dim3(256), 0, s, R, cur, M, hh, w, (hh + 7) / 8, FlowUp{});
@@ -1722,7 +1891,7 @@ extern "C" {
 
 // both entries: the argument checks, then the pairs in chunks that the workspace bounds
 static int optical_flow_run(relax_handle* h, const char* who, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
-                            const FlowParams& fp, float* flow, uint8_t* flow_bgr, relax_stream stream) {
+                            const FlowParams& fp, float* flow, uint8_t* flow_bgr, relax_stream stream, const float* init = nullptr) {
     RELAX_REQUIRE(h, orig && next && T > 0 && H >= 16 && W >= 16, "%s: bad arguments", who);
     RELAX_REQUIRE(h, flow || flow_bgr, "%s: no output requested", who);
     RELAX_REQUIRE(h, pair_stride >= (int64_t)H * W * 3 || T == 1, "%s: pair stride smaller than a frame", who);
@@ -1740,7 +1909,7 @@ static int optical_flow_run(relax_handle* h, const char* who, const uint8_t* ori
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int P = T - t0 < chunk ? T - t0 : chunk;
         RELAX_TRY(flow_chunk(h, orig + t0 * pair_stride, next + t0 * pair_stride, pair_stride, P, H, W, fp,
-                             flow ? flow + (int64_t)t0 * HW * 2 : nullptr, flow_bgr ? flow_bgr + (int64_t)t0 * HW * 3 : nullptr, s));
+                             init ? init + (int64_t)t0 * HW * 2 : nullptr, flow ? flow + (int64_t)t0 * HW * 2 : nullptr, flow_bgr ? flow_bgr + (int64_t)t0 * HW * 3 : nullptr, s));
     }
     return RELAX_OK;
 }
@@ -1772,6 +1941,77 @@ int relax_optical_flow_ex(relax_handle* h, const uint8_t* orig, const uint8_t* n
     }
     const FlowParams fp = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma};
     return optical_flow_run(h, "relax_optical_flow_ex", orig, next, pair_stride, T, H, W, fp, flow, flow_bgr, stream);
+}
+
+int relax_optical_flow_flags(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
+                             double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                             const float* init_flow, float* flow, uint8_t* flow_bgr, relax_stream stream) {
+    // as relax_optical_flow_ex: the rules first, answered through relax_last_error(NULL) when there is no handle
+    std::string err;
+    if (!host::flow_check_params_flags(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, err)) {
+        set_error(h, "relax_optical_flow_flags: %s", err.c_str());
+        return RELAX_ERR_INVALID;
+    }
+    if ((flags & host::kFlowFlagInitial) && !init_flow) {
+        set_error(h, "relax_optical_flow_flags: flags=%d has OPTFLOW_USE_INITIAL_FLOW (4) but init_flow is NULL", flags);
+        return RELAX_ERR_INVALID;
+    }
+    if (!(flags & host::kFlowFlagInitial) && init_flow) {
+        set_error(h, "relax_optical_flow_flags: init_flow is given but flags=%d lacks OPTFLOW_USE_INITIAL_FLOW (4)", flags);
+        return RELAX_ERR_INVALID;
+    }
+    if (!h) {
+        set_error(nullptr, "relax_optical_flow_flags: the handle is NULL");
+        return RELAX_ERR_INVALID;
+    }
+    {
+        int n;
+        host::FlowLevel plan[host::kFlowMaxLevels + 1];
+        RELAX_REQUIRE(h, host::flow_plan(H, W, pyr_scale, levels, &n, plan, err), "relax_optical_flow_flags: %s", err.c_str());
+    }
+    if (init_flow && flow && init_flow != flow && T > 0) {   // in place is OpenCV's in/out use (a chunk reads its field before it writes its flow)
+        const uintptr_t a = reinterpret_cast<uintptr_t>(init_flow), b = reinterpret_cast<uintptr_t>(flow);
+        const uintptr_t bytes = (uintptr_t)T * H * W * 2 * sizeof(float);
+        RELAX_REQUIRE(h, a + bytes <= b || b + bytes <= a, "relax_optical_flow_flags: init_flow and flow overlap without being the same buffer");
+    }
+    const FlowParams fp = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
+    return optical_flow_run(h, "relax_optical_flow_flags", orig, next, pair_stride, T, H, W, fp, flow, flow_bgr, stream, init_flow);
+}
+
+int relax_flow_gauss_window(int winsize, float* half_taps) {
+    if (!half_taps) {
+        set_error(nullptr, "relax_flow_gauss_window: half_taps is NULL");
+        return RELAX_ERR_INVALID;
+    }
+    if (!host::flow_gauss_window(winsize, half_taps)) {
+        set_error(nullptr, "relax_flow_gauss_window: winsize=%d is not an odd number in %d..%d", winsize, host::kFlowMinWinsize, host::kFlowMaxWinsize);
+        return RELAX_ERR_INVALID;
+    }
+    return RELAX_OK;
+}
+
+int relax_flow_area_table(int src, int dst, int32_t* first, int32_t* count, double* weights) {
+    if (!first || !count || !weights) {
+        set_error(nullptr, "relax_flow_area_table: a table pointer is NULL");
+        return RELAX_ERR_INVALID;
+    }
+    if (!host::flow_area_table(src, dst, first, count, weights)) {
+        set_error(nullptr, "relax_flow_area_table: src=%d, dst=%d: needs src >= dst >= 1", src, dst);
+        return RELAX_ERR_INVALID;
+    }
+    return RELAX_OK;
+}
+
+int relax_flow_initial_level(relax_handle* h, const float* init_flow, int T, int H, int W, double pyr_scale, int levels, float* out,
+                             relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, init_flow && out && T > 0, "relax_flow_initial_level: bad arguments");
+    int n;
+    host::FlowLevel plan[host::kFlowMaxLevels + 1];
+    std::string err;
+    RELAX_REQUIRE(h, host::flow_plan(H, W, pyr_scale, levels, &n, plan, err), "relax_flow_initial_level: %s", err.c_str());
+    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    return launch_resize_area(h, init_flow, T, H, W, plan[0].h, plan[0].w, (float)plan[0].scale, out, static_cast<hipStream_t>(stream));
 }
 
 int relax_flow_plan(int H, int W, double pyr_scale, int levels, int* n_levels, int32_t* level_hw_ksize, double* level_sigma) {

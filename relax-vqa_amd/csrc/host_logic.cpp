@@ -708,8 +708,128 @@ bool flow_plan(int H, int W, double pyr_scale, int levels, int* n_levels, FlowLe
     return true;
 }
 
+bool flow_gauss_window(int winsize, float* half_taps) {
+    if (!half_taps || winsize < kFlowMinWinsize || winsize > kFlowMaxWinsize || winsize % 2 == 0) return false;
+    const int m = winsize / 2;
+    const double sigma = 0.3 * m;
+    double s = 1.0;
+    half_taps[0] = 1.f;
+    for (int i = 1; i <= m; ++i) {
+        half_taps[i] = (float)std::exp(-(double)(i * i) / (2 * sigma * sigma));
+        s += 2.0 * half_taps[i];
+    }
+    s = 1.0 / s;
+    for (int i = 0; i <= m; ++i) half_taps[i] = (float)(half_taps[i] * s);
+    return true;
+}
+
+bool flow_area_table(int src, int dst, int32_t* first, int32_t* count, double* weights) {
+    if (!first || !count || !weights || dst < 1 || src < dst) return false;
+    const int taps = flow_area_taps(src, dst);
+    const double S = (double)src / dst;
+    for (int d = 0; d < dst; ++d) {
+        const double f1 = d * S, f2 = f1 + S;
+        const double cw = std::min(S, src - f1);
+        int s1 = (int)std::ceil(f1), s2 = (int)std::floor(f2);
+        s2 = std::min(s2, src - 1);
+        s1 = std::min(s1, s2);
+        double* w = weights + (size_t)d * taps;
+        int n = 0, at = s1;
+        if (s1 - f1 > 1e-3) {
+            at = s1 - 1;
+            w[n++] = (s1 - f1) / cw;
+        }
+        for (int sx = s1; sx < s2; ++sx) w[n++] = 1.0 / cw;
+        if (f2 - s2 > 1e-3) w[n++] = std::min(std::min(f2 - s2, 1.0), cw) / cw;
+        first[d] = at;
+        count[d] = n;
+    }
+    return true;
+}
+
+bool flow_check_params_flags(double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags, std::string& err) {
+    if (!flow_check_params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, 0, err)) return false;
+    if (flags & ~(kFlowFlagInitial | kFlowFlagGaussian)) {
+        char buf[400];
+        std::snprintf(buf, sizeof buf, "flags=%d has bits outside OPTFLOW_USE_INITIAL_FLOW (4) | OPTFLOW_FARNEBACK_GAUSSIAN (256): %d (those two "
+                      "modes are pinned to the formulas stated in relax_hip.h and to float64, not to an OpenCV build; no other mode is restated)",
+                      flags, flags & ~(kFlowFlagInitial | kFlowFlagGaussian));
+        err = buf;
+        return false;
+    }
+    return true;
+}
+
 }  // namespace host
 }  // namespace relax
+
+#ifdef RELAX_FLOW_FLAGS_MAIN
+// ---- stand-alone program (make flow_flags_san: AddressSanitizer + UBSan, CPU only): the Gaussian window of every odd winsize and the area table of
+// a grid of (src, dst) into heap arrays of exactly the stated sizes; taps sum to 1 +- 1e-6, every table index in range, rows sum to 1 +- 1e-12 -
+// except where the definition itself drops an overlap of at most 1e-3 pixel (possible only when dst / gcd(src, dst) >= 1000: the fractional parts
+// of d * src / dst are multiples of gcd / dst), where a row may fall short of 1 by at most 2e-3 / cw ---------------------------------------------
+static int flags_gcd(int a, int b) { return b ? flags_gcd(b, a % b) : a; }
+int main() {
+    using namespace relax::host;
+    long windows = 0, tables = 0, short_tables = 0;
+    for (int ws = kFlowMinWinsize; ws <= kFlowMaxWinsize; ws += 2) {
+        std::vector<float> k((size_t)ws / 2 + 1);
+        if (!flow_gauss_window(ws, k.data())) return 1;
+        double sum = k[0];
+        for (int i = 1; i <= ws / 2; ++i) {
+            sum += 2.0 * k[i];
+            if (!(k[i] > 0 && k[i] < k[i - 1])) {
+                std::printf("winsize %d: tap %d not positive and decreasing\n", ws, i);
+                return 1;
+            }
+        }
+        if (std::fabs(sum - 1.0) > 1e-6) {
+            std::printf("winsize %d: taps sum to %.9f\n", ws, sum);
+            return 1;
+        }
+        ++windows;
+    }
+    float none[1];
+    if (flow_gauss_window(14, none) || flow_gauss_window(65, none) || flow_gauss_window(1, none)) return 1;
+    std::vector<int> sides;
+    for (int n = 16; n <= 2200; n += 53) sides.push_back(n);
+    for (int n : {31, 32, 33, 48, 66, 78, 97, 105, 131, 256, 264, 1000, 1001, 1080, 1920, 2160, 2199, 2200}) sides.push_back(n);
+    for (int src : sides)
+        for (int dst : sides) {
+            if (dst > src) continue;
+            const int taps = flow_area_taps(src, dst);
+            std::vector<int32_t> first((size_t)dst), count((size_t)dst);
+            std::vector<double> w((size_t)dst * taps);
+            if (!flow_area_table(src, dst, first.data(), count.data(), w.data())) return 1;
+            const bool may_drop = dst / flags_gcd(src, dst) >= 1000;
+            const double S = (double)src / dst;
+            for (int d = 0; d < dst; ++d) {
+                double sum = 0;
+                for (int j = 0; j < count[d]; ++j) sum += w[(size_t)d * taps + j];
+                const double cw = std::min(S, src - d * S);
+                const bool ok = count[d] >= 1 && count[d] <= taps && first[d] >= 0 && first[d] + count[d] <= src &&
+                                (may_drop ? sum <= 1 + 1e-12 && sum >= 1 - 2e-3 / cw - 1e-12 : std::fabs(sum - 1.0) <= 1e-12);
+                if (!ok) {
+                    std::printf("bad area row %d of %d -> %d: first %d, count %d, sum %.17g\n", d, src, dst, first[d], count[d], sum);
+                    return 1;
+                }
+            }
+            ++tables;
+            short_tables += may_drop;
+        }
+    int32_t i1[1];
+    double d1[4];
+    if (flow_area_table(16, 17, i1, i1, d1) || flow_area_table(16, 0, i1, i1, d1)) return 1;
+    std::string err;
+    for (int fl : {0, 4, 256, 260})
+        if (!flow_check_params_flags(0.5, 3, 15, 3, 5, 1.2, fl, err)) return 1;
+    for (int fl : {1, 2, 8, 261, 512, -1})
+        if (flow_check_params_flags(0.5, 3, 15, 3, 5, 1.2, fl, err) || err.find("flags=") == std::string::npos) return 1;
+    if (flow_check_params_flags(0.5, 3, 14, 3, 5, 1.2, 256, err) || err.find("winsize=14") == std::string::npos) return 1;
+    std::printf("flow_flags ok: %ld windows, %ld area tables (%ld of them may drop an overlap under 1e-3)\n", windows, tables, short_tables);
+    return 0;
+}
+#endif
 
 #ifdef RELAX_FLOW_PLAN_MAIN
 // ---- stand-alone program (make flow_plan_san: AddressSanitizer + UBSan, CPU only): every plan of a grid of sizes, scales and depths into a heap

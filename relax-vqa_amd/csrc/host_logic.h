@@ -136,6 +136,24 @@ bool flow_check_params(double pyr_scale, int levels, int winsize, int iterations
 // outside the limits, or a coarsest used scale under kFlowMinScale.
 bool flow_plan(int H, int W, double pyr_scale, int levels, int* n_levels, FlowLevel* lv, std::string& err);
 
+// ---- the two flag bits of relax_optical_flow_flags (flow.hip: gauss_solve_any, resize_area_f32x2) ------------------------------------------
+// Both are pinned to the formulas stated here (restated in tests/flow_flag_ref.py in float64), not to an OpenCV build: there is none to run.
+constexpr int kFlowFlagInitial = 4, kFlowFlagGaussian = 256;      // OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_FARNEBACK_GAUSSIAN
+constexpr int kFlowMaxHalfWindow = kFlowMaxWinsize / 2;           // half_taps holds winsize / 2 + 1 <= 32 floats
+// The Gaussian window of FarnebackUpdateFlow_GaussianBlur, one half of it: m = winsize / 2, sigma = 0.3 m, k[0] = 1,
+// k[i] = (float)exp(-i^2 / (2 sigma^2)), s = 1 / (1 + 2 sum k[1..m]) in double, k[i] = (float)(k[i] s).  half_taps[0 .. m]; all 2 m + 1 taps are
+// used (the outermost is 3.9e-3 of the centre).  winsize: odd, kFlowMinWinsize .. kFlowMaxWinsize (anything else: false, nothing written).
+bool flow_gauss_window(int winsize, float* half_taps);
+// cv::resize(INTER_AREA)'s table for one axis, src >= dst >= 1: with S = src / dst in double, cell d covers [d S, d S + S), cw = min(S, src - d S);
+// full pixels s1 = ceil(d S) .. s2 = min(floor(d S + S), src - 1) exclusive (s1 = min(s1, s2)) at 1 / cw, the left partial pixel s1 - 1 at
+// (s1 - d S) / cw and the right one s2 at min(d S + S - s2, 1, cw) / cw where the overlap exceeds 1e-3 (a smaller one is DROPPED, as OpenCV does:
+// such a row sums to a little under 1; it needs dst / gcd(src, dst) >= 1000).  first[d], count[d] and weights[d * flow_area_taps(src, dst) + j],
+// j < count[d], source pixels first[d] + j in order.  With dst == src: a copy (one weight of exactly 1 per cell).
+inline int flow_area_taps(int src, int dst) { return src / dst + 2; }
+bool flow_area_table(int src, int dst, int32_t* first, int32_t* count, double* weights);
+// flow_check_params' rules and wording for the six parameters; flags: any of 0, 4, 256, 260 - another bit is refused with the value named
+bool flow_check_params_flags(double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags, std::string& err);
+
 // ---- the options table: every relax_set_option / relax_get_option key once ------------------------------------------------------------------
 // How a row takes a value: as given; != 0; a non-positive value becomes `a`; one of {a, b}; the closed range [a, b].  The last two refuse
 // anything else with "relax_set_option: <key> must be <must_be>" and leave the stored value as it was.

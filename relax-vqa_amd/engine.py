@@ -474,16 +474,118 @@ class RelaxEngine:
     FLOW_DEFAULTS = dict(pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2, flags=0)
 
     def optical_flow(self, frames, want_flow=False, want_image=True, *, pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5,
-                     poly_sigma=1.2, flags=0):
+                     poly_sigma=1.2, flags=0, initial_flow=None, extended=False):
         """frames uint8 [T,2,H,W,3] BGR -> (flow fp32 [T,H,W,2] | None, flow image uint8 [T,H,W,3] | None): Farneback flow
         and the reference's flow_to_rgb visualisation (src/main_fragment_layerstack.py:313-316).  The keywords are
         cv2.calcOpticalFlowFarneback's parameters; their defaults are the reference's literals, and with all of them at the default the
         call is relax_optical_flow as ever.  Anything else goes through relax_optical_flow_ex (include/relax_hip.h has the limits:
         pyr_scale 0.5..0.95, levels 0..8 down to scale 1/32, odd winsize 3..63, iterations 1..10, poly_n 5 or 7, flags 0); the literals
-        passed explicitly through it give the same bits."""
+        passed explicitly through it give the same bits.
+        extended=True (the opt-in): the call goes through relax_optical_flow_flags, which also takes flags 256 (OPTFLOW_FARNEBACK_GAUSSIAN:
+        the Gaussian window), 4 (OPTFLOW_USE_INITIAL_FLOW, with initial_flow fp32 [T,H,W,2]) and 260.  Both modes are pinned to the formulas
+        stated in include/relax_hip.h and to their float64 restatement (tests/flow_flag_ref.py), not to an OpenCV build.  Without it
+        nothing changes: flags 4 and 256 are refused as before."""
         given = dict(pyr_scale=pyr_scale, levels=levels, winsize=winsize, iterations=iterations, poly_n=poly_n, poly_sigma=poly_sigma,
                      flags=flags)
+        if extended:
+            return self._optical_flow_flags(frames, want_flow, want_image, given, initial_flow)
+        if initial_flow is not None:
+            raise ValueError("optical_flow: initial_flow needs extended=True (and flags with bit 4)")
         return self._optical_flow(frames, want_flow, want_image, None if given == self.FLOW_DEFAULTS else given)
+
+    def optical_flow_flags(self, frames, want_flow=False, want_image=True, **params):
+        """optical_flow through relax_optical_flow_flags whatever the parameters are (missing ones: the literals; initial_flow: the field
+        flags bit 4 starts from) - the direct form of optical_flow(..., extended=True)."""
+        initial_flow = params.pop("initial_flow", None)
+        unknown = set(params) - set(self.FLOW_DEFAULTS)
+        if unknown:
+            raise TypeError(f"optical_flow_flags: unknown parameters {sorted(unknown)}")
+        return self._optical_flow_flags(frames, want_flow, want_image, {**self.FLOW_DEFAULTS, **params}, initial_flow)
+
+    def clip_flow_images(self, frames, flow_params=None):
+        """The flow images of a clip's pairs for the clip methods' flow_params keyword: a dict of optical_flow's keywords (None: the literals),
+        'extended' among them - {'flags': 256, 'extended': True} is the Gaussian window.  'initial_flow' is refused: the pairs of a clip are
+        computed as one batch of independent pairs, and chaining pair t - 1's flow into pair t is not what these methods do."""
+        flow_params = dict(flow_params or {})
+        if "initial_flow" in flow_params:
+            raise ValueError("flow_params: initial_flow is not accepted by the clip methods (a clip's pairs are independent); "
+                             "call optical_flow(..., initial_flow=..., extended=True) and pass flow_images")
+        return self.optical_flow(frames, **flow_params)[1]
+
+    def _optical_flow_flags(self, frames, want_flow, want_image, params, initial_flow):
+        frames = self._dev_u8(frames)
+        if frames.dim() != 5 or frames.shape[1] != 2 or frames.shape[4] != 3:
+            raise ValueError(f"frames must be [T,2,H,W,3], got {tuple(frames.shape)}")
+        T, _, H, W, _ = frames.shape
+        init = None
+        if initial_flow is not None:
+            init = initial_flow
+            if not (isinstance(init, torch.Tensor) and init.device == frames.device and init.dtype == torch.float32 and init.is_contiguous()):
+                init = torch.as_tensor(init).to(self.device, torch.float32).contiguous()
+            if tuple(init.shape) != (T, H, W, 2):
+                raise ValueError(f"initial_flow must be [T,H,W,2] = {(T, H, W, 2)}, got {tuple(init.shape)}")
+        fl = torch.empty((T, H, W, 2), dtype=torch.float32, device=self.device) if want_flow else None
+        im = torch.empty((T, H, W, 3), dtype=torch.uint8, device=self.device) if want_image else None
+        fb = H * W * 3
+        base = frames.data_ptr()
+        rc = self.lib.relax_optical_flow_flags(self.h, C.c_void_p(base), C.c_void_p(base + fb), 2 * fb, T, H, W, float(params["pyr_scale"]),
+                                               int(params["levels"]), int(params["winsize"]), int(params["iterations"]), int(params["poly_n"]),
+                                               float(params["poly_sigma"]), int(params["flags"]), _ptr(init), _ptr(fl), _ptr(im), _stream())
+        self._check(rc, "relax_optical_flow_flags")
+        return fl, im
+
+    def optical_flow_in_place(self, frames, flow, want_image=False, **params):
+        """OpenCV's in/out use: `flow` fp32 [T,H,W,2] on the device is the initial field (flags must have bit 4) and receives the result
+        (relax_optical_flow_flags with init_flow == flow) -> (flow, flow image | None)."""
+        frames = self._dev_u8(frames)
+        T, _, H, W, _ = frames.shape
+        if not (isinstance(flow, torch.Tensor) and flow.is_cuda and flow.dtype == torch.float32 and flow.is_contiguous()
+                and tuple(flow.shape) == (T, H, W, 2)):
+            raise ValueError(f"optical_flow_in_place: flow must be a contiguous fp32 device tensor {(T, H, W, 2)}")
+        unknown = set(params) - set(self.FLOW_DEFAULTS)
+        if unknown:
+            raise TypeError(f"optical_flow_in_place: unknown parameters {sorted(unknown)}")
+        p = {**self.FLOW_DEFAULTS, **params}
+        im = torch.empty((T, H, W, 3), dtype=torch.uint8, device=self.device) if want_image else None
+        fb = H * W * 3
+        base = frames.data_ptr()
+        rc = self.lib.relax_optical_flow_flags(self.h, C.c_void_p(base), C.c_void_p(base + fb), 2 * fb, T, H, W, float(p["pyr_scale"]),
+                                               int(p["levels"]), int(p["winsize"]), int(p["iterations"]), int(p["poly_n"]), float(p["poly_sigma"]),
+                                               int(p["flags"]), _ptr(flow), _ptr(flow), _ptr(im), _stream())
+        self._check(rc, "relax_optical_flow_flags")
+        return flow, im
+
+    def flow_initial_level(self, initial_flow, pyr_scale=0.5, levels=3):
+        """initial_flow fp32 [T,H,W,2] -> fp32 [T,h_c,w_c,2]: the field relax_optical_flow_flags' coarsest level starts from under flags bit 4
+        (relax_flow_initial_level: cv::resize(INTER_AREA)'s table, times (float)scale; (h_c, w_c) = flow_plan(H, W, pyr_scale, levels)[0])."""
+        init = torch.as_tensor(initial_flow).to(self.device, torch.float32).contiguous()
+        if init.dim() != 4 or init.shape[3] != 2:
+            raise ValueError(f"initial_flow must be [T,H,W,2], got {tuple(init.shape)}")
+        T, H, W, _ = init.shape
+        top = self.flow_plan(H, W, pyr_scale, levels)[0]
+        out = torch.empty((T, top["h"], top["w"], 2), dtype=torch.float32, device=self.device)
+        self._check(self.lib.relax_flow_initial_level(self.h, _ptr(init), T, H, W, float(pyr_scale), int(levels), _ptr(out), _stream()),
+                    "relax_flow_initial_level")
+        return out
+
+    def flow_gauss_window(self, winsize):
+        """The half window of flags 256 (relax_flow_gauss_window; no GPU work) -> numpy float32 [winsize // 2 + 1], centre first."""
+        k = np.zeros(max(int(winsize) // 2 + 1, 1), dtype=np.float32)
+        if self.lib.relax_flow_gauss_window(int(winsize), k.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError(f"relax_flow_gauss_window failed: {self.lib.relax_last_error(None).decode()}")
+        return k
+
+    def flow_area_table(self, src, dst):
+        """cv::resize(INTER_AREA)'s table for one axis (relax_flow_area_table; no GPU work) -> (first int32 [dst], count int32 [dst],
+        weights float64 [dst, src // dst + 2]): cell d is sum_j weights[d, j] * source[first[d] + j], j < count[d]."""
+        src, dst = int(src), int(dst)
+        n = max(dst, 1)
+        first, count = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        weights = np.zeros((n, src // n + 2), np.float64)
+        if self.lib.relax_flow_area_table(src, dst, first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p),
+                                          weights.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError(f"relax_flow_area_table failed: {self.lib.relax_last_error(None).decode()}")
+        return first, count, weights
 
     def optical_flow_ex(self, frames, want_flow=False, want_image=True, **params):
         """optical_flow through relax_optical_flow_ex whatever the parameters are (missing ones: the literals) - what a test of the
@@ -827,7 +929,7 @@ class RelaxEngine:
         positions, counts = fr["positions"], fr["counts"]
         if fragment in ("residual_of_imp", "residual_merged_frag"):
             if flow_images is None:
-                _, flow_images = self.optical_flow(frames, **(flow_params or {}))
+                flow_images = self.clip_flow_images(frames, flow_params)
             fl = self.fragment_image(flow_images, **kw)
         if fragment == "residual_imp":
             image = fr["diff_frag"]
@@ -860,7 +962,7 @@ class RelaxEngine:
         fr = self.fragment_pairs(frames, **kw)
         resid = fr["diff_frag"]
         if flow and flow_images is None:
-            _, flow_images = self.optical_flow(frames, **(flow_params or {}))     # full ReLaX: Farneback + flow_to_rgb on the GPU
+            flow_images = self.clip_flow_images(frames, flow_params)     # full ReLaX: Farneback + flow_to_rgb on the GPU
         if flow_images is not None:
             fl = self.fragment_image(flow_images, **kw)
             resid = self.merge_fragments(resid, fl["frag"])
@@ -991,7 +1093,7 @@ class RelaxEngine:
             return self.residual_resize(frames, bilinear=bilinear, lanczos=lanczos, out_bilinear=out_bilinear,
                                         out_lanczos=out_lanczos)[:2]
         if flow_images is None:
-            _, flow_images = self.optical_flow(frames, **(flow_params or {}))
+            flow_images = self.clip_flow_images(frames, flow_params)
         return self.resize_frames(flow_images, bilinear=bilinear, lanczos=lanczos, out_bilinear=out_bilinear, out_lanczos=out_lanczos)
 
     def _check_residual_name(self, residual_name):
@@ -1030,7 +1132,7 @@ class RelaxEngine:
             return dict(self._pool_blocks(bil, lan, resnet, vit, vgg16))
         # the ViT's input on its own canvas (a second pass over the pairs); the BILINEAR 224 x 224 bytes of the other backbones as before
         if residual_name == "optical_flow" and flow_images is None:
-            _, flow_images = self.optical_flow(frames, **(flow_params or {}))
+            flow_images = self.clip_flow_images(frames, flow_params)
         bil = self._whole_residual_inputs(frames, residual_name, True, False, flow_images)[0] if resnet or vgg16 else None
         if residual_name == "frame_diff":
             lan = self.residual_resize(frames, bilinear=False, lanczos=True, size=vit_size)[1]
@@ -1127,7 +1229,7 @@ class RelaxEngine:
             self.fragment_pairs(c, out_ori=vit_in[at:at + t], out_diff=res, **kw)
             fimg = None if flow_images is None else flow_images[i]
             if flow and fimg is None:
-                _, fimg = self.optical_flow(c, **(flow_params or {}))
+                fimg = self.clip_flow_images(c, flow_params)
             if fimg is not None:
                 self.merge_fragments(res, self.fragment_image(fimg, **kw)["frag"], out=res)
             tw = wcounts[i]

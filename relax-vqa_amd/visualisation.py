@@ -16,7 +16,7 @@ def example_set_arrays(engine, frames, flow=True, overlays=None, flow_params=Non
            "residual_imp": fr["diff_frag"], "ori_frag": fr["ori_frag"]}
     flow_images = None
     if flow:
-        _, flow_images = engine.optical_flow(frames, **(flow_params or {}))
+        flow_images = engine.clip_flow_images(frames, flow_params)
         fl = engine.fragment_image(flow_images)
         out["residual_of"] = flow_images
         out["residual_of_imp"] = fl["frag"]
