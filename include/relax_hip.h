@@ -356,7 +356,10 @@ int relax_flow_to_rgb(relax_handle* h, const float* flow, int T, int H, int W, u
  *   - N above 65535 (the launch grid; once a failed launch) and H above RELAX_RESIZE_MAX_IN_H (once computed: the table builder
  *     itself has no limit) are refused with RELAX_ERR_INVALID and the value named;
  *   - the tables come from the handle's cache of 16 (least recently used replaced; a call needs at most four), and a table with
- *     a coefficient outside 24 bits would be refused - for out = 224 none is (the largest over the input sizes tested is 5 386 769). */
+ *     a coefficient outside 24 bits would be refused - for out = 224 none is (the largest over the input sizes tested is 5 386 769);
+ *   - a table that is not in the cache is built inside the call: device memory is allocated (and the least recently used table freed,
+ *     which waits for the device) and the table is uploaded with a blocking copy.  Such a call cannot be captured into a graph; a call
+ *     whose tables are all cached only enqueues on `stream`.  The same holds for the three other resize entries below. */
 int relax_resize_frames(relax_handle* h, const uint8_t* frames, int64_t item_stride, int N, int H, int W,
                         uint8_t* out_bilinear, uint8_t* out_lanczos, relax_stream stream);
 
@@ -409,7 +412,8 @@ int relax_resize_table(int in_size, int out_size, int filt, int32_t* bounds, int
  * as uint8 [N,H,out_w,3] in the handle's workspace, then the vertical pass; a pass whose dimension already matches is skipped and
  * the bytes are copied.  One read of each frame serves both filters.  Rows are staged 16 bytes per lane when W*3, item_stride and
  * frames are multiples of 16, bytewise otherwise (decided per call).  The tables are cached on the handle per (input size, output
- * size, filter), the least recently used of 16 replaced.  relax_resize_frames is this entry at 224 x 224 with its own width limit. */
+ * size, filter), the least recently used of 16 replaced; a table that is not cached is built inside the call, which then waits for the
+ * device (see relax_resize_frames).  relax_resize_frames is this entry at 224 x 224 with its own width limit. */
 int relax_resize_frames_ex(relax_handle* h, const uint8_t* frames, int64_t item_stride, int N, int H, int W, int out_h, int out_w,
                            uint8_t* out_bilinear, uint8_t* out_lanczos, relax_stream stream);
 
@@ -587,7 +591,8 @@ int relax_head_train_export_optimizer(relax_handle* h, int which, float* out, in
  * relax_head_train_import into set 0 resets all three (a new optimizer), so call this after it.  Waits for the device. */
 int relax_head_train_import_optimizer(relax_handle* h, const float* const* exp_avg, const float* const* exp_avg_sq, const char* const* names,
                                       const int64_t* numels, int n, int64_t t);
-/* relax_head_train_pad_abs_sum with exp_avg_sq as a third sum: out[3] HOST = sum | . [:, F:Fpad]| of fc1.weight, exp_avg, exp_avg_sq. */
+/* relax_head_train_pad_abs_sum with exp_avg_sq as a third sum: out[3] HOST = sum | . [:, F:Fpad]| of fc1.weight, exp_avg, exp_avg_sq.
+ * Waits for `stream`, as relax_head_train_pad_abs_sum does. */
 int relax_head_train_pad_abs_sum_adam(relax_handle* h, double* out, relax_stream stream);
 /* relax_head_train_dw1 under Adam / AdamW (a measurement, tools/head_train_bench.py): fused != 0 the Adam step's own kernel, fused == 0
  * the same tiles writing dW1, then a separate update pass.  Both change fc1.weight and both moments; the step count stays. */

@@ -47,6 +47,29 @@ int ensure_buf(relax_handle* h, DevBuf& b, size_t bytes) {
     return poison_buf(h, b);
 }
 
+// fill_async's kernels: element i < n of a uint4 / uint32 / byte view, grid-stride; the widest view the address and the size allow
+template <typename T>
+__global__ void __launch_bounds__(256) fill_k(T* p, T v, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = v;
+}
+
+template <typename T>
+static hipError_t fill_launch(void* p, T v, size_t n, hipStream_t s) {
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(fill_k<T>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, static_cast<T*>(p), v, n);
+    return hipGetLastError();
+}
+
+hipError_t fill_async(void* p, int value, size_t bytes, hipStream_t s) {
+    if (bytes == 0) return hipSuccess;
+    if (!p) return hipErrorInvalidValue;
+    const uint32_t b = (uint32_t)value & 255u, w = b * 0x01010101u;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    if ((a | bytes) % 16 == 0) return fill_launch<uint4>(p, make_uint4(w, w, w, w), bytes / 16, s);
+    if ((a | bytes) % 4 == 0) return fill_launch<uint32_t>(p, w, bytes / 4, s);
+    return fill_launch<uint8_t>(p, (uint8_t)b, bytes, s);
+}
+
 int allow_dynamic_lds(relax_handle* h, std::initializer_list<const void*> kernels, size_t bytes, std::atomic<bool>* done) {
     if (done[h->device].load(std::memory_order_acquire)) return RELAX_OK;
     for (const void* kernel : kernels) RELAX_HIP_CHECK(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));

@@ -1556,8 +1556,8 @@ static inline bool vec4_ok(int w, int64_t plane_elems, const void* a, const void
 }
 
 static int minmax_reset(relax_handle* h, int P, unsigned* mm, hipStream_t s) {
-    RELAX_HIP_CHECK(h, hipMemsetAsync(mm, 0xff, sizeof(unsigned) * P, s));       // running minima
-    RELAX_HIP_CHECK(h, hipMemsetAsync(mm + P, 0, sizeof(unsigned) * P, s));       // running maxima
+    RELAX_HIP_CHECK(h, fill_async(mm, 0xff, sizeof(unsigned) * P, s));       // running minima
+    RELAX_HIP_CHECK(h, fill_async(mm + P, 0, sizeof(unsigned) * P, s));       // running maxima
     return RELAX_OK;
 }
 
@@ -1757,7 +1757,7 @@ static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next,
             RELAX_TRY(launch_resize_area(h, init, P, H, W, hh, w, (float)scale, cur, s));
             stage_bytes += 8.0 * P * ((double)HW + (double)hw);
         } else if (!prev_flow) {
-            RELAX_HIP_CHECK(h, hipMemsetAsync(cur, 0, sizeof(float) * P * 2 * hw, s));
+            RELAX_HIP_CHECK(h, fill_async(cur, 0, sizeof(float) * P * 2 * hw, s));
         }
         // finer levels: the first matrix update resizes the coarser flow where it reads it - no resized plane - when the pyramid step doubles
         // it (x 2 is written into flow_up_value); any other pyr_scale: resize_linear_f32<2>, the same operations, x (float)(1 / pyr_scale)

@@ -380,10 +380,10 @@ static int fragment_run(relax_handle* h, bool pair, const uint8_t* a, const uint
     const int ph = H / P, pw = W / P;
     const int npatch = ph * pw;
     if (npatch == 0) {  // frame smaller than one patch: empty selection, zero canvases
-        RELAX_HIP_CHECK(h, hipMemsetAsync(counts, 0, sizeof(int32_t) * T, s));
-        RELAX_HIP_CHECK(h, hipMemsetAsync(positions, 0xff, sizeof(int32_t) * 2 * slots * T, s));
-        if (frag_a) RELAX_HIP_CHECK(h, hipMemsetAsync(frag_a, 0, frag_bytes * T, s));
-        if (frag_diff) RELAX_HIP_CHECK(h, hipMemsetAsync(frag_diff, 0, frag_bytes * T, s));
+        RELAX_HIP_CHECK(h, fill_async(counts, 0, sizeof(int32_t) * T, s));
+        RELAX_HIP_CHECK(h, fill_async(positions, 0xff, sizeof(int32_t) * 2 * slots * T, s));
+        if (frag_a) RELAX_HIP_CHECK(h, fill_async(frag_a, 0, frag_bytes * T, s));
+        if (frag_diff) RELAX_HIP_CHECK(h, fill_async(frag_diff, 0, frag_bytes * T, s));
         return RELAX_OK;
     }
     if (!scores) {

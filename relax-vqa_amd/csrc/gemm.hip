@@ -773,7 +773,7 @@ int relax_op_conv2d_nhwc_ex(relax_handle* h, const float* in, const float* w, co
     RELAX_REQUIRE(h, !b2b || (narrow && bias3 && Cout3 > 0 && Cout3 % 64 == 0 && Cout % 16 == 0),
                   "relax_op_conv2d_nhwc_ex: the back-to-back form is a narrow KxK convolution followed by a 1x1 onto Cout3 %% 64 == 0 columns with its bias");
     RELAX_REQUIRE(h, !residual_h2 || (wide && !b2b), "relax_op_conv2d_nhwc_ex: a residual as fp16 planes goes with the wide form (gemm_h3)");
-    if (amax_out) RELAX_HIP_CHECK(h, hipMemsetAsync(amax_out, 0, sizeof(uint32_t) * (size_t)Nimg, s));
+    if (amax_out) RELAX_HIP_CHECK(h, fill_async(amax_out, 0, sizeof(uint32_t) * (size_t)Nimg, s));
     const size_t w3_al = b2b ? (((size_t)Cout3 * Cout * 4 + 255) & ~(size_t)255) : 0;
     H2OpOperands o{};
     RELAX_TRY(h2_op_operands(h, in, w, Nimg, H, W, Cin, Cout, K, 2 * w3_al + (size_t)Cout3 * 4, o, s));

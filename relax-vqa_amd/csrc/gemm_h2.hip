@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void image_absmax_kernel(const float* __restri
 
 int launch_image_absmax(relax_handle* h, const float* x, int64_t per_image, int n_images, unsigned* amax, hipStream_t s) {
     RELAX_REQUIRE(h, x && amax && n_images > 0 && per_image > 0 && per_image % 4 == 0, "image_absmax: bad arguments");
-    RELAX_HIP_CHECK(h, hipMemsetAsync(amax, 0, sizeof(unsigned) * (size_t)n_images, s));
+    RELAX_HIP_CHECK(h, fill_async(amax, 0, sizeof(unsigned) * (size_t)n_images, s));
     const int blocks = (int)((per_image / 4 + 255) / 256 < 64 ? (per_image / 4 + 255) / 256 : 64);
     hipLaunchKernelGGL(image_absmax_kernel, dim3(blocks, n_images), dim3(256), 0, s, x, per_image, amax);
     RELAX_HIP_CHECK(h, hipGetLastError());

@@ -206,7 +206,7 @@ struct ExScanKernelOf {
 };
 
 int zero_records(const char* who, int32_t* out, int N, hipStream_t stream) {
-    const hipError_t e = hipMemsetAsync(out, 0, static_cast<size_t>(N) * grey::kRecordWords * sizeof(int32_t), stream);
+    const hipError_t e = relax::fill_async(out, 0, static_cast<size_t>(N) * grey::kRecordWords * sizeof(int32_t), stream);
     if (e != hipSuccess) {
         relax::set_error(nullptr, "%s: clearing the records failed: %s", who, hipGetErrorString(e));
         return RELAX_ERR_HIP;

@@ -1134,7 +1134,7 @@ int relax_head_train_loss_read(relax_handle* h, int which, int reset, double* ou
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     RELAX_HIP_CHECK(h, hipMemcpyAsync(out, t.loss + 3 * which, sizeof(double) * 3, hipMemcpyDeviceToHost, s));
-    if (reset) RELAX_HIP_CHECK(h, hipMemsetAsync(t.loss + 3 * which, 0, sizeof(double) * 3, s));
+    if (reset) RELAX_HIP_CHECK(h, fill_async(t.loss + 3 * which, 0, sizeof(double) * 3, s));
     RELAX_HIP_CHECK(h, hipStreamSynchronize(s));
     return RELAX_OK;
 }

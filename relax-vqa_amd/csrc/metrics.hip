@@ -234,7 +234,7 @@ bool on_device(const void* p) {
 }
 
 int pair_pass(relax_handle* h, const double* x, const double* y, int n, const Ws& ws, hipStream_t s) {
-    RELAX_HIP_CHECK(h, hipMemsetAsync(ws.counts, 0, (size_t)5 * n * sizeof(uint32_t), s));
+    RELAX_HIP_CHECK(h, fill_async(ws.counts, 0, (size_t)5 * n * sizeof(uint32_t), s));
     const dim3 grid((unsigned)((n + kPairThreads - 1) / kPairThreads), (unsigned)((n + kTile - 1) / kTile));
     hipLaunchKernelGGL(mt_pair, grid, dim3(kPairThreads), 0, s, x, y, n, ws.counts);
     hipLaunchKernelGGL(mt_rank, dim3(1), dim3(kFitThreads), 0, s, x, y, ws.counts, n, ws.rank_out);

@@ -357,6 +357,11 @@ namespace relax {
 
 int ensure_buf(relax_handle* h, DevBuf& b, size_t bytes);
 
+// hipMemsetAsync's place on every path a caller may capture into a graph: `bytes` bytes of `value` at p, by a kernel of this library on `s`
+// (api.hip).  A memset NODE of a few hundred bytes wrote other bytes than asked for from the second replay of its graph on (seen with
+// 64 and 1152 bytes, not with 1 MiB; tests/test_gpu_stream_contract.py replays twice); a kernel node carries its arguments itself.
+hipError_t fill_async(void* p, int value, size_t bytes, hipStream_t s);
+
 // The opt-in of a launch site's kernel (or of the instantiations it chooses among) to `bytes` of dynamic LDS - more than the 64 KB a launch
 // gets unasked -, once per site and device (api.hip).  `done` is the site's own flags [kMaxDevices]: the attribute lives on the device's code
 // object, per kernel instantiation, so inside a templated launcher the array is a function-local static of that instantiation.  Atomic: two

@@ -400,7 +400,7 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
             if (g.out_h2) { g.img_out_scale = slot_scale(slot_out); g.amax_out = slot_amax(slot_out); }
             return launch_gemm_h2(h, g, s);
         };
-        if (plan.n_slots) RELAX_HIP_CHECK(h, hipMemsetAsync(imgtab, 0, sizeof(float) * 3 * kImgSlots * n, s));
+        if (plan.n_slots) RELAX_HIP_CHECK(h, fill_async(imgtab, 0, sizeof(float) * 3 * kImgSlots * n, s));
         unsigned* blockmax = reinterpret_cast<unsigned*>(imgtab + 3 * kImgSlots * n);
         if (plan.pool_f32)
             RELAX_TRY(launch_bn_relu_maxpool_f32(h, bufA, rn.bn1_scale, rn.bn1_shift, bufD, N, 112, 112, 64, s, slot_amax(plan.s_stem), blockmax));

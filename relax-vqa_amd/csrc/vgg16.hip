@@ -264,7 +264,7 @@ static int vgg_chunk(relax_handle* h, const uint8_t* frags, int N, float* layer_
     auto slot_amax = [&](int t) { return reinterpret_cast<unsigned*>(tab + (size_t)(3 * t) * n); };
     auto slot_scale = [&](int t) { return tab + (size_t)(3 * t + 1) * n; };
     auto slot_inv = [&](int t) { return tab + (size_t)(3 * t + 2) * n; };
-    RELAX_HIP_CHECK(h, hipMemsetAsync(tab, 0, sizeof(float) * 3 * kVggSlots * n, s));
+    RELAX_HIP_CHECK(h, fill_async(tab, 0, sizeof(float) * 3 * kVggSlots * n, s));
 
     int off = 0;   // layer-stack column of the current tap
     auto tap_out = [&](int i, const float* f32, int HW, int C, int group) -> int {   // the mean (group > 0: from the fused group sums) and the export

@@ -133,7 +133,7 @@ def scan_yuv_frames(planes, H, W, pixfmt, matrix="bt601", offsets=None, out=None
     if offsets is None:
         if src.numel() % fb:
             raise ValueError(f"{src.numel()} bytes is not a whole number of {W}x{H} {pixfmt} frames of {fb} bytes")
-        offsets = torch.arange(src.numel() // fb, dtype=torch.int64) * fb
+        offsets = torch.arange(src.numel() // fb, dtype=torch.int64, device=src.device) * fb    # on the device: no host copy to wait for
     offsets = torch.as_tensor(offsets, dtype=torch.int64).reshape(-1).to(src.device).contiguous()
     N = offsets.numel()
     lib = _lib.load()

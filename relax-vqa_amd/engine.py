@@ -153,8 +153,9 @@ class RelaxEngine:
         if N == 0:
             return out
         stride = out.stride(0) if N > 1 else slot
-        items = torch.stack([torch.arange(N, dtype=torch.int64) * fb, torch.arange(N, dtype=torch.int64) * stride], dim=1)
-        items = items.contiguous().to(self.device)
+        # built on the device, on the current stream: a host tensor copied over would wait for the stream (tests/test_gpu_stream_contract.py)
+        n_idx = torch.arange(N, dtype=torch.int64, device=self.device)
+        items = torch.stack([n_idx * fb, n_idx * stride], dim=1).contiguous()
         status = torch.empty(N, dtype=torch.int32, device=self.device)
         rc = convert(_ptr(src), src.numel(), _ptr(items), N, layout, H, W, sampling.YUV_MATRICES[matrix],
                      int(full_range), _ptr(out), (N - 1) * stride + slot, _ptr(status), _stream())
@@ -300,11 +301,16 @@ class RelaxEngine:
 
     def head_train_transform(self, features, scale, min_):
         """The training transform: NaN / +-inf -> 0, x * scale + min_ in float64, to fp32 [n, Fpad] (columns padded to a
-        multiple of 32 with zeros) - the matrix the training steps read."""
+        multiple of 32 with zeros) - the matrix the training steps read.  scale / min_: host arrays (uploaded, which waits for the current
+        stream) or float64 device tensors, which are read where they are: the call then only enqueues."""
         features = features.to(self.device, torch.float32).contiguous()
         n, F = features.shape
-        sc = torch.as_tensor(np.ascontiguousarray(scale, dtype=np.float64)).to(self.device)
-        mn = torch.as_tensor(np.ascontiguousarray(min_, dtype=np.float64)).to(self.device)
+
+        def f64(v):
+            if isinstance(v, torch.Tensor) and v.is_cuda:
+                return v.to(self.device, torch.float64).contiguous()
+            return torch.as_tensor(np.ascontiguousarray(v, dtype=np.float64)).to(self.device)
+        sc, mn = f64(scale), f64(min_)
         xp = torch.empty((n, (F + 31) // 32 * 32), dtype=torch.float32, device=self.device)
         rc = self.lib.relax_head_train_transform(self.h, _ptr(features), n, F, _ptr(sc), _ptr(mn), _ptr(xp), _stream())
         self._check(rc, "relax_head_train_transform")
