@@ -434,7 +434,11 @@ int relax_resize_residual_ex(relax_handle* h, const uint8_t* orig, const uint8_t
  *   pool        : fp32 [N,2051]  = get_deep_feature(..,'pool') + process_video_feature(..,'pool')
  *                 (main_fragment_layerstack.py:97-99,141-149; extractor/visualise_resnet_layer.py:62-102) (may be NULL)
  *   taps_nchw   : NULL, or RELAX_RN50_NUM_TAPS device pointers (each NULL or fp32 [N,C,H,W]) receiving the
- *                 hooked activations themselves (visualise_resnet.process_video_frame's dict values). */
+ *                 hooked activations themselves (visualise_resnet.process_video_frame's dict values).
+ * 224 x 224 is the canvas of a freshly loaded model.  After relax_resnet50_set_canvas(h, Hc, Wc) the images are read as uint8 [N,Hc,Wc,3]
+ * and the taps are written as [N,C,h_t,w_t] of that canvas (relax_resnet50_canvas_geometry's tap_hw); layer_stack and pool keep their
+ * widths, the model ends in spatial means.  The canvas is read when the call is made: a captured graph keeps the canvas it was captured
+ * with. */
 int relax_resnet50_features(relax_handle* h, const uint8_t* frags, int N, float* layer_stack, float* pool,
                             float* const* taps_nchw, relax_stream stream);
 
@@ -444,9 +448,34 @@ int relax_resnet50_features(relax_handle* h, const uint8_t* frags, int N, float*
  *   images [0, n_layer_stack)  -> layer_stack fp32 [n_layer_stack, 13120]
  *   images [n_layer_stack, N)  -> pool        fp32 [N - n_layer_stack, 2051]
  * Same values as relax_resnet50_features on the respective images; the taps of the second group are neither reduced nor written
- * as fp32, the pool statistics of the first group are not formed.  Either group may be empty (its pointer may then be NULL). */
+ * as fp32, the pool statistics of the first group are not formed.  Either group may be empty (its pointer may then be NULL).
+ * The images are read at the handle's canvas, as relax_resnet50_features reads them. */
 int relax_resnet50_clip_features(relax_handle* h, const uint8_t* frags, int N, int n_layer_stack, float* layer_stack, float* pool,
                                  relax_stream stream);
+
+/* ResNet-50 on any canvas.  torchvision's ResNet-50 takes any input size (convolutions, one 3x3 / 2 max-pool, an adaptive average pool:
+ * src/extractor/visualise_resnet.py:21), and the layer-stack row (13120 channel means) and the pool row (2051) have the same width on
+ * every canvas.  The kernels take the canvases on which every stage map is even down to layer4 and the stem's output is whole 256-pixel
+ * tiles per image: Hc and Wc multiples of 32 in [64, 1024].  The canvas is a property of the loaded model, set by a host-only call as
+ * relax_load_vit_ex fixes a patch size; relax_resnet50_features and relax_resnet50_clip_features run at it.  (A one-call
+ * relax_resnet50_features_canvas entry with the canvas as an argument, like relax_vit_features_canvas, is left for a change that is free to
+ * extend the stream-contract table of the tests.)
+ *
+ * relax_resnet50_canvas_geometry: host arithmetic, no handle, no GPU.  tap_hw (may be NULL) receives [RELAX_RN50_NUM_TAPS][2] ints, the
+ * {height, width} of every tap's map: {Hc / 2, Wc / 2} for tap 0, then Hc / 4 (3 taps), / 8 (4), / 16 (4), / 32 (3) - at 224 x 224: 112, 56,
+ * 28, 14, 7.  arena_bytes_per_image (may be NULL): what one image of that canvas takes of the forward's workspace (relax_reserve).
+ * RELAX_ERR_INVALID for anything but an accepted canvas; relax_last_error(NULL) then names the offending value, as relax_resnet50_set_canvas'
+ * message does. */
+int relax_resnet50_canvas_geometry(int Hc, int Wc, int* tap_hw, int64_t* arena_bytes_per_image);
+/* Sets the canvas of the loaded ResNet-50 for the calls that follow on this handle: validation and two integers - no launch, no allocation,
+ * no synchronisation; the workspace grows in the next forward as it does for a larger batch (relax_reserve sizes it for the canvas set at
+ * that moment).  A refused canvas (RELAX_ERR_INVALID) leaves the previous one, and relax_last_error names the offending value ("resnet50:
+ * canvas height 230 is not a multiple of 32 in [64, 1024] (canvas 230 x 224)").  relax_load_resnet50 puts 224 x 224 back.  At 224 x 224
+ * a forward launches the kernels it always launched, with the same bits; at any other canvas the stem runs its 16 x 16-tile form
+ * (csrc/conv1_x6.hip) and every bottleneck the first launch form whose kernel takes its maps (csrc/host_logic.h: rn_maps_*). */
+int relax_resnet50_set_canvas(relax_handle* h, int Hc, int Wc);
+/* the canvas the next forward runs at (either pointer may be NULL) */
+int relax_resnet50_get_canvas(relax_handle* h, int* Hc, int* Wc);
 
 /* VGG-16 on N fragments (uint8 [N,224,224,3] BGR; images are processed in chunks of at most 32).  Every tap is read POST-ReLU:
  * torchvision's ReLU(inplace=True) behind each hooked module rectifies the hooked tensor before the reference copies it.

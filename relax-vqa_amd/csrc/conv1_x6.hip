@@ -233,6 +233,216 @@ __global__ __launch_bounds__(512) void conv1_x6(const uint8_t* __restrict__ frag
 #endif
 }
 
+// ---- the same stem on any accepted canvas (Hc, Wc multiples of 32: host_logic.h, rn_canvas_geometry) -------------------------------------------
+// Geometry at run time.  conv1_x6 above walks 256 CONSECUTIVE output pixels and keeps their up to 13 input rows at full width: 18 KB per patch
+// at 224, but 3 output rows of a 288-wide canvas already take 39 KB and half a row of a 1024-wide one 87 KB - two of them do not fit beside
+// the 85 KB of weights.  Here a tile is 16 x 16 output pixels: the output maps are multiples of 16 both ways, so a tile never straddles two
+// images, there are (Hc / 2) (Wc / 2) / 256 per image as before, and its 16 rows of 16 pixels ARE the aligned 16-pixel groups of the fused
+// spatial mean (16 consecutive pixels never cross a row end).  Its patch is 37 rows x 37 pixels on every canvas (19 KB): a wave owns two of the
+// tile's rows, the K loop, the split and the order of the products are conv1_x6's (conv1_mma below restates its loop; the 224 kernel keeps its
+// own copy so that its code stays as it was) - every output value and every group sum has the bits the 224 kernel gives it.
+// A patch row is the 29 dwords that cover pixels 2 x0 - 4 .. 2 x0 + 34 of an image row (x0 a multiple of 16: byte 96 k - 12, dword-aligned
+// and a multiple of 3); dwords left or right of the image and rows above or below it are deposited as zeros, so every tile rewrites its whole
+// window and nothing depends on the tile that used the buffer before.
+constexpr int C1C_T = 16;                                  // tile side in output pixels
+constexpr int C1C_PROWS = 2 * (C1C_T - 1) + 7;             // 37 input rows
+constexpr int C1C_ROW_DW = 29;                             // dwords per patch row: bytes -12 .. 104 of the window (pixels -4 .. 34 + 2 bytes)
+constexpr int C1C_COL0 = 4;                                // patch column of pixel 2 x0 - 3, channel R (even: 8-byte aligned fragment reads)
+constexpr int C1C_PROW = 130;                              // floats per patch row: 3 + 116 deposited, the padded k columns of the last pixel read up to 125
+constexpr int C1C_PATCH_FLOATS = C1C_PROWS * C1C_PROW + 64;
+[[maybe_unused]] constexpr int C1C_LOADS = (C1C_PROWS * C1C_ROW_DW + 511) / 512;   // 3 dwords per thread and tile
+constexpr size_t C1C_LDS = C1_W_BYTES + 2 * sizeof(float) * C1C_PATCH_FLOATS + 3 * 256 * sizeof(float);   // 126.4 KiB
+static_assert(C1C_COL0 + 6 * (C1C_T - 1) + 8 + 16 + 8 <= C1C_PROW && C1C_PROW % 2 == 0 && C1C_PATCH_FLOATS % 2 == 0, "the last lane's fragment stays inside its patch row");
+static_assert(4 * (C1C_ROW_DW - 1) + 3 + 3 < C1C_PROW, "every deposited byte lands inside its patch row");
+
+// dword d of a patch row's window (bytes 4 d .. 4 d + 3 from byte 96 k - 12 of a BGR image row, channel (d + b) % 3) -> patch columns
+// C1C_COL0 + 3 (px - (2 x0 - 3)) + (2 - c) = 4 d + b + 3 - 2 c   (>= 1: column 0 and the columns behind 118 stay the zeros they start as)
+__device__ inline void conv1_canvas_put4(float* prow, int d, unsigned v, bool valid, const float* lut) {
+    const int d3 = d % 3;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int c = (d3 + b) % 3;
+        prow[4 * d + b + 3 - 2 * c] = valid ? lut[c * 256 + ((v >> (8 * b)) & 255u)] : 0.f;
+    }
+}
+
+// The K loop of one tile for one wave: acc (+ accs: H2's small products) = the wave's 32 pixels x 64 channels.  arow: this lane's pixel in the
+// fp32 patch (rows of PROW floats) + 8 * half; wl: the weight planes in LDS.  Statement for statement the loop of conv1_x6.
+template <bool H2, int PROW>
+__device__ __forceinline__ void conv1_mma(const float* arow, const char* wl, int r, int half, c1_floatx16 (&acc)[2], c1_floatx16 (&accs)[2]) {
+    constexpr int CH = H2 ? kH2ChunkBytes : kChunkBytes;
+    constexpr int WROW = C1_CHUNKS * CH + 16;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; accs[0][i] = 0.f; accs[1][i] = 0.f; }
+#pragma unroll
+    for (int ky = 0; ky < 7; ++ky) {
+#pragma unroll
+        for (int jc = 0; jc < 2; ++jc) {
+            const float* a = arow + ky * PROW + 16 * jc;
+            const c1_f32x2 a0 = *reinterpret_cast<const c1_f32x2*>(a), a1 = *reinterpret_cast<const c1_f32x2*>(a + 2),
+                           a2 = *reinterpret_cast<const c1_f32x2*>(a + 4), a3 = *reinterpret_cast<const c1_f32x2*>(a + 6);
+            const int chunk = ky * 2 + jc;
+            if constexpr (H2) {
+                h2_u32x4 ah, al;
+                split2_x8((h2_f32x4){a0.x, a0.y, a1.x, a1.y} * kC1PatchScale, (h2_f32x4){a2.x, a2.y, a3.x, a3.y} * kC1PatchScale, ah, al);
+                const c1_f16x8 Ah = __builtin_bit_cast(c1_f16x8, ah), Al = __builtin_bit_cast(c1_f16x8, al);
+                c1_f16x8 Bh[2], Bl[2];
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) {
+                    const char* wp = wl + (cb * 32 + r) * WROW + chunk * CH + half * 16;
+                    Bh[cb] = *reinterpret_cast<const c1_f16x8*>(wp);
+                    Bl[cb] = *reinterpret_cast<const c1_f16x8*>(wp + 32);
+                }
+                accs[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh[0], accs[0], 0, 0, 0);
+                accs[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh[1], accs[1], 0, 0, 0);
+                accs[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl[0], accs[0], 0, 0, 0);
+                accs[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl[1], accs[1], 0, 0, 0);
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[0], acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[1], acc[1], 0, 0, 0);
+                continue;
+            }
+            sp3_u32x4 ah, am, al;
+            split3_x8((sp3_f32x4){a0.x, a0.y, a1.x, a1.y}, (sp3_f32x4){a2.x, a2.y, a3.x, a3.y}, ah, am, al);
+            const c1_bf16x8 Ah = __builtin_bit_cast(c1_bf16x8, ah), Am = __builtin_bit_cast(c1_bf16x8, am),
+                            Al = __builtin_bit_cast(c1_bf16x8, al);
+            c1_bf16x8 Bh[2], Bm[2], Bl[2];
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                const char* wp = wl + (cb * 32 + r) * WROW + chunk * CH + half * 16;
+                Bh[cb] = *reinterpret_cast<const c1_bf16x8*>(wp);
+                Bm[cb] = *reinterpret_cast<const c1_bf16x8*>(wp + 32);
+                Bl[cb] = *reinterpret_cast<const c1_bf16x8*>(wp + 64);
+            }
+            // the six partial products, smallest first; the two accumulators alternate (no MFMA waits on the one before it)
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh[0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh[1], acc[1], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm[0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm[1], acc[1], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl[0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl[1], acc[1], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh[0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh[1], acc[1], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm[0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm[1], acc[1], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh[0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh[1], acc[1], 0, 0, 0);
+        }
+    }
+}
+
+// Hc, Wc: the canvas; OH = Hc / 2, OW = Wc / 2 multiples of 16.  n_tiles = N * (OH / 16) * (OW / 16), walked image by image, row of tiles by row
+template <bool H2>
+__global__ __launch_bounds__(512) void conv1_x6_canvas(const uint8_t* __restrict__ frags, const char* __restrict__ w_sp3, float* __restrict__ out,
+                                                       float* __restrict__ gap, int n_tiles, const float* __restrict__ w_inv, int Hc, int Wc) {
+#if __HIP_DEVICE_COMPILE__
+    constexpr int CH = H2 ? kH2ChunkBytes : kChunkBytes;
+    constexpr int UPR = C1_CHUNKS * CH / 16;
+    constexpr int WROW = C1_CHUNKS * CH + 16;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* wl = smem;
+    float* patch0 = reinterpret_cast<float*>(smem + C1_W_BYTES);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, half = lane >> 5;
+    const int OH = Hc >> 1, OW = Wc >> 1;
+    const int tiles_x = OW / C1C_T, tiles_img = (OH / C1C_T) * tiles_x;
+    const int row_dw = Wc * 3 / 4;                             // dwords per image row (Wc a multiple of 4)
+
+    for (int u = tid; u < 64 * UPR; u += 512) {
+        const int n = u / UPR, q = u - n * UPR;
+        *reinterpret_cast<sp3_u32x4*>(wl + n * WROW + q * 16) = *reinterpret_cast<const sp3_u32x4*>(w_sp3 + ((int64_t)n * UPR + q) * 16);
+    }
+    for (int i = tid; i < 2 * C1C_PATCH_FLOATS; i += 512) patch0[i] = 0.f;
+    float* lut = patch0 + 2 * C1C_PATCH_FLOATS;
+    for (int i = tid; i < 3 * 256; i += 512) {
+        const int c = i >> 8;
+        const float u = (float)(i & 255) / 255.0f;                                                      // as rn_preprocess
+        lut[i] = c == 2 ? (u - 0.485f) / 0.229f : c == 1 ? (u - 0.456f) / 0.224f : (u - 0.406f) / 0.225f;
+    }
+    __syncthreads();
+
+    unsigned raw[C1C_LOADS];
+    // tile t: image, first output row / column, first input row, first dword of the window in an image row (negative left of the image)
+    auto tile_geom = [&](int t, int& img, int& y0, int& x0, int& iy0, int& dw0) {
+        img = t / tiles_img;
+        const int rem = t - img * tiles_img;
+        const int ty = rem / tiles_x;
+        y0 = ty * C1C_T;
+        x0 = (rem - ty * tiles_x) * C1C_T;
+        iy0 = 2 * y0 - 3;
+        dw0 = (6 * x0 - 12) / 4;
+    };
+    auto request = [&](int t) {
+        int img, y0, x0, iy0, dw0;
+        tile_geom(t, img, y0, x0, iy0, dw0);
+        const unsigned* im = reinterpret_cast<const unsigned*>(frags + (int64_t)img * Hc * Wc * 3);
+#pragma unroll
+        for (int i = 0; i < C1C_LOADS; ++i) {
+            const int e = tid + 512 * i;
+            const int row = e / C1C_ROW_DW, d = e - row * C1C_ROW_DW;
+            const int iy = iy0 + row, dw = dw0 + d;
+            raw[i] = (row < C1C_PROWS && (unsigned)iy < (unsigned)Hc && (unsigned)dw < (unsigned)row_dw) ? im[iy * row_dw + dw] : 0u;
+        }
+    };
+    auto deposit = [&](int t, float* patch) {
+        int img, y0, x0, iy0, dw0;
+        tile_geom(t, img, y0, x0, iy0, dw0);
+#pragma unroll
+        for (int i = 0; i < C1C_LOADS; ++i) {
+            const int e = tid + 512 * i;
+            const int row = e / C1C_ROW_DW, d = e - row * C1C_ROW_DW;
+            if (row < C1C_PROWS)
+                conv1_canvas_put4(patch + row * C1C_PROW, d, raw[i], (unsigned)(iy0 + row) < (unsigned)Hc && (unsigned)(dw0 + d) < (unsigned)row_dw, lut);
+        }
+    };
+
+    int cur = 0;
+    if ((int)blockIdx.x < n_tiles) {
+        request(blockIdx.x);
+        deposit(blockIdx.x, patch0);
+    }
+    __syncthreads();
+    for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        int img, y0, x0, iy0, dw0;
+        tile_geom(t, img, y0, x0, iy0, dw0);
+        const float* patch = patch0 + cur * C1C_PATCH_FLOATS;
+        const int next = t + gridDim.x;
+        if (next < n_tiles) request(next);                 // in flight under the MFMAs below
+
+        // this lane's output pixel: rows 2 wave and 2 wave + 1 of the tile, 16 pixels each (A rows of the wave's 32x64 block)
+        const int yl = 2 * wave + (r >> 4), xl = r & 15;
+        const float* arow = patch + (2 * yl) * C1C_PROW + C1C_COL0 + 6 * xl + 8 * half;
+        c1_floatx16 acc[2], accs[2];
+        conv1_mma<H2, C1C_PROW>(arow, wl, r, half, acc, accs);
+        // acc[cb][i]: channel cb*32 + r of the wave's pixel (i & 3) + 8 * (i >> 2) + 4 * half: row (i >> 3) of its two, column (i & 3) + 8 * ((i >> 2) & 1) + 4 * half
+        if constexpr (H2) {   // the scales are powers of two: exact
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) acc[cb] = (acc[cb] + accs[cb]) * (w_inv[cb * 32 + r] * (1.f / kC1PatchScale));
+        }
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const int64_t pixg = ((int64_t)img * OH + y0 + 2 * wave + g) * OW + x0;   // first pixel of the row: a multiple of 16
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    out[(pixg + (i & 3) + 8 * (i >> 2) + 4 * half) * 64 + cb * 32 + r] = acc[cb][8 * g + i];
+                if (gap) {   // the row's 16 pixels are one aligned group of the image's pixels, summed in conv1_x6's order
+                    float s = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) s += acc[cb][8 * g + i];
+                    s += __shfl_xor(s, 32);
+                    if (half == 0) gap[(pixg >> 4) * 64 + cb * 32 + r] = s;
+                }
+            }
+        }
+        if (next < n_tiles) deposit(next, patch0 + (cur ^ 1) * C1C_PATCH_FLOATS);   // the other buffer: nobody reads it during this tile
+        __syncthreads();                                   // next patch complete, every wave done with this one
+        cur ^= 1;
+    }
+#endif
+}
+
 // fp32 staging rows [64][224]: the packed conv1 rows in this kernel's K layout
 static int conv1_staged(relax_handle* h, const float* w_packed, int kpad, ScopedDev& tmp, const char* what) {
     if (!tmp.alloc(h, 64 * C1_K, what)) return RELAX_ERR_NOMEM;
@@ -264,23 +474,41 @@ int make_conv1_h2_weights(relax_handle* h, const float* w_packed, int kpad, void
     return conv1_converted(h, derive_h2_rows(h, mem, tmp.p, 64, C1_K, w_h2_out, w_inv_out, what));
 }
 
-// frags uint8 [N,224,224,3] BGR -> out fp32 [N,112,112,64] (raw conv1), gap_groups [N*784][64] (16-pixel sums) or null.
-// w_inv != null: `w` holds fp16 planes (make_conv1_h2_weights) and the kernel runs its f16x2 form
-int launch_conv1_x6(relax_handle* h, const uint8_t* frags, const void* w_sp3, float* out, float* gap_groups, int N, hipStream_t s, const float* w_inv) {
+// frags uint8 [N,Hc,Wc,3] BGR -> out fp32 [N,Hc/2,Wc/2,64] (raw conv1), gap_groups [N*(Hc/2)(Wc/2)/16][64] (16-pixel sums) or null.
+// w_inv != null: `w` holds fp16 planes (make_conv1_h2_weights) and the kernel runs its f16x2 form.  224 x 224 runs conv1_x6, compiled for that
+// size; every other accepted canvas conv1_x6_canvas
+int launch_conv1_x6(relax_handle* h, const uint8_t* frags, const void* w_sp3, float* out, float* gap_groups, int N, int Hc, int Wc, hipStream_t s,
+                    const float* w_inv) {
     RELAX_REQUIRE(h, frags && w_sp3 && out && N > 0, "conv1_x6: bad arguments");
-    static std::atomic<bool> lds_allowed[kMaxDevices];
-    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&conv1_x6<false>), reinterpret_cast<const void*>(&conv1_x6<true>)}, C1_LDS, lds_allowed));
-    const int n_tiles = N * (C1_OPIX / C1_TILE);
-    const double flops = 2.0 * N * (double)C1_OPIX * 64.0 * 147.0;
-    const double bytes = (double)N * (C1_HW * C1_HW * 3 + (double)C1_OPIX * 64 * 4);
+    const bool fixed = Hc == C1_HW && Wc == C1_HW;
+    RELAX_REQUIRE(h, fixed || (Hc >= 2 * C1C_T && Wc >= 2 * C1C_T && Hc % (2 * C1C_T) == 0 && Wc % (2 * C1C_T) == 0),
+                  "conv1_x6: canvas %d x %d: the output map must be whole 16 x 16 tiles", Hc, Wc);
+    RELAX_REQUIRE(h, (int64_t)N * (Hc / 2) * (Wc / 2) / C1_TILE < 0x7fffffff, "conv1_x6: %d images of %d x %d are too many tiles", N, Hc, Wc);
+    static std::atomic<bool> lds_allowed[kMaxDevices], lds_allowed_canvas[kMaxDevices];
+    if (fixed)
+        RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&conv1_x6<false>), reinterpret_cast<const void*>(&conv1_x6<true>)}, C1_LDS, lds_allowed));
+    else
+        RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&conv1_x6_canvas<false>), reinterpret_cast<const void*>(&conv1_x6_canvas<true>)}, C1C_LDS,
+                                    lds_allowed_canvas));
+    static_assert(C1_OPIX % C1_TILE == 0 && (C1_HW / 2) * (C1_HW / 2) == C1_OPIX, "the 224 kernel walks whole tiles");
+    const int64_t opix = (int64_t)(Hc / 2) * (Wc / 2);
+    const int n_tiles = (int)(N * (opix / C1_TILE));
+    const double flops = 2.0 * N * (double)opix * 64.0 * 147.0;
+    const double bytes = (double)N * ((double)Hc * Wc * 3 + (double)opix * 64 * 4);
     int span;
     RELAX_TRY(prof_begin(h, s, w_inv ? 5 : 2, flops, &span, bytes));
-    if (w_inv)
-        hipLaunchKernelGGL(conv1_x6<true>, dim3(n_tiles < 256 ? n_tiles : 256), dim3(512), C1_LDS, s, frags, static_cast<const char*>(w_sp3), out,
-                           gap_groups, n_tiles, w_inv);
+    const dim3 grid(n_tiles < 256 ? n_tiles : 256);
+    if (fixed && w_inv)
+        hipLaunchKernelGGL(conv1_x6<true>, grid, dim3(512), C1_LDS, s, frags, static_cast<const char*>(w_sp3), out, gap_groups, n_tiles, w_inv);
+    else if (fixed)
+        hipLaunchKernelGGL(conv1_x6<false>, grid, dim3(512), C1_LDS, s, frags, static_cast<const char*>(w_sp3), out, gap_groups, n_tiles,
+                           static_cast<const float*>(nullptr));
+    else if (w_inv)
+        hipLaunchKernelGGL(conv1_x6_canvas<true>, grid, dim3(512), C1C_LDS, s, frags, static_cast<const char*>(w_sp3), out, gap_groups, n_tiles, w_inv,
+                           Hc, Wc);
     else
-        hipLaunchKernelGGL(conv1_x6<false>, dim3(n_tiles < 256 ? n_tiles : 256), dim3(512), C1_LDS, s, frags, static_cast<const char*>(w_sp3), out,
-                           gap_groups, n_tiles, static_cast<const float*>(nullptr));
+        hipLaunchKernelGGL(conv1_x6_canvas<false>, grid, dim3(512), C1C_LDS, s, frags, static_cast<const char*>(w_sp3), out, gap_groups, n_tiles,
+                           static_cast<const float*>(nullptr), Hc, Wc);
     if (hipGetLastError() != hipSuccess) { prof_abort(h, span); set_error(h, "conv1_x6: launch failed"); return RELAX_ERR_HIP; }
     RELAX_TRY(prof_end(h, s, span));
     return RELAX_OK;

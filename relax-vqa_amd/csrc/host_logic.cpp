@@ -232,19 +232,67 @@ const RnBlockGeom* rn_geometry() {
     return t.g;
 }
 
+bool rn_canvas_geometry(int Hc, int Wc, RnCanvasGeometry* g, std::string& err) {
+    for (int axis = 0; axis < 2; ++axis) {
+        const int v = axis == 0 ? Hc : Wc;
+        if (v >= kRnCanvasMin && v <= kRnCanvasMax && v % kRnCanvasStep == 0) continue;
+        err = std::string("resnet50: canvas ") + (axis == 0 ? "height " : "width ") + std::to_string(v) + " is not a multiple of " +
+              std::to_string(kRnCanvasStep) + " in [" + std::to_string(kRnCanvasMin) + ", " + std::to_string(kRnCanvasMax) + "] (canvas " +
+              std::to_string(Hc) + " x " + std::to_string(Wc) + ")";
+        return false;
+    }
+    RnCanvasGeometry r{};
+    const RnBlockGeom* blocks = rn_geometry();
+    // conv1 7x7 / 2 pad 3, then the 3x3 / 2 pad 1 max-pool, then a 3x3 / stride pad 1 convolution per block: floor((n + 2 p - k) / s) + 1
+    int H = (Hc + 2 * 3 - 7) / 2 + 1, W = (Wc + 2 * 3 - 7) / 2 + 1;
+    r.tap_hw[0][0] = H; r.tap_hw[0][1] = W;
+    static const int tap_c[kRnTaps] = {64, 256, 256, 256, 512, 512, 512, 512, 1024, 1024, 1024, 1024, 2048, 2048, 2048};
+    H = (H + 2 - 3) / 2 + 1; W = (W + 2 - 3) / 2 + 1;
+    const int64_t hw1 = (int64_t)H * W;      // layer1's maps
+    r.block_max = (hw1 * (64 / 4) / 256 + 63) / 64 * 64;
+    for (int b = 0; b < kRnBlocks; ++b) {
+        H = (H + 2 - 3) / blocks[b].stride + 1; W = (W + 2 - 3) / blocks[b].stride + 1;
+        if (blocks[b].tap >= 0) { r.tap_hw[blocks[b].tap][0] = H; r.tap_hw[blocks[b].tap][1] = W; }
+    }
+    r.x0 = (int64_t)Hc * Wc * 4;
+    r.big = (int64_t)r.tap_hw[0][0] * r.tap_hw[0][1] * 64;
+    r.t1 = hw1 * 128;
+    r.t2 = hw1 * 64;
+    r.gap_ws = 16 * 2048;
+    for (int t = 0; t < kRnTaps; ++t) {
+        const int64_t hw = (int64_t)r.tap_hw[t][0] * r.tap_hw[t][1];
+        if (hw % 4 != 0) continue;                                  // (no fused mean on such a map: rn_maps_fused_mean)
+        const int64_t groups = hw / (hw % 16 == 0 ? 16 : 4) * tap_c[t];
+        if (groups > r.gap_ws) r.gap_ws = groups;
+    }
+    r.floats_f32 = r.x0 + 3 * r.big + r.t1 + r.t2 + r.gap_ws + kRnAvgFloats;
+    // bf16x6 path: block inputs / outputs exist twice (fp32 for the residual add and the taps, split planes = 1.5 floats per
+    // value for the next convolutions), the intermediates of a block only as split planes
+    r.floats_x6 = r.x0 + 3 * r.big + 2 * (r.big * 3 / 2) + (r.t1 + r.t2) * 3 / 2 + r.gap_ws + kRnAvgFloats + 3 * kRnImgSlots + r.block_max;
+    *g = r;
+    return true;
+}
+
 bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* plan, std::string& err) {
+    return rn_plan(o, rq, RnCanvas{}, max_slots, plan, err);
+}
+
+bool rn_plan(const RnOptions& o, const RnRequest& rq, const RnCanvas& cv, int max_slots, RnPlan* plan, std::string& err) {
     const RnBlockGeom* g = rn_geometry();
+    RnCanvasGeometry geo;
+    if (!rn_canvas_geometry(cv.Hc, cv.Wc, &geo, err)) return false;
+    const int H1 = geo.tap_hw[1][0], W1 = geo.tap_hw[1][1];   // layer1's maps: the max-pool's output
     RnPlan p{};
     // f16x2 for layer3 / layer4 ("gemm_precision" 3 with "rn_h2"): per-image tables {maximum, scale, 1 / scale}, one slot per tensor
     const bool use_h2 = o.precision == 3 && o.rn_h2;
     // "rn_h2_early": the 3x3 convolutions of layer1 / layer2 on f16x2 as well (gemm_x6.hip, H2 form).  Their input (conv1's output)
     // is written as fp16 planes with the image's Hoelder scale  l1max(conv1) max|block input| + max|bias|; the block input's maximum
     // is measured by its producer: the max-pool (block maxima, reduced per image) or the previous block's conv3 epilogue.
-    bool use_early = use_h2 && o.rn_h2_early;
+    bool use_early = use_h2 && o.rn_h2_early && rn_maps_pool_maxima(H1, W1, g[0].cin);
     for (int b = 0; b < kRnFirstH2Block && use_early; ++b) use_early = rn_early_h2(g[b].width, g[b].width);
     // "rn_fuse": layer1[0] back to back too, with the downsample convolution folded into its conv3 - the block input then travels as fp32 rows
     // (4 B per value instead of 6: conv1 splits them in its K loop, the fused launch reads each pixel's row as conv3's second source)
-    const bool fuse0 = use_early && o.rn_fuse && o.fp32_rows && rn_can_b2b_x2(g[0]);
+    const bool fuse0 = use_early && o.rn_fuse && o.fp32_rows && rn_can_b2b_x2(g[0]) && rn_maps_b2b(H1, W1);
     // layer2[0] (stride 2, 256 -> 512 downsample: too many channels for a second source in registers): the downsample convolution as a
     // launch of its own (f16x2, on the compact fp16 planes of the input's stride-2 sample) whose fp32 output is the residual of the
     // block's back-to-back launch (3x3 with the stride -> conv3) - instead of the 3x3 + the two-source bf16x6 conv3
@@ -264,11 +312,11 @@ bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* pla
     // column tile, so every value is split exactly once, as the producer's epilogue would have) splits them inside its K loop
     // and its conv3 adds them as an fp32 residual - the same values bit for bit.  A layer's last block writes planes: the next
     // layer's first conv3 reads them as its second activation source.
-    int in_form = fuse0 ? kRnF32 : kRnSp3, in_sample = kRnNoSample, s_x = -1, s_xin = p.s_stem, s_dr = -1, H = 56;
+    int in_form = fuse0 ? kRnF32 : kRnSp3, in_sample = kRnNoSample, s_x = -1, s_xin = p.s_stem, s_dr = -1, H = H1, W = W1;
     for (int b = 0; b < kRnBlocks; ++b) {
         const RnBlockGeom& k = g[b];
         RnBlockPlan& q = p.blk[b];
-        const int Ho = H / k.stride, HWo = Ho * Ho;
+        const int Ho = (H + 2 - 3) / k.stride + 1, Wo = (W + 2 - 3) / k.stride + 1, HWo = Ho * Wo;   // (the 3x3, pad 1)
         const bool is_last = b + 1 == kRnBlocks, tapped = k.tap >= 0;
         const bool pool_needs32 = is_last && rq.want_pool && !rn_pool_from_stack(rq);
         q.want_mean = tapped && rq.n_ls > 0;
@@ -283,22 +331,23 @@ bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* pla
             // weights).  fp32 copies as above; the residual of a block without a downsample branch is read from the block input's PLANES.
             q.form = kRnFormH2;
             q.s_t1 = next_slot++; q.s_t2 = next_slot++; q.s_out = next_slot++;
-            q.fuse_mean = q.want_mean && HWo % 4 == 0 && HWo % 16 != 0;   // 14x14 maps: 4-row groups (gemm_h3's fused mean)
-            q.no_split = tapped && HWo % 4 == 0 && HWo % 16 != 0;
+            q.fuse_mean = q.want_mean && rn_maps_fused_mean(Ho, Wo) && HWo % 16 != 0;   // 14x14 maps: 4-row groups (gemm_h3's fused mean)
+            q.no_split = tapped && rn_maps_fused_mean(Ho, Wo) && HWo % 16 != 0;
             q.out_form = is_last ? kRnNone : kRnH2;
         } else {
             const bool cur_f32 = in_form == kRnF32;
             // "rn_fuse": conv2 and conv3 back to back in one launch - the 3x3's tile never leaves the CU; conv3 on f16x2 with one scale per pixel row
             const bool fuse_x2 = b == 0 && fuse0;
-            const bool fuse_dr = b > 0 && cur_f32 && down_launch(k) && HWo >= 256 && in_sample == kRnSampleH2;
-            const bool fuse = fuse_x2 || fuse_dr || (use_early && o.rn_fuse && !k.has_down && rn_can_b2b(k) && cur_f32 && k.stride == 1 && H * H >= 256);
+            const bool fuse_dr = b > 0 && cur_f32 && down_launch(k) && rn_maps_b2b(Ho, Wo) && in_sample == kRnSampleH2;
+            const bool fuse = fuse_x2 || fuse_dr || (use_early && o.rn_fuse && !k.has_down && rn_can_b2b(k) && cur_f32 && k.stride == 1 && rn_maps_b2b(Ho, Wo));
             // a layer's last block in front of a downsample block: its output travelled as three bf16 planes (6 B per value: the next block's conv1 and
             // the second source of its conv3 read planes).  Back to back it leaves as fp32 rows like the others (conv1 splits in its K loop) PLUS the
             // planes of the stride-2 sample only - all the downsample branch reads -, compacted: 4 + 1.5 bytes per value instead of 6, and conv1 reads 4
             // (fp16 planes with a per-image scale where the next block runs its downsample convolution as a launch of its own)
             const bool next_down = !is_last && g[b + 1].has_down;
-            const bool next_dr = next_down && fuse && down_launch(g[b + 1]);
-            const bool compact = fuse && next_down && !next_dr && rn_early(g[b + 1]) && o.fp32_rows && k.cout <= 512 && Ho % 2 == 0 && g[b + 1].stride == 2;
+            // (the sample is of even maps, and the next block runs back to back behind its downsample launch only on maps that form takes)
+            const bool next_dr = next_down && fuse && down_launch(g[b + 1]) && rn_maps_sample2(Ho, Wo) && rn_maps_b2b(Ho / 2, Wo / 2);
+            const bool compact = fuse && next_down && !next_dr && rn_early(g[b + 1]) && o.fp32_rows && k.cout <= 512 && rn_maps_sample2(Ho, Wo) && g[b + 1].stride == 2;
             out_f32 = o.fp32_rows && k.cout <= 512 && !is_last && (!next_down || compact || next_dr);
             q.handover = use_h2 && b + 1 == kRnFirstH2Block;
             q.pre_handover = use_h2 && b + 2 == kRnFirstH2Block;
@@ -311,8 +360,8 @@ bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* pla
             q.c1_h2 = use_early && cur_f32 && o.rn_c1_h2 && rn_can_c1_h2(k);
             if (q.c1_h2) q.s_c1 = next_slot++;
             if (next_dr) q.s_dr_out = next_slot++;
-            q.fuse_mean = q.want_mean && HWo % 4 == 0;
-            q.no_split = !fuse && tapped && HWo % 4 == 0;
+            q.fuse_mean = q.want_mean && rn_maps_fused_mean(Ho, Wo);
+            q.no_split = !fuse && tapped && rn_maps_fused_mean(Ho, Wo);
             q.out_form = q.handover ? kRnH2 : out_f32 ? kRnF32 : kRnSp3;
             q.out_sample = compact ? kRnSampleSp3 : next_dr ? kRnSampleH2 : kRnNoSample;
         }
@@ -324,7 +373,7 @@ bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* pla
         in_form = q.out_form; in_sample = q.out_sample;
         s_x = q.out_form == kRnH2 ? q.s_out : -1;
         s_xin = q.s_out; s_dr = q.s_dr_out;
-        H = Ho;
+        H = Ho; W = Wo;
     }
     p.n_slots = next_slot;
     if (next_slot > max_slots) {
@@ -1002,6 +1051,37 @@ int relax_host_rn_plan(const int* opts, const int* req, int max_slots, int* out,
     return 0;
 }
 // the 16 bottlenecks: block, layer, index, cin, width, cout, stride, has_down, tap (16 * 9 ints)
+// the same on an [Hc, Wc] canvas; a refused canvas: -1 and rn_canvas_geometry's message
+int relax_host_rn_plan_canvas(const int* opts, const int* req, int Hc, int Wc, int max_slots, int* out, char* err, int err_len) {
+    using namespace relax::host;
+    const RnOptions o{opts[0], opts[1], opts[2], opts[3], opts[4], opts[5]};
+    const RnRequest rq{req[0], req[1], req[2], req[3], (unsigned)req[4]};
+    RnCanvas cv;
+    cv.Hc = Hc; cv.Wc = Wc;
+    RnPlan p;
+    std::string e;
+    if (!rn_plan(o, rq, cv, max_slots, &p, e)) {
+        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return -1;
+    }
+    std::memcpy(out, &p, sizeof(p));
+    return 0;
+}
+// canvas geometry: tap_hw [15][2]; sizes = x0, big, t1, t2, gap_ws, block_max, floats_f32, floats_x6 (8 values).  0, or -1 and the message
+int relax_host_rn_canvas_geometry(int Hc, int Wc, int* tap_hw, int64_t* sizes, char* err, int err_len) {
+    relax::host::RnCanvasGeometry g;
+    std::string e;
+    if (!relax::host::rn_canvas_geometry(Hc, Wc, &g, e)) {
+        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return -1;
+    }
+    if (tap_hw) std::memcpy(tap_hw, g.tap_hw, sizeof(g.tap_hw));
+    if (sizes) {
+        const int64_t v[8] = {g.x0, g.big, g.t1, g.t2, g.gap_ws, g.block_max, g.floats_f32, g.floats_x6};
+        std::memcpy(sizes, v, sizeof(v));
+    }
+    return 0;
+}
 void relax_host_rn_geometry(int* out) { std::memcpy(out, relax::host::rn_geometry(), sizeof(relax::host::RnBlockGeom) * relax::host::kRnBlocks); }
 
 // ViT geometry: out = patch, side, npatch, ntok, patch_k; 0, or -1 and a message.  Arena floats per image: out[0] fp32 layout, out[1] bf16x6 layout.

@@ -278,6 +278,39 @@ struct RnPlan {
 // The schedule of one forward: host arithmetic only.  false and a message if it needs more than max_slots per-image tables.
 bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* plan, std::string& err);
 
+// ---- ResNet-50 on any accepted canvas -------------------------------------------------------------------------------------------------------
+// The model takes any input size (convolutions, one 3x3/2 max-pool, an adaptive average pool); the kernels take the canvases on which every
+// stage map is even down to layer4 and the stem's output is whole 256-pixel tiles per image: Hc and Wc multiples of 32 in [64, 1024].
+constexpr int kRnTaps = 15;
+constexpr int kRnCanvasDefault = 224, kRnCanvasStep = 32, kRnCanvasMin = 64, kRnCanvasMax = 1024;
+struct RnCanvas { int Hc = kRnCanvasDefault, Wc = kRnCanvasDefault; };
+// Map sizes and the per-image floats of the forward's arena (resnet50.hip carves it in this order; every count is a multiple of 4).
+struct RnCanvasGeometry {
+    int tap_hw[kRnTaps][2];       // {h, w} of every tap: the stem's raw output, then the tapped blocks (224 x 224: 112, 56 x 3, 28 x 4, 14 x 4, 7 x 3)
+    int64_t x0;                   // the preprocessed input, NHWC4 (exact-fp32 path)
+    int64_t big;                  // the stem's raw output == a layer1 block output: the largest block input / output
+    int64_t t1, t2;               // the largest conv1-of-block output (layer2[0] before its stride), the largest conv2 output
+    int64_t gap_ws;               // spatial-mean workspace: the two-stage kernel's partial sums (16 x 2048) or the largest table of fused group sums
+    int64_t block_max;            // block maxima of the max-pool (one word per 256-thread block of an image), rounded up to 64
+    int64_t floats_f32, floats_x6;   // the exact-fp32 carving and the bf16x6 / f16x2 one; the arena holds the larger
+};
+// false and a message that names the offending value (height before width) for anything but an accepted canvas
+bool rn_canvas_geometry(int Hc, int Wc, RnCanvasGeometry* g, std::string& err);
+constexpr int kRnAvgFloats = 2048, kRnImgSlots = 64;   // per image: the avgpool vector; the per-image tables {maximum, scale, 1 / scale} of the f16x2 launches
+
+// What a launch form asks of the MAPS of the block it runs on, restated from the kernels' own preconditions: a form is planned for a block only
+// where they hold, else the block falls to the next form that does, down to plain bf16x6 (which takes any map).
+// back to back (gemm_x6.hip, launch_conv_x6: "images of >= 256 pixels (a multiple of 16)")
+inline bool rn_maps_b2b(int Ho, int Wo) { return Ho * Wo >= 256 && (Ho * Wo) % 16 == 0; }
+// the spatial mean fused into conv3's epilogue (gemm_x6.hip / gemm_h2.hip: "the fused spatial mean needs Ho*Wo % 4 == 0")
+inline bool rn_maps_fused_mean(int Ho, int Wo) { return (Ho * Wo) % 4 == 0; }
+// the planes of the output's stride-2 sample (gemm_x6.hip: "the stride-2 plane output goes with ... even maps")
+inline bool rn_maps_sample2(int Ho, int Wo) { return Ho % 2 == 0 && Wo % 2 == 0; }
+// per-image maxima of the max-pool's Hp x Wp x C output (layers.hip: "per-image maxima need whole blocks per image": 256 threads x 4 channels)
+inline bool rn_maps_pool_maxima(int Hp, int Wp, int C) { return ((int64_t)Hp * Wp * (C / 4)) % 256 == 0; }
+// The schedule on an accepted canvas (the caller has run rn_canvas_geometry).  At 224 x 224 it is rn_plan's above, int for int.
+bool rn_plan(const RnOptions& o, const RnRequest& rq, const RnCanvas& cv, int max_slots, RnPlan* plan, std::string& err);
+
 // ---- DINO ViT geometry (224x224 input, 64-d heads) and the streaming attention kernel's plan (vit.hip, attention_stream.hip) ----------
 struct VitGeometry { int patch, side, npatch, ntok, patch_k; };   // patch 16: 14 per side, 196 patches, 197 tokens, K = 768; patch 8: 28, 784, 785, 192
 // the geometry of patch size 8 or 16; anything else is refused (false and a message)

@@ -208,6 +208,7 @@ struct ResNet50W {
     float* bn1_shift = nullptr;  // [64]
     std::vector<Bottleneck> blocks;  // 16
     DeviceOwner mem;
+    int canvas_h = 224, canvas_w = 224;   // the canvas the forward reads its images at (relax_resnet50_set_canvas; a load puts 224 x 224 back)
 };
 
 struct LinearW {
@@ -422,8 +423,8 @@ int launch_b2b_permute_k(relax_handle* h, const float* w, float* wp, int rows, i
 int launch_to_sp3(relax_handle* h, const float* x, int64_t ld, void* y, int64_t rows, int K, hipStream_t s);
 // conv1_x6.hip: ResNet-50 conv1 on the bf16x6 arithmetic, straight from the uint8 fragments
 int make_conv1_x6_weights(relax_handle* h, const float* w_packed, int kpad, void** w_sp3_out, DeviceOwner& mem);
-int launch_conv1_x6(relax_handle* h, const uint8_t* frags, const void* w_sp3, float* out, float* gap_groups, int N, hipStream_t s,
-                    const float* w_inv = nullptr);   // w_inv: `w_sp3` holds fp16 planes and the f16x2 form runs
+int launch_conv1_x6(relax_handle* h, const uint8_t* frags, const void* w_sp3, float* out, float* gap_groups, int N, int Hc, int Wc, hipStream_t s,
+                    const float* w_inv = nullptr);   // frags [N,Hc,Wc,3]; w_inv: `w_sp3` holds fp16 planes and the f16x2 form runs
 int make_conv1_h2_weights(relax_handle* h, const float* w_packed, int kpad, void** w_h2_out, float** w_inv_out, DeviceOwner& mem);
 inline int launch_gemm_x6(relax_handle* h, const void* A_sp3, const void* W_sp3, const float* bias, const float* residual,
                           float* out, void* out_sp3, int M, int N, int K, int act, hipStream_t s) {
@@ -501,7 +502,7 @@ void free_head(relax_handle* h);
 void free_head_train(relax_handle* h);
 void free_vgg(relax_handle* h);
 size_t vgg_arena_bytes(int n_images);
-size_t resnet_arena_bytes(int n_images);
+size_t resnet_arena_bytes(int n_images, int Hc = 224, int Wc = 224);   // 0 for a canvas the forward does not take
 size_t vit_arena_bytes(const VitW& v, int n_images);                          // at the loaded geometry (224 x 224: relax_reserve)
 size_t vit_arena_bytes(const VitW& v, int n_images, int ntok, int npatch);    // at a call's geometry
 

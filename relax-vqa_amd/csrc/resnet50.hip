@@ -10,6 +10,7 @@
 // eval-mode BatchNorm folded in (scale into the weights, shift as bias); bn1 stays separate because
 // the conv1 tap is taken before it.
 #include <cmath>
+#include <cstring>
 
 #include "relax_internal.h"
 #include "host_logic.h"
@@ -21,10 +22,9 @@ int launch_gap_ws(relax_handle* h, const float* x, float* out, int Nimg, int HW,
 
 static const int kTapChannels[RELAX_RN50_NUM_TAPS] = {64, 256, 256, 256, 512, 512, 512, 512,
                                                       1024, 1024, 1024, 1024, 2048, 2048, 2048};
-static const int kTapHW[RELAX_RN50_NUM_TAPS] = {112, 56, 56, 56, 28, 28, 28, 28, 14, 14, 14, 14, 7, 7, 7};
 
 // ---- kernels ---------------------------------------------------------------------------------------
-// uint8 BGR [N,224,224,3] -> fp32 NHWC4 RGB0, ((x/255) - mean) / std   (ToTensor + Normalize)
+// uint8 BGR [N,Hc,Wc,3] -> fp32 NHWC4 RGB0, ((x/255) - mean) / std   (ToTensor + Normalize)
 __global__ __launch_bounds__(256) void rn_preprocess(const uint8_t* __restrict__ frag, float* __restrict__ x,
                                                      int64_t npix) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -130,29 +130,26 @@ void free_resnet(relax_handle* h) {
     h->rn = ResNet50W();
 }
 
-// floats per image of the activation arena (see relax_resnet50_features)
-static constexpr size_t kX0 = 224 * 224 * 4;        // preprocessed input, NHWC4
-static constexpr size_t kBig = 112 * 112 * 64;      // == 56*56*256: largest block in/out and conv1 raw
-static constexpr size_t kT1 = 56 * 56 * 128;        // largest conv1-of-block output (layer2.0 before the stride)
-static constexpr size_t kT2 = 56 * 56 * 64;         // largest conv2 output
-static constexpr size_t kGapWs = 196 * 256;         // GAP partial sums (16 x 2048 two-stage kernel; 3136/16 x 256 fused group sums)
-static constexpr size_t kAvg = 2048;
-static constexpr size_t kImgSlots = 64;             // per-image tables of the f16x2 blocks: slot t = {maximum, scale, 1 / scale} x images
-static constexpr size_t kRnFloatsPerImage = kX0 + 3 * kBig + kT1 + kT2 + kGapWs + kAvg;
-// bf16x6 path: block inputs / outputs exist twice (fp32 for the residual add and the taps, split planes = 1.5 floats per
-// value for the next convolutions), the intermediates of a block only as split planes
-static constexpr size_t kBlockMax = 256;            // block maxima of the max-pool (196 blocks of 16 output pixels per image)
-static constexpr size_t kRnFloatsPerImageX6 = kX0 + 3 * kBig + 2 * (kBig * 3 / 2) + (kT1 + kT2) * 3 / 2 + kGapWs + kAvg + 3 * kImgSlots + kBlockMax;
+// floats per image of the activation arena (see relax_resnet50_features): host_logic.cpp's rn_canvas_geometry, by the canvas - at 224 x 224
+// x0 = 224*224*4, big = 112*112*64 (== 56*56*256), t1 = 56*56*128, t2 = 56*56*64, gap_ws = 196*256, block_max = 256
+static constexpr size_t kAvg = host::kRnAvgFloats;
+static constexpr size_t kImgSlots = host::kRnImgSlots;   // per-image tables of the f16x2 blocks: slot t = {maximum, scale, 1 / scale} x images
 
-size_t resnet_arena_bytes(int n) {
-    return sizeof(float) * (kRnFloatsPerImage > kRnFloatsPerImageX6 ? kRnFloatsPerImage : kRnFloatsPerImageX6) * (size_t)n;
+size_t resnet_arena_bytes(int n, int Hc, int Wc) {
+    host::RnCanvasGeometry g;
+    std::string err;
+    if (!host::rn_canvas_geometry(Hc, Wc, &g, err)) return 0;
+    return sizeof(float) * (size_t)(g.floats_f32 > g.floats_x6 ? g.floats_f32 : g.floats_x6) * (size_t)n;
 }
 
-// geometry, bf16x6 weights and bias of one folded convolution over N square maps of H x H
-static ConvDescX6 conv_x6(const ConvW& c, const void* in_sp3, int Nimg, int H, int act = 1) {
+// output side of a convolution along one axis
+static int conv_out(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }
+
+// geometry, bf16x6 weights and bias of one folded convolution over N maps of H x W
+static ConvDescX6 conv_x6(const ConvW& c, const void* in_sp3, int Nimg, int H, int W, int act = 1) {
     ConvDescX6 d{};
-    d.in = in_sp3; d.Nimg = Nimg; d.H = H; d.W = H; d.Cin = c.Cin;
-    d.Ho = d.Wo = (H + 2 * c.pad - c.KH) / c.stride + 1;
+    d.in = in_sp3; d.Nimg = Nimg; d.H = H; d.W = W; d.Cin = c.Cin;
+    d.Ho = conv_out(H, c.KH, c.stride, c.pad); d.Wo = conv_out(W, c.KW, c.stride, c.pad);
     d.KH = c.KH; d.KW = c.KW; d.stride = c.stride; d.pad = c.pad;
     d.w = c.w_sp3; d.Cout = c.Cout; d.bias = c.bias; d.act = act;
     return d;
@@ -174,8 +171,8 @@ static int run_conv(relax_handle* h, const ConvW& c, const float* in, int Nimg, 
                     float* out, int act, hipStream_t s, double flops = 0) {
     ConvDesc d{};
     d.in = in; d.Nimg = Nimg; d.H = H; d.W = W; d.Cin = c.Cin;
-    d.Ho = (H + 2 * c.pad - c.KH) / c.stride + 1;
-    d.Wo = (W + 2 * c.pad - c.KW) / c.stride + 1;
+    d.Ho = conv_out(H, c.KH, c.stride, c.pad);
+    d.Wo = conv_out(W, c.KW, c.stride, c.pad);
     d.KH = c.KH; d.KW = c.KW; d.stride = c.stride; d.pad = c.pad;
     d.w = c.w; d.Cout = c.Cout; d.Kpad = c.Kpad;
     d.bias = c.bias; d.residual = residual; d.out = out; d.act = act; d.flops = flops;
@@ -313,11 +310,52 @@ int relax_load_resnet50(relax_handle* h, const float* const* tensors, const char
     return rc;
 }
 
+int relax_resnet50_canvas_geometry(int Hc, int Wc, int* tap_hw, int64_t* arena_bytes_per_image) {
+    host::RnCanvasGeometry g;
+    std::string err;
+    if (!host::rn_canvas_geometry(Hc, Wc, &g, err)) {
+        set_error(nullptr, "%s", err.c_str());   // (no handle: relax_last_error(NULL), this thread's)
+        return RELAX_ERR_INVALID;
+    }
+    if (tap_hw) std::memcpy(tap_hw, g.tap_hw, sizeof(g.tap_hw));
+    if (arena_bytes_per_image) *arena_bytes_per_image = (int64_t)resnet_arena_bytes(1, Hc, Wc);
+    return RELAX_OK;
+}
+
+// validation and two integers: no launch, no allocation, no synchronisation (the arena grows in the forward)
+int relax_resnet50_set_canvas(relax_handle* h, int Hc, int Wc) {
+    if (!h) return RELAX_ERR_INVALID;
+    host::RnCanvasGeometry g;
+    std::string err;
+    RELAX_REQUIRE(h, host::rn_canvas_geometry(Hc, Wc, &g, err), "%s", err.c_str());
+    h->rn.canvas_h = Hc;
+    h->rn.canvas_w = Wc;
+    return RELAX_OK;
+}
+
+int relax_resnet50_get_canvas(relax_handle* h, int* Hc, int* Wc) {
+    if (!h) return RELAX_ERR_INVALID;
+    if (Hc) *Hc = h->rn.canvas_h;
+    if (Wc) *Wc = h->rn.canvas_w;
+    return RELAX_OK;
+}
+
 // One forward over N images.  Images [0, n_ls) get layer-stack rows (n_ls = 0: none), images [pool_from, N) get pool rows
 // (pool == nullptr: none); taps_nchw (all N images) as in relax_resnet50_features.
 static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls, int pool_from, float* layer_stack, float* pool,
                           float* const* taps_nchw, hipStream_t s) {
-    RELAX_TRY(ensure_buf(h, h->arena, resnet_arena_bytes(N)));
+    // the canvas is read here, once: a captured graph keeps the canvas it was captured with
+    const int Hc = h->rn.canvas_h, Wc = h->rn.canvas_w;
+    host::RnCanvasGeometry geo;
+    {
+        std::string geo_err;
+        RELAX_REQUIRE(h, host::rn_canvas_geometry(Hc, Wc, &geo, geo_err), "%s", geo_err.c_str());
+    }
+    const size_t kX0 = (size_t)geo.x0, kBig = (size_t)geo.big, kT1 = (size_t)geo.t1, kT2 = (size_t)geo.t2, kGapWs = (size_t)geo.gap_ws;
+    const int H0 = geo.tap_hw[0][0], W0 = geo.tap_hw[0][1];       // the stem's output (112 x 112)
+    const int H1 = geo.tap_hw[1][0], W1 = geo.tap_hw[1][1];       // the max-pool's (56 x 56)
+    const int HWlast = geo.tap_hw[RELAX_RN50_NUM_TAPS - 1][0] * geo.tap_hw[RELAX_RN50_NUM_TAPS - 1][1];   // layer4's map (49 positions)
+    RELAX_TRY(ensure_buf(h, h->arena, resnet_arena_bytes(N, Hc, Wc)));
     float* base = static_cast<float*>(h->arena.p);
     const size_t n = (size_t)N;
     float* X0 = base;
@@ -339,7 +377,7 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
         for (int t = 0; t < tap; ++t) off += kTapChannels[t];
         return off;
     };
-    auto pool_tail = [&](const float* last32, float* avg_ws, float* gap_scratch) -> int {   // last32: fp32 [N,49,2048] of the last block
+    auto pool_tail = [&](const float* last32, float* avg_ws, float* gap_scratch) -> int {   // last32: fp32 [N,HWlast,2048] of the last block
         if (!pool) return RELAX_OK;
         const float* avg_src;
         int64_t avg_stride;
@@ -347,7 +385,7 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
             avg_src = layer_stack + (RELAX_RN50_LAYER_STACK_DIM - 2048);
             avg_stride = RELAX_RN50_LAYER_STACK_DIM;
         } else {
-            RELAX_TRY(launch_gap_ws(h, last32 + (size_t)pool_from * 49 * 2048, avg_ws, n_pool, 49, 2048, 2048, gap_scratch, s));
+            RELAX_TRY(launch_gap_ws(h, last32 + (size_t)pool_from * HWlast * 2048, avg_ws, n_pool, HWlast, 2048, 2048, gap_scratch, s));
             avg_src = avg_ws;
             avg_stride = 2048;
         }
@@ -361,17 +399,19 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
         for (int t = 0; taps_nchw && t < RELAX_RN50_NUM_TAPS; ++t) rq.taps |= taps_nchw[t] ? 1u << t : 0u;
         host::RnPlan plan;
         std::string plan_err;
-        RELAX_REQUIRE(h, rn.blocks.size() == (size_t)host::kRnBlocks && host::rn_plan(opt, rq, (int)kImgSlots, &plan, plan_err), "%s",
+        host::RnCanvas cv;
+        cv.Hc = Hc; cv.Wc = Wc;
+        RELAX_REQUIRE(h, rn.blocks.size() == (size_t)host::kRnBlocks && host::rn_plan(opt, rq, cv, (int)kImgSlots, &plan, plan_err), "%s",
                       plan_err.empty() ? "resnet50: not the 16 bottlenecks of the schedule" : plan_err.c_str());
         // bf16x6.  conv1 7x7/2 (raw) straight from the uint8 fragments (conv1_x6.hip: preprocess, im2col, split and contraction in one
         // kernel, the 16-pixel sums of the tap's spatial mean formed in its epilogue); from the max-pool on, every convolution input
         // travels as split planes written by its producer
         float* gap0 = T2 + kT2 * n;   // = the fp32 carving's gapws: free until the blocks carve the arena anew below
         RELAX_REQUIRE(h, !plan.conv1_h2 || rn.conv1.w_h2, "resnet50: the stem's fp16-plane weights are missing");
-        RELAX_TRY(launch_conv1_x6(h, frags, plan.conv1_h2 ? rn.conv1.w_h2 : rn.conv1.w_sp3, bufA, layer_stack ? gap0 : nullptr, N, s,
+        RELAX_TRY(launch_conv1_x6(h, frags, plan.conv1_h2 ? rn.conv1.w_h2 : rn.conv1.w_sp3, bufA, layer_stack ? gap0 : nullptr, N, Hc, Wc, s,
                                   plan.conv1_h2 ? rn.conv1.w_inv : nullptr));
-        if (layer_stack) RELAX_TRY(launch_gap_groups_finish(h, gap0, layer_stack, n_ls, 112 * 112, 64, RELAX_RN50_LAYER_STACK_DIM, s));
-        if (taps_nchw && taps_nchw[0]) RELAX_TRY(launch_nhwc_to_nchw(h, bufA, taps_nchw[0], N, 112 * 112, 64, s));
+        if (layer_stack) RELAX_TRY(launch_gap_groups_finish(h, gap0, layer_stack, n_ls, H0 * W0, 64, RELAX_RN50_LAYER_STACK_DIM, s));
+        if (taps_nchw && taps_nchw[0]) RELAX_TRY(launch_nhwc_to_nchw(h, bufA, taps_nchw[0], N, H0 * W0, 64, s));
         float* f32a = bufB;                                   // block outputs as fp32, where something needs them (ping-pong with f32b)
         float* f32b = bufD;
         char* spa = reinterpret_cast<char*>(T1);              // carve the rest of the arena anew
@@ -390,10 +430,10 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
             return launch_h2_image_scales(h, slot_amax(a), la, b >= 0 ? slot_amax(b) : nullptr, lb, r >= 0 ? slot_amax(r) : nullptr, c, slot_scale(t),
                                           slot_inv(t), N, s);
         };
-        auto conv_h2 = [&](const ConvW& c, const void* in, int Hin, int slot_in, GemmDescH2 g, int slot_out, int act) {
+        auto conv_h2 = [&](const ConvW& c, const void* in, int Hin, int Win, int slot_in, GemmDescH2 g, int slot_out, int act) {
             g.a = in; g.w = c.w_h2; g.colscale = c.w_inv; g.bias = c.bias; g.act = act;
-            g.pixels = 1; g.Nimg = N; g.H = Hin; g.W = Hin; g.Cin = c.Cin;
-            g.Ho = (Hin + 2 * c.pad - c.KH) / c.stride + 1; g.Wo = g.Ho;
+            g.pixels = 1; g.Nimg = N; g.H = Hin; g.W = Win; g.Cin = c.Cin;
+            g.Ho = conv_out(Hin, c.KH, c.stride, c.pad); g.Wo = conv_out(Win, c.KW, c.stride, c.pad);
             g.KH = c.KH; g.KW = c.KW; g.stride = c.stride; g.pad = c.pad;
             g.M = N * g.Ho * g.Wo; g.N = c.Cout; g.K = c.KH * c.KW * c.Cin;
             g.rows_per_img = g.Ho * g.Wo; g.img_in_inv = slot_inv(slot_in);
@@ -403,20 +443,20 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
         if (plan.n_slots) RELAX_HIP_CHECK(h, fill_async(imgtab, 0, sizeof(float) * 3 * kImgSlots * n, s));
         unsigned* blockmax = reinterpret_cast<unsigned*>(imgtab + 3 * kImgSlots * n);
         if (plan.pool_f32)
-            RELAX_TRY(launch_bn_relu_maxpool_f32(h, bufA, rn.bn1_scale, rn.bn1_shift, bufD, N, 112, 112, 64, s, slot_amax(plan.s_stem), blockmax));
+            RELAX_TRY(launch_bn_relu_maxpool_f32(h, bufA, rn.bn1_scale, rn.bn1_shift, bufD, N, H0, W0, 64, s, slot_amax(plan.s_stem), blockmax));
         else
-            RELAX_TRY(launch_bn_relu_maxpool_sp3(h, bufA, rn.bn1_scale, rn.bn1_shift, spa, N, 112, 112, 64, s,
+            RELAX_TRY(launch_bn_relu_maxpool_sp3(h, bufA, rn.bn1_scale, rn.bn1_shift, spa, N, H0, W0, 64, s,
                                                  plan.s_stem >= 0 ? slot_amax(plan.s_stem) : nullptr, blockmax));
         const float* cur32 = plan.pool_f32 ? bufD : nullptr;   // (f32b: block 0 writes f32a, block 1 - which overwrites f32b - runs when block 0 is through)
         char* cursp = spa;       // the block input's planes; a stride-2 sample the previous block left (in_sample) lies in othersp
         char* othersp = spb;
         float* out32 = f32a;
-        int H = 56;
+        int H = H1, W = W1;
         for (size_t b = 0; b < rn.blocks.size(); ++b) {
             const Bottleneck& blk = rn.blocks[b];
             const host::RnBlockPlan& q = plan.blk[b];
-            const int Ho = H / blk.c2.stride;
-            const int HWo = Ho * Ho, Cout = blk.c3.Cout;
+            const int Ho = conv_out(H, blk.c2.KH, blk.c2.stride, blk.c2.pad), Wo = conv_out(W, blk.c2.KW, blk.c2.stride, blk.c2.pad);
+            const int HWo = Ho * Wo, Cout = blk.c3.Cout;
             const bool b2b = q.form == host::kRnFormB2B || q.form == host::kRnFormB2BX2 || q.form == host::kRnFormB2BDown;
             float* y32 = q.need32 ? out32 : nullptr;
             float* gap = q.fuse_mean ? gapws : nullptr;
@@ -425,17 +465,17 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
                 // ---- an f16x2 block (gemm_h2.hip): cursp = the block input's planes (slot s_in)
                 // conv1 1x1 + ReLU
                 RELAX_TRY(scales(q.s_t1, q.s_in, blk.c1.l1max, -1, 0.f, -1, blk.c1.bmax));
-                { GemmDescH2 g{}; g.out_h2 = T1s; RELAX_TRY(conv_h2(blk.c1, cursp, H, q.s_in, g, q.s_t1, 1)); }
+                { GemmDescH2 g{}; g.out_h2 = T1s; RELAX_TRY(conv_h2(blk.c1, cursp, H, W, q.s_in, g, q.s_t1, 1)); }
                 // conv2 3x3 (stride) + ReLU
                 RELAX_TRY(scales(q.s_t2, q.s_t1, blk.c2.l1max, -1, 0.f, -1, blk.c2.bmax));
-                { GemmDescH2 g{}; g.out_h2 = T2s; RELAX_TRY(conv_h2(blk.c2, T1s, H, q.s_t1, g, q.s_t2, 1)); }
+                { GemmDescH2 g{}; g.out_h2 = T2s; RELAX_TRY(conv_h2(blk.c2, T1s, H, W, q.s_t1, g, q.s_t2, 1)); }
                 // conv3 1x1 + identity + ReLU: the identity is the block input (its planes) or the downsample convolution of it (fp32, no
                 // activation; bounded by its own Hoelder term)
                 GemmDescH2 g3{};
                 if (blk.has_down) {
                     GemmDescH2 gd{};
                     gd.out = bufA;
-                    RELAX_TRY(conv_h2(blk.down, cursp, H, q.s_in, gd, -1, 0));
+                    RELAX_TRY(conv_h2(blk.down, cursp, H, W, q.s_in, gd, -1, 0));
                     g3.residual = bufA;
                     RELAX_TRY(scales(q.s_out, q.s_t2, blk.c3.l1max, q.s_in, blk.down.l1max, -1, blk.c3.bmax + blk.down.bmax));
                 } else {
@@ -446,11 +486,11 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
                 g3.out_h2 = q.out_form == host::kRnH2 ? othersp : nullptr;
                 g3.gap_groups = gap; g3.gap_rows = n_ls * HWo;
                 g3.no_split = q.no_split;
-                RELAX_TRY(conv_h2(blk.c3, T2s, Ho, q.s_t2, g3, q.s_out, 1));
+                RELAX_TRY(conv_h2(blk.c3, T2s, Ho, Wo, q.s_t2, g3, q.s_out, 1));
             } else {
                 // ---- conv1 1x1 + ReLU, from fp32 rows (split in the K loop) or planes
                 const bool in_f32 = q.in_form == host::kRnF32;
-                ConvDescX6 d = conv_x6(blk.c1, in_f32 ? static_cast<const void*>(cur32) : cursp, N, H);
+                ConvDescX6 d = conv_x6(blk.c1, in_f32 ? static_cast<const void*>(cur32) : cursp, N, H, W);
                 d.in_f32 = in_f32;
                 if (q.c1_h2) {
                     // f16x2: the rows are split into fp16 planes in the K loop, with the image's scale from the MEASURED maximum of the block input
@@ -466,24 +506,24 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
                 }
                 RELAX_TRY(launch_conv_x6(h, d, s));
                 // ---- conv2 3x3 (stride) + ReLU; back to back, conv3 in the same launch
-                ConvDescX6 d2 = conv_x6(blk.c2, T1s, N, H);
+                ConvDescX6 d2 = conv_x6(blk.c2, T1s, N, H, W);
                 if (q.s_t1 >= 0) { d2.in_h2 = 1; d2.w = blk.c2.w_h2; d2.colscale = blk.c2.w_inv; d2.img_in_inv = slot_inv(q.s_t1); }
                 // ---- conv3 1x1 + identity + ReLU.  Its output: fp32 rows where the plan wants them, and bf16 planes, or - the hand-over block - fp16
                 // planes with a per-image scale, or fp32 rows only plus the planes of the stride-2 sample the next block's downsample branch reads
-                ConvDescX6 d3 = conv_x6(blk.c3, T2s, N, Ho);
+                ConvDescX6 d3 = conv_x6(blk.c3, T2s, N, Ho, Wo);
                 ConvDescX6& y = b2b ? d2 : d3;      // the launch that writes the block output
                 int s_planes = q.handover ? q.s_out : q.s_dr_out;   // scale of the fp16 planes the block output leaves as, if any
                 if (b2b) {
                     d2.w3 = blk.c3.w_h2p; d2.colscale3 = blk.c3.w_invp; d2.bias3 = blk.c3.bias; d2.Cout3 = Cout;
                     d2.residual = cur32;
                     if (q.form == host::kRnFormB2BDown) {
-                        // the downsample branch first: fp32 [N*Ho*Ho][Cout] into bufA (the stem's raw output: dead since the max-pool), on gemm_h3's
+                        // the downsample branch first: fp32 [N*Ho*Wo][Cout] into bufA (the stem's raw output: dead since the max-pool), on gemm_h3's
                         // 1x1 form from the compact fp16 planes of the input's stride-2 sample the previous block left (its per-image scale: s_dr_in)
                         ConvW down1 = blk.down;
                         down1.stride = 1;
                         GemmDescH2 g{};
                         g.out = bufA;
-                        RELAX_TRY(conv_h2(down1, othersp, Ho, q.s_dr_in, g, -1, 0));
+                        RELAX_TRY(conv_h2(down1, othersp, Ho, Wo, q.s_dr_in, g, -1, 0));
                         d2.residual = bufA;
                     }
                     if (q.form == host::kRnFormB2BX2) { d2.w3 = blk.c3d_w_h2p; d2.colscale3 = blk.c3d_w_invp; d2.bias3 = blk.c3d_bias; d2.residual = nullptr; d2.x2 = cur32; }
@@ -503,8 +543,8 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
                         // conv3 and the downsample convolution in ONE contraction over K = [conv2 output | block input sampled with the
                         // block's stride]: no fp32 copy of the branch is written and read back (layer1.0: 6.6 GB per 1024 images)
                         d3.w = blk.c3d_w_sp3; d3.bias = blk.c3d_bias;
-                        d3.in2 = cursp; d3.H2 = H; d3.W2 = H; d3.Cin2 = blk.down.Cin; d3.stride2 = blk.down.stride;
-                        if (q.in_sample == host::kRnSampleSp3) { d3.in2 = othersp; d3.H2 = Ho; d3.W2 = Ho; d3.stride2 = 1; }   // (the previous block left the stride-2 sample only)
+                        d3.in2 = cursp; d3.H2 = H; d3.W2 = W; d3.Cin2 = blk.down.Cin; d3.stride2 = blk.down.stride;
+                        if (q.in_sample == host::kRnSampleSp3) { d3.in2 = othersp; d3.H2 = Ho; d3.W2 = Wo; d3.stride2 = 1; }   // (the previous block left the stride-2 sample only)
                     } else if (in_f32) {
                         d3.residual = cur32;
                     } else {
@@ -525,7 +565,7 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
             cur32 = y32;
             if (y32) out32 = out32 == f32a ? f32b : f32a;
             if (q.out_form != host::kRnF32) { char* t = cursp; cursp = othersp; othersp = t; }   // (fp32 rows: a stride-2 sample, if any, stays in othersp)
-            H = Ho;
+            H = Ho; W = Wo;
             const int off = q.want_mean ? tap_offset(blk.tap) : 0;
             if (q.fuse_mean)
                 RELAX_TRY(launch_gap_groups_finish(h, gapws, layer_stack + off, n_ls, HWo, Cout, RELAX_RN50_LAYER_STACK_DIM, s));
@@ -536,34 +576,34 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
         return pool_tail(cur32, avg6, gapws);
     }
     auto emit_tap = [&](int tap, const float* act) -> int {
-        const int C = kTapChannels[tap], HW = kTapHW[tap] * kTapHW[tap];
+        const int C = kTapChannels[tap], HW = geo.tap_hw[tap][0] * geo.tap_hw[tap][1];
         if (layer_stack)
             RELAX_TRY(launch_gap_ws(h, act, layer_stack + tap_offset(tap), n_ls, HW, C, RELAX_RN50_LAYER_STACK_DIM, gapws, s));
         if (taps_nchw && taps_nchw[tap]) RELAX_TRY(launch_nhwc_to_nchw(h, act, taps_nchw[tap], N, HW, C, s));
         return RELAX_OK;
     };
-    const int64_t npix = (int64_t)N * 224 * 224;
+    const int64_t npix = (int64_t)N * Hc * Wc;
     hipLaunchKernelGGL(rn_preprocess, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, frags, X0, npix);
     RELAX_HIP_CHECK(h, hipGetLastError());
     // conv1 7x7/2 (raw), algorithmic FLOPs use the real 3 input channels
-    RELAX_TRY(run_conv(h, rn.conv1, X0, N, 224, 224, nullptr, bufA, 0, s, 2.0 * N * 112.0 * 112.0 * 64.0 * 147.0));
+    RELAX_TRY(run_conv(h, rn.conv1, X0, N, Hc, Wc, nullptr, bufA, 0, s, 2.0 * N * (double)H0 * W0 * 64.0 * 147.0));
     RELAX_TRY(emit_tap(0, bufA));
-    RELAX_TRY(launch_bn_relu_maxpool(h, bufA, rn.bn1_scale, rn.bn1_shift, bufB, N, 112, 112, 64, s));
+    RELAX_TRY(launch_bn_relu_maxpool(h, bufA, rn.bn1_scale, rn.bn1_shift, bufB, N, H0, W0, 64, s));
     float* cur = bufB;
     float* other = bufA;
-    int H = 56;
+    int H = H1, W = W1;
     for (const Bottleneck& blk : rn.blocks) {
-        const int Ho = H / blk.c2.stride;
-        RELAX_TRY(run_conv(h, blk.c1, cur, N, H, H, nullptr, T1, 1, s));
-        RELAX_TRY(run_conv(h, blk.c2, T1, N, H, H, nullptr, T2, 1, s));
+        const int Ho = conv_out(H, blk.c2.KH, blk.c2.stride, blk.c2.pad), Wo = conv_out(W, blk.c2.KW, blk.c2.stride, blk.c2.pad);
+        RELAX_TRY(run_conv(h, blk.c1, cur, N, H, W, nullptr, T1, 1, s));
+        RELAX_TRY(run_conv(h, blk.c2, T1, N, H, W, nullptr, T2, 1, s));
         const float* identity = cur;
         if (blk.has_down) {
-            RELAX_TRY(run_conv(h, blk.down, cur, N, H, H, nullptr, bufD, 0, s));
+            RELAX_TRY(run_conv(h, blk.down, cur, N, H, W, nullptr, bufD, 0, s));
             identity = bufD;
         }
-        RELAX_TRY(run_conv(h, blk.c3, T2, N, Ho, Ho, identity, other, 1, s));
+        RELAX_TRY(run_conv(h, blk.c3, T2, N, Ho, Wo, identity, other, 1, s));
         float* t = cur; cur = other; other = t;
-        H = Ho;
+        H = Ho; W = Wo;
         if (blk.tap >= 0) RELAX_TRY(emit_tap(blk.tap, cur));
     }
     return pool_tail(cur, avg, gapws);

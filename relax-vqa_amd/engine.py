@@ -790,6 +790,79 @@ class RelaxEngine:
         self._check(rc, "relax_resnet50_clip_features")
         return ls, pl
 
+    # ---- ResNet-50 on any canvas ---------------------------------------------------------------
+    def resnet50_canvas_geometry(self, Hc, Wc):
+        """-> ([(h, w)] * 15: the map of every tap on an [Hc, Wc] canvas, arena bytes per image).  Accepted: Hc and Wc multiples of 32 in
+        [64, 1024] (every stage map even down to layer4, the stem's output whole 256-pixel tiles); anything else is a ValueError that names
+        the offending value.  Host arithmetic: no model needs to be loaded."""
+        taps = (C.c_int * 30)()
+        arena = C.c_int64(0)
+        if self.lib.relax_resnet50_canvas_geometry(int(Hc), int(Wc), taps, C.byref(arena)) != 0:
+            raise ValueError(self.lib.relax_last_error(None).decode())
+        return [(taps[2 * t], taps[2 * t + 1]) for t in range(15)], int(arena.value)
+
+    def resnet50_canvas(self):
+        """(Hc, Wc) the ResNet-50 entries run at: 224 x 224 unless a *_canvas method is under way."""
+        hc, wc = C.c_int(0), C.c_int(0)
+        self._check(self.lib.relax_resnet50_get_canvas(self.h, C.byref(hc), C.byref(wc)), "relax_resnet50_get_canvas")
+        return hc.value, wc.value
+
+    def _rn_canvas_images(self, images):
+        images = self._dev_u8(images)
+        if images.dim() == 3:
+            images = images.unsqueeze(0)
+        if images.dim() != 4 or images.shape[3] != 3 or images.shape[0] < 1:
+            raise ValueError(f"images must be [N,Hc,Wc,3], got {tuple(images.shape)}")
+        return images
+
+    def resnet50_features_canvas(self, images, layer_stack=True, pool=True, taps=None):
+        """images uint8 [N,Hc,Wc,3] BGR on any accepted canvas (resnet50_canvas_geometry) -> what resnet50_features returns: (layer_stack fp32
+        [N,13120] | None, pool fp32 [N,2051] | None[, taps]), the exported taps [N,C,h_t,w_t] of that canvas.  torchvision's ResNet-50 takes
+        any size; both rows are spatial means and keep their widths.  At 224 x 224 this is resnet50_features, launch for launch.  The canvas is
+        set on the handle for this call and 224 x 224 put back when it returns or raises, so every other method keeps finding the default."""
+        images = self._rn_canvas_images(images)
+        N, Hc, Wc = (int(v) for v in images.shape[:3])
+        shapes = self.resnet50_canvas_geometry(Hc, Wc)[0]       # (a refused canvas: ValueError naming the value, the handle untouched)
+        try:
+            self._check(self.lib.relax_resnet50_set_canvas(self.h, Hc, Wc), "relax_resnet50_set_canvas")
+            dev = self.device
+            ls = torch.empty((N, LAYER_STACK_DIM), dtype=torch.float32, device=dev) if layer_stack else None
+            pl = torch.empty((N, RN50_POOL_DIM), dtype=torch.float32, device=dev) if pool else None
+            tap_out, tap_ptrs = {}, None
+            if taps is not None:
+                arr = (C.c_void_p * 15)()
+                for t in taps:
+                    c, (th, tw) = RN50_TAP_SHAPES[t][0], shapes[t]
+                    tap_out[t] = torch.empty((N, c, th, tw), dtype=torch.float32, device=dev)
+                    arr[t] = tap_out[t].data_ptr()
+                tap_ptrs = arr
+            rc = self.lib.relax_resnet50_features(self.h, _ptr(images), N, _ptr(ls), _ptr(pl), tap_ptrs, _stream())
+            self._check(rc, "relax_resnet50_features")
+        finally:
+            self.lib.relax_resnet50_set_canvas(self.h, TARGET, TARGET)
+        return (ls, pl, tap_out) if taps is not None else (ls, pl)
+
+    def resnet50_clip_features_canvas(self, images, n_layer_stack):
+        """resnet50_clip_features on any accepted canvas: images uint8 [N,Hc,Wc,3], the first n_layer_stack -> layer stack fp32
+        [n_layer_stack,13120], the others -> pool fp32 [N - n_layer_stack,2051]; ONE forward.  224 x 224 is put back as in
+        resnet50_features_canvas."""
+        images = self._rn_canvas_images(images)
+        N, Hc, Wc = (int(v) for v in images.shape[:3])
+        n_ls = int(n_layer_stack)
+        if not 0 <= n_ls <= N:
+            raise ValueError(f"n_layer_stack={n_ls} outside [0, {N}]")
+        self.resnet50_canvas_geometry(Hc, Wc)
+        try:
+            self._check(self.lib.relax_resnet50_set_canvas(self.h, Hc, Wc), "relax_resnet50_set_canvas")
+            ls = torch.empty((n_ls, LAYER_STACK_DIM), dtype=torch.float32, device=self.device)
+            pl = torch.empty((N - n_ls, RN50_POOL_DIM), dtype=torch.float32, device=self.device)
+            rc = self.lib.relax_resnet50_clip_features(self.h, _ptr(images), N, n_ls, _ptr(ls) if n_ls else None, _ptr(pl) if N > n_ls else None,
+                                                       _stream())
+            self._check(rc, "relax_resnet50_clip_features")
+        finally:
+            self.lib.relax_resnet50_set_canvas(self.h, TARGET, TARGET)
+        return ls, pl
+
     def _canvas(self, images):
         """-> (uint8 [N,Hc,Wc,3] on the device, ntok of that canvas under the loaded ViT)"""
         if self.vit_dim is None:
@@ -962,7 +1035,8 @@ class RelaxEngine:
         The residual fragment is the frame-difference fragment, merged 50/50 with the optical-flow
         fragment when flow_images (uint8 [T,H,W,3]) are supplied (src/main_fragment_layerstack.py:313-325).
         patch_size / top_n: the fragments' geometry on the 224 x 224 canvas (8 / 16 / 32; top_n=None = all (224 / patch_size)^2 slots;
-        positions come back as [T,slots,2]); target_size is refused: the backbones take 224 (fragment_geometry.backbone_geometry).
+        positions come back as [T,slots,2]); target_size is refused: the clip paths cut 224 x 224 (fragment_geometry.backbone_geometry; other
+        canvases: fragment_resnet_vectors / fragment_vit_vectors / fragment_canvas_vectors).
         flow_params: a dict of optical_flow's keywords for the flow computed here (flow=True without flow_images); None = the literals."""
         kw = self._clip_geometry(patch_size, top_n, target_size)
         fr = self.fragment_pairs(frames, **kw)
@@ -991,6 +1065,31 @@ class RelaxEngine:
         T = fr["ori_frag"].shape[0]
         _, pooled = self.vit_features(torch.cat([fr["ori_frag"], fr["diff_frag"]], dim=0), tokens=False, pooled=True)
         return torch.cat([pooled[:T], pooled[T:]], dim=1)
+
+    def fragment_resnet_vectors(self, frames, patch_size=16, target_size=TARGET, top_n=None):
+        """frames uint8 [T,2,H,W,3] -> fp32 [T, 13120 + 2051]: the ResNet-50 layer stack of the original fragment | the pool of the
+        frame-difference fragment, both cut by fragment_pairs at patch_size on a target_size x target_size canvas and run through ResNet-50 at
+        that canvas in ONE forward - the row of extract_clip's 'resnet' block, which is this at target_size 224.  target_size: a multiple of
+        patch_size (fragment_pairs) and of 32 (resnet50_canvas_geometry) up to 448; e.g. 232 at patch 8 is a fragment canvas but not a
+        ResNet-50 one and is refused naming the value, before anything is cut."""
+        self.resnet50_canvas_geometry(target_size, target_size)
+        fr = self.fragment_pairs(frames, top_n=top_n, patch_size=patch_size, target_size=target_size)
+        return self._fragment_resnet_row(fr)
+
+    def _fragment_resnet_row(self, fr):
+        T = fr["ori_frag"].shape[0]
+        ls, pool = self.resnet50_clip_features_canvas(torch.cat([fr["ori_frag"], fr["diff_frag"]], dim=0), T)
+        return torch.cat([ls, pool], dim=1)
+
+    def fragment_canvas_vectors(self, frames, target_size, patch_size=16, top_n=None):
+        """frames uint8 [T,2,H,W,3] -> fp32 [T, 15171 + 6*dim]: fragment_resnet_vectors | fragment_vit_vectors of the same fragments (ONE
+        fragment_pairs call) - extract_clip's 'resnet' | 'vit' row on a canvas of the caller's choosing (a multiple of 32 and of patch_size, up
+        to 448)."""
+        self.resnet50_canvas_geometry(target_size, target_size)
+        fr = self.fragment_pairs(frames, top_n=top_n, patch_size=patch_size, target_size=target_size)
+        T = fr["ori_frag"].shape[0]
+        _, pooled = self.vit_features(torch.cat([fr["ori_frag"], fr["diff_frag"]], dim=0), tokens=False, pooled=True)
+        return torch.cat([self._fragment_resnet_row(fr), pooled[:T], pooled[T:]], dim=1)
 
     def fragment_vit_layer_stack(self, frames, n=4, cls=False, patch_size=16, target_size=TARGET, top_n=None):
         """frames uint8 [T,2,H,W,3] -> fp32 [T, 2*n*3*dim] (+ 2*n*dim columns with cls=True): fragment_vit_vectors with the last n blocks'
@@ -1087,6 +1186,19 @@ class RelaxEngine:
         else:
             lan = self.resize_frames_to(frames, size, bilinear=False, lanczos=True)[1]
         return self.vit_features(lan, tokens=tokens, pooled=pooled, attention=attention)
+
+    def whole_frame_resnet_canvas(self, frames, size, layer_stack=True, pool=True):
+        """frames uint8 [N,H,W,3] BGR -> resnet50_features_canvas of the frames BILINEAR-resized to the canvas `size` (an int: the shorter side,
+        as transforms.Resize(size); or an (h, w) pair) on the GPU, Pillow-exact: the reference's whole-frame ResNet input (transforms.Resize,
+        src/extractor/visualise_resnet.py:40-50) without squashing the frame to a square - for 16:9 frames (288, 512) keeps the aspect
+        ratio on an accepted canvas.  A size whose result is not an accepted canvas (e.g. the int 288 on 1080 x 1920 -> 288 x 512 is, (270,
+        480) is not) is refused naming the value, before anything is resized.  size=(224, 224) is whole_frame_features' ResNet half."""
+        if len(frames.shape) != 4 or frames.shape[3] != 3:
+            raise ValueError(f"frames must be uint8 [N,H,W,3], got {tuple(frames.shape)}")
+        oh, ow = self._resize_target(int(frames.shape[1]), int(frames.shape[2]), size)
+        self.resnet50_canvas_geometry(oh, ow)
+        bil = self.resize_frames_to(frames, (oh, ow), bilinear=True, lanczos=False)[0]
+        return self.resnet50_features_canvas(bil, layer_stack=layer_stack, pool=pool)
 
     # ---- fragment-free ablation rows (src/main_residual.py, src/main_layer.py) ---------------------------------
     RESIDUAL_NAMES = ("frame_diff", "optical_flow")

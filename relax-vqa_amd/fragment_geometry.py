@@ -10,7 +10,7 @@ from collections import namedtuple
 
 PATCH_SIZES = (8, 16, 32)
 MAX_TARGET = 448
-BACKBONE_TARGET = 224          # the only canvas the backbones take
+BACKBONE_TARGET = 224          # the canvas of the clip paths (the ViT and ResNet-50 take others through their *_canvas methods; VGG-16 takes this one only)
 
 Geometry = namedtuple("Geometry", "patch_size target_size top_n slots tiles_per_row")
 
@@ -38,8 +38,10 @@ def fragment_geometry(patch_size=16, target_size=224, top_n=None):
 
 
 def backbone_geometry(patch_size=16, top_n=None, target_size=None):
-    """The geometry of a clip path that feeds the backbones: the canvas is 224 x 224; resizing another canvas before them is
-    out of scope, so passing target_size at all is refused."""
+    """The geometry of a clip path that feeds the backbones (extract_clip, clip_vectors, full_clip_vector(s)): the canvas is 224 x 224, the
+    one all three backbones take and the one the reference's feature files are cut at, so passing target_size at all is refused.  Other
+    canvases have methods of their own: RelaxEngine.fragment_vit_vectors, fragment_resnet_vectors and fragment_canvas_vectors take
+    target_size (the ViT any multiple of the patch size, ResNet-50 multiples of 32: resnet50_canvas_geometry)."""
     if target_size is not None:
         raise ValueError(f"target_size={target_size}: the clip paths cut {BACKBONE_TARGET} x {BACKBONE_TARGET} canvases, the only input the "
                          "backbones take; resizing another canvas before them is out of scope (fragment_pairs takes target_size)")
