@@ -14,7 +14,10 @@
 //   blur in double + 2x2 solve in one kernel; the first one takes the x2 linear upsampling of the coarser level's flow on the fly, the
 //   last one of the finest level the magnitude range)   [flow_fused = 0: update_matrices_k + box_solve_fused, the matrix plane through HBM]
 //   flow_visualise: fastAtan2, normalisation, 8-bit HSV -> BGR (float formula, truncated).
-// relax_optical_flow_ex takes OpenCV's six parameters (FlowParams below): the literals run exactly the launches above; other values take
+// Which of these run is decided by host::flow_schedule (host_logic.cpp: pure host arithmetic, checked on the CPU by
+// tests/test_flow_schedule_cpu.py) before anything launches: routes, grids, row segments, the ping-pong of the flow buffers, the carve of the
+// workspace, the algorithmic bytes and every refusal of the geometry.  flow_chunk below executes a schedule and decides nothing.
+// relax_optical_flow_ex takes OpenCV's six parameters (host::FlowParams): the literals run exactly the launches above; other values take
 // poly_expansion<7>, the per-level pyramid kernels (wide instantiations down to scale 1/32), resize_linear_f32<2> for the pyramid step and,
 // for windows other than 15, update_matrices_k + box_solve_any.  DESIGN.md has the band / halo / segment arithmetic.
 // relax_optical_flow_flags adds the two flag bits: OPTFLOW_FARNEBACK_GAUSSIAN - update_matrices_k + gauss_solve_any at every window - and
@@ -45,12 +48,13 @@ namespace relax {
 
 // The reference's literals (relax_optical_flow, and relax_optical_flow_ex when it is given them).  WINSIZE is also the window of the
 // register-ring kernels below (box_solve_fused, flow_iteration); every other odd window goes through box_solve_any.
-constexpr int WINSIZE = 15;
+// The geometry constants host::flow_schedule decides by are host_logic.h's: one definition each.
+constexpr int WINSIZE = host::kFlowWinsize;
 constexpr int ITERS = 3;
 constexpr int POLY_N_LITERAL = 5;
 constexpr double POLY_SIGMA_LITERAL = 1.2;
-constexpr int MAX_GAUSS = 32;        // taps of the literal pyramid's kernels (scales down to 1/8: 19)
-constexpr int MAX_GAUSS_WIDE = 80;   // relax_optical_flow_ex: scales down to 1/32, 79 taps
+constexpr int MAX_GAUSS = host::kFlowMaxGauss;            // taps of the literal pyramid's kernels (scales down to 1/8: 19)
+constexpr int MAX_GAUSS_WIDE = host::kFlowMaxGaussWide;   // relax_optical_flow_ex: scales down to 1/32, 79 taps
 typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector: 16-byte loads / stores of the 4-pixel kernels
 
 template <int N>
@@ -178,8 +182,8 @@ __device__ inline void linear_tap(int d, double scale, int n_in, int* s0, int* s
 // horizontal blur at the two sample columns of every output column: src [B][H][W] -> tmp [B][H][w][2].  A block first copies
 // the stretch of the source row its 256 outputs tap (reflected at the borders while copying) into LDS with coalesced loads;
 // the 9 / 19 taps per output then come from LDS instead of strided global loads.
-constexpr int GH_SEG = 1280;   // floats of source row per block: 128 output columns x scale <= 8, plus the taps
-constexpr int GH_SEG_WIDE = 4352;   // relax_optical_flow_ex: 128 output columns x scale <= 32 (x 1.016: a 32-pixel level rounded down), plus 79 taps
+constexpr int GH_SEG = host::kFlowGhSeg;   // 1280 floats of source row per block: 128 output columns x scale <= 8, plus the taps
+constexpr int GH_SEG_WIDE = host::kFlowGhSegWide;   // 4352; relax_optical_flow_ex: 128 output columns x scale <= 32 (x 1.016: a 32-pixel level rounded down), plus 79 taps
 template <int MAXG = MAX_GAUSS, int SEG = GH_SEG>
 __global__ __launch_bounds__(256) void gauss_h_sampled(const float* __restrict__ src, float* __restrict__ tmp, int H, int W,
                                                        int w, double scale_x, GaussTaps<MAXG> gk) {
@@ -444,7 +448,7 @@ template <int N>
 __global__ __launch_bounds__(256) void poly_expansion(const float* __restrict__ I, float* __restrict__ R, int h, int w, int seg,
                                                       PolyConstsT<N> pc) {
     constexpr int POLY_N = N;
-    constexpr int POLY_OUT = 256 - 2 * N;        // 246 (224-pixel bands, whose rows start on 128-byte lines, measured the same: profiles/r04_write_bw.txt has the pattern alone)
+    constexpr int POLY_OUT = host::flow_poly_band(N);        // 256 - 2 N = 246 (224-pixel bands, whose rows start on 128-byte lines, measured the same: profiles/r04_write_bw.txt has the pattern alone)
     constexpr int POLY_RING = 2 * N + 1;         // 11
     constexpr int POLY_SLOTS = POLY_RING + 5;    // 16: the window + 5 rows in flight
     __shared__ f32x4 lt[2][256];                           // (t0, t1, t2, -) of a column side by side: one 16-byte read per neighbour
@@ -737,7 +741,7 @@ __global__ __launch_bounds__(256) void update_matrices_k(const float* __restrict
 //     the vertical part instead of reading M: 1.59 vs 1.30 ms per 2160p pair.)
 // HBM traffic per pixel: ~24 bytes of M + 8 of flow instead of 68 with a separate vertical pass that stores its row sums.
 constexpr int FUSE_ROWS = 3;                          // divides the ring period
-constexpr int FUSE_OUT = 240;                         // output columns per block
+constexpr int FUSE_OUT = host::kFlowFusedBand;        // 240 output columns per block
 constexpr int FUSE_STRIPS = FUSE_OUT / 4;             // 60 strips per row, 180 strip threads per group
 static_assert(WINSIZE % FUSE_ROWS == 0 && FUSE_OUT + WINSIZE - 1 <= 256 && FUSE_ROWS * FUSE_STRIPS <= 256, "fused box geometry");
 // MINMAX (the last iteration of the finest level, when the flow image is asked for): the per-pair minimum and maximum of the flow
@@ -984,7 +988,7 @@ __global__ __launch_bounds__(256) void box_solve_any(const float* __restrict__ M
 // tile of GS_TH x (GS_TW + 2 m) floats (accumulated in double in the order of the definition - centre, then (below + above) x k[i], i = 1 .. m -
 // and rounded to float once), the horizontal pass in double into registers: a thread owns 8 outputs (one column, every 4th row) and keeps their
 // five blurred values across the planes.  LDS addresses of a wave are consecutive in both passes.  63.5 KB of dynamic LDS at most.
-constexpr int GS_TH = 32, GS_TW = 64, GS_PER = GS_TH * GS_TW / 256;
+constexpr int GS_TH = host::kFlowGaussTileH, GS_TW = host::kFlowGaussTileW, GS_PER = GS_TH * GS_TW / 256;
 struct GaussHalfTaps {
     float k[host::kFlowMaxHalfWindow + 1];
 };
@@ -1575,74 +1579,41 @@ static int visualise(relax_handle* h, const float* flow, int P, int HW, uint8_t*
     return RELAX_OK;
 }
 
-// Rows per block of the box-filter kernels.  Long segments keep the 15-row warm-up (and its re-read operands) small; shorter ones when
-// the level is small, so that a clip's 32 pairs still give every CU work.  The choice depends on the level's geometry only - never on
-// the number of pairs in the launch: the running column sums restart at a segment's first row, so the segmentation is part of what
-// fixes the last bits of the flow, and a pair's flow must not depend on its batch.
-// A segment is a multiple of the window (15: the ring period of the register-ring kernels; 270, 135, 90, 60, 45 or 30 rows).
-static int flow_segment_rows(const relax_handle* h, int bands, int hh, int winsize = WINSIZE) {
-    if (h->gemm.flow_seg_rows > 0) return (h->gemm.flow_seg_rows + winsize - 1) / winsize * winsize;   // tests: force a segmentation
-    for (const int mult : {18, 9, 6, 4, 3})
-        if (bands * ((hh + mult * winsize - 1) / (mult * winsize)) >= 16) return mult * winsize;
-    return 2 * winsize;
-}
-
-// What calcOpticalFlowFarneback takes besides the frames (flags: 0 only).  The literal set runs the launches relax_optical_flow has always
-// run; what another value changes: pyr_scale / levels - the per-level pyramid kernels instead of pyramid_fused, and the coarser flow resized by
-// resize_linear_f32<2> (x 1 / pyr_scale) where the x 2 written into flow_up_value does not apply; winsize - update_matrices_k + box_solve_any;
-// poly_n / poly_sigma - poly_expansion<7>, other constants; iterations - the loop count.
-// flags (relax_optical_flow_flags alone; 0 everywhere else, and then no launch differs): OPTFLOW_FARNEBACK_GAUSSIAN - update_matrices_k +
-// gauss_solve_any at every window, 15 too (the fused iteration is the box window's); OPTFLOW_USE_INITIAL_FLOW - the coarsest level starts from
-// resize_area_f32x2 of the caller's field instead of zeros.
-struct FlowParams {
-    double pyr_scale;
-    int levels, winsize, iterations, poly_n;
-    double poly_sigma;
-    int flags;
-};
-static const FlowParams kFlowLiteral = {0.5, 3, WINSIZE, ITERS, POLY_N_LITERAL, POLY_SIGMA_LITERAL};
+// Which kernels run, on which grids and buffers, is host::flow_schedule's (host_logic.cpp); the launchers below take a level of it.
+using host::FlowLevelPlan;
+using host::FlowParams;
+using host::FlowSchedule;
+static const FlowParams kFlowLiteral = {0.5, 3, WINSIZE, ITERS, POLY_N_LITERAL, POLY_SIGMA_LITERAL, 0};
 
 template <int N>
-static void launch_poly_expansion(const float* I, float* R, int hh, int w, int P, double sigma, hipStream_t s) {
+static void launch_poly_expansion(const float* I, float* R, const FlowLevelPlan& L, int P, double sigma, hipStream_t s) {
     PolyConstsT<N> pc;
     prepare_poly<N>(sigma, &pc);
-    int seg = 64;   // rows per block (a ring of rows to fill before the first one); shorter segments when the level is small (enough blocks for 256 CUs)
-    const int bands = (w + (256 - 2 * N) - 1) / (256 - 2 * N);
-    while (seg > 16 && (int64_t)bands * ((hh + seg - 1) / seg) * P * 2 < 2048) seg -= 16;
-    hipLaunchKernelGGL(poly_expansion<N>, dim3(bands, (hh + seg - 1) / seg, P * 2), dim3(256), 0, s, I, R, hh, w, seg, pc);
+    hipLaunchKernelGGL(poly_expansion<N>, dim3(L.poly_bands, (L.lv.h + L.poly_seg - 1) / L.poly_seg, P * 2), dim3(256), 0, s, I, R, L.lv.h, L.lv.w,
+                       L.poly_seg, pc);
 }
 
-// box_solve_fused (winsize 15) or box_solve_any over M, in place on `flow`; minmax: the magnitude range rides on this launch
-static void launch_box_solve(const relax_handle* h, const float* M, float* flow, int hh, int w, int P, int winsize, bool minmax, unsigned* mm,
-                             hipStream_t s) {
-    if (winsize == WINSIZE) {
-        const int bands = (w + FUSE_OUT - 1) / FUSE_OUT;
-        const int seg = flow_segment_rows(h, bands, hh);   // multiples of the 15-row ring period; the same segments as flow_iteration
-        const dim3 gf(bands, (hh + seg - 1) / seg, P);
-        if (minmax) hipLaunchKernelGGL(box_solve_fused<true>, gf, dim3(256), 0, s, M, flow, hh, w, seg, mm);
-        else hipLaunchKernelGGL(box_solve_fused<false>, gf, dim3(256), 0, s, M, flow, hh, w, seg, nullptr);
-        return;
-    }
-    const int out_cols = (256 - 2 * (winsize / 2)) & ~3;
-    const int bands = (w + out_cols - 1) / out_cols;
-    const int seg = flow_segment_rows(h, bands, hh, winsize);
-    const dim3 gf(bands, (hh + seg - 1) / seg, P);
+// box_solve_fused: over M, in place on `flow`; MINMAX: the magnitude range rides on this launch
+template <bool MINMAX>
+static void launch_box_solve_fused(const float* M, float* flow, const FlowLevelPlan& L, int P, unsigned* mm, hipStream_t s) {
+    hipLaunchKernelGGL(box_solve_fused<MINMAX>, dim3(L.bands, L.segments, P), dim3(256), 0, s, M, flow, L.lv.h, L.lv.w, L.seg, MINMAX ? mm : nullptr);
+}
+
+// box_solve_any: the same for any odd window
+template <bool MINMAX>
+static void launch_box_solve_any(const float* M, float* flow, const FlowLevelPlan& L, int P, int winsize, unsigned* mm, hipStream_t s) {
     const double reg = 1e-3 * ((double)winsize * winsize) * ((double)winsize * winsize);
-    if (minmax) hipLaunchKernelGGL(box_solve_any<true>, gf, dim3(256), 0, s, M, flow, hh, w, seg, winsize, out_cols, reg, mm);
-    else hipLaunchKernelGGL(box_solve_any<false>, gf, dim3(256), 0, s, M, flow, hh, w, seg, winsize, out_cols, reg, nullptr);
+    hipLaunchKernelGGL(box_solve_any<MINMAX>, dim3(L.bands, L.segments, P), dim3(256), 0, s, M, flow, L.lv.h, L.lv.w, L.seg, winsize, L.out_cols, reg,
+                       MINMAX ? mm : nullptr);
 }
 
-// gauss_solve_any over M, in place on `flow`
-static int launch_gauss_solve(relax_handle* h, const float* M, float* flow, int hh, int w, int P, int winsize, bool minmax, unsigned* mm,
-                              hipStream_t s) {
-    GaussHalfTaps taps = {};
-    RELAX_REQUIRE(h, host::flow_gauss_window(winsize, taps.k), "optical flow: no Gaussian window of %d", winsize);
+// gauss_solve_any: tiles of GS_TH x GS_TW, the window's half taps as an argument
+template <bool MINMAX>
+static void launch_gauss_solve(const float* M, float* flow, const FlowLevelPlan& L, int P, int winsize, const GaussHalfTaps& taps, unsigned* mm,
+                               hipStream_t s) {
     const int m = winsize / 2;
-    const dim3 g((w + GS_TW - 1) / GS_TW, (hh + GS_TH - 1) / GS_TH, P);
-    if (minmax) hipLaunchKernelGGL(gauss_solve_any<true>, g, dim3(256), gauss_solve_lds(m), s, M, flow, hh, w, m, taps, mm);
-    else hipLaunchKernelGGL(gauss_solve_any<false>, g, dim3(256), gauss_solve_lds(m), s, M, flow, hh, w, m, taps, nullptr);
-    RELAX_HIP_CHECK(h, hipGetLastError());
-    return RELAX_OK;
+    hipLaunchKernelGGL(gauss_solve_any<MINMAX>, dim3(L.bands, L.segments, P), dim3(256), gauss_solve_lds(m), s, M, flow, L.lv.h, L.lv.w, m, taps,
+                       MINMAX ? mm : nullptr);
 }
 
 // resize_area_f32x2: src [P][H][W][2] -> dst [P][hh][w][2] x scale.  The two tables go through h->scratch; the call waits for the stream before
@@ -1668,217 +1639,167 @@ static int launch_resize_area(relax_handle* h, const float* src, int P, int H, i
 }
 
 template <bool UP, bool MINMAX>
-static int launch_flow_iteration(relax_handle* h, const float* R, const float* flow_in, float* flow_out, int hh, int w, int P, const FlowUp& up,
-                                 unsigned* mm, hipStream_t s) {
+static int launch_flow_iteration(relax_handle* h, const float* R, const float* flow_in, float* flow_out, const FlowLevelPlan& L, int P,
+                                 const FlowUp& up, unsigned* mm, hipStream_t s) {
     static std::atomic<bool> lds_allowed[kMaxDevices];
     RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&flow_iteration<UP, MINMAX>)}, IT_LDS, lds_allowed));
-    const int bands = (w + IT_OUT - 1) / IT_OUT;
-    const int seg = flow_segment_rows(h, bands, hh);
-    hipLaunchKernelGGL((flow_iteration<UP, MINMAX>), dim3(bands, (hh + seg - 1) / seg, P), dim3(512), IT_LDS, s, R, flow_in, flow_out, hh, w,
-                       seg, up, mm);
+    hipLaunchKernelGGL((flow_iteration<UP, MINMAX>), dim3(L.bands, L.segments, P), dim3(512), IT_LDS, s, R, UP ? nullptr : flow_in, flow_out,
+                       L.lv.h, L.lv.w, L.seg, UP ? up : FlowUp{}, MINMAX ? mm : nullptr);
     RELAX_HIP_CHECK(h, hipGetLastError());
     return RELAX_OK;
 }
 
-static int flow_chunk(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int P, int H, int W,
+// One chunk of P pairs: the executor of a schedule.  It carves the arena by the schedule's offsets and walks the levels, coarsest first; it
+// decides nothing about routes, grids or buffers.  What reaches a kernel as a float or double (scale ratios, taps, constants) is computed here,
+// under this file's -ffp-contract=off.
+static int flow_chunk(relax_handle* h, const FlowSchedule& sc, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int P, int H, int W,
                       const FlowParams& fp, const float* init, float* flow_out, uint8_t* bgr_out, hipStream_t s) {
     const int64_t HW = (int64_t)H * W;
-    const bool gaussian = (fp.flags & host::kFlowFlagGaussian) != 0;
-    // the matrix kernels address a pair's two coefficient images through ONE buffer resource with 32-bit byte offsets
-    RELAX_REQUIRE(h, HW * 40 < (int64_t)0x7fffffff, "optical flow: frames of %d x %d exceed the 2 GB a buffer resource addresses (40 bytes per pixel)", W, H);
-    // workspace carve (floats unless noted), all sized for level 0
-    const size_t per_pair = (size_t)HW * (2 + 2 + 2 + 2 + 10 + 5 + 2 + 2) * sizeof(float) + 16;
-    RELAX_TRY(ensure_buf(h, h->flow_ws, per_pair * P));
-    float* gray = static_cast<float*>(h->flow_ws.p);
-    float* tmp = gray + (size_t)P * 2 * HW;
-    float* blur = tmp + (size_t)P * 2 * HW;
-    float* I = blur + (size_t)P * 2 * HW;
-    float* R = I + (size_t)P * 2 * HW;         // [P][2][h][w][5]
-    float* M = R + (size_t)P * 10 * HW;        // [P][h][w][5]
-    float* flowA = M + (size_t)P * 5 * HW;     // [P][h][w][2]
-    float* flowB = flowA + (size_t)P * 2 * HW;
-    unsigned* mm = reinterpret_cast<unsigned*>(flowB + (size_t)P * 2 * HW);
+    RELAX_TRY(ensure_buf(h, h->flow_ws, (size_t)sc.arena_bytes));
+    float* const ws = static_cast<float*>(h->flow_ws.p);
+    RELAX_REQUIRE(h, (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "optical flow: the workspace is not 16-byte aligned");   // (the schedule was told it is)
+    float *const gray = ws + sc.gray_off, *const tmp = ws + sc.tmp_off, *const blur = ws + sc.blur_off, *const I = ws + sc.I_off;
+    float *const R = ws + sc.R_off, *const M = ws + sc.M_off;
+    float* const flow_buf[2] = {ws + sc.flow_off[0], ws + sc.flow_off[1]};
+    unsigned* const mm = reinterpret_cast<unsigned*>(ws + sc.mm_off);
+    GaussHalfTaps gtaps = {};
+    host::flow_gauss_window(fp.winsize, gtaps.k);      // (read by gauss_solve_any alone)
 
-    // measurement (relax_profile_read kind 6): the whole stage, first launch to last; its algorithmic bytes are added up launch by launch
-    double stage_bytes = 0;
+    // measurement (relax_profile_read kind 6): the whole stage, first launch to last, with the schedule's algorithmic bytes
     int stage_span;
     RELAX_TRY(prof_begin(h, s, 4, 0.0, &stage_span));
-    // the levels used and their sizes, smoothing kernels and sigmas: OpenCV's loop, in host_logic.cpp (what relax_flow_plan returns)
-    int levels = 0;
-    host::FlowLevel plan[host::kFlowMaxLevels + 1];
-    {
-        std::string err;
-        RELAX_REQUIRE(h, host::flow_plan(H, W, fp.pyr_scale, fp.levels, &levels, plan, err), "optical flow: %s", err.c_str());
-    }
-    // the four level inputs in one pass over the frames (pyramid_fused) when the scales are exact: blur -> level 0, I -> level 1,
-    // tmp -> levels 2 and 3; otherwise the gray plane and the per-level blur / resize kernels below
-    const bool pyr = h->gemm.flow_pyramid_fused && levels == 3 && fp.pyr_scale == 0.5 && H % 8 == 0 && W % 8 == 0 && pair_stride % 4 == 0 &&
-                     ((reinterpret_cast<uintptr_t>(orig) | reinterpret_cast<uintptr_t>(next)) & 3) == 0;
-    float* lvl_in[4] = {blur, I, tmp, tmp + (size_t)P * 2 * (HW / 16)};
-    if (pyr) {
+    switch (sc.gray) {
+    case host::kFlowGrayNone: {
         PyramidTaps tp;
+        float* const dst[4] = {tp.k0, tp.k1, tp.k2, tp.k3};
         for (int k = 0; k <= 3; ++k) {
-            const double scale = 1.0 / (1 << k), sigma = (1. / scale - 1) * 0.5;
-            int smooth = (int)lrint(sigma * 5) | 1;
-            if (smooth < 3) smooth = 3;
             GaussKernel gk;
-            make_gauss(smooth, sigma, &gk);
-            RELAX_REQUIRE(h, gk.ksize == (k < 2 ? 3 : (k == 2 ? 9 : 19)), "optical flow: unexpected smoothing kernel %d at level %d", gk.ksize, k);
-            float* dst = k == 0 ? tp.k0 : (k == 1 ? tp.k1 : (k == 2 ? tp.k2 : tp.k3));
-            for (int i = 0; i < gk.ksize; ++i) dst[i] = gk.k[i];
+            make_gauss(sc.lvl[3 - k].lv.ksize, sc.lvl[3 - k].lv.sigma, &gk);
+            for (int i = 0; i < gk.ksize; ++i) dst[k][i] = gk.k[i];
         }
         const int seg = 256;
         hipLaunchKernelGGL(pyramid_fused, dim3((W + 255) / 256, (H + seg - 1) / seg, P * 2), dim3(256), 0, s, orig, next, pair_stride, H, W,
-                           lvl_in[0], lvl_in[1], lvl_in[2], lvl_in[3], seg, tp);
-        stage_bytes += 2.0 * P * HW * (3 + 4 * (1 + 0.25 + 0.0625 + 0.015625));      // the frames once, the four level inputs once
-    } else if (HW % 4 == 0 && pair_stride % 4 == 0 && ((reinterpret_cast<uintptr_t>(orig) | reinterpret_cast<uintptr_t>(next)) & 3) == 0 &&
-        (reinterpret_cast<uintptr_t>(gray) & 15) == 0)
+                           ws + sc.pyr_off[0], ws + sc.pyr_off[1], ws + sc.pyr_off[2], ws + sc.pyr_off[3], seg, tp);
+        break;
+    }
+    case host::kFlowGrayV4:
         hipLaunchKernelGGL(flow_gray_v4, dim3(nblocks(HW / 4), 1, P * 2), dim3(256), 0, s, orig, next, pair_stride, (int)HW, gray);
-    else
+        break;
+    default:
         hipLaunchKernelGGL(flow_gray, dim3(nblocks(HW), 1, P * 2), dim3(256), 0, s, orig, next, pair_stride, (int)HW, gray);
-    if (!pyr) stage_bytes += 2.0 * P * HW * (3 + 4);
+    }
 
-    float* prev_flow = nullptr;
-    int ph = 0, pw = 0;
-    float* cur = flowA;
-    for (int k = levels; k >= 0; --k) {
-        const host::FlowLevel& lv = plan[levels - k];
-        const double scale = lv.scale, sigma = lv.sigma;
-        const int smooth = lv.ksize, w = lv.w, hh = lv.h;
-        // coarse levels (scale < 1/2: levels 2 and 3 of the literal pyramid) blur only where the resize samples; past 32 taps, or a row stage
-        // past GH_SEG floats (scales under 1/8), the wide instantiations of the same kernels
-        const bool sampled = scale < 0.5;
-        const bool wide = smooth > MAX_GAUSS || (sampled && 129.0 * W / w + smooth + 4 > GH_SEG);
-        RELAX_REQUIRE(h, smooth < MAX_GAUSS_WIDE, "optical flow: smoothing kernel %d too large", smooth);
-        RELAX_REQUIRE(h, !sampled || 129.0 * W / w + smooth + 4 <= GH_SEG_WIDE, "optical flow: pyramid scale %g too coarse for the row stage", scale);
-        RELAX_REQUIRE(h, !wide || sampled, "optical flow: %d smoothing taps at scale %g", smooth, scale);   // (scale >= 1/2 has 3 taps)
+    for (int i = 0; i <= sc.n_levels; ++i) {
+        const FlowLevelPlan& L = sc.lvl[i];
+        const int k = sc.n_levels - i, w = L.lv.w, hh = L.lv.h, smooth = L.lv.ksize;
+        const int ph = i ? sc.lvl[i - 1].lv.h : 0, pw = i ? sc.lvl[i - 1].lv.w : 0;
         const int64_t hw = (int64_t)w * hh;
-        if (!prev_flow && init) {          // OPTFLOW_USE_INITIAL_FLOW: the caller's field, area-resized to the coarsest level, x (float)scale
-            RELAX_TRY(launch_resize_area(h, init, P, H, W, hh, w, (float)scale, cur, s));
-            stage_bytes += 8.0 * P * ((double)HW + (double)hw);
-        } else if (!prev_flow) {
+        float* const cur = flow_buf[L.start];
+        const float* const coarser = flow_buf[1 - L.start];      // the coarser level's result
+        switch (L.up) {
+        case host::kFlowUpZeros:
             RELAX_HIP_CHECK(h, fill_async(cur, 0, sizeof(float) * P * 2 * hw, s));
-        }
-        // finer levels: the first matrix update resizes the coarser flow where it reads it - no resized plane - when the pyramid step doubles
-        // it (x 2 is written into flow_up_value); any other pyr_scale: resize_linear_f32<2>, the same operations, x (float)(1 / pyr_scale)
-        const bool up_fused = prev_flow && fp.pyr_scale == 0.5;
-        if (prev_flow && !up_fused) {
-            hipLaunchKernelGGL(resize_linear_f32<2>, dim3(nblocks(2 * w), hh, P), dim3(256), 0, s, prev_flow, cur, ph, pw, hh, w, (double)ph / hh,
+            break;
+        case host::kFlowUpArea:      // the caller's field, area-resized to the coarsest level, x (float)scale
+            RELAX_TRY(launch_resize_area(h, init, P, H, W, hh, w, (float)L.lv.scale, cur, s));
+            break;
+        case host::kFlowUpResize:
+            hipLaunchKernelGGL(resize_linear_f32<2>, dim3(nblocks(2 * w), hh, P), dim3(256), 0, s, coarser, cur, ph, pw, hh, w, (double)ph / hh,
                                (double)pw / w, (float)(1.0 / fp.pyr_scale));
-            stage_bytes += 8.0 * P * ((double)ph * pw + (double)hw);
+            break;
+        default:;                    // kFlowUpFusedX2: the first matrix update reads the coarser flow, no resized plane
         }
         GaussKernel gk;
         GaussTaps<MAX_GAUSS_WIDE> gkw;
-        if (wide) make_gauss(smooth, sigma, &gkw);
-        else make_gauss(smooth, sigma, &gk);
-        const float* Isrc;
-        const dim3 g_full(nblocks(W), H, P * 2), g_lvl2(nblocks(w), hh, P * 2), g_um(nblocks(w), 8 * ((hh + 7) / 8), P);
-        if (!pyr)   // per-level blur (+ resize): the gray frame read once, the level input written once (+ the full-size blur written and read at level 1)
-            stage_bytes += 2.0 * P * (4.0 * HW + 4.0 * hw + (k >= 1 && !sampled ? 8.0 * HW : 0.0));
-        if (pyr) {
-            Isrc = lvl_in[k];
-        } else if (sampled && wide) {
+        const float* Isrc = blur;
+        const dim3 g_full(nblocks(W), H, P * 2), g_lvl2(nblocks(w), hh, P * 2), g_um(L.um_gx, 8 * L.um_rows, P);
+        switch (L.pyramid) {
+        case host::kFlowPyrFused:
+            Isrc = ws + sc.pyr_off[k];
+            break;
+        case host::kFlowPyrSampledWide:
+            make_gauss(smooth, L.lv.sigma, &gkw);
             hipLaunchKernelGGL((gauss_h_sampled<MAX_GAUSS_WIDE, GH_SEG_WIDE>), dim3(nblocks(2 * w), H, P * 2), dim3(256), 0, s, gray, tmp, H, W, w,
                                (double)W / w, gkw);
             hipLaunchKernelGGL(gauss_v_sampled_resize<MAX_GAUSS_WIDE>, g_lvl2, dim3(256), 0, s, tmp, I, H, W, hh, w, (double)H / hh,
                                (double)W / w, gkw);
             Isrc = I;
-        } else if (sampled) {   // coarse levels: blur only where the resize samples
+            break;
+        case host::kFlowPyrSampled:
+            make_gauss(smooth, L.lv.sigma, &gk);
             hipLaunchKernelGGL((gauss_h_sampled<>), dim3(nblocks(2 * w), H, P * 2), dim3(256), 0, s, gray, tmp, H, W, w, (double)W / w, gk);
             hipLaunchKernelGGL(gauss_v_sampled_resize<>, g_lvl2, dim3(256), 0, s, tmp, I, H, W, hh, w, (double)H / hh,
                                (double)W / w, gk);
             Isrc = I;
-        } else {
-            if (gk.ksize == 3 && vec4_ok(W, HW, gray, blur)) {
-                hipLaunchKernelGGL(gauss3_v4, dim3(nblocks((W + 3) / 4), H, P * 2), dim3(256), 0, s, gray, blur, H, W, gk.k[0], gk.k[1],
-                                   gk.k[2]);
-            } else {
-                hipLaunchKernelGGL(gauss_pass<false>, g_full, dim3(256), 0, s, gray, tmp, H, W, gk);
-                hipLaunchKernelGGL(gauss_pass<true>, g_full, dim3(256), 0, s, tmp, blur, H, W, gk);
-            }
-            Isrc = blur;
-            if (w != W || hh != H) {
-                hipLaunchKernelGGL(resize_linear_f32<1>, g_lvl2, dim3(256), 0, s, blur, I, H, W, hh, w, (double)H / hh,
-                                   (double)W / w, 1.0f);
-                Isrc = I;
-            }
+            break;
+        case host::kFlowPyrGauss3V4:
+            make_gauss(smooth, L.lv.sigma, &gk);
+            hipLaunchKernelGGL(gauss3_v4, dim3(nblocks((W + 3) / 4), H, P * 2), dim3(256), 0, s, gray, blur, H, W, gk.k[0], gk.k[1], gk.k[2]);
+            break;
+        default:                     // kFlowPyrGaussPass
+            make_gauss(smooth, L.lv.sigma, &gk);
+            hipLaunchKernelGGL(gauss_pass<false>, g_full, dim3(256), 0, s, gray, tmp, H, W, gk);
+            hipLaunchKernelGGL(gauss_pass<true>, g_full, dim3(256), 0, s, tmp, blur, H, W, gk);
         }
-        if (fp.poly_n == 7) launch_poly_expansion<7>(Isrc, R, hh, w, P, fp.poly_sigma, s);
-        else launch_poly_expansion<5>(Isrc, R, hh, w, P, fp.poly_sigma, s);
-        stage_bytes += 2.0 * P * hw * 24;      // 4 bytes in, 5 coefficients out per pixel and frame
-        const int iters = fp.iterations;
-        // the fused iteration kernel is written for the 15-pixel window (its ring, its fill steps); every other window takes the two kernels
-        if (h->gemm.flow_fused && fp.winsize == WINSIZE && !gaussian) {
-            // one kernel per iteration (flow_iteration): M stays on the chip.  The iterations ping-pong between the two flow buffers:
-            // a block reads flow rows its neighbours may already have rewritten otherwise.
-            // measurement (relax_profile_read kind 5): algorithmic bytes per pixel = 2 x 5 floats of R at the pixel and at the displaced
-            // position (counted once: neighbours share the lines) + the flow in and out = 56 bytes
-            const double it_bytes = 56.0 * (double)hw * P;
-            stage_bytes += iters * it_bytes;
-            float* other = (cur == flowA) ? flowB : flowA;
-            const float* in = cur;                // coarsest level: zeros
-            float* out = other;
-            const FlowUp up = up_fused ? FlowUp{prev_flow, ph, pw, (double)ph / hh, (double)pw / w} : FlowUp{};
-            if (up_fused) out = cur;              // finer levels: the first iteration interpolates the coarser flow (in `other`)
-            for (int it = 0; it < iters; ++it) {
-                int span;
-                RELAX_TRY(prof_begin(h, s, 3, it_bytes, &span));
-                const bool last = k == 0 && it == iters - 1 && bgr_out;   // the final flow: its magnitude range is taken on the way out
-                if (last) RELAX_TRY(minmax_reset(h, P, mm, s));
-                if (it == 0 && up_fused && last) {                        // (one iteration per level)
-                    RELAX_TRY((launch_flow_iteration<true, true>(h, R, nullptr, out, hh, w, P, up, mm, s)));
-                } else if (it == 0 && up_fused) {
-                    RELAX_TRY((launch_flow_iteration<true, false>(h, R, nullptr, out, hh, w, P, up, nullptr, s)));
-                } else if (last) {
-                    RELAX_TRY((launch_flow_iteration<false, true>(h, R, in, out, hh, w, P, FlowUp{}, mm, s)));
-                } else {
-                    RELAX_TRY((launch_flow_iteration<false, false>(h, R, in, out, hh, w, P, FlowUp{}, nullptr, s)));
-                }
+        if (L.resize) {
+            hipLaunchKernelGGL(resize_linear_f32<1>, g_lvl2, dim3(256), 0, s, blur, I, H, W, hh, w, (double)H / hh, (double)W / w, 1.0f);
+            Isrc = I;
+        }
+        if (L.poly_n == 7) launch_poly_expansion<7>(Isrc, R, L, P, fp.poly_sigma, s);
+        else launch_poly_expansion<5>(Isrc, R, L, P, fp.poly_sigma, s);
+
+        const bool up_x2 = L.up == host::kFlowUpFusedX2;
+        const FlowUp up = up_x2 ? FlowUp{coarser, ph, pw, (double)ph / hh, (double)pw / w} : FlowUp{};
+        // measurement (relax_profile_read kind 5): the dominant kernel of the stage - flow_iteration, or update_matrices_k - with L.it_bytes
+        int span;
+        if (L.iteration != host::kFlowItFused) {      // the two-kernel routes: the matrix plane through HBM, the solve in place on `cur`
+            RELAX_TRY(prof_begin(h, s, 3, L.it_bytes, &span));
+            if (up_x2) hipLaunchKernelGGL(update_matrices_k<true>, g_um, dim3(256), 0, s, R, cur, M, hh, w, L.um_rows, up);
+            else hipLaunchKernelGGL(update_matrices_k<false>, g_um, dim3(256), 0, s, R, cur, M, hh, w, L.um_rows, FlowUp{});
+            RELAX_TRY(prof_end(h, s, span));
+        }
+        for (int it = 0; it < sc.iterations; ++it) {
+            const host::FlowStep& st = L.step[it];
+            const float* const in = flow_buf[st.in];
+            float* const out = flow_buf[st.out];
+            const bool first_x2 = it == 0 && up_x2;
+            if (L.iteration == host::kFlowItFused) RELAX_TRY(prof_begin(h, s, 3, L.it_bytes, &span));
+            if (st.minmax) RELAX_TRY(minmax_reset(h, P, mm, s));      // the final flow: its magnitude range is taken on the way out
+            switch (L.iteration) {
+            case host::kFlowItFused:      // one kernel per iteration: M stays on the chip
+                if (first_x2 && st.minmax) RELAX_TRY((launch_flow_iteration<true, true>(h, R, in, out, L, P, up, mm, s)));   // (one iteration per level)
+                else if (first_x2) RELAX_TRY((launch_flow_iteration<true, false>(h, R, in, out, L, P, up, mm, s)));
+                else if (st.minmax) RELAX_TRY((launch_flow_iteration<false, true>(h, R, in, out, L, P, up, mm, s)));
+                else RELAX_TRY((launch_flow_iteration<false, false>(h, R, in, out, L, P, up, mm, s)));
                 RELAX_TRY(prof_end(h, s, span));
-                in = out;
-                out = (out == flowA) ? flowB : flowA;
+                continue;
+            case host::kFlowItBoxFused:
+                if (st.minmax) launch_box_solve_fused<true>(M, out, L, P, mm, s);
+                else launch_box_solve_fused<false>(M, out, L, P, mm, s);
+                break;
+            case host::kFlowItBoxAny:
+                if (st.minmax) launch_box_solve_any<true>(M, out, L, P, fp.winsize, mm, s);
+                else launch_box_solve_any<false>(M, out, L, P, fp.winsize, mm, s);
+                break;
+            default:                      // kFlowItGaussAny
+                if (st.minmax) launch_gauss_solve<true>(M, out, L, P, fp.winsize, gtaps, mm, s);
+                else launch_gauss_solve<false>(M, out, L, P, fp.winsize, gtaps, mm, s);
+                RELAX_HIP_CHECK(h, hipGetLastError());
             }
-            cur = const_cast<float*>(in);         // the level's result
-        } else {
-            // measurement (relax_profile_read kind 5): the dominant kernel of the stage, with its algorithmic bytes: per pixel
-            // 2 x 5 floats of R at the pixel + 5 floats of R1 gathered at the displaced position (counted once: neighbours share
-            // the lines) ... = 40 + 8 (flow) + 20 (M written) = 68 bytes
-            const double um_bytes = 68.0 * (double)hw * P;
-            stage_bytes += iters * (um_bytes + 28.0 * (double)hw * P);      // + box_solve_fused: M read, flow written
-            int um_span;
-            RELAX_TRY(prof_begin(h, s, 3, um_bytes, &um_span));
-            if (up_fused) {
-                const FlowUp up{prev_flow, ph, pw, (double)ph / hh, (double)pw / w};
-                hipLaunchKernelGGL(update_matrices_k<true>, g_um, dim3(256), 0, s, R, cur, M, hh, w, (hh + 7) / 8, up);
-            } else {
-                hipLaunchKernelGGL(update_matrices_k<false>, g_um, dim3(256), 0, s, R, cur, M, hh, w, (hh + 7) / 8, FlowUp{});
-            }
-            RELAX_TRY(prof_end(h, s, um_span));
-            for (int it = 0; it < iters; ++it) {
-                const bool last = k == 0 && it == iters - 1 && bgr_out;   // the final flow: its magnitude range is taken on the way out
-                if (last) RELAX_TRY(minmax_reset(h, P, mm, s));
-                if (gaussian) RELAX_TRY(launch_gauss_solve(h, M, cur, hh, w, P, fp.winsize, last, mm, s));
-                else launch_box_solve(h, M, cur, hh, w, P, fp.winsize, last, mm, s);
-                if (it < iters - 1) {
-                    RELAX_TRY(prof_begin(h, s, 3, um_bytes, &um_span));
-                    hipLaunchKernelGGL(update_matrices_k<false>, g_um, dim3(256), 0, s, R, cur, M, hh, w, (hh + 7) / 8, FlowUp{});
-                    RELAX_TRY(prof_end(h, s, um_span));
-                }
+            if (it < sc.iterations - 1) {
+                RELAX_TRY(prof_begin(h, s, 3, L.it_bytes, &span));
+                hipLaunchKernelGGL(update_matrices_k<false>, g_um, dim3(256), 0, s, R, out, M, hh, w, L.um_rows, FlowUp{});
+                RELAX_TRY(prof_end(h, s, span));
             }
         }
-        prev_flow = cur;
-        ph = hh;
-        pw = w;
-        cur = (cur == flowA) ? flowB : flowA;
     }
     RELAX_HIP_CHECK(h, hipGetLastError());
+    const float* const result = flow_buf[sc.result];
     if (flow_out)
-        RELAX_HIP_CHECK(h, hipMemcpyAsync(flow_out, prev_flow, sizeof(float) * P * 2 * HW, hipMemcpyDeviceToDevice, s));
-    if (bgr_out) {
-        RELAX_TRY(visualise(h, prev_flow, P, (int)HW, bgr_out, mm, s, true));
-        stage_bytes += 11.0 * P * HW;              // the flow read, 3 bytes per pixel written
-    }
-    prof_set_work(h, stage_span, stage_bytes);
+        RELAX_HIP_CHECK(h, hipMemcpyAsync(flow_out, result, sizeof(float) * P * 2 * HW, hipMemcpyDeviceToDevice, s));
+    if (bgr_out)
+        RELAX_TRY(visualise(h, result, P, (int)HW, bgr_out, mm, s, true));
+    prof_set_work(h, stage_span, sc.bytes);
     RELAX_TRY(prof_end(h, s, stage_span));
     return RELAX_OK;
 }
@@ -1889,27 +1810,44 @@ using namespace relax;
 
 extern "C" {
 
-// both entries: the argument checks, then the pairs in chunks that the workspace bounds
-static int optical_flow_run(relax_handle* h, const char* who, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
-                            const FlowParams& fp, float* flow, uint8_t* flow_bgr, relax_stream stream, const float* init = nullptr) {
+// The three entries, in this order: the parameter rules (`rules`: empty, or the refusal of host::flow_check_params* - answered through
+// relax_last_error(NULL) when there is no handle: the rules can be asked without a GPU), the handle, the geometry - the schedule of the full
+// chunk and of the tail chunk, so that every refusal precedes the first launch of the call -, the arguments; then the pairs in chunks that
+// the workspace bounds (up to RELAX_FLOW_WS_GB, default 32, GB: 288 GB of HBM make large chunks cheap, and more pairs per launch fill the
+// chip better at the coarse pyramid levels)
+static int optical_flow_run(relax_handle* h, const char* who, const std::string& rules, const uint8_t* orig, const uint8_t* next,
+                            int64_t pair_stride, int T, int H, int W, const FlowParams& fp, float* flow, uint8_t* flow_bgr, relax_stream stream,
+                            const float* init = nullptr) {
+    if (!rules.empty()) {
+        set_error(h, "%s: %s", who, rules.c_str());
+        return RELAX_ERR_INVALID;
+    }
+    if (!h) {
+        set_error(nullptr, "%s: the handle is NULL", who);
+        return RELAX_ERR_INVALID;
+    }
+    int64_t ws_gb = 32;
+    if (const char* e = getenv("RELAX_FLOW_WS_GB")) ws_gb = atoll(e) > 0 ? atoll(e) : ws_gb;
+    const int chunk = host::flow_chunk_pairs(H, W, ws_gb, h->gemm.flow_max_pairs, T), tail = T % chunk;
+    const host::FlowOptions opt = {h->gemm.flow_fused, h->gemm.flow_pyramid_fused, h->gemm.flow_seg_rows};
+    host::FlowRequest rq = {H, W, chunk, flow_bgr != nullptr, flow != nullptr, init != nullptr, pair_stride % 4 == 0,
+                            ((reinterpret_cast<uintptr_t>(orig) | reinterpret_cast<uintptr_t>(next)) & 3) == 0, /*arena16 (flow_chunk checks it)*/ 1};
+    FlowSchedule sc[2];      // the full chunk, the tail chunk
+    std::string err;
+    RELAX_REQUIRE(h, host::flow_schedule(fp, rq, opt, &sc[0], err), "%s: %s", who, err.c_str());
+    rq.P = tail;
+    RELAX_REQUIRE(h, !tail || host::flow_schedule(fp, rq, opt, &sc[1], err), "%s: %s", who, err.c_str());
     RELAX_REQUIRE(h, orig && next && T > 0 && H >= 16 && W >= 16, "%s: bad arguments", who);
     RELAX_REQUIRE(h, flow || flow_bgr, "%s: no output requested", who);
     RELAX_REQUIRE(h, pair_stride >= (int64_t)H * W * 3 || T == 1, "%s: pair stride smaller than a frame", who);
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // bound the workspace: 108 B per pixel per pair; chunks of up to RELAX_FLOW_WS_GB (default 32) GB - 288 GB of HBM make
-    // large chunks cheap, and more pairs per launch fill the chip better at the coarse pyramid levels
     const int64_t HW = (int64_t)H * W;
-    int64_t ws_gb = 32;
-    if (const char* e = getenv("RELAX_FLOW_WS_GB")) ws_gb = atoll(e) > 0 ? atoll(e) : ws_gb;
-    int chunk = (int)((ws_gb << 30) / (HW * 112));
-    if (h->gemm.flow_max_pairs > 0 && chunk > h->gemm.flow_max_pairs) chunk = h->gemm.flow_max_pairs;   // tests: force the chunk loop
-    if (chunk < 1) chunk = 1;
-    if (chunk > T) chunk = T;
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int P = T - t0 < chunk ? T - t0 : chunk;
-        RELAX_TRY(flow_chunk(h, orig + t0 * pair_stride, next + t0 * pair_stride, pair_stride, P, H, W, fp,
-                             init ? init + (int64_t)t0 * HW * 2 : nullptr, flow ? flow + (int64_t)t0 * HW * 2 : nullptr, flow_bgr ? flow_bgr + (int64_t)t0 * HW * 3 : nullptr, s));
+        RELAX_TRY(flow_chunk(h, sc[P != chunk], orig + t0 * pair_stride, next + t0 * pair_stride, pair_stride, P, H, W, fp,
+                             init ? init + (int64_t)t0 * HW * 2 : nullptr, flow ? flow + (int64_t)t0 * HW * 2 : nullptr,
+                             flow_bgr ? flow_bgr + (int64_t)t0 * HW * 3 : nullptr, s));
     }
     return RELAX_OK;
 }
@@ -1917,66 +1855,41 @@ static int optical_flow_run(relax_handle* h, const char* who, const uint8_t* ori
 int relax_optical_flow(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
                        float* flow, uint8_t* flow_bgr, relax_stream stream) {
     if (!h) return RELAX_ERR_INVALID;
-    return optical_flow_run(h, "relax_optical_flow", orig, next, pair_stride, T, H, W, kFlowLiteral, flow, flow_bgr, stream);
+    return optical_flow_run(h, "relax_optical_flow", "", orig, next, pair_stride, T, H, W, kFlowLiteral, flow, flow_bgr, stream);
 }
 
 int relax_optical_flow_ex(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
                           double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
                           float* flow, uint8_t* flow_bgr, relax_stream stream) {
-    // the parameters first, before the handle is looked at and before anything is launched (a NULL handle gets the refusal through
-    // relax_last_error(NULL): the rules can be asked without a GPU)
-    std::string err;
-    if (!host::flow_check_params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, err)) {
-        set_error(h, "relax_optical_flow_ex: %s", err.c_str());
-        return RELAX_ERR_INVALID;
-    }
-    if (!h) {
-        set_error(nullptr, "relax_optical_flow_ex: the handle is NULL");
-        return RELAX_ERR_INVALID;
-    }
-    {   // (frames under 16 x 16, and a pyramid whose coarsest used level lies under scale 1/32)
-        int n;
-        host::FlowLevel plan[host::kFlowMaxLevels + 1];
-        RELAX_REQUIRE(h, host::flow_plan(H, W, pyr_scale, levels, &n, plan, err), "relax_optical_flow_ex: %s", err.c_str());
-    }
-    const FlowParams fp = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma};
-    return optical_flow_run(h, "relax_optical_flow_ex", orig, next, pair_stride, T, H, W, fp, flow, flow_bgr, stream);
+    std::string rules;
+    host::flow_check_params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, rules);
+    const FlowParams fp = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, 0};
+    return optical_flow_run(h, "relax_optical_flow_ex", rules, orig, next, pair_stride, T, H, W, fp, flow, flow_bgr, stream);
 }
 
 int relax_optical_flow_flags(relax_handle* h, const uint8_t* orig, const uint8_t* next, int64_t pair_stride, int T, int H, int W,
                              double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
                              const float* init_flow, float* flow, uint8_t* flow_bgr, relax_stream stream) {
-    // as relax_optical_flow_ex: the rules first, answered through relax_last_error(NULL) when there is no handle
-    std::string err;
-    if (!host::flow_check_params_flags(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, err)) {
-        set_error(h, "relax_optical_flow_flags: %s", err.c_str());
-        return RELAX_ERR_INVALID;
-    }
-    if ((flags & host::kFlowFlagInitial) && !init_flow) {
-        set_error(h, "relax_optical_flow_flags: flags=%d has OPTFLOW_USE_INITIAL_FLOW (4) but init_flow is NULL", flags);
-        return RELAX_ERR_INVALID;
-    }
-    if (!(flags & host::kFlowFlagInitial) && init_flow) {
-        set_error(h, "relax_optical_flow_flags: init_flow is given but flags=%d lacks OPTFLOW_USE_INITIAL_FLOW (4)", flags);
-        return RELAX_ERR_INVALID;
-    }
-    if (!h) {
-        set_error(nullptr, "relax_optical_flow_flags: the handle is NULL");
-        return RELAX_ERR_INVALID;
-    }
-    {
-        int n;
-        host::FlowLevel plan[host::kFlowMaxLevels + 1];
-        RELAX_REQUIRE(h, host::flow_plan(H, W, pyr_scale, levels, &n, plan, err), "relax_optical_flow_flags: %s", err.c_str());
-    }
-    if (init_flow && flow && init_flow != flow && T > 0) {   // in place is OpenCV's in/out use (a chunk reads its field before it writes its flow)
-        const uintptr_t a = reinterpret_cast<uintptr_t>(init_flow), b = reinterpret_cast<uintptr_t>(flow);
-        const uintptr_t bytes = (uintptr_t)T * H * W * 2 * sizeof(float);
-        RELAX_REQUIRE(h, a + bytes <= b || b + bytes <= a, "relax_optical_flow_flags: init_flow and flow overlap without being the same buffer");
+    std::string rules;
+    char buf[160];
+    buf[0] = 0;
+    const bool wants_init = (flags & host::kFlowFlagInitial) != 0;
+    if (host::flow_check_params_flags(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, rules)) {
+        if (wants_init && !init_flow) {
+            snprintf(buf, sizeof buf, "flags=%d has OPTFLOW_USE_INITIAL_FLOW (4) but init_flow is NULL", flags);
+        } else if (!wants_init && init_flow) {
+            snprintf(buf, sizeof buf, "init_flow is given but flags=%d lacks OPTFLOW_USE_INITIAL_FLOW (4)", flags);
+        } else if (init_flow && flow && init_flow != flow && T > 0) {   // in place is OpenCV's in/out use (a chunk reads its field before it writes its flow)
+            const uintptr_t a = reinterpret_cast<uintptr_t>(init_flow), b = reinterpret_cast<uintptr_t>(flow);
+            const uintptr_t bytes = (uintptr_t)T * H * W * 2 * sizeof(float);
+            if (!(a + bytes <= b || b + bytes <= a)) snprintf(buf, sizeof buf, "init_flow and flow overlap without being the same buffer");
+        }
+        rules = buf;
     }
     const FlowParams fp = {pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags};
-    return optical_flow_run(h, "relax_optical_flow_flags", orig, next, pair_stride, T, H, W, fp, flow, flow_bgr, stream, init_flow);
+    return optical_flow_run(h, "relax_optical_flow_flags", rules, orig, next, pair_stride, T, H, W, fp, flow, flow_bgr, stream, init_flow);
 }
+
 
 int relax_flow_gauss_window(int winsize, float* half_taps) {
     if (!half_taps) {

@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 namespace relax {
@@ -809,6 +810,148 @@ bool flow_check_params_flags(double pyr_scale, int levels, int winsize, int iter
     return true;
 }
 
+int flow_chunk_pairs(int H, int W, int64_t ws_gb, int flow_max_pairs, int T) {
+    if (H < 1 || W < 1 || T < 1) return 1;      // (refused by the caller; no division by zero on the way there)
+    int chunk = (int)((ws_gb << 30) / ((int64_t)H * W * kFlowWsBytesPerPixel));
+    if (flow_max_pairs > 0 && chunk > flow_max_pairs) chunk = flow_max_pairs;   // tests: force the chunk loop
+    if (chunk < 1) chunk = 1;
+    return chunk > T ? T : chunk;
+}
+
+// Long segments keep the window's warm-up rows (and their re-read operands) small; shorter ones when the level is small, so that a clip's 32
+// pairs still give every CU work: 18, 9, 6, 4, 3 or 2 windows (270 .. 30 rows at 15, the ring period of the register-ring kernels).
+int flow_segment_rows(int seg_rows, int bands, int h, int winsize) {
+    if (seg_rows > 0) return (seg_rows + winsize - 1) / winsize * winsize;
+    for (const int mult : {18, 9, 6, 4, 3})
+        if (bands * ((h + mult * winsize - 1) / (mult * winsize)) >= 16) return mult * winsize;
+    return 2 * winsize;
+}
+
+bool flow_schedule(const FlowParams& fp, const FlowRequest& rq, const FlowOptions& o, FlowSchedule* sc, std::string& err) {
+    const int H = rq.H, W = rq.W, P = rq.P;
+    FlowLevel plan[kFlowMaxLevels + 1];
+    int levels = 0;
+    if (!flow_plan(H, W, fp.pyr_scale, fp.levels, &levels, plan, err)) return false;
+    const int64_t HW = (int64_t)H * W;
+    char buf[200];
+    auto refuse = [&]() {
+        err = buf;
+        return false;
+    };
+    // the matrix kernels address a pair's two coefficient images through ONE buffer resource with 32-bit byte offsets
+    if (HW * 40 >= (int64_t)0x7fffffff) {
+        std::snprintf(buf, sizeof buf, "frames of %d x %d exceed the 2 GB a buffer resource addresses (40 bytes per pixel)", W, H);
+        return refuse();
+    }
+    const bool gaussian = (fp.flags & kFlowFlagGaussian) != 0;
+    float taps[kFlowMaxHalfWindow + 1];
+    if (gaussian && !flow_gauss_window(fp.winsize, taps)) {
+        std::snprintf(buf, sizeof buf, "no Gaussian window of %d", fp.winsize);
+        return refuse();
+    }
+    *sc = FlowSchedule{};
+    sc->n_levels = levels;
+    sc->iterations = fp.iterations;
+    // the arena, all regions sized for level 0
+    const int64_t plane = (int64_t)P * 2 * HW;       // [P][2][H][W], or a flow [P][H][W][2]
+    sc->gray_off = 0;
+    sc->tmp_off = plane;
+    sc->blur_off = 2 * plane;
+    sc->I_off = 3 * plane;
+    sc->R_off = 4 * plane;                           // [P][2][h][w][5]
+    sc->M_off = sc->R_off + (int64_t)P * 10 * HW;    // [P][h][w][5]
+    sc->flow_off[0] = sc->M_off + (int64_t)P * 5 * HW;
+    sc->flow_off[1] = sc->flow_off[0] + plane;
+    sc->mm_off = sc->flow_off[1] + plane;
+    sc->arena_bytes = (HW * kFlowArenaFloatsPerPixel * (int64_t)sizeof(float) + 16) * P;
+    // the four level inputs in one pass over the frames when the scales are exact: blur -> level 0, I -> level 1, tmp -> levels 2 and 3
+    const bool pyr = o.pyramid_fused && levels == 3 && fp.pyr_scale == 0.5 && H % 8 == 0 && W % 8 == 0 && rq.stride4 && rq.frames4;
+    sc->pyr_off[0] = sc->blur_off;
+    sc->pyr_off[1] = sc->I_off;
+    sc->pyr_off[2] = sc->tmp_off;
+    sc->pyr_off[3] = sc->tmp_off + (int64_t)P * 2 * (HW / 16);
+    sc->gray = pyr ? kFlowGrayNone : (HW % 4 == 0 && rq.stride4 && rq.frames4 && rq.arena16 ? kFlowGrayV4 : kFlowGray);
+    // bytes: the frames once and the four level inputs once | the frames read, the gray plane written
+    sc->bytes = pyr ? 2.0 * P * HW * (3 + 4 * (1 + 0.25 + 0.0625 + 0.015625)) : 2.0 * P * HW * (3 + 4);
+
+    int cur = 0, prev = -1, ph = 0, pw = 0;          // the buffer the level starts in; the coarser level's result and its size
+    for (int k = levels; k >= 0; --k) {
+        FlowLevelPlan& L = sc->lvl[levels - k];
+        L.lv = plan[levels - k];
+        const double scale = L.lv.scale;
+        const int smooth = L.lv.ksize, w = L.lv.w, hh = L.lv.h;
+        const int64_t hw = (int64_t)w * hh;
+        // coarse levels (scale < 1/2) blur only where the resize samples; past kFlowMaxGauss taps, or a row stage past kFlowGhSeg floats
+        // (scales under 1/8), the wide instantiations of the same kernels
+        const bool sampled = scale < 0.5;
+        const bool wide = smooth > kFlowMaxGauss || (sampled && 129.0 * W / w + smooth + 4 > kFlowGhSeg);
+        if (smooth >= kFlowMaxGaussWide) {
+            std::snprintf(buf, sizeof buf, "smoothing kernel %d too large", smooth);
+            return refuse();
+        }
+        if (sampled && 129.0 * W / w + smooth + 4 > kFlowGhSegWide) {
+            std::snprintf(buf, sizeof buf, "pyramid scale %g too coarse for the row stage", scale);
+            return refuse();
+        }
+        if (wide && !sampled) {      // (scale >= 1/2 has 3 taps)
+            std::snprintf(buf, sizeof buf, "%d smoothing taps at scale %g", smooth, scale);
+            return refuse();
+        }
+        if (pyr && smooth != (k < 2 ? 3 : (k == 2 ? 9 : 19))) {      // PyramidTaps holds 3, 3, 9 and 19
+            std::snprintf(buf, sizeof buf, "unexpected smoothing kernel %d at level %d", smooth, k);
+            return refuse();
+        }
+        L.start = cur;
+        L.up = prev < 0 ? (rq.have_init ? kFlowUpArea : kFlowUpZeros) : (fp.pyr_scale == 0.5 ? kFlowUpFusedX2 : kFlowUpResize);
+        if (L.up == kFlowUpArea) L.bytes += 8.0 * P * ((double)HW + (double)hw);
+        if (L.up == kFlowUpResize) L.bytes += 8.0 * P * ((double)ph * pw + (double)hw);
+        if (pyr) L.pyramid = kFlowPyrFused;
+        else if (sampled) L.pyramid = wide ? kFlowPyrSampledWide : kFlowPyrSampled;
+        else L.pyramid = smooth == 3 && W % 4 == 0 && HW % 4 == 0 && rq.arena16 ? kFlowPyrGauss3V4 : kFlowPyrGaussPass;   // (blur_off is whole 16 bytes)
+        L.resize = !pyr && !sampled && (w != W || hh != H);
+        if (!pyr)   // the gray frame read once, the level input written once (+ the full-size blur written and read below full size)
+            L.bytes += 2.0 * P * (4.0 * HW + 4.0 * hw + (k >= 1 && !sampled ? 8.0 * HW : 0.0));
+        L.poly_n = fp.poly_n;
+        L.poly_bands = (w + flow_poly_band(fp.poly_n) - 1) / flow_poly_band(fp.poly_n);
+        L.poly_seg = 64;   // a ring of rows to fill before the first one; shorter segments when the level is small (enough blocks for 256 CUs)
+        while (L.poly_seg > 16 && (int64_t)L.poly_bands * ((hh + L.poly_seg - 1) / L.poly_seg) * P * 2 < 2048) L.poly_seg -= 16;
+        L.bytes += 2.0 * P * hw * 24;      // 4 bytes in, 5 coefficients out per pixel and frame
+        // the fused iteration kernel is written for the 15-pixel box window (its ring, its fill steps); every other window takes two kernels
+        L.iteration = o.fused && fp.winsize == kFlowWinsize && !gaussian ? kFlowItFused
+                      : (gaussian ? kFlowItGaussAny : (fp.winsize == kFlowWinsize ? kFlowItBoxFused : kFlowItBoxAny));
+        if (L.iteration == kFlowItGaussAny) {
+            L.out_cols = kFlowGaussTileW;
+            L.seg = kFlowGaussTileH;
+        } else {
+            L.out_cols = flow_box_band(fp.winsize);
+            L.seg = flow_segment_rows(o.seg_rows, (w + L.out_cols - 1) / L.out_cols, hh, fp.winsize);
+        }
+        L.bands = (w + L.out_cols - 1) / L.out_cols;
+        L.segments = (hh + L.seg - 1) / L.seg;
+        L.um_gx = (w + 255) / 256;
+        L.um_rows = (hh + 7) / 8;
+        // per pixel: flow_iteration - 2 x 5 floats of R at the pixel and at the displaced position (counted once: neighbours share the lines) +
+        // the flow in and out = 56 bytes; update_matrices_k - the same 40 + 8 (flow) + 20 (M written) = 68, and the solve's 28: M read, flow written
+        const bool fused = L.iteration == kFlowItFused;
+        L.it_bytes = (fused ? 56.0 : 68.0) * (double)hw * P;
+        L.bytes += fp.iterations * (fused ? L.it_bytes : L.it_bytes + 28.0 * (double)hw * P);
+        int in = L.up == kFlowUpFusedX2 ? prev : cur, out = fused && L.up != kFlowUpFusedX2 ? 1 - cur : cur;
+        for (int it = 0; it < fp.iterations; ++it) {
+            L.step[it] = FlowStep{in, out, k == 0 && it == fp.iterations - 1 && rq.want_image};
+            in = out;
+            if (fused) out = 1 - out;
+        }
+        prev = in;       // the level's result
+        ph = hh;
+        pw = w;
+        cur = 1 - prev;
+        sc->bytes += L.bytes;
+    }
+    sc->result = prev;
+    if (rq.want_image) sc->bytes += 11.0 * P * HW;      // the flow read, 3 bytes per pixel written
+    return true;
+}
+
 }  // namespace host
 }  // namespace relax
 
@@ -882,11 +1025,11 @@ int main() {
 
 #ifdef RELAX_FLOW_PLAN_MAIN
 // ---- stand-alone program (make flow_plan_san: AddressSanitizer + UBSan, CPU only): every plan of a grid of sizes, scales and depths into a heap
-// array of exactly kFlowMaxLevels + 1 entries, its invariants checked; every refusal of flow_check_params once ---------------------------------
+// array of exactly kFlowMaxLevels + 1 entries, its invariants checked, and eight schedules of it into heap structs; every refusal of flow_check_params once ---------------------------------
 int main() {
     using namespace relax::host;
     const double scales[] = {0.5, 0.6, 0.7, 0.75, 0.8, 0.9, 0.95};
-    long plans = 0, refused = 0;
+    long plans = 0, refused = 0, schedules = 0;
     std::string err;
     for (int H = 16; H <= 2200; H += 37)
         for (int W = 16; W <= 4200; W += 211)
@@ -907,6 +1050,23 @@ int main() {
                         std::printf("bad plan for %d x %d, pyr_scale %g, levels %d\n", H, W, ps, levels);
                         return 1;
                     }
+                    // the schedule of the same plan into a heap struct of exactly its size: both windows' kinds, both flag bits, every option
+                    for (int v = 0; v < 8; ++v) {
+                        const FlowParams fp{ps, levels, v & 1 ? 15 : 63, v & 2 ? 10 : 1, v & 4 ? 7 : 5, 1.2, (v & 1 ? 0 : kFlowFlagGaussian) | (v & 2 ? kFlowFlagInitial : 0)};
+                        const FlowRequest rq{H, W, v & 4 ? 32 : 1, v & 1, 1, v & 2 ? 1 : 0, (v >> 1) & 1, 1, v & 1};
+                        const FlowOptions o{v & 1, (v >> 2) & 1, v == 7 ? 40 : 0};
+                        std::unique_ptr<FlowSchedule> sc(new FlowSchedule);
+                        if (!flow_schedule(fp, rq, o, sc.get(), err)) {
+                            std::printf("no schedule for %d x %d, pyr_scale %g, levels %d: %s\n", H, W, ps, levels, err.c_str());
+                            return 1;
+                        }
+                        const FlowLevelPlan& l0 = sc->lvl[sc->n_levels];
+                        ++schedules;
+                        if (sc->n_levels != n || l0.lv.h != H || l0.step[fp.iterations - 1].out != sc->result || sc->arena_bytes <= 0 || !(sc->bytes > 0)) {
+                            std::printf("bad schedule for %d x %d, pyr_scale %g, levels %d\n", H, W, ps, levels);
+                            return 1;
+                        }
+                    }
                 }
     const struct { double ps; int lv, ws, it, pn; double sg; int fl; } bad[] = {
         {0.49, 3, 15, 3, 5, 1.2, 0}, {1.0, 3, 15, 3, 5, 1.2, 0}, {0.5, 9, 15, 3, 5, 1.2, 0}, {0.5, 3, 14, 3, 5, 1.2, 0}, {0.5, 3, 65, 3, 5, 1.2, 0},
@@ -918,7 +1078,7 @@ int main() {
             return 1;
         }
     if (!flow_check_params(0.5, 3, 15, 3, 5, 1.2, 0, err) || !flow_check_params(0.95, 8, 63, 10, 7, 0.1, 0, err)) return 1;
-    std::printf("flow_plan ok: %ld plans, %ld refused\n", plans, refused);
+    std::printf("flow_plan ok: %ld plans, %ld refused, %ld schedules\n", plans, refused, schedules);
     return 0;
 }
 #endif
@@ -1049,6 +1209,46 @@ int relax_host_rn_plan(const int* opts, const int* req, int max_slots, int* out,
     static_assert(sizeof(RnPlan) == (4 + kRnBlocks * 23) * sizeof(int), "RnPlan is a flat array of ints");
     std::memcpy(out, &p, sizeof(p));
     return 0;
+}
+// Farneback schedule as plain numbers.  par: pyr_scale, poly_sigma; ipar: levels, winsize, iterations, poly_n, flags; req: the nine FlowRequest
+// fields in order; opts: the three FlowOptions.  iout: [n_levels, iterations, gray, result, the 9 offsets gray .. mm, pyr_off[4], arena_bytes]
+// (18) + per level, coarsest first, 9 levels: [h, w, ksize, pyramid, resize, up, start, poly_n, poly_bands, poly_seg, iteration, bands, out_cols,
+// seg, segments, um_gx, um_rows] + 10 steps x [in, out, minmax] (47).  dout: [bytes] + per level [scale, sigma, it_bytes, bytes].
+// 0, or -1 with the message and both arrays untouched.
+int relax_host_flow_schedule(const double* par, const int* ipar, const int* req, const int* opts, int64_t* iout, double* dout, char* err,
+                             int err_len) {
+    using namespace relax::host;
+    const FlowParams fp{par[0], ipar[0], ipar[1], ipar[2], ipar[3], par[1], ipar[4]};
+    const FlowRequest rq{req[0], req[1], req[2], req[3], req[4], req[5], req[6], req[7], req[8]};
+    const FlowOptions o{opts[0], opts[1], opts[2]};
+    FlowSchedule sc;
+    std::string e;
+    if (!flow_schedule(fp, rq, o, &sc, e)) {
+        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return -1;
+    }
+    const int64_t head[18] = {sc.n_levels, sc.iterations, sc.gray, sc.result, sc.gray_off, sc.tmp_off, sc.blur_off, sc.I_off, sc.R_off, sc.M_off,
+                              sc.flow_off[0], sc.flow_off[1], sc.mm_off, sc.pyr_off[0], sc.pyr_off[1], sc.pyr_off[2], sc.pyr_off[3], sc.arena_bytes};
+    std::memcpy(iout, head, sizeof head);
+    dout[0] = sc.bytes;
+    for (int i = 0; i <= kFlowMaxLevels; ++i) {
+        const FlowLevelPlan& L = sc.lvl[i];
+        const int v[17] = {L.lv.h, L.lv.w, L.lv.ksize, L.pyramid, L.resize, L.up, L.start, L.poly_n, L.poly_bands, L.poly_seg, L.iteration, L.bands,
+                           L.out_cols, L.seg, L.segments, L.um_gx, L.um_rows};
+        int64_t* p = iout + 18 + i * 47;
+        for (int j = 0; j < 17; ++j) p[j] = v[j];
+        for (int j = 0; j < kFlowMaxIterations; ++j) {
+            p[17 + 3 * j] = L.step[j].in;
+            p[18 + 3 * j] = L.step[j].out;
+            p[19 + 3 * j] = L.step[j].minmax;
+        }
+        const double d[4] = {L.lv.scale, L.lv.sigma, L.it_bytes, L.bytes};
+        std::memcpy(dout + 1 + 4 * i, d, sizeof d);
+    }
+    return 0;
+}
+int relax_host_flow_chunk_pairs(int H, int W, int64_t ws_gb, int flow_max_pairs, int T) {
+    return relax::host::flow_chunk_pairs(H, W, ws_gb, flow_max_pairs, T);
 }
 // the 16 bottlenecks: block, layer, index, cin, width, cout, stride, has_down, tap (16 * 9 ints)
 // the same on an [Hc, Wc] canvas; a refused canvas: -1 and rn_canvas_geometry's message

@@ -154,6 +154,88 @@ bool flow_area_table(int src, int dst, int32_t* first, int32_t* count, double* w
 // flow_check_params' rules and wording for the six parameters; flags: any of 0, 4, 256, 260 - another bit is refused with the value named
 bool flow_check_params_flags(double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags, std::string& err);
 
+// ---- the launch schedule of a Farneback chunk (flow.hip: flow_chunk executes it) -------------------------------------------------------------
+// Every route is decided here, before anything launches and before a profiler span opens; flow.hip's kernels use these constants or
+// static_assert equality with them.
+constexpr int kFlowWinsize = 15;                              // the literal window: the register-ring kernels (box_solve_fused, flow_iteration)
+constexpr int kFlowFusedBand = 240;                           // their output columns per block (FUSE_OUT, IT_OUT)
+constexpr int kFlowMaxGauss = 32, kFlowMaxGaussWide = 80;     // smoothing taps the pyramid kernels hold: the literal pyramid's | down to scale 1/32
+constexpr int kFlowGhSeg = 1280, kFlowGhSegWide = 4352;       // floats of source row per block of gauss_h_sampled, and of its wide instantiation
+constexpr int kFlowGaussTileH = 32, kFlowGaussTileW = 64;     // a block of gauss_solve_any (GS_TH, GS_TW)
+constexpr int flow_poly_band(int poly_n) { return 256 - 2 * poly_n; }            // output columns per block of poly_expansion<N>
+constexpr int flow_box_band(int winsize) { return winsize == kFlowWinsize ? kFlowFusedBand : (256 - 2 * (winsize / 2)) & ~3; }
+// The workspace of a chunk: 27 floats per pixel and pair (gray, tmp, blur, I: 2 each; R 10; M 5; the two flow buffers 2 each) and 16 bytes per
+// pair for the magnitude range (2 words used).  The chunk size budgets kFlowWsBytesPerPixel, which covers it from the smallest frame on.
+constexpr int kFlowArenaFloatsPerPixel = 27, kFlowWsBytesPerPixel = 112;
+static_assert(kFlowWsBytesPerPixel * 16 * 16 >= kFlowArenaFloatsPerPixel * 4 * 16 * 16 + 16, "the chunk budget covers the carve at 16 x 16 and above");
+// pairs per chunk of a call of T pairs: what ws_gb GB hold, capped by "flow_max_pairs" (> 0) and T, at least 1
+int flow_chunk_pairs(int H, int W, int64_t ws_gb, int flow_max_pairs, int T);
+
+// What calcOpticalFlowFarneback takes besides the frames (flags: host::kFlowFlag*; 0 outside relax_optical_flow_flags)
+struct FlowParams {
+    double pyr_scale;
+    int levels, winsize, iterations, poly_n;
+    double poly_sigma;
+    int flags;
+};
+// What the dispatch reads of the call: the pairs of the chunk, the outputs asked for, whether the caller gave a field, and the facts about
+// the buffers - pair_stride % 4 == 0, both frame pointers 4-byte aligned, the arena base 16-byte aligned (flow_gray_v4, gauss3_v4)
+struct FlowRequest { int H, W, P, want_image, want_flow, have_init, stride4, frames4, arena16; };
+struct FlowOptions { int fused, pyramid_fused, seg_rows; };       // "flow_fused", "flow_pyramid_fused", "flow_seg_rows"
+enum FlowPyramid {       // how a level's input is made
+    kFlowPyrFused = 0,   // pyramid_fused: the four level inputs in one pass over the frames (three levels at pyr_scale 0.5, sides multiples of 8)
+    kFlowPyrSampled,     // gauss_h_sampled + gauss_v_sampled_resize: scale < 1/2, the blur only where the resize samples
+    kFlowPyrSampledWide, // their wide instantiations: more than kFlowMaxGauss taps or a row stage past kFlowGhSeg floats
+    kFlowPyrGauss3V4,    // gauss3_v4: three taps, rows of whole 16-byte groups
+    kFlowPyrGaussPass    // gauss_pass<false> + gauss_pass<true>
+};                       // (the last two: + resize_linear_f32<1> below full size, FlowLevelPlan::resize)
+enum FlowUp {            // how the coarser flow arrives
+    kFlowUpZeros = 0,    // coarsest level
+    kFlowUpArea,         // coarsest level, OPTFLOW_USE_INITIAL_FLOW: resize_area_f32x2 of the caller's field
+    kFlowUpFusedX2,      // pyr_scale 0.5: read inside the first matrix update (x 2 is written into flow_up_value)
+    kFlowUpResize        // any other pyr_scale: resize_linear_f32<2>, x (float)(1 / pyr_scale)
+};
+enum FlowIteration {     // one iteration
+    kFlowItFused = 0,    // flow_iteration: M stays on the chip ("flow_fused", the box window of 15)
+    kFlowItBoxFused,     // update_matrices_k + box_solve_fused (window 15)
+    kFlowItBoxAny,       // update_matrices_k + box_solve_any (every other window)
+    kFlowItGaussAny      // update_matrices_k + gauss_solve_any (OPTFLOW_FARNEBACK_GAUSSIAN, every window, 15 too)
+};
+enum FlowGray { kFlowGrayNone = 0, kFlowGrayV4, kFlowGray };      // none under pyramid_fused
+// One iteration: the flow buffer (0 = A, 1 = B) it reads and the one it writes.  flow_iteration ping-pongs (a block reads rows its neighbours
+// may already have rewritten otherwise); the two-kernel routes solve in place.  The first iteration under kFlowUpFusedX2 reads the coarser level's result.
+struct FlowStep { int in, out, minmax; };     // minmax: the magnitude range rides on this launch (the last one of level 0 when an image is asked for)
+struct FlowLevelPlan {
+    FlowLevel lv;
+    int pyramid, resize;                      // FlowPyramid; resize_linear_f32<1> follows
+    int up, start;                            // FlowUp; the buffer the zeros / the resized field land in (== step[0].in except under kFlowUpFusedX2)
+    int poly_n, poly_bands, poly_seg;         // poly_expansion<poly_n>: bands of flow_poly_band columns, rows per block (shorter for few pairs: the only entry P changes)
+    int iteration;                            // FlowIteration
+    int bands, out_cols, seg, segments;       // its grid: bands of out_cols columns x segments of seg rows (gauss_solve_any: tiles)
+    int um_gx, um_rows;                       // update_matrices_k: blocks per row, rows per block of its 8 row groups
+    FlowStep step[kFlowMaxIterations];
+    double it_bytes;                          // algorithmic bytes of one flow_iteration / update_matrices_k launch (relax_profile_read kind 5)
+    double bytes;                             // of the whole level (pyramid, pyramid step, poly_expansion, iterations)
+};
+struct FlowSchedule {
+    int n_levels;                             // used below the full-size one; lvl[0 .. n_levels], coarsest first
+    int iterations, gray, result;             // FlowGray; the buffer that holds the flow of level 0
+    int64_t gray_off, tmp_off, blur_off, I_off, R_off, M_off, flow_off[2], mm_off;     // the arena in floats (mm: 2 P words)
+    int64_t pyr_off[4];                       // pyramid_fused's outputs, levels 0..3: blur, I, tmp, tmp + 2 P (HW / 16)
+    int64_t arena_bytes;
+    double bytes;                             // the stage's algorithmic bytes (relax_profile_read kind 6): frames and gray, the levels, copy-free outputs, the image
+    FlowLevelPlan lvl[kFlowMaxLevels + 1];
+};
+// Rows per block of the box kernels: a multiple of the window, by the level's geometry only (never the pairs of the launch: the running column
+// sums restart at a segment's first row, so the segmentation fixes the last bits of the flow); seg_rows > 0 forces one (rounded up to the window)
+int flow_segment_rows(int seg_rows, int bands, int h, int winsize);
+// What another parameter value changes from the literal set's launches: pyr_scale / levels - the per-level pyramid kernels instead of
+// pyramid_fused and resize_linear_f32<2> for the pyramid step; winsize - update_matrices_k + box_solve_any; poly_n / poly_sigma -
+// poly_expansion<7>, other constants; iterations - the loop count; flags 256 - update_matrices_k + gauss_solve_any; flags 4 - kFlowUpArea.
+// false and a message: flow_plan's refusals, frames past the 2 GB of a buffer resource, a smoothing kernel or row stage past the wide
+// kernels, no Gaussian window for the winsize (none of the last three is reachable for parameters flow_check_params_flags accepts).
+bool flow_schedule(const FlowParams& fp, const FlowRequest& rq, const FlowOptions& o, FlowSchedule* sc, std::string& err);
+
 // ---- the options table: every relax_set_option / relax_get_option key once ------------------------------------------------------------------
 // How a row takes a value: as given; != 0; a non-positive value becomes `a`; one of {a, b}; the closed range [a, b].  The last two refuse
 // anything else with "relax_set_option: <key> must be <must_be>" and leave the stored value as it was.

@@ -13,7 +13,8 @@ code.  What stays outside: the 39- and 79-tap wide pyramid kernels in combinatio
 
 route() restates, as a pure function of (parameters, H, W), which launches flow_chunk takes (the conditions of csrc/flow.hip, on the level
 sizes relax_flow_plan returns); the coverage assertions of tests/test_flow_param_space_cpu.py count on it.  It is a table in the tests, not a
-probe of the binary."""
+probe of the binary: tests/test_flow_schedule_cpu.py holds it, field by field, to the schedule flow_chunk executes (host::flow_schedule,
+csrc/host_logic.cpp), so a condition that changes there without changing here fails on the CPU."""
 import ctypes as C
 import functools
 
@@ -218,6 +219,27 @@ def route(params, H, W, fused=True, pyramid_fused=True):
                     "poly": params["poly_n"], "poly_bands": -(-w // POLY_BAND[params["poly_n"]]),
                     "iteration": iteration, "bands": bands, "seg": seg, "segments": -(-h // seg)})
     return out
+
+
+def stage_bytes(params, H, W, pairs, image=True, **options):
+    """The algorithmic bytes of the Farneback stage (relax_profile_read kind 6) of `pairs` pairs, in closed form over route(): every kernel's
+    inputs read once and outputs written once.  Per pixel of a frame: 3 bytes read and 4 written for the gray plane, or, under pyramid_fused,
+    the four level inputs written with it (4 x (1 + 1/4 + 1/16 + 1/64)); per level and frame 4 HW read and 4 hw written by the blur (+ the
+    full-size blur written and read again, 8 HW, where a resize follows it), and 24 hw of poly_expansion (4 in, 5 coefficients out); per level
+    and pair 8 (coarser + this size) for resize_linear_f32<2>, and per iteration 56 hw (flow_iteration: 2 x 5 floats of R twice, the flow in
+    and out) or 68 + 28 hw (update_matrices_k with M written, then the solve: M read, flow written); 11 HW for the image (flow read, 3 written)."""
+    r = route(params, H, W, **options)
+    HW = H * W
+    total = 2 * pairs * HW * ((3 + 4 * (1 + 1 / 4 + 1 / 16 + 1 / 64)) if r[0]["pyramid"] == "fused" else 7)
+    for i, lv in enumerate(r):
+        hw = lv["h"] * lv["w"]
+        if lv["up"] == "resize_linear_f32<2>":
+            total += 8 * pairs * (r[i - 1]["h"] * r[i - 1]["w"] + hw)
+        if lv["pyramid"] != "fused":
+            total += 2 * pairs * (4 * HW + 4 * hw + (8 * HW if lv["k"] >= 1 and lv["pyramid"] != "sampled" else 0))
+        total += 2 * pairs * hw * 24
+        total += params["iterations"] * pairs * hw * (56 if lv["iteration"] == "flow_iteration" else 68 + 28)
+    return total + (11 * pairs * HW if image else 0)
 
 
 def group_route(group, **options):

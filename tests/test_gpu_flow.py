@@ -227,3 +227,25 @@ def test_flow_does_not_depend_on_the_row_segmentation():
             assert torch.equal(got, ref), seg
     finally:
         eng.set_option("flow_seg_rows", 0)
+
+
+@pytest.mark.parametrize("params,h,w,t", [(dict(pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2), 256, 264, 2),
+                                          (dict(pyr_scale=0.8, levels=4, winsize=9, iterations=1, poly_n=5, poly_sigma=1.2), 79, 246, 1)],
+                         ids=["literal-256x264x2", "s0.8-l4-w9-i1-79x246"])
+def test_the_profiled_stage_bytes_are_the_closed_form_of_the_schedule(params, h, w, t):
+    """The bytes relax_profile_read(6) reports for one call are what the executed schedule accounts (csrc/host_logic.cpp: flow_schedule),
+    equal to the closed form of tests/flow_param_space.stage_bytes (tests/test_flow_schedule_cpu.py holds the schedule to it on the CPU) within
+    the rounding of a double sum whose order may change."""
+    from tests import flow_param_space as sp
+    frames = torch.from_numpy(np.stack([np.stack(_smooth_pair(h, w, 40 + i)) for i in range(t)])).cuda()
+    eng = engine()
+    eng.profile_enable(True)
+    try:
+        flow, img = eng.optical_flow_ex(frames, want_flow=True, want_image=True, **params)
+        ms, got, stages = eng.profile_read(6)
+    finally:
+        eng.profile_enable(False)
+    want = sp.stage_bytes(params, h, w, t)
+    print(f"{h} x {w} x {t}: stage bytes {got:.0f}, closed form {want:.0f}, {stages} stage in {ms:.3f} ms")
+    assert bool(torch.isfinite(flow).all()) and stages == 1 and ms > 0
+    assert abs(got - want) <= 1e-12 * want, (got, want)
