@@ -528,7 +528,9 @@ int relax_vit_intermediate_layers(relax_handle* h, const uint8_t* images, int N,
 /* Replaces imputer.transform + scaler.transform + Mlp.forward (src/demo_test.py:177-208, src/model_regression.py:37-58).
  * State-dict keys of the reference's Mlp (fc1/bn1/fc2/fc3; a 'module.' prefix is stripped and 'n_averaged' ignored as
  * fix_state_dict does, demo_test.py:25-35); HOST pointers.  imputer_statistics = SimpleImputer.statistics_ (may be
- * NULL), scaler_scale / scaler_min = MinMaxScaler.scale_ / .min_, all HOST float64 [input_features]. */
+ * NULL), scaler_scale / scaler_min = MinMaxScaler.scale_ / .min_, all HOST float64 [input_features].
+ * A state dict with no bn1.* key at all is the plain Mlp of src/model_regression_simple.py:37-58: fc1.weight is padded and fc1.bias
+ * copied as they are, nothing is folded; some but not all of the four bn1 tensors is refused. */
 int relax_load_mlp_head(relax_handle* h, const float* const* tensors, const char* const* names, const int64_t* numels,
                         int n, const double* imputer_statistics, const double* scaler_scale, const double* scaler_min,
                         int input_features);
@@ -553,6 +555,20 @@ int relax_head_train_transform(relax_handle* h, const float* x, int n, int F, co
  * (AveragedModel, :388), 2 a snapshot (copy.deepcopy(model), :445) - all zero until relax_head_train_import, Adam's second-moment block, and the workspace
  * of batches of up to max_batch rows (2..1024).  Waits for the device. */
 int relax_head_train_init(relax_handle* h, int input_features, int hidden_features, int max_batch);
+/* relax_head_train_init with the head's variant.  batchnorm = 1: relax_head_train_init itself, bit for bit.  batchnorm = 0: the plain
+ * Mlp of src/model_regression_simple.py:37-58 (fc1 -> GELU -> dropout -> fc2 -> GELU -> dropout -> fc3, bn1 commented out) - the head
+ * behind the reference's KoNViD-1k / YouTube-UGC / LIVE-VQC / CVD2014 numbers.  Its three sets hold fc1.weight [H1,Fpad], fc1.bias,
+ * fc2.weight, fc2.bias, fc3.weight, fc3.bias and no bn1 block; the optimizer blocks follow.  Any other value is refused.  The variant
+ * is a property of the state: every relax_head_train_* entry below acts on whichever variant the state has.  On a plain state
+ *   - a step computes a1 = dropout(GELU(z1)) under the same mask key as the BatchNorm step (one (seed, step): the same masks),
+ *     dz1 = (dz2 W2) * mask / (1 - rate) * GELU'(z1), and fc1.bias has a real gradient, db1 = sum_b dz1, summed in a fixed order;
+ *   - import / import_optimizer refuse any bn1.* key by name; export / export_optimizer write the six tensors in the order above and
+ *     relax_head_train_export_numel reports that count; counters[0] (num_batches_tracked) stays 0;
+ *   - relax_head_train_bn_pass checks its arguments and returns RELAX_OK without a launch, as torch.optim.swa_utils.update_bn returns
+ *     at once for a model without BatchNorm.  Waits for the device. */
+int relax_head_train_init_ex(relax_handle* h, int input_features, int hidden_features, int max_batch, int batchnorm);
+/* *batchnorm = 1 for a state with bn1, 0 for a plain one; RELAX_ERR_INVALID without a state. */
+int relax_head_train_arch(relax_handle* h, int* batchnorm);
 /* Loads a state dict (the keys relax_load_mlp_head takes; HOST pointers) into a set: the initial model, or the checkpoint
  * fine_tune.py:130-136 starts from.  Into set 0 it also zeroes the momentum buffers, Adam's second moments and its step count (a new optimizer).  Waits for the device. */
 int relax_head_train_import(relax_handle* h, int set, const float* const* tensors, const char* const* names, const int64_t* numels, int n,
@@ -585,7 +601,8 @@ int relax_head_train_eval(relax_handle* h, int set, const float* xp, const float
                           float rank_w, float* pred, relax_stream stream);
 /* torch.optim.swa_utils.update_bn (model_regression.py:459), one batch per call: with reset != 0 first running_mean = 0,
  * running_var = 1, num_batches_tracked = 0; then (B > 0) a train-mode forward through bn1 whose momentum is
- * 1 / num_batches_tracked.  B = 0 only resets. */
+ * 1 / num_batches_tracked.  B = 0 only resets.  On a plain state (relax_head_train_init_ex, batchnorm 0) the arguments are checked
+ * and RELAX_OK returned with no launch: update_bn likewise returns at once for a model without BatchNorm. */
 int relax_head_train_bn_pass(relax_handle* h, int set, int reset, const float* xp, int n, const int32_t* index, int B, relax_stream stream);
 /* swa_model.update_parameters(model) (model_regression.py:410): set 1 <- running average of set 0's parameters (buffers are
  * not averaged: AveragedModel's use_buffers=False), n_averaged += 1.  One launch over all parameters. */

@@ -76,6 +76,8 @@ PROTOTYPES = {
     "relax_head_fit_scaler": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "relax_head_train_transform": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp]),
     "relax_head_train_init": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_int]),
+    "relax_head_train_init_ex": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "relax_head_train_arch": (C.c_int, [c_vp, C.POINTER(C.c_int)]),
     "relax_head_train_import": (C.c_int, [c_vp, C.c_int, C.POINTER(c_vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
                                           C.c_int64, C.c_int64]),
     "relax_head_train_export_numel": (C.c_int64, [c_vp]),

@@ -4,6 +4,9 @@
 //   src/model_regression.py:37-58 Mlp: fc1 -> BatchNorm1d(eval) -> GELU -> fc2 -> GELU -> fc3   (dropout is identity in eval)
 //   src/demo_test.py:25-35        fix_state_dict: 'module.' prefix stripped, 'n_averaged' dropped
 // fc1/fc2 run on the contraction kernel (BatchNorm folded into fc1, GELU in the epilogue); fc3 is a 128-long dot product.
+// A state dict without bn1 keys is the plain Mlp of src/model_regression_simple.py:37-58 (fc1 -> GELU -> fc2 -> GELU -> fc3): the
+// same launches with fc1 unfolded.
+#include <algorithm>
 #include <cmath>
 
 #include "relax_internal.h"
@@ -73,12 +76,18 @@ int relax_load_mlp_head(relax_handle* h, const float* const* tensors, const char
     const int H1 = (int)(nw1 / F);
     const int H2 = H1 / 2;
     RELAX_REQUIRE(h, H1 % 64 == 0 && H2 % 64 == 0, "mlp head: hidden sizes %d/%d must be multiples of 64", H1, H2);
+    // no bn1.* key at all: the plain Mlp of src/model_regression_simple.py:37-58; some but not all of the four: refused, by the missing key
+    bool plain = true;
+    for (const auto& kv : sd.t) plain = plain && kv.first.rfind("bn1.", 0) != 0;
     const float *w1 = get("fc1.weight", (int64_t)H1 * F), *b1 = get("fc1.bias", H1);
-    const float *g = get("bn1.weight", H1), *be = get("bn1.bias", H1), *mu = get("bn1.running_mean", H1),
-                *var = get("bn1.running_var", H1);
+    const float *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
+    if (!plain) {
+        g = get("bn1.weight", H1), be = get("bn1.bias", H1), mu = get("bn1.running_mean", H1), var = get("bn1.running_var", H1);
+        if (!g || !be || !mu || !var) return RELAX_ERR_INVALID;
+    }
     const float *w2 = get("fc2.weight", (int64_t)H2 * H1), *b2 = get("fc2.bias", H2);
     const float *w3 = get("fc3.weight", H2), *b3 = get("fc3.bias", 1);
-    if (!w1 || !b1 || !g || !be || !mu || !var || !w2 || !b2 || !w3 || !b3) return RELAX_ERR_INVALID;
+    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3) return RELAX_ERR_INVALID;
     HeadW& hw = h->head;
     hw.F = F;
     hw.Fpad = ((F + 31) / 32) * 32;
@@ -86,7 +95,12 @@ int relax_load_mlp_head(relax_handle* h, const float* const* tensors, const char
     hw.H2 = H2;
     // fold BatchNorm1d (eval) into fc1: y = (x W^T + b - mu) * s + beta, s = gamma / sqrt(var + eps)   (host_logic.cpp)
     std::vector<float> w1p((size_t)H1 * hw.Fpad), b1p(H1);
-    host::fold_fc_bn(w1, b1, g, be, mu, var, 1e-5f, H1, F, hw.Fpad, w1p.data(), b1p.data());
+    if (plain) {   // nothing to fold: fc1.weight padded to Fpad and fc1.bias as they are, no arithmetic
+        for (int o = 0; o < H1; ++o) std::copy(w1 + (size_t)o * F, w1 + (size_t)(o + 1) * F, w1p.begin() + (size_t)o * hw.Fpad);
+        std::copy(b1, b1 + H1, b1p.begin());
+    } else {
+        host::fold_fc_bn(w1, b1, g, be, mu, var, 1e-5f, H1, F, hw.Fpad, w1p.data(), b1p.data());
+    }
     int rc = hw.mem.upload(h, w1p.data(), w1p.size(), &hw.w1);
     if (rc == RELAX_OK) rc = hw.mem.upload(h, b1p.data(), H1, &hw.b1);
     if (rc == RELAX_OK) rc = hw.mem.upload(h, w2, (size_t)H2 * H1, &hw.w2);

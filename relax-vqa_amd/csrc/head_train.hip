@@ -6,6 +6,7 @@
 //   src/model_regression.py:292-322  train_one_epoch / evaluate
 //   src/model_regression.py:381-389  optim.SGD(momentum=0.9) | optim.Adam, AveragedModel;  :459 torch.optim.swa_utils.update_bn
 //   src/fine_tune.py:151-155         optim.AdamW
+//   src/model_regression_simple.py:37-58   the plain Mlp (bn1 commented out): a state made by relax_head_train_init_ex(batchnorm = 0)
 // Everything of a step is enqueued on the caller's stream; nothing here waits for the device except the entries that
 // say so (init, import, export, loss_read).  All arithmetic is fp32 with fp32 accumulation (fc1 / fc2 forward on the
 // exact-fp32 contraction of gemm.hip whatever "gemm_precision" is set: ht_gemm).
@@ -35,20 +36,22 @@ struct HtLayout {
     size_t w1, b1, gamma, beta, w2, b2, w3, b3, rmean, rvar, n_params, n_all;
 };
 
-HtLayout ht_layout(int Fpad, int H1, int H2) {
+// batchnorm == false: the plain head - the four bn1 blocks are empty (their offsets are never used), n_all == n_params
+HtLayout ht_layout(int Fpad, int H1, int H2, bool batchnorm) {
     HtLayout L{};
+    const size_t bn = batchnorm ? (size_t)H1 : 0;
     size_t o = 0;
     L.w1 = o; o += (size_t)H1 * Fpad;
     L.b1 = o; o += H1;
-    L.gamma = o; o += H1;
-    L.beta = o; o += H1;
+    L.gamma = o; o += bn;
+    L.beta = o; o += bn;
     L.w2 = o; o += (size_t)H2 * H1;
     L.b2 = o; o += H2;
     L.w3 = o; o += H2;
     L.b3 = o; o += 4;   // one float, padded: rmean stays 16-byte aligned
     L.n_params = o;
-    L.rmean = o; o += H1;
-    L.rvar = o; o += H1;
+    L.rmean = o; o += bn;
+    L.rvar = o; o += bn;
     L.n_all = o;
     return L;
 }
@@ -239,6 +242,24 @@ __global__ __launch_bounds__(256) void ht_bn_eval(const float* __restrict__ z1, 
     const int j = (int)(e % H1);
     const float xh = (z1[e] - rmean[j]) / sqrtf(rvar[j] + kBnEps);
     a1[e] = gelu_erf(fmaf(gamma[j], xh, beta[j]));
+}
+
+// The plain head (no bn1) in train mode: a1 = dropout(GELU(z1)), four elements per thread (B * H1 is a multiple of four).  The key of
+// an element is ht_bn_fwd's - (seed, step, layer 0, e) - so one (seed, step) gives both variants the same mask.
+__global__ __launch_bounds__(256) void ht_plain_fwd(const float* __restrict__ z1, int64_t total4, float* __restrict__ a1, HtDrop drop,
+                                                    uint8_t* __restrict__ mask_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total4) return;
+    const float4 z = reinterpret_cast<const float4*>(z1)[i];
+    const float zv[4] = {z.x, z.y, z.z, z.w};
+    float av[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const bool keep = ht_rand(drop.seed, drop.step, 0, (uint64_t)(4 * i + c)) >= drop.threshold;
+        av[c] = keep ? gelu_erf(zv[c]) * drop.scale : 0.f;
+        if (mask_out) mask_out[4 * i + c] = keep ? 1 : 0;   // bytes: the caller's mask need not be 4-byte aligned
+    }
+    reinterpret_cast<float4*>(a1)[i] = make_float4(av[0], av[1], av[2], av[3]);
 }
 
 // one block per row: a2 = dropout(GELU(z2)) (train) or a2 = z2 as the contraction's GELU epilogue left it (eval); p = a2 . w3 + b3
@@ -432,6 +453,48 @@ __global__ __launch_bounds__(256) void ht_bn_bwd(const float* __restrict__ du1, 
     }
 }
 
+// The plain head's backward through fc2 and the first activation, and fc1.bias - which has a real gradient here - in one launch:
+//   dz1[b,j] = keep ? (sum_k dz2[b,k] W2[k,j]) * scale * GELU'(z1[b,j]) : 0     k ascending with fmaf, ht_bwd_u1's order
+//   db1[j]   = sum_b dz1[b,j], then the optimizer's update of fc1.bias[j]
+// A block owns kPbJ = 4 columns j and all B rows: thread (ty, tx) takes column j0 + tx and the rows ty, ty + 64, ... in ascending order;
+// its partial column sum goes to LDS and thread (0, tx) adds the 64 partials in the order of ty.  Nothing atomic, no order that
+// depends on the launch: the same bits on every run.  Runs before ht_update_small, which changes W2.
+constexpr int kPbJ = 4, kPbRows = 256 / kPbJ;
+
+template <class Opt>
+__global__ __launch_bounds__(256) void ht_plain_bwd(const float* __restrict__ dz2, const float* __restrict__ w2, const float* __restrict__ z1,
+                                                    int B, int H1, int H2, HtDrop drop, float* __restrict__ b1, float* __restrict__ m_b1,
+                                                    float* __restrict__ v_b1, Opt opt, float* __restrict__ dz1) {
+    __shared__ float part[kPbRows][kPbJ];
+    const int tx = threadIdx.x & (kPbJ - 1), ty = threadIdx.x / kPbJ;
+    const int j = blockIdx.x * kPbJ + tx;   // H1 % 128 == 0: always a column
+    float colsum = 0.f;
+    for (int b = ty; b < B; b += kPbRows) {
+        const float4* row = reinterpret_cast<const float4*>(dz2 + (int64_t)b * H2);   // H2 % 64 == 0 and dz2 is 16-byte aligned
+        float s = 0.f;
+        for (int k4 = 0; k4 < H2 / 4; ++k4) {
+            const float4 d = row[k4];
+            const float* w = w2 + (int64_t)(4 * k4) * H1 + j;
+            s = fmaf(d.x, w[0], s);
+            s = fmaf(d.y, w[H1], s);
+            s = fmaf(d.z, w[2 * (int64_t)H1], s);
+            s = fmaf(d.w, w[3 * (int64_t)H1], s);
+        }
+        const int64_t e = (int64_t)b * H1 + j;
+        const bool keep = ht_rand(drop.seed, drop.step, 0, (uint64_t)e) >= drop.threshold;
+        const float d1 = keep ? s * drop.scale * gelu_erf_grad(z1[e]) : 0.f;
+        dz1[e] = d1;
+        colsum += d1;
+    }
+    part[ty][tx] = colsum;
+    __syncthreads();
+    if (ty == 0) {
+        float db1 = 0.f;
+        for (int r = 0; r < kPbRows; ++r) db1 += part[r][tx];
+        ht_update(b1, m_b1, v_b1, j, db1, opt);
+    }
+}
+
 // fc2.weight (dW2 = dz2^T a1), fc2.bias, fc3.weight, fc3.bias: gradient and the optimizer's update, one thread per parameter.  These
 // four tensors are contiguous in the set (W2 | b2 | w3 | b3), `par` / `mom` / `var` point at W2.
 template <class Opt>
@@ -597,6 +660,24 @@ HtDrop make_drop(float rate, uint64_t seed, uint64_t step) {
     return d;
 }
 
+struct HtItem {   // a tensor of a state dict and where it sits in a set
+    const char* key;
+    size_t off;
+    int64_t numel;
+};
+
+// A plain state (no bn1) takes no bn1.* tensor: the first such key is refused by name ('module.' stripped as the loaders strip it)
+int ht_refuse_bn_keys(relax_handle* h, const char* what, const char* const* names, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (!names[i]) continue;
+        std::string key(names[i]);
+        if (key.rfind("module.", 0) == 0) key = key.substr(7);
+        RELAX_REQUIRE(h, key.rfind("bn1.", 0) != 0, "%s: key '%s' into a state without BatchNorm (relax_head_train_init_ex, batchnorm 0)", what,
+                      key.c_str());
+    }
+    return RELAX_OK;
+}
+
 int ht_check_batch(relax_handle* h, const char* what, const void* xp, const void* idx, int n, int B, int min_b) {
     const HeadTrain& t = h->head_train;
     RELAX_REQUIRE(h, t.ready, "%s: call relax_head_train_init first", what);
@@ -621,7 +702,7 @@ dim3 gather_grid(int B, int Fpad) { return dim3((unsigned)B, (unsigned)std::min(
 // the parameter part alone - zeros go under the two buffer keys
 int ht_export_block(relax_handle* h, const float* src, bool params_only, float* out) {
     const HeadTrain& t = h->head_train;
-    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2);
+    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2, t.batchnorm);
     float* o = out;
     RELAX_HIP_CHECK(h, hipMemcpy2D(o, sizeof(float) * t.F, src + L.w1, sizeof(float) * t.Fpad, sizeof(float) * t.F, t.H1, hipMemcpyDeviceToHost));
     o += (size_t)t.H1 * t.F;
@@ -633,12 +714,14 @@ int ht_export_block(relax_handle* h, const float* src, bool params_only, float* 
         return e;
     };
     // order of the flat block: fc1.weight [H1,F], fc1.bias, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, fc2.weight, fc2.bias,
-    // fc3.weight, fc3.bias
+    // fc3.weight, fc3.bias; a plain state has no bn1 tensors and writes the other six
     RELAX_HIP_CHECK(h, put(L.b1, t.H1));
-    RELAX_HIP_CHECK(h, put(L.gamma, t.H1));
-    RELAX_HIP_CHECK(h, put(L.beta, t.H1));
-    RELAX_HIP_CHECK(h, put(L.rmean, t.H1));
-    RELAX_HIP_CHECK(h, put(L.rvar, t.H1));
+    if (t.batchnorm) {
+        RELAX_HIP_CHECK(h, put(L.gamma, t.H1));
+        RELAX_HIP_CHECK(h, put(L.beta, t.H1));
+        RELAX_HIP_CHECK(h, put(L.rmean, t.H1));
+        RELAX_HIP_CHECK(h, put(L.rvar, t.H1));
+    }
     RELAX_HIP_CHECK(h, put(L.w2, (size_t)t.H2 * t.H1));
     RELAX_HIP_CHECK(h, put(L.b2, t.H2));
     RELAX_HIP_CHECK(h, put(L.w3, t.H2));
@@ -677,7 +760,7 @@ int ht_step(relax_handle* h, const float* xp, const float* target, int n, const 
             float rank_w, float drop_rate, uint64_t seed, uint64_t step, uint8_t* mask1, uint8_t* mask2, hipStream_t s) {
     HeadTrain& t = h->head_train;
     const int H1 = t.H1, H2 = t.H2, Fpad = t.Fpad;
-    const HtLayout L = ht_layout(Fpad, H1, H2);
+    const HtLayout L = ht_layout(Fpad, H1, H2, t.batchnorm);
     const HtAct A = ht_act(t.max_batch, H1, H2);
     float* P = t.set[0];
     float* M = t.mom;
@@ -686,19 +769,30 @@ int ht_step(relax_handle* h, const float* xp, const float* target, int n, const 
     const HtDrop drop = make_drop(drop_rate, seed, step);
     const int64_t n1 = (int64_t)B * H1, n2 = (int64_t)B * H2;
 
-    hipLaunchKernelGGL(ht_gather, gather_grid(B, Fpad), dim3(256), 0, s, xp, target, index, n, Fpad, t.xb, a + A.yb, t.counters + 0);
+    // a plain state has no num_batches_tracked to tick: counters[0] stays 0
+    hipLaunchKernelGGL(ht_gather, gather_grid(B, Fpad), dim3(256), 0, s, xp, target, index, n, Fpad, t.xb, a + A.yb,
+                       t.batchnorm ? t.counters + 0 : (int64_t*)nullptr);
     RELAX_TRY(ht_gemm(h, t.xb, P + L.w1, P + L.b1, a + A.z1, B, H1, Fpad, 0, s));
-    hipLaunchKernelGGL(ht_bn_fwd, dim3((unsigned)H1), dim3(256), 0, s, a + A.z1, B, H1, P + L.gamma, P + L.beta, P + L.rmean, P + L.rvar,
-                       t.counters + 0, 0, a + A.xhat, a + A.invstd, a + A.a1, drop, mask1);
+    if (t.batchnorm) {
+        hipLaunchKernelGGL(ht_bn_fwd, dim3((unsigned)H1), dim3(256), 0, s, a + A.z1, B, H1, P + L.gamma, P + L.beta, P + L.rmean, P + L.rvar,
+                           t.counters + 0, 0, a + A.xhat, a + A.invstd, a + A.a1, drop, mask1);
+    } else {
+        hipLaunchKernelGGL(ht_plain_fwd, dim3((unsigned)((n1 / 4 + 255) / 256)), dim3(256), 0, s, a + A.z1, n1 / 4, a + A.a1, drop, mask1);
+    }
     RELAX_TRY(ht_gemm(h, a + A.a1, P + L.w2, P + L.b2, a + A.z2, B, H2, H1, 0, s));
     hipLaunchKernelGGL(ht_fwd_tail, dim3((unsigned)B), dim3(256), 0, s, a + A.z2, H2, P + L.w3, P + L.b3, 1, a + A.a2, a + A.p, drop, mask2);
     hipLaunchKernelGGL(ht_criterion, dim3((unsigned)B), dim3(256), 0, s, a + A.p, a + A.yb, B, l1_w, rank_w, a + A.rowloss, a + A.dp);
     hipLaunchKernelGGL(ht_loss_finish, dim3(1), dim3(256), 0, s, a + A.rowloss, B, t.loss, (float*)nullptr);
     hipLaunchKernelGGL(ht_bwd_z2, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, a + A.dp, P + L.w3, a + A.z2, n2, H2, drop, a + A.dz2);
-    hipLaunchKernelGGL(ht_bwd_u1, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, a + A.dz2, P + L.w2, a + A.xhat, P + L.gamma, P + L.beta,
-                       n1, H1, H2, drop, a + A.du1);
-    hipLaunchKernelGGL(ht_bn_bwd<Opt>, dim3((unsigned)H1), dim3(256), 0, s, a + A.du1, a + A.xhat, a + A.invstd, B, H1, P + L.gamma, P + L.beta,
-                       P + L.b1, M + L.gamma, M + L.beta, M + L.b1, V + L.gamma, V + L.beta, V + L.b1, opt, a + A.dz1);
+    if (t.batchnorm) {
+        hipLaunchKernelGGL(ht_bwd_u1, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, a + A.dz2, P + L.w2, a + A.xhat, P + L.gamma, P + L.beta,
+                           n1, H1, H2, drop, a + A.du1);
+        hipLaunchKernelGGL(ht_bn_bwd<Opt>, dim3((unsigned)H1), dim3(256), 0, s, a + A.du1, a + A.xhat, a + A.invstd, B, H1, P + L.gamma, P + L.beta,
+                           P + L.b1, M + L.gamma, M + L.beta, M + L.b1, V + L.gamma, V + L.beta, V + L.b1, opt, a + A.dz1);
+    } else {   // one launch where the BatchNorm step has two: a plain step makes one launch fewer
+        hipLaunchKernelGGL(ht_plain_bwd<Opt>, dim3((unsigned)(H1 / kPbJ)), dim3(256), 0, s, a + A.dz2, P + L.w2, a + A.z1, B, H1, H2, drop,
+                           P + L.b1, M + L.b1, V + L.b1, opt, a + A.dz1);
+    }
     const int n_small = H2 * H1 + 2 * H2 + 1;
     hipLaunchKernelGGL(ht_update_small<Opt>, dim3((unsigned)((n_small + 255) / 256)), dim3(256), 0, s, a + A.dz2, a + A.a1, a + A.a2, a + A.dp, B,
                        H1, H2, P + L.w2, M + L.w2, V + L.w2, opt);
@@ -748,12 +842,12 @@ int relax_head_train_transform(relax_handle* h, const float* x, int n, int F, co
     return RELAX_OK;
 }
 
-int relax_head_train_init(relax_handle* h, int input_features, int hidden_features, int max_batch) {
-    if (!h) return RELAX_ERR_INVALID;
-    RELAX_REQUIRE(h, input_features > 0 && hidden_features > 0, "relax_head_train_init: bad arguments");
-    RELAX_REQUIRE(h, hidden_features % 128 == 0, "relax_head_train_init: hidden_features %d must be a multiple of 128 (fc2 is half of it, "
-                  "and the contraction takes multiples of 64)", hidden_features);
-    RELAX_REQUIRE(h, max_batch >= 2 && max_batch <= HeadTrain::kMaxBatch, "relax_head_train_init: max_batch %d outside 2..%d", max_batch,
+// relax_head_train_init and relax_head_train_init_ex; `what` names the entry in the messages
+static int ht_init(relax_handle* h, const char* what, int input_features, int hidden_features, int max_batch, bool batchnorm) {
+    RELAX_REQUIRE(h, input_features > 0 && hidden_features > 0, "%s: bad arguments", what);
+    RELAX_REQUIRE(h, hidden_features % 128 == 0, "%s: hidden_features %d must be a multiple of 128 (fc2 is half of it, "
+                  "and the contraction takes multiples of 64)", what, hidden_features);
+    RELAX_REQUIRE(h, max_batch >= 2 && max_batch <= HeadTrain::kMaxBatch, "%s: max_batch %d outside 2..%d", what, max_batch,
                   HeadTrain::kMaxBatch);
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     RELAX_HIP_CHECK(h, hipDeviceSynchronize());
@@ -764,7 +858,8 @@ int relax_head_train_init(relax_handle* h, int input_features, int hidden_featur
     t.H1 = hidden_features;
     t.H2 = hidden_features / 2;
     t.max_batch = max_batch;
-    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2);
+    t.batchnorm = batchnorm;
+    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2, t.batchnorm);
     t.n_params = L.n_params;
     t.n_all = L.n_all;
     int rc = RELAX_OK;
@@ -776,7 +871,7 @@ int relax_head_train_init(relax_handle* h, int input_features, int hidden_featur
             return nullptr;
         }
         if (hipMemset(p, 0, bytes) != hipSuccess) {
-            set_error(h, "relax_head_train_init: hipMemset failed");
+            set_error(h, "%s: hipMemset failed", what);
             rc = RELAX_ERR_HIP;
         }
         return p;
@@ -792,7 +887,7 @@ int relax_head_train_init(relax_handle* h, int input_features, int hidden_featur
     // chip at most once (768 work units of 64 KiB = 48 MiB): sized here, a step never finds it too small and so never waits for the device
     if (rc == RELAX_OK) rc = ensure_buf(h, h->splitk_ws, kSplitKWsFloor);
     if (rc == RELAX_OK && hipDeviceSynchronize() != hipSuccess) {   // the zero fills above have completed before anything is enqueued on another stream
-        set_error(h, "relax_head_train_init: hipDeviceSynchronize failed");
+        set_error(h, "%s: hipDeviceSynchronize failed", what);
         rc = RELAX_ERR_HIP;
     }
     if (rc != RELAX_OK) {
@@ -803,6 +898,26 @@ int relax_head_train_init(relax_handle* h, int input_features, int hidden_featur
     return RELAX_OK;
 }
 
+int relax_head_train_init(relax_handle* h, int input_features, int hidden_features, int max_batch) {
+    if (!h) return RELAX_ERR_INVALID;
+    return ht_init(h, "relax_head_train_init", input_features, hidden_features, max_batch, true);
+}
+
+int relax_head_train_init_ex(relax_handle* h, int input_features, int hidden_features, int max_batch, int batchnorm) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, batchnorm == 0 || batchnorm == 1, "relax_head_train_init_ex: batchnorm %d (1: the Mlp with bn1, 0: the plain Mlp)",
+                  batchnorm);
+    return ht_init(h, "relax_head_train_init_ex", input_features, hidden_features, max_batch, batchnorm != 0);
+}
+
+int relax_head_train_arch(relax_handle* h, int* batchnorm) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, h->head_train.ready, "relax_head_train_arch: call relax_head_train_init first");
+    RELAX_REQUIRE(h, batchnorm, "relax_head_train_arch: bad arguments");
+    *batchnorm = h->head_train.batchnorm ? 1 : 0;
+    return RELAX_OK;
+}
+
 int relax_head_train_import(relax_handle* h, int set, const float* const* tensors, const char* const* names, const int64_t* numels, int n,
                             int64_t num_batches_tracked, int64_t n_averaged) {
     if (!h) return RELAX_ERR_INVALID;
@@ -810,21 +925,28 @@ int relax_head_train_import(relax_handle* h, int set, const float* const* tensor
     RELAX_REQUIRE(h, t.ready, "relax_head_train_import: call relax_head_train_init first");
     RELAX_REQUIRE(h, set >= 0 && set < HeadTrain::kSets && tensors && names && numels && n > 0, "relax_head_train_import: bad arguments");
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    if (!t.batchnorm) {
+        RELAX_TRY(ht_refuse_bn_keys(h, "relax_head_train_import", names, n));
+        RELAX_REQUIRE(h, num_batches_tracked == 0, "relax_head_train_import: num_batches_tracked %lld into a state without BatchNorm",
+                      (long long)num_batches_tracked);
+    }
     host::StateDict sd;
     for (int i = 0; i < n; ++i) {
         if (names[i] && std::string(names[i]) == "n_averaged") continue;
         sd.add(names[i], tensors[i], numels[i], /*strip_module=*/true);
     }
-    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2);
-    struct Item { const char* key; size_t off; int64_t numel; };
-    const Item items[] = {{"fc1.bias", L.b1, t.H1}, {"bn1.weight", L.gamma, t.H1}, {"bn1.bias", L.beta, t.H1},
-                          {"bn1.running_mean", L.rmean, t.H1}, {"bn1.running_var", L.rvar, t.H1},
-                          {"fc2.weight", L.w2, (int64_t)t.H2 * t.H1}, {"fc2.bias", L.b2, t.H2}, {"fc3.weight", L.w3, t.H2},
-                          {"fc3.bias", L.b3, 1}};
+    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2, t.batchnorm);
+    std::vector<HtItem> items = {{"fc1.bias", L.b1, t.H1}};
+    if (t.batchnorm) {
+        items.insert(items.end(), {{"bn1.weight", L.gamma, t.H1}, {"bn1.bias", L.beta, t.H1}, {"bn1.running_mean", L.rmean, t.H1},
+                                   {"bn1.running_var", L.rvar, t.H1}});
+    }
+    items.insert(items.end(), {{"fc2.weight", L.w2, (int64_t)t.H2 * t.H1}, {"fc2.bias", L.b2, t.H2}, {"fc3.weight", L.w3, t.H2},
+                               {"fc3.bias", L.b3, 1}});
     std::string err;
     const float* w1 = sd.get("fc1.weight", (int64_t)t.H1 * t.F, err, "mlp head state dict");
     RELAX_REQUIRE(h, w1, "%s", err.c_str());
-    for (const Item& it : items) {
+    for (const HtItem& it : items) {
         const float* p = sd.get(it.key, it.numel, err, "mlp head state dict");
         RELAX_REQUIRE(h, p, "%s", err.c_str());
     }
@@ -833,7 +955,7 @@ int relax_head_train_import(relax_handle* h, int set, const float* const* tensor
     RELAX_HIP_CHECK(h, hipMemset(dst, 0, sizeof(float) * L.n_all));
     RELAX_HIP_CHECK(h, hipMemcpy2D(dst + L.w1, sizeof(float) * t.Fpad, w1, sizeof(float) * t.F, sizeof(float) * t.F, t.H1,
                                    hipMemcpyHostToDevice));
-    for (const Item& it : items) {
+    for (const HtItem& it : items) {
         const float* p = sd.get(it.key, it.numel, err, "mlp head state dict");
         RELAX_HIP_CHECK(h, hipMemcpy(dst + it.off, p, sizeof(float) * it.numel, hipMemcpyHostToDevice));
     }
@@ -851,7 +973,7 @@ int relax_head_train_import(relax_handle* h, int set, const float* const* tensor
 int64_t relax_head_train_export_numel(relax_handle* h) {
     if (!h || !h->head_train.ready) return -1;
     const HeadTrain& t = h->head_train;
-    return (int64_t)t.H1 * t.F + 5 * (int64_t)t.H1 + (int64_t)t.H2 * t.H1 + 2 * (int64_t)t.H2 + 1;
+    return (int64_t)t.H1 * t.F + (t.batchnorm ? 5 : 1) * (int64_t)t.H1 + (int64_t)t.H2 * t.H1 + 2 * (int64_t)t.H2 + 1;
 }
 
 int relax_head_train_export(relax_handle* h, int set, int momentum, float* out, int64_t* counters, relax_stream stream) {
@@ -886,11 +1008,12 @@ int relax_head_train_import_optimizer(relax_handle* h, const float* const* exp_a
     RELAX_REQUIRE(h, t.ready, "relax_head_train_import_optimizer: call relax_head_train_init first");
     RELAX_REQUIRE(h, exp_avg && exp_avg_sq && names && numels && n > 0 && t_in >= 0, "relax_head_train_import_optimizer: bad arguments");
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
-    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2);
-    struct Item { const char* key; size_t off; int64_t numel; };
-    const Item items[] = {{"fc1.bias", L.b1, t.H1}, {"bn1.weight", L.gamma, t.H1}, {"bn1.bias", L.beta, t.H1},
-                          {"fc2.weight", L.w2, (int64_t)t.H2 * t.H1}, {"fc2.bias", L.b2, t.H2}, {"fc3.weight", L.w3, t.H2},
-                          {"fc3.bias", L.b3, 1}};
+    if (!t.batchnorm) RELAX_TRY(ht_refuse_bn_keys(h, "relax_head_train_import_optimizer", names, n));
+    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2, t.batchnorm);
+    std::vector<HtItem> items = {{"fc1.bias", L.b1, t.H1}};
+    if (t.batchnorm) items.insert(items.end(), {{"bn1.weight", L.gamma, t.H1}, {"bn1.bias", L.beta, t.H1}});
+    items.insert(items.end(), {{"fc2.weight", L.w2, (int64_t)t.H2 * t.H1}, {"fc2.bias", L.b2, t.H2}, {"fc3.weight", L.w3, t.H2},
+                               {"fc3.bias", L.b3, 1}});
     host::StateDict sd[2];
     for (int i = 0; i < n; ++i) {
         sd[0].add(names[i], exp_avg[i], numels[i], /*strip_module=*/true);
@@ -900,7 +1023,7 @@ int relax_head_train_import_optimizer(relax_handle* h, const float* const* exp_a
     std::string err;
     for (int k = 0; k < 2; ++k) {   // every tensor is there with its size before anything is written
         RELAX_REQUIRE(h, sd[k].get("fc1.weight", (int64_t)t.H1 * t.F, err, what[k]), "%s", err.c_str());
-        for (const Item& it : items) RELAX_REQUIRE(h, sd[k].get(it.key, it.numel, err, what[k]), "%s", err.c_str());
+        for (const HtItem& it : items) RELAX_REQUIRE(h, sd[k].get(it.key, it.numel, err, what[k]), "%s", err.c_str());
     }
     RELAX_HIP_CHECK(h, hipDeviceSynchronize());
     float* dst[2] = {t.mom, t.var};
@@ -908,7 +1031,7 @@ int relax_head_train_import_optimizer(relax_handle* h, const float* const* exp_a
         RELAX_HIP_CHECK(h, hipMemset(dst[k], 0, sizeof(float) * L.n_params));
         RELAX_HIP_CHECK(h, hipMemcpy2D(dst[k] + L.w1, sizeof(float) * t.Fpad, sd[k].get("fc1.weight", -1, err, what[k]), sizeof(float) * t.F,
                                        sizeof(float) * t.F, t.H1, hipMemcpyHostToDevice));
-        for (const Item& it : items)
+        for (const HtItem& it : items)
             RELAX_HIP_CHECK(h, hipMemcpy(dst[k] + it.off, sd[k].get(it.key, it.numel, err, what[k]), sizeof(float) * it.numel, hipMemcpyHostToDevice));
     }
     t.adam_t = t_in;
@@ -984,15 +1107,19 @@ int relax_head_train_eval(relax_handle* h, int set, const float* xp, const float
     hipStream_t s = static_cast<hipStream_t>(stream);
     HeadTrain& t = h->head_train;
     const int H1 = t.H1, H2 = t.H2, Fpad = t.Fpad;
-    const HtLayout L = ht_layout(Fpad, H1, H2);
+    const HtLayout L = ht_layout(Fpad, H1, H2, t.batchnorm);
     const HtAct A = ht_act(t.max_batch, H1, H2);
     const float* P = t.set[set];
     float* a = t.act;
     const int64_t n1 = (int64_t)B * H1;
     hipLaunchKernelGGL(ht_gather, gather_grid(B, Fpad), dim3(256), 0, s, xp, target, index, n, Fpad, t.xb, a + A.yb, (int64_t*)nullptr);
-    RELAX_TRY(ht_gemm(h, t.xb, P + L.w1, P + L.b1, a + A.z1, B, H1, Fpad, 0, s));
-    hipLaunchKernelGGL(ht_bn_eval, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, a + A.z1, n1, H1, P + L.gamma, P + L.beta, P + L.rmean,
-                       P + L.rvar, a + A.a1);
+    if (t.batchnorm) {
+        RELAX_TRY(ht_gemm(h, t.xb, P + L.w1, P + L.b1, a + A.z1, B, H1, Fpad, 0, s));
+        hipLaunchKernelGGL(ht_bn_eval, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, a + A.z1, n1, H1, P + L.gamma, P + L.beta, P + L.rmean,
+                           P + L.rvar, a + A.a1);
+    } else {   // a1 = GELU(z1): the contraction's own epilogue, as fc2 below
+        RELAX_TRY(ht_gemm(h, t.xb, P + L.w1, P + L.b1, a + A.a1, B, H1, Fpad, 2, s));
+    }
     RELAX_TRY(ht_gemm(h, a + A.a1, P + L.w2, P + L.b2, a + A.z2, B, H2, H1, 2, s));
     hipLaunchKernelGGL(ht_fwd_tail, dim3((unsigned)B), dim3(256), 0, s, a + A.z2, H2, P + L.w3, P + L.b3, 0, a + A.a2, pred, HtDrop{},
                        (uint8_t*)nullptr);
@@ -1009,10 +1136,14 @@ int relax_head_train_bn_pass(relax_handle* h, int set, int reset, const float* x
     HeadTrain& t = h->head_train;
     RELAX_REQUIRE(h, t.ready, "relax_head_train_bn_pass: call relax_head_train_init first");
     RELAX_REQUIRE(h, set >= 0 && set < HeadTrain::kSets, "relax_head_train_bn_pass: bad set %d", set);
+    if (!t.batchnorm) {   // no BatchNorm to refresh (update_bn returns at once for such a model): the arguments are checked, nothing is launched
+        if (B > 0) RELAX_TRY(ht_check_batch(h, "relax_head_train_bn_pass", xp, index, n, B, 2));
+        return RELAX_OK;
+    }
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int H1 = t.H1, H2 = t.H2, Fpad = t.Fpad;
-    const HtLayout L = ht_layout(Fpad, H1, H2);
+    const HtLayout L = ht_layout(Fpad, H1, H2, t.batchnorm);
     const HtAct A = ht_act(t.max_batch, H1, H2);
     float* P = t.set[set];
     int64_t* nbt = t.counters + 2 * set;
@@ -1084,7 +1215,7 @@ int relax_head_train_dw1(relax_handle* h, int fused, int B, float lr, float mome
     RELAX_REQUIRE(h, B >= 2 && B <= t.max_batch, "relax_head_train_dw1: batch of %d rows (this state takes 2..%d)", B, t.max_batch);
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2);
+    const HtLayout L = ht_layout(t.Fpad, t.H1, t.H2, t.batchnorm);
     const HtAct A = ht_act(t.max_batch, t.H1, t.H2);
     const HtSgd sgd{lr, momentum, weight_decay};
     const dim3 grid((unsigned)(t.H1 / kDwTJ), (unsigned)((t.Fpad + kDwTF - 1) / kDwTF));

@@ -278,6 +278,7 @@ struct HeadTrain {
     static constexpr int kSets = 3;
     static constexpr int kMaxBatch = 1024;
     bool ready = false;
+    bool batchnorm = true;            // false: the plain Mlp of model_regression_simple.py (no bn1; relax_head_train_init_ex)
     int F = 0, Fpad = 0, H1 = 0, H2 = 0, max_batch = 0;
     size_t n_params = 0, n_all = 0;   // floats of the parameter part / of the whole set
     float* set[kSets] = {};

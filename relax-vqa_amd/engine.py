@@ -265,7 +265,8 @@ class RelaxEngine:
         return tuple(int(x.value) for x in v)
 
     def load_mlp_head(self, state_dict, scaler_scale, scaler_min, imputer_statistics=None):
-        """state_dict: the reference Mlp's keys (src/model_regression.py:37-58); scaler_* / imputer_statistics: the
+        """state_dict: the reference Mlp's keys (src/model_regression.py:37-58; without any bn1 key: the plain Mlp of
+        src/model_regression_simple.py, loaded unfolded); scaler_* / imputer_statistics: the
         MinMaxScaler.scale_/.min_ and SimpleImputer.statistics_ arrays of the reference's model/scaler/*.pkl."""
         ptrs, names, numels, n, keep = self._marshal_state_dict(state_dict)
         sc = np.ascontiguousarray(scaler_scale, dtype=np.float64)
@@ -321,8 +322,15 @@ class RelaxEngine:
         from . import head_train
         return head_train.fit_head(self, features, mos, config)
 
+    def fit_head_simple(self, features, mos, config=None):
+        """Trains the plain head (no BatchNorm) on one 80/20 validation split, as the reference's model_regression_simple.py does;
+        see head_train.fit_head_simple."""
+        from . import head_train
+        return head_train.fit_head_simple(self, features, mos, config)
+
     def fine_tune_head(self, state_dict, features, mos, config=None):
-        """Fine-tunes a trained head as the reference's fine_tune_model does; see head_train.fine_tune_head."""
+        """Fine-tunes a trained head as the reference's fine_tune_model does (a state dict without bn1 keys: the plain head); see
+        head_train.fine_tune_head."""
         from . import head_train
         return head_train.fine_tune_head(self, state_dict, features, mos, config)
 
@@ -350,7 +358,7 @@ class RelaxEngine:
         return metrics.holdout_protocol(self, features, mos, config, n_repeats, test_size, groups, drop_indices)
 
     def load_fitted_head(self, result):
-        """load_mlp_head on what fit_head / fine_tune_head returned."""
+        """load_mlp_head on what fit_head / fit_head_simple / fine_tune_head returned (either variant of the head)."""
         state_dict, scaler = result[0], result[1]
         self.load_mlp_head(state_dict, scaler["scale"], scaler["min"], scaler["imputer_statistics"])
 

@@ -26,12 +26,22 @@ from . import metrics as _metrics
 DEFAULTS = dict(n_splits=10, batch_size=256, epochs=20, hidden_features=256, drop_rate=0.1, loss_type="MAERankLoss",
                 optimizer_type="sgd", select_criteria="bykrcc", initial_lr=1e-1, weight_decay=0.005, patience=5, use_swa=True,
                 l1_w=0.6, rank_w=1.0, momentum=0.9, seed=0, logistic_fit="scipy",
-                beta1=0.9, beta2=0.999, adam_eps=1e-8, lr_step_size=2, lr_gamma=0.95)   # optimizer_type 'adam' only
+                beta1=0.9, beta2=0.999, adam_eps=1e-8, lr_step_size=2, lr_gamma=0.95,   # optimizer_type 'adam' only
+                batchnorm=True, validation="kfold")   # False / 'holdout': model_regression_simple.py's head and split (SIMPLE_DEFAULTS)
 LIVE, SWA, BEST = 0, 1, 2      # parameter sets of the device state
 ETA_MIN = 1e-5                 # CosineAnnealingLR(eta_min=1e-5), model_regression.py:383
 SWA_ANNEAL_EPOCHS = 10         # SWALR's default anneal_epochs
 STATE_KEYS = ("fc1.weight", "fc1.bias", "bn1.weight", "bn1.bias", "bn1.running_mean", "bn1.running_var", "fc2.weight", "fc2.bias",
               "fc3.weight", "fc3.bias")
+PLAIN_STATE_KEYS = tuple(k for k in STATE_KEYS if not k.startswith("bn1."))   # the plain Mlp of model_regression_simple.py:37-58
+# model_regression_simple.py's protocol (its argparse defaults, :735-742, where they differ from model_regression.py's): the plain
+# head, one train_test_split(test_size=0.2, random_state=42) for validation instead of the K folds
+SIMPLE_DEFAULTS = dict(batchnorm=False, validation="holdout", epochs=120, initial_lr=1e-2, weight_decay=5e-4)
+
+
+def is_plain_state_dict(state_dict):
+    """True when no key of the state dict (a 'module.' prefix aside) belongs to bn1: the plain Mlp's."""
+    return not any((k[7:] if k.startswith("module.") else k).startswith("bn1.") for k in state_dict)
 
 
 # ---- pure host arithmetic ---------------------------------------------------------------------------------------------
@@ -128,9 +138,10 @@ def epoch_batches(n, batch_size, rng=None):
     return batches
 
 
-def init_state_dict(input_features, hidden_features=256, seed=0):
+def init_state_dict(input_features, hidden_features=256, seed=0, batchnorm=True):
     """A fresh Mlp's state dict: nn.Linear's default U(-1/sqrt(fan_in), 1/sqrt(fan_in)) for weights and biases, BatchNorm
-    gamma 1 / beta 0 / mean 0 / var 1 - drawn from numpy's RandomState(seed), not torch's generator."""
+    gamma 1 / beta 0 / mean 0 / var 1 - drawn from numpy's RandomState(seed), not torch's generator.  batchnorm=False: the plain
+    Mlp's six tensors, the same draws."""
     rng = np.random.RandomState(seed)
     h1, h2 = hidden_features, hidden_features // 2
 
@@ -140,6 +151,8 @@ def init_state_dict(input_features, hidden_features=256, seed=0):
     w1, b1 = lin(h1, input_features)
     w2, b2 = lin(h2, h1)
     w3, b3 = lin(1, h2)
+    if not batchnorm:
+        return {"fc1.weight": w1, "fc1.bias": b1, "fc2.weight": w2, "fc2.bias": b2, "fc3.weight": w3, "fc3.bias": b3}
     return {"fc1.weight": w1, "fc1.bias": b1, "bn1.weight": np.ones(h1, np.float32), "bn1.bias": np.zeros(h1, np.float32),
             "bn1.running_mean": np.zeros(h1, np.float32), "bn1.running_var": np.ones(h1, np.float32),
             "bn1.num_batches_tracked": np.int64(0), "fc2.weight": w2, "fc2.bias": b2, "fc3.weight": w3, "fc3.bias": b3}
@@ -158,15 +171,29 @@ class HeadTrainer:
     """The training state of one Mlp inside a RelaxEngine (relax_head_train_*).  `xp` is the matrix after
     RelaxEngine.head_train_transform ([n, Fpad] fp32 on the device), `y` its targets (fp32 [n] on the device).
     An engine holds ONE training state: creating another HeadTrainer on it replaces the state, and every method of the
-    earlier object raises from then on (its matrices may have another width than the kernels would stride by)."""
+    earlier object raises from then on (its matrices may have another width than the kernels would stride by).
+    batchnorm=False: the plain Mlp of model_regression_simple.py (no bn1) - the state holds the six tensors of PLAIN_STATE_KEYS,
+    fc1.bias has a real gradient, update_bn does nothing; every method acts on whichever variant the state has."""
 
-    def __init__(self, engine, input_features, hidden_features=256, max_batch=256):
+    def __init__(self, engine, input_features, hidden_features=256, max_batch=256, batchnorm=True):
         self.eng, self.lib, self.h = engine, engine.lib, engine.h
         self.F, self.H1, self.H2 = int(input_features), int(hidden_features), int(hidden_features) // 2
         self.max_batch = int(max_batch)
         self.Fpad = (self.F + 31) // 32 * 32
-        engine._check(self.lib.relax_head_train_init(self.h, self.F, self.H1, self.max_batch), "relax_head_train_init")
+        self.batchnorm = bool(batchnorm)
+        self.keys = STATE_KEYS if self.batchnorm else PLAIN_STATE_KEYS
+        if self.batchnorm:
+            engine._check(self.lib.relax_head_train_init(self.h, self.F, self.H1, self.max_batch), "relax_head_train_init")
+        else:
+            engine._check(self.lib.relax_head_train_init_ex(self.h, self.F, self.H1, self.max_batch, 0), "relax_head_train_init_ex")
         engine._head_train_generation = self.generation = getattr(engine, "_head_train_generation", 0) + 1
+
+    def arch(self):
+        """The variant the device state reports (relax_head_train_arch): True with bn1, False for the plain head."""
+        self._live()
+        out = C.c_int(-1)
+        self.eng._check(self.lib.relax_head_train_arch(self.h, C.byref(out)), "relax_head_train_arch")
+        return bool(out.value)
 
     def _live(self, xp=None, y=None):
         if getattr(self.eng, "_head_train_generation", None) != self.generation:
@@ -193,7 +220,9 @@ class HeadTrainer:
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
         nbt = int(np.asarray(torch.as_tensor(sd.get("bn1.num_batches_tracked", 0)).cpu()))
         nav = int(np.asarray(torch.as_tensor(sd.get("n_averaged", 0)).cpu()))
-        ptrs, names, numels, n, keep = self.eng._marshal_state_dict({k: v for k, v in sd.items() if k in STATE_KEYS})
+        # a plain trainer hands bn1's tensors on as well: relax_head_train_import refuses them by name rather than dropping them
+        wanted = STATE_KEYS if self.batchnorm else PLAIN_STATE_KEYS + tuple(k for k in STATE_KEYS if k.startswith("bn1."))
+        ptrs, names, numels, n, keep = self.eng._marshal_state_dict({k: v for k, v in sd.items() if k in wanted})
         self.eng._check(self.lib.relax_head_train_import(self.h, which, ptrs, names, numels, n, nbt, nav), "relax_head_train_import")
         del keep
 
@@ -206,10 +235,11 @@ class HeadTrainer:
         return self._unflatten(flat), counters
 
     def _unflatten(self, flat):
-        shapes = [(self.H1, self.F), (self.H1,), (self.H1,), (self.H1,), (self.H1,), (self.H1,), (self.H2, self.H1), (self.H2,),
-                  (1, self.H2), (1,)]
+        shapes = {"fc1.weight": (self.H1, self.F), "fc2.weight": (self.H2, self.H1), "fc2.bias": (self.H2,), "fc3.weight": (1, self.H2),
+                  "fc3.bias": (1,)}
         out, o = {}, 0
-        for key, shape in zip(STATE_KEYS, shapes):
+        for key in self.keys:
+            shape = shapes.get(key, (self.H1,))
             size = int(np.prod(shape))
             out[key] = flat[o:o + size].reshape(shape).copy()
             o += size
@@ -217,9 +247,10 @@ class HeadTrainer:
 
     def export_state(self, which=LIVE):
         """The set as host fp32 arrays under the reference's key names and shapes (+ bn1.num_batches_tracked; n_averaged for
-        the SWA set).  RelaxEngine.load_mlp_head takes it as it is."""
+        the SWA set; a plain trainer: the six tensors, no bn1 key).  RelaxEngine.load_mlp_head takes it as it is."""
         out, counters = self._export_flat(which, False)
-        out["bn1.num_batches_tracked"] = np.int64(counters[0])
+        if self.batchnorm:
+            out["bn1.num_batches_tracked"] = np.int64(counters[0])
         if which == SWA:
             out["n_averaged"] = np.int64(counters[1])
         return out
@@ -277,9 +308,11 @@ class HeadTrainer:
     def import_optimizer_state(self, state):
         """What export_optimizer_state returned (or the same from torch), after import_state, which starts a new optimizer."""
         self._live()
-        keys = [k for k in STATE_KEYS if not k.startswith("bn1.running_")]
         strip = lambda d: {(k[7:] if k.startswith("module.") else k): v for k, v in d.items()}
         avg, sq = strip(state["exp_avg"]), strip(state["exp_avg_sq"])
+        keys = [k for k in self.keys if not k.startswith("bn1.running_")]
+        if not self.batchnorm:   # bn1's moments, if the caller brings them, go along: the library refuses them by name
+            keys += [k for k in ("bn1.weight", "bn1.bias") if k in avg and k in sq]
         ptrs, names, numels, n, keep = self.eng._marshal_state_dict({k: avg[k] for k in keys})
         ptrs_sq, _, numels_sq, _, keep_sq = self.eng._marshal_state_dict({k: sq[k] for k in keys})
         if list(numels) != list(numels_sq):
@@ -313,7 +346,11 @@ class HeadTrainer:
         self.eng._check(rc, "relax_head_train_bn_pass")
 
     def update_bn(self, xp, batches, which):
-        """torch.optim.swa_utils.update_bn over `batches` (lists of rows)."""
+        """torch.optim.swa_utils.update_bn over `batches` (lists of rows); nothing on a plain trainer, as update_bn returns at once
+        for a model without BatchNorm."""
+        if not self.batchnorm:
+            self._live()
+            return
         self.bn_pass(None, None, which, reset=True)
         for b in batches:
             self.bn_pass(xp, b, which)
@@ -380,6 +417,10 @@ def _config(config):
         raise ValueError(f"head training: select_criteria {cfg['select_criteria']!r}")
     if cfg["logistic_fit"] not in ("scipy", "device"):
         raise ValueError(f"head training: logistic_fit {cfg['logistic_fit']!r} (scipy | device)")
+    if not isinstance(cfg["batchnorm"], (bool, np.bool_)):
+        raise ValueError(f"head training: batchnorm {cfg['batchnorm']!r} (True | False)")
+    if cfg["validation"] not in ("kfold", "holdout"):
+        raise ValueError(f"head training: validation {cfg['validation']!r} (kfold | holdout)")
     if cfg["select_criteria"] == "byrmse" and cfg["logistic_fit"] == "scipy" and not _have_scipy():
         cfg["logistic_fit"] = "device"   # no curve_fit here: the device fit (csrc/metrics.hip) takes its place
     return cfg
@@ -438,13 +479,18 @@ def fit_head(engine, features, mos, config=None):
     leaves it, or anything torch.as_tensor takes), mos [n].  Returns (state_dict, scaler, history): the kept model under the
     reference's key names, {'imputer_statistics', 'scale', 'min'} float64 [F], and per-fold 'train_loss' / 'val_loss' /
     'metric' / 'lr' lists plus 'best' = (fold, epoch, metric) and 'predictions', the kept model's eval-mode scores of every row
-    as the training path computes them (host arrays only: nothing of the device state outlives the call)."""
+    as the training path computes them (host arrays only: nothing of the device state outlives the call).
+    config['batchnorm'] = False trains the plain Mlp of model_regression_simple.py (six tensors, no bn1 key); config['validation']
+    = 'holdout' runs the body once on that script's single 80/20 split (:357) instead of the K folds - the LR chain, the SWA start,
+    the selection, the early stopping and the snapshot on improvement are one fold's, and history['folds'] holds that one split.
+    (The script's loss-list padding, which slipped into its epoch loop when the fold loop went, is not reproduced: one list per epoch.)"""
     cfg = _config(config)   # optimizer_type 'adam': optim.Adam (weight decay as an L2 term) under StepLR, model_regression.py:385-386
     xp, y, scaler = _prepare(engine, features, mos)
     y_host = y.cpu().numpy().astype(np.float64)
     n, F = xp.shape[0], int(features.shape[1])
     epochs, bs = cfg["epochs"], cfg["batch_size"]
-    tr = HeadTrainer(engine, F, cfg["hidden_features"], max_batch=max(2, min(bs, 1024)))
+    batchnorm = bool(cfg["batchnorm"])
+    tr = HeadTrainer(engine, F, cfg["hidden_features"], max_batch=max(2, min(bs, 1024)), batchnorm=batchnorm)
     use_swa = bool(cfg["use_swa"])
     swa_start = int(epochs * 0.7) if use_swa else epochs
     lrs = _schedule(cfg, swa_start, use_swa)
@@ -453,8 +499,12 @@ def fit_head(engine, features, mos, config=None):
     history = {"train_loss": [], "val_loss": [], "metric": [], "lr": lrs, "best": None, "folds": []}
     have_best = False
     step = 0
-    for fold, (train_idx, val_idx) in enumerate(kfold_indices(n, cfg["n_splits"])):
-        tr.import_state(init_state_dict(F, cfg["hidden_features"], seed=cfg["seed"] + fold), LIVE)
+    if cfg["validation"] == "holdout":   # model_regression_simple.py:357: one train_test_split(test_size=0.2, random_state=42), no KFold
+        splits = [_metrics.holdout_split(n, 0.2, 42)]
+    else:
+        splits = kfold_indices(n, cfg["n_splits"])
+    for fold, (train_idx, val_idx) in enumerate(splits):
+        tr.import_state(init_state_dict(F, cfg["hidden_features"], seed=cfg["seed"] + fold, batchnorm=batchnorm), LIVE)
         if use_swa:
             tr.copy(SWA, LIVE)   # AveragedModel(model): a deep copy, n_averaged 0
         rng = np.random.RandomState(cfg["seed"] * 1000003 + fold)
@@ -510,6 +560,13 @@ def fit_head(engine, features, mos, config=None):
     return tr.export_state(BEST), scaler, history
 
 
+def fit_head_simple(engine, features, mos, config=None):
+    """train_and_evaluate of model_regression_simple.py (:335-467), the protocol behind the reference's KoNViD-1k / YouTube-UGC /
+    LIVE-VQC / CVD2014 numbers: fit_head under SIMPLE_DEFAULTS (the plain head, one 80/20 validation split, 120 epochs, lr 1e-2,
+    weight decay 5e-4); `config` overrides them."""
+    return fit_head(engine, features, mos, dict(SIMPLE_DEFAULTS, **(config or {})))
+
+
 def fine_tune_head(engine, state_dict, features, mos, config=None):
     """fine_tune_model (fine_tune.py:130-190): start from state_dict, one split, batches in order, SWA from int(0.75 epochs);
     the result is the SWA average after update_bn (or the live model without SWA).  optimizer_type 'adam' is AdamW here
@@ -521,7 +578,8 @@ def fine_tune_head(engine, state_dict, features, mos, config=None):
     n, F = xp.shape[0], int(features.shape[1])
     epochs, bs = cfg["epochs"], cfg["batch_size"]
     hidden = int(np.asarray(state_dict["fc1.bias" if "fc1.bias" in state_dict else "module.fc1.bias"]).shape[0])
-    tr = HeadTrainer(engine, F, hidden, max_batch=max(2, min(bs, 1024)))
+    # a state dict without bn1 keys fine-tunes the plain head (beyond the reference, whose fine_tune.py builds the BatchNorm Mlp)
+    tr = HeadTrainer(engine, F, hidden, max_batch=max(2, min(bs, 1024)), batchnorm=not is_plain_state_dict(state_dict))
     tr.import_state(state_dict, LIVE)
     use_swa = bool(cfg["use_swa"])
     swa_start = int(epochs * 0.75) if use_swa else epochs

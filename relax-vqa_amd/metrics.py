@@ -212,6 +212,8 @@ def evaluate_head(engine, features_train, mos_train, features_test, mos_test, co
     and a MinMaxScaler fitted ON THE TEST MATRIX ITSELF, not with the train set's.  config['test_scaler'] = 'train' selects
     the conventional behaviour (the train set's scaler on both).  Both sets are scored by the inference head (load_mlp_head +
     mlp_head, BatchNorm folded), so the engine's loaded head is the fitted one (with the test-side scaler) afterwards.
+    `config` goes to fit_head as it is: head_train.SIMPLE_DEFAULTS (or any config with batchnorm=False / validation='holdout') runs
+    model_regression_simple.py's protocol - the plain state dict is loaded unfolded and scored the same way.
 
     Returns {'train': metrics, 'test': metrics, 'y_train_pred', 'y_test_pred' (host float64), 'y_train_pred_logistic',
     'y_test_pred_logistic' (host float64), 'state_dict', 'scaler', 'test_scaler', 'history'}."""

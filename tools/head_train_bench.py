@@ -2,6 +2,7 @@
 
     python tools/head_train_bench.py [--out profiles/head_train_bench.json] [--steps 200] [--no-fit]
     python tools/head_train_bench.py --optimizer adam          # the Adam step, into profiles/head_train_adam_bench.json
+    python tools/head_train_bench.py --plain --repeats 7       # the plain head (no BatchNorm) beside the BatchNorm head, into profiles/head_plain_bench.json
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o F35203 -- \
         python tools/head_train_bench.py --features 35203 --steps 50 --no-fit --no-torch --no-dw1 --out DIR/under_profiler.json
                                                        # per-kernel breakdown of ONE width per run (profiles/head_train_kernel_stats_F*.csv)
@@ -74,8 +75,92 @@ def torch_step_fn(F, H1, x, y, rows, optimizer="sgd"):
     return fn
 
 
+def one_run(fn, steps, warmup):
+    """ms per step of `steps` back-to-back calls after a warm-up, between two device events."""
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def spread(samples, steps):
+    return {"median_ms": float(np.median(samples)), "min_ms": float(min(samples)), "max_ms": float(max(samples)), "repeats": len(samples),
+            "steps": steps}
+
+
+def torch_plain_step_fn(F, H1, x, y, rows, optimizer):
+    import head_plain_ref as P
+    model = P.PlainMlp(F, H1, 0.0).cuda()
+    drop = torch.nn.Dropout(0.1)
+    if optimizer == "adam":
+        opt = torch.optim.Adam(model.parameters(), lr=0.001, weight_decay=0.005)
+    else:
+        opt = torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9, weight_decay=0.005)
+    model.train()
+
+    def fn():
+        xb, yb = x[rows], y[rows]
+        opt.zero_grad()
+        h = drop(torch.nn.functional.gelu(model.fc1(xb)))
+        h = drop(torch.nn.functional.gelu(model.fc2(h)))
+        loss = P.mae_rank_loss(model.fc3(h).reshape(-1), yb, 0.6, 1.0)
+        loss.backward()
+        opt.step()
+    return fn
+
+
+def plain_bench(args, eng):
+    """--plain: the plain head's step (no BatchNorm) beside the BatchNorm head's, under SGD and under Adam, and the plain step in stock
+    torch ops.  An engine holds one training state, so the two variants alternate state by state: each of the `--repeats` rounds
+    builds the plain state, times `--steps` steps, then the same for the BatchNorm state; medians and spread over the rounds."""
+    H1, B, n = 256, 256, 960
+    res = {"device": torch.cuda.get_device_name(0), "B": B, "H1": H1, "drop_rate": 0.1, "arithmetic": "fp32 (the only one built)",
+           "timing": "device events around --steps back-to-back steps after --warmup; median / min / max over --repeats alternated rounds",
+           "shapes": {}}
+    for F in [int(v) for v in args.features.split(",")]:
+        g = torch.Generator(device="cuda").manual_seed(F)
+        xp = torch.zeros((n, (F + 31) // 32 * 32), device="cuda")
+        xp[:, :F] = torch.rand((n, F), device="cuda", generator=g)
+        y = 1 + 4 * torch.rand((n,), device="cuda", generator=g)
+        rows = torch.randperm(n, device="cuda", generator=g)[:B].to(torch.int32)
+        inits = {bn: head_train.init_state_dict(F, H1, seed=1, batchnorm=bn) for bn in (False, True)}
+        entry = {}
+        for optimizer in ("sgd", "adam"):
+            samples = {False: [], True: []}
+            for _ in range(args.repeats):
+                for bn in (False, True):
+                    tr = head_train.HeadTrainer(eng, F, H1, max_batch=B, batchnorm=bn)
+                    tr.import_state(inits[bn])
+                    counter = [0]
+
+                    def step():
+                        if optimizer == "adam":
+                            tr.step_adam(xp, y, rows, 0.001, weight_decay=0.005, drop_rate=0.1, seed=1, step=counter[0])
+                        else:
+                            tr.step(xp, y, rows, 0.01, 0.9, 0.005, 0.6, 1.0, 0.1, seed=1, step=counter[0])
+                        counter[0] += 1
+                    samples[bn].append(one_run(step, args.steps, args.warmup))
+            entry[f"hip_plain_{optimizer}"] = spread(samples[False], args.steps)
+            entry[f"hip_batchnorm_{optimizer}"] = spread(samples[True], args.steps)
+            if not args.no_torch:
+                fn = torch_plain_step_fn(F, H1, xp[:, :F].contiguous(), y, rows.long(), optimizer)
+                entry[f"torch_plain_{optimizer}"] = spread([one_run(fn, args.steps, args.warmup) for _ in range(args.repeats)], args.steps)
+                del fn
+        res["shapes"][str(F)] = entry
+        print(F, json.dumps(entry))
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--plain", action="store_true", help="the plain head (no BatchNorm) beside the BatchNorm head, SGD and Adam; "
+                    "into profiles/head_plain_bench.json")
     ap.add_argument("--optimizer", choices=("sgd", "adam"), default="sgd")
     ap.add_argument("--out", default=None, help="default: profiles/head_train_bench.json, or head_train_adam_bench.json under --optimizer adam")
     ap.add_argument("--steps", type=int, default=100)
@@ -87,6 +172,9 @@ def main():
     ap.add_argument("--features", default="35203,19779", help="comma-separated feature widths")
     args = ap.parse_args()
     adam = args.optimizer == "adam"
+    if args.plain:
+        args.out = args.out or os.path.join(ROOT, "profiles", "head_plain_bench.json")
+        return plain_bench(args, RelaxEngine(0))
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "head_train_adam_bench.json" if adam else "head_train_bench.json")
     eng = RelaxEngine(0)
