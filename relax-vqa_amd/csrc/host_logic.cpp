@@ -454,22 +454,33 @@ void pos_interp_taps(int side, int g, int32_t* idx, float* w) {
     }
 }
 
-size_t vit_floats_per_image(int dim, int ntok, int npatch, int patch_k) {
-    return (size_t)npatch * patch_k        // P   patches
-           + (size_t)npatch * dim          // PE  patch-embed output
-           + (size_t)ntok * dim * 2        // X, Y
-           + (size_t)ntok * dim * 3        // QKV
-           + (size_t)ntok * dim * 4;       // Hid
+VitArena vit_arena(bool planes, int dim, int ntok, int npatch, int patch_k) {
+    const int64_t td = (int64_t)ntok * dim, pk = (int64_t)npatch * patch_k;
+    VitArena a{};
+    a.embedded = planes ? pk * 3 / 2 : pk;                           // behind the patches (sp3: 3/2 floats per value)
+    a.residual = a.embedded + (int64_t)npatch * dim;                 // behind the patch-embed output
+    a.operand = a.residual + td;                                     // LayerNorm / attention output: what the next GEMM reads
+    a.qkv = a.operand + (planes ? td * 3 / 2 : td);
+    a.final = planes ? a.qkv + td * 3 : a.operand;                   // the final LayerNorm's fp32 rows
+    a.hidden = planes ? a.final + td : a.qkv + td * 3;               // GELU(fc1)
+    a.floats = a.hidden + (planes ? td * 4 * 3 / 2 : td * 4);
+    return a;
 }
 
-size_t vit_floats_per_image_x6(int dim, int ntok, int npatch, int patch_k) {
-    return (size_t)npatch * patch_k * 3 / 2     // P    patches, sp3
-           + (size_t)npatch * dim               // PE   patch-embed output
-           + (size_t)ntok * dim                 // X    residual stream
-           + (size_t)ntok * dim * 3 / 2         // Y    LayerNorm / attention output, sp3
-           + (size_t)ntok * dim * 3             // QKV
-           + (size_t)ntok * dim                 // ATT  attention output / final LayerNorm, fp32
-           + (size_t)ntok * dim * 4 * 3 / 2;    // Hid  GELU(fc1), sp3
+VitPlan vit_plan(const VitOptions& o, const VitModel& m, const VitRequest& rq) {
+    VitPlan p{};
+    p.arith = o.precision == 3 && m.dim % 256 == 0 ? kVitH2 : o.precision >= 2 ? kVitX6 : kVitF32;
+    p.patch_embed = p.arith == kVitH2 && m.patch == 8 ? kVitX6 : p.arith;
+    const bool single_tile = rq.ntok == 197;
+    p.qkv_planes = p.arith == kVitH2 && o.att_h2 && (single_tile || o.att_h2_stream);
+    // (f16x2 without qkv planes: attention keeps its bf16x6 arithmetic inside and writes fp16 planes)
+    p.attention = p.arith == kVitF32 ? (single_tile ? kVitAttention : kVitAttentionStreamF32)
+                  : p.qkv_planes     ? (single_tile ? kVitAttentionH2 : kVitAttentionStreamH2)
+                                     : (single_tile ? kVitAttentionX6 : kVitAttentionStreamX6);
+    p.attention_only = rq.want_cls_attention && !rq.want_tokens && !rq.want_pooled;
+    p.final_norm = rq.n_last == 0 && !p.attention_only;
+    p.arena = vit_arena(p.arith != kVitF32, m.dim, rq.ntok, rq.npatch, m.patch_k);
+    return p;
 }
 
 bool att_stream_plan(int Nimg, int heads, int ntok, int arith, AttStreamPlan* plan, std::string& err) {
@@ -1309,8 +1320,18 @@ int relax_host_vit_canvas_geometry(int patch, int Hc, int Wc, int* out, char* er
 // one axis of the position table's bicubic resampling: idx[4 g], w[4 g]
 void relax_host_pos_interp_taps(int side, int g, int32_t* idx, float* w) { relax::host::pos_interp_taps(side, g, idx, w); }
 void relax_host_vit_arena_floats(int dim, int ntok, int npatch, int patch_k, int64_t* out) {
-    out[0] = (int64_t)relax::host::vit_floats_per_image(dim, ntok, npatch, patch_k);
-    out[1] = (int64_t)relax::host::vit_floats_per_image_x6(dim, ntok, npatch, patch_k);
+    out[0] = relax::host::vit_arena(false, dim, ntok, npatch, patch_k).floats;
+    out[1] = relax::host::vit_arena(true, dim, ntok, npatch, patch_k).floats;
+}
+// the forward's plan.  in = precision, att_h2, att_h2_stream | dim, depth, heads, patch, patch_k | ntok, npatch, want_tokens, want_pooled,
+// want_cls_attention, n_last; out = arith, patch_embed, qkv_planes, attention, attention_only, final_norm, then the arena's eight offsets
+void relax_host_vit_plan(const int* in, int64_t* out) {
+    using namespace relax::host;
+    const VitPlan p = vit_plan(VitOptions{in[0], in[1], in[2]}, VitModel{in[3], in[4], in[5], in[6], in[7]},
+                               VitRequest{in[8], in[9], in[10], in[11], in[12], in[13]});
+    const int64_t v[14] = {p.arith, p.patch_embed, p.qkv_planes, p.attention, p.attention_only, p.final_norm, p.arena.patches, p.arena.embedded,
+                           p.arena.residual, p.arena.operand, p.arena.qkv, p.arena.final, p.arena.hidden, p.arena.floats};
+    std::memcpy(out, v, sizeof(v));
 }
 // streaming-attention plan: out = qblock, qblocks, key_tiles, lds_bytes, items; 0, or -1 and a message
 int relax_host_att_stream_plan(int Nimg, int heads, int ntok, int arith, int* out, char* err, int err_len) {

@@ -410,9 +410,27 @@ bool vit_canvas_geometry(int patch, int Hc, int Wc, VitCanvasGeometry* g, std::s
 // (A = -0.75) are evaluated in fp32.  Output position i reads
 // source positions idx[4 i .. 4 i + 3] (floor - 1 .. floor + 2, clamped to [0, side - 1]) with weights w[4 i .. 4 i + 3].
 void pos_interp_taps(int side, int g, int32_t* idx, float* w);
-// per-image floats of the forward's arena: the exact-fp32 layout and the bf16x6 / f16x2 one (sp3 operands take 6 bytes per value)
-size_t vit_floats_per_image(int dim, int ntok, int npatch, int patch_k);
-size_t vit_floats_per_image_x6(int dim, int ntok, int npatch, int patch_k);
+// The forward's arena: per-image float offsets of its slots, by role and in carving order, and their total.  Two layouts: exact fp32 (every slot
+// fp32 rows; `final`, the final norm's output, is the operand slot again) and planes (bf16x6 / f16x2: the GEMM operands - patches, operand,
+// hidden - take the 6 bytes per value of split planes, fp16 planes use 4 of them; `final` is a slot of its own behind qkv).
+struct VitArena { int64_t patches, embedded, residual, operand, qkv, final, hidden, floats; };
+VitArena vit_arena(bool planes, int dim, int ntok, int npatch, int patch_k);
+// The routes of one forward (vit.hip executes them): host arithmetic only.  Every block runs the same launches, so there is no per-launch table.
+enum VitArith { kVitF32 = 0, kVitX6, kVitH2 };   // exact fp32 (or bf16x3: the fp32 GEMM's own choice) / bf16x6 / f16x2
+enum VitAttention { kVitAttention = 0, kVitAttentionStreamF32, kVitAttentionX6, kVitAttentionStreamX6, kVitAttentionH2, kVitAttentionStreamH2 };
+struct VitOptions { int precision, att_h2, att_h2_stream; };
+struct VitModel { int dim, depth, heads, patch, patch_k; };
+struct VitRequest { int ntok, npatch, want_tokens, want_pooled, want_cls_attention, n_last; };   // n_last: taps after the last n blocks, 0 = none
+struct VitPlan {
+    int arith;            // VitArith of the forward: f16x2 under precision 3 where the tile takes the width (dim % 256 == 0), bf16x6 under 2 and above
+    int patch_embed;      // VitArith of the patchify kernel and the patch-embed GEMM: `arith`, but bf16x6 for patch 8 under f16x2 (K = 192 < 256)
+    int qkv_planes;       // qkv leaves its GEMM as fp16 planes, which attention and vit_cls_attention read as they are
+    int attention;        // VitAttention: 197 tokens run the single-tile kernels, any other count the streaming ones
+    int attention_only;   // CLS attention alone: the forward ends behind the last block's qkv GEMM
+    int final_norm;       // not under taps (the last tap is the final norm) nor under attention_only
+    VitArena arena;       // the layout `arith` runs in (the arena itself holds the larger one, planes: vit_arena_bytes)
+};
+VitPlan vit_plan(const VitOptions& o, const VitModel& m, const VitRequest& rq);
 
 // attention_stream.hip: one workgroup = one (image, head, block of kAttStreamQBlock queries); it walks ceil(ntok / 32) key tiles, the K and V
 // images of ONE tile in LDS at a time (fp32 rows under kAttStreamF32, bf16 plane images under kAttStreamX6)

@@ -190,8 +190,8 @@ void free_vit(relax_handle* h) {
 }
 
 size_t vit_arena_bytes(const VitW& v, int n, int ntok, int npatch) {
-    const size_t a = host::vit_floats_per_image(v.dim, ntok, npatch, v.patch_k), b = host::vit_floats_per_image_x6(v.dim, ntok, npatch, v.patch_k);
-    return sizeof(float) * (a > b ? a : b) * (size_t)n;
+    const int64_t a = host::vit_arena(false, v.dim, ntok, npatch, v.patch_k).floats, b = host::vit_arena(true, v.dim, ntok, npatch, v.patch_k).floats;
+    return sizeof(float) * (size_t)(a > b ? a : b) * (size_t)n;
 }
 size_t vit_arena_bytes(const VitW& v, int n) { return vit_arena_bytes(v, n, v.ntok, v.npatch); }
 
@@ -317,7 +317,7 @@ static int load_vit(relax_handle* h, const host::StateDict& sd, const host::VitG
         return launch_to_h2(h, l->w, l->in, l->w_h2, l->out, l->in, 1.f, d_scale, nullptr);
     };
     if (dim % 256 == 0) {   // (the f16x2 tile takes N % 256 == 0: ViT-B; smaller models run bf16x6 under "gemm_precision" 3)
-        // (patch 8: the patch-embed GEMM runs on bf16x6 under f16x2 too - see vit_forward - and needs no fp16 planes)
+        // (patch 8: the patch-embed GEMM runs on bf16x6 under f16x2 too - host::vit_plan's patch_embed - and needs no fp16 planes)
         if (geo.patch == 16) RELAX_TRY(h2w(&v.patch_w, "patch_embed.proj", kPatchScale));
         for (int i = 0; i < depth; ++i) {
             const std::string p = "blocks." + std::to_string(i) + ".";
@@ -420,165 +420,92 @@ static int vit_forward(relax_handle* h, const char* what, const uint8_t* frags, 
         RELAX_REQUIRE(h, host::vit_canvas_geometry(h->vit.patch, Hc, Wc, &cg, err), "%s: %s", what, err.c_str());
     }
     RELAX_REQUIRE(h, (int64_t)N * cg.ntok <= (int64_t)INT32_MAX, "%s: %d images of %d tokens pass 2^31 - 1 rows", what, N, cg.ntok);
+    const VitW& v = h->vit;
+    const int dim = v.dim, NTOK = cg.ntok, NPATCH = cg.npatch, PATCH_K = v.patch_k, rows = N * NTOK;
+    // which arithmetic, which kernels, where the forward ends and where its buffers lie: host::vit_plan; below, the one sequence that runs it
+    const host::VitPlan pl = host::vit_plan({h->gemm.precision, h->gemm.att_h2, h->gemm.att_h2_stream}, {dim, v.depth, v.heads, v.patch, PATCH_K},
+                                            {NTOK, NPATCH, tokens != nullptr, pooled != nullptr, cls_attention != nullptr, taps ? taps->n_last : 0});
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const VitW& v = h->vit;
-    const int dim = v.dim;
     const float* pos = nullptr;
     RELAX_TRY(vit_pos_table(h, cg, s, &pos));
-    RELAX_TRY(ensure_buf(h, h->arena, vit_arena_bytes(v, N, cg.ntok, cg.npatch)));
-    const size_t n = (size_t)N;
-    const int NTOK = cg.ntok, NPATCH = cg.npatch, PATCH_K = v.patch_k;
-    const PatchGeom pg{v.patch == 8 ? 3 : 4, cg.gw, NPATCH, PATCH_K, Hc, Wc};
-    // 197 tokens: the single-tile kernels (every key of an (image, head) on the chip at once); any other count: the streaming ones
-    const bool single_tile = NTOK == 197;
-    auto attention_x6 = [&](const float* qkv, void* out_planes, float out_h2_scale) {
-        return single_tile ? launch_attention_x6(h, qkv, nullptr, out_planes, N, v.heads, s, out_h2_scale)
-                           : launch_attention_stream_x6(h, qkv, nullptr, out_planes, N, NTOK, v.heads, s, out_h2_scale);
+    RELAX_TRY(ensure_buf(h, h->arena, vit_arena_bytes(v, N, NTOK, NPATCH)));
+    // GEMM inputs (P, Y, Hid) travel in the arithmetic's operand form, written by the kernel that produces them: fp32 rows, bf16 split planes, or
+    // two fp16 planes of (value x a static power of two).  GEMM outputs that feed LayerNorm / attention / the residual stream X stay fp32.
+    auto slot = [&](int64_t floats_per_image) { return static_cast<float*>(h->arena.p) + (size_t)floats_per_image * (size_t)N; };
+    float *P = slot(pl.arena.patches), *PE = slot(pl.arena.embedded), *X = slot(pl.arena.residual), *Y = slot(pl.arena.operand);
+    float *QKV = slot(pl.arena.qkv), *Final = slot(pl.arena.final), *Hid = slot(pl.arena.hidden);
+
+    // out = act(A W^T + bias) (+ residual) as fp32 rows into out_f32, or as the next GEMM's operand into out_operand (f16x2: of value x out_scale)
+    auto linear = [&](int arith, const float* A, const LinearW& l, const float* residual, float* out_f32, float* out_operand, float out_scale, int M, int act) {
+        switch (arith) {
+            case host::kVitF32: return launch_gemm(h, A, l.w, l.b, residual, out_f32 ? out_f32 : out_operand, M, l.out, l.in, act, s);
+            case host::kVitX6: return launch_gemm_x6(h, A, l.w_sp3, l.b, residual, out_f32, out_operand, M, l.out, l.in, act, s);
+        }
+        GemmDescH2 d{};
+        d.a = A; d.w = l.w_h2; d.colscale = l.colscale; d.bias = l.b; d.residual = residual; d.out = out_f32; d.out_h2 = out_operand;
+        d.out_scale = out_scale; d.M = M; d.N = l.out; d.K = l.in; d.act = act;
+        return launch_gemm_h2(h, d, s);
     };
-    float* P = static_cast<float*>(h->arena.p);
-    float* PE = P + n * NPATCH * PATCH_K;
-    float* X = PE + n * NPATCH * dim;
-    float* Y = X + n * NTOK * dim;
-    float* QKV = Y + n * NTOK * dim;
-    float* Hid = QKV + n * NTOK * dim * 3;
-    const int rows = N * NTOK;
+    auto patchify_embed = [&]() {
+        const int64_t total = (int64_t)N * NPATCH * PATCH_K, p8 = total / 8;
+        const PatchGeom pg{v.patch == 8 ? 3 : 4, cg.gw, NPATCH, PATCH_K, Hc, Wc};
+        char* Pc = reinterpret_cast<char*>(P);
+        switch (pl.patch_embed) {
+            case host::kVitF32: hipLaunchKernelGGL(vit_patchify, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frags, P, total, pg); break;
+            case host::kVitX6: hipLaunchKernelGGL(vit_patchify_sp3, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Pc, p8, pg); break;
+            default: hipLaunchKernelGGL(vit_patchify_h2, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Pc, p8, kPatchScale, pg);
+        }
+        return linear(pl.patch_embed, P, v.patch_w, nullptr, PE, nullptr, 0.f, N * NPATCH, 0);
+    };
+    auto norm_to_operand = [&](const float* g, const float* b, float scale) {
+        switch (pl.arith) {
+            case host::kVitF32: return launch_layernorm(h, X, g, b, Y, rows, dim, kLnEps, s);
+            case host::kVitX6: return launch_layernorm_sp3(h, X, g, b, Y, rows, dim, kLnEps, s);
+        }
+        return launch_layernorm_h2(h, X, g, b, Y, scale, rows, dim, kLnEps, s);
+    };
+    // QKV -> Y in the operand form.  The bf16x6 kernels serve f16x2 too when qkv is fp32 rows: they write fp16 planes of value x s_att then
+    auto attention = [&](const VitBlockW& b) {
+        const float x6_h2_scale = pl.arith == host::kVitH2 ? b.s_att : 0.f;
+        switch (pl.attention) {
+            case host::kVitAttention: return launch_attention(h, QKV, Y, N, v.heads, s);
+            case host::kVitAttentionStreamF32: return launch_attention_stream_f32(h, QKV, Y, N, NTOK, v.heads, s);
+            case host::kVitAttentionX6: return launch_attention_x6(h, QKV, nullptr, Y, N, v.heads, s, x6_h2_scale);
+            case host::kVitAttentionStreamX6: return launch_attention_stream_x6(h, QKV, nullptr, Y, N, NTOK, v.heads, s, x6_h2_scale);
+            case host::kVitAttentionH2: return launch_attention_h2(h, QKV, b.s_qkv, Y, b.s_att, N, v.heads, s);
+        }
+        return launch_attention_stream_h2(h, QKV, b.s_qkv, Y, b.s_att, N, NTOK, v.heads, s);
+    };
+
+    RELAX_TRY(patchify_embed());
+    const int64_t at = (int64_t)rows * (dim / 4);
+    hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PE, v.cls, pos, X, dim / 4, at, NTOK);
+    RELAX_HIP_CHECK(h, hipGetLastError());
     // cls_attention: block `last`'s CLS row, launched right after its qkv GEMM (before its attention core, so nothing later in the
     // forward can overwrite the qkv buffer first).  Without tokens / pooled the forward stops there (get_last_selfattention).
     const int last = v.depth - 1;
-    const bool attention_only = cls_attention && !tokens && !pooled;
-
-    if (h->gemm.precision == 3 && dim % 256 == 0) {
-        // f16x2: GEMM inputs travel as two fp16 planes of (value x a static power of two), written by the kernel that produces them;
-        // GEMM outputs that feed LayerNorm / attention / the residual stream stay fp32.  The buffers of the bf16x6 layout are reused
-        // (4-byte plane values fit its 6-byte slots).  Attention keeps its bf16x6 arithmetic inside (attention_x6.hip: 4 % of the FLOPs).
-        float* base = static_cast<float*>(h->arena.p);
-        char* Ps = reinterpret_cast<char*>(base);
-        float* PEx = base + n * NPATCH * PATCH_K * 3 / 2;
-        float* Xx = PEx + n * NPATCH * dim;
-        char* Ys = reinterpret_cast<char*>(Xx + n * NTOK * dim);
-        float* QKVx = reinterpret_cast<float*>(Ys) + n * NTOK * dim * 3 / 2;
-        float* ATT = QKVx + n * NTOK * dim * 3;
-        char* Hs = reinterpret_cast<char*>(ATT + n * NTOK * dim);
-        auto gemm = [&](const void* A, const LinearW& l, const float* residual, float* out, void* out_h2, float out_scale, int M, int act) {
-            GemmDescH2 d{};
-            d.a = A; d.w = l.w_h2; d.colscale = l.colscale; d.bias = l.b; d.residual = residual; d.out = out; d.out_h2 = out_h2;
-            d.out_scale = out_scale; d.M = M; d.N = l.out; d.K = l.in; d.act = act;
-            return launch_gemm_h2(h, d, s);
-        };
-        const int64_t p8 = (int64_t)N * NPATCH * (PATCH_K / 8);
-        if (v.patch == 16) {
-            hipLaunchKernelGGL(vit_patchify_h2, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Ps, p8, kPatchScale, pg);
-            RELAX_TRY(gemm(Ps, v.patch_w, nullptr, PEx, nullptr, 0.f, N * NPATCH, 0));
-        } else {
-            // patch 8: K = 192 is below the 256 from which the f16x2 kernel runs its three-product form, and this GEMM is 0.3 % of the forward's
-            // FLOPs: it runs on bf16x6 (split planes fit the slot: the layout reserves 6 bytes per value)
-            hipLaunchKernelGGL(vit_patchify_sp3, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Ps, p8, pg);
-            RELAX_TRY(launch_gemm_x6(h, Ps, v.patch_w.w_sp3, v.patch_w.b, nullptr, PEx, nullptr, N * NPATCH, dim, PATCH_K, 0, s));
-        }
-        const int64_t at = (int64_t)rows * (dim / 4);
-        hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, pos, Xx, dim / 4, at, NTOK);
-        RELAX_HIP_CHECK(h, hipGetLastError());
-        for (int i = 0; i < v.depth; ++i) {
-            const VitBlockW& b = v.blocks[i];
-            RELAX_TRY(launch_layernorm_h2(h, Xx, b.ln1_g, b.ln1_b, Ys, b.s_ln1, rows, dim, kLnEps, s));
-            if (h->gemm.att_h2 && (single_tile || h->gemm.att_h2_stream)) {   // q, k, v leave the GEMM as fp16 planes (the same 4 bytes per value) and attention reads them as they are: attention_h2 at 197 tokens, its streaming form ("att_h2_stream") at any other count
-                RELAX_TRY(gemm(Ys, b.qkv, nullptr, nullptr, QKVx, b.s_qkv, rows, 0));
-                if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, true, b.s_qkv, cls_attention, N, NTOK, v.heads, s));
-                if (attention_only && i == last) return RELAX_OK;
-                if (single_tile) RELAX_TRY(launch_attention_h2(h, QKVx, b.s_qkv, Ys, b.s_att, N, v.heads, s));
-                else RELAX_TRY(launch_attention_stream_h2(h, QKVx, b.s_qkv, Ys, b.s_att, N, NTOK, v.heads, s));
-            } else {
-                RELAX_TRY(gemm(Ys, b.qkv, nullptr, QKVx, nullptr, 0.f, rows, 0));
-                if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, false, 0.f, cls_attention, N, NTOK, v.heads, s));
-                if (attention_only && i == last) return RELAX_OK;
-                RELAX_TRY(attention_x6(QKVx, Ys, b.s_att));   // output straight into fp16 planes
-            }
-            RELAX_TRY(gemm(Ys, b.proj, Xx, Xx, nullptr, 0.f, rows, 0));                     // x += proj(attn)
-            RELAX_TRY(launch_layernorm_h2(h, Xx, b.ln2_g, b.ln2_b, Ys, b.s_ln2, rows, dim, kLnEps, s));
-            RELAX_TRY(gemm(Ys, b.fc1, nullptr, nullptr, Hs, b.s_hid, rows, 2));              // GELU(erf) -> fp16 planes
-            RELAX_TRY(gemm(Hs, b.fc2, Xx, Xx, nullptr, 0.f, rows, 0));                      // x += mlp
-            if (taps) RELAX_TRY(vit_tap(h, *taps, i, Xx, N, NTOK, s));
-        }
-        if (taps) return RELAX_OK;
-        RELAX_TRY(launch_layernorm(h, Xx, v.norm_g, v.norm_b, ATT, rows, dim, kLnEps, s));
-        if (tokens) {
-            const int64_t t = (int64_t)N * NPATCH * (dim / 4);
-            hipLaunchKernelGGL(vit_drop_cls, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, ATT, tokens, dim / 4, t, NTOK);
-        }
-        if (pooled) hipLaunchKernelGGL(vit_token_stats, dim3(dim / 64, N), dim3(256), 0, s, ATT, pooled, dim, NTOK, 1, NPATCH);
-        RELAX_HIP_CHECK(h, hipGetLastError());
-        return RELAX_OK;
-    }
-
-    if (h->gemm.precision >= 2) {   // (3 with a dim the f16x2 tile does not take, e.g. vit_tiny's 192: bf16x6)
-        // bf16x6: GEMM inputs travel as split planes (written by the kernel that produces them), GEMM outputs that feed
-        // LayerNorm / attention / the residual stream stay fp32
-        float* base = static_cast<float*>(h->arena.p);
-        char* Ps = reinterpret_cast<char*>(base);
-        float* PEx = base + n * NPATCH * PATCH_K * 3 / 2;
-        float* Xx = PEx + n * NPATCH * dim;
-        char* Ys = reinterpret_cast<char*>(Xx + n * NTOK * dim);
-        float* QKVx = reinterpret_cast<float*>(Ys) + n * NTOK * dim * 3 / 2;
-        float* ATT = QKVx + n * NTOK * dim * 3;
-        char* Hs = reinterpret_cast<char*>(ATT + n * NTOK * dim);
-        const int64_t p8 = (int64_t)N * NPATCH * (PATCH_K / 8);
-        hipLaunchKernelGGL(vit_patchify_sp3, dim3((unsigned)((p8 + 255) / 256)), dim3(256), 0, s, frags, Ps, p8, pg);
-        RELAX_TRY(launch_gemm_x6(h, Ps, v.patch_w.w_sp3, v.patch_w.b, nullptr, PEx, nullptr, N * NPATCH, dim, PATCH_K, 0, s));
-        const int64_t at = (int64_t)rows * (dim / 4);
-        hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, PEx, v.cls, pos, Xx, dim / 4, at, NTOK);
-        RELAX_HIP_CHECK(h, hipGetLastError());
-        for (int i = 0; i < v.depth; ++i) {
-            const VitBlockW& b = v.blocks[i];
-            RELAX_TRY(launch_layernorm_sp3(h, Xx, b.ln1_g, b.ln1_b, Ys, rows, dim, kLnEps, s));
-            RELAX_TRY(launch_gemm_x6(h, Ys, b.qkv.w_sp3, b.qkv.b, nullptr, QKVx, nullptr, rows, 3 * dim, dim, 0, s));
-            if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKVx, false, 0.f, cls_attention, N, NTOK, v.heads, s));
-            if (attention_only && i == last) return RELAX_OK;
-            RELAX_TRY(attention_x6(QKVx, Ys, 0.f));   // output straight into split planes
-            RELAX_TRY(launch_gemm_x6(h, Ys, b.proj.w_sp3, b.proj.b, Xx, Xx, nullptr, rows, dim, dim, 0, s));      // x += proj(attn)
-            RELAX_TRY(launch_layernorm_sp3(h, Xx, b.ln2_g, b.ln2_b, Ys, rows, dim, kLnEps, s));
-            RELAX_TRY(launch_gemm_x6(h, Ys, b.fc1.w_sp3, b.fc1.b, nullptr, nullptr, Hs, rows, 4 * dim, dim, 2, s)); // GELU(erf) -> sp3
-            RELAX_TRY(launch_gemm_x6(h, Hs, b.fc2.w_sp3, b.fc2.b, Xx, Xx, nullptr, rows, dim, 4 * dim, 0, s));     // x += mlp
-            if (taps) RELAX_TRY(vit_tap(h, *taps, i, Xx, N, NTOK, s));
-        }
-        if (taps) return RELAX_OK;
-        RELAX_TRY(launch_layernorm(h, Xx, v.norm_g, v.norm_b, ATT, rows, dim, kLnEps, s));
-        if (tokens) {
-            const int64_t t = (int64_t)N * NPATCH * (dim / 4);
-            hipLaunchKernelGGL(vit_drop_cls, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, ATT, tokens, dim / 4, t, NTOK);
-        }
-        if (pooled) hipLaunchKernelGGL(vit_token_stats, dim3(dim / 64, N), dim3(256), 0, s, ATT, pooled, dim, NTOK, 1, NPATCH);
-        RELAX_HIP_CHECK(h, hipGetLastError());
-        return RELAX_OK;
-    }
-
-    const int64_t ptotal = (int64_t)N * NPATCH * PATCH_K;
-    hipLaunchKernelGGL(vit_patchify, dim3((unsigned)((ptotal + 255) / 256)), dim3(256), 0, s, frags, P, ptotal, pg);
-    RELAX_TRY(launch_gemm(h, P, v.patch_w.w, v.patch_w.b, nullptr, PE, N * NPATCH, dim, PATCH_K, 0, s));
-    const int64_t atotal = (int64_t)rows * (dim / 4);
-    hipLaunchKernelGGL(vit_assemble, dim3((unsigned)((atotal + 255) / 256)), dim3(256), 0, s, PE, v.cls, pos, X,
-                       dim / 4, atotal, NTOK);
-    RELAX_HIP_CHECK(h, hipGetLastError());
     for (int i = 0; i < v.depth; ++i) {
         const VitBlockW& b = v.blocks[i];
-        RELAX_TRY(launch_layernorm(h, X, b.ln1_g, b.ln1_b, Y, rows, dim, kLnEps, s));
-        RELAX_TRY(launch_gemm(h, Y, b.qkv.w, b.qkv.b, nullptr, QKV, rows, 3 * dim, dim, 0, s));
-        if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKV, false, 0.f, cls_attention, N, NTOK, v.heads, s));
-        if (attention_only && i == last) return RELAX_OK;
-        RELAX_TRY(single_tile ? launch_attention(h, QKV, Y, N, v.heads, s) : launch_attention_stream_f32(h, QKV, Y, N, NTOK, v.heads, s));
-        RELAX_TRY(launch_gemm(h, Y, b.proj.w, b.proj.b, X, X, rows, dim, dim, 0, s));       // x += proj(attn)
-        RELAX_TRY(launch_layernorm(h, X, b.ln2_g, b.ln2_b, Y, rows, dim, kLnEps, s));
-        RELAX_TRY(launch_gemm(h, Y, b.fc1.w, b.fc1.b, nullptr, Hid, rows, 4 * dim, dim, 2, s));   // GELU(erf)
-        RELAX_TRY(launch_gemm(h, Hid, b.fc2.w, b.fc2.b, X, X, rows, dim, 4 * dim, 0, s));   // x += mlp
+        const float s_qkv = pl.qkv_planes ? b.s_qkv : 0.f;
+        RELAX_TRY(norm_to_operand(b.ln1_g, b.ln1_b, b.s_ln1));
+        RELAX_TRY(linear(pl.arith, Y, b.qkv, nullptr, pl.qkv_planes ? nullptr : QKV, pl.qkv_planes ? QKV : nullptr, s_qkv, rows, 0));
+        if (cls_attention && i == last) RELAX_TRY(launch_vit_cls_attention(h, QKV, pl.qkv_planes, s_qkv, cls_attention, N, NTOK, v.heads, s));
+        if (pl.attention_only && i == last) return RELAX_OK;
+        RELAX_TRY(attention(b));
+        RELAX_TRY(linear(pl.arith, Y, b.proj, X, X, nullptr, 0.f, rows, 0));         // x += proj(attn)
+        RELAX_TRY(norm_to_operand(b.ln2_g, b.ln2_b, b.s_ln2));
+        RELAX_TRY(linear(pl.arith, Y, b.fc1, nullptr, nullptr, Hid, b.s_hid, rows, 2));   // GELU(erf) -> operand form
+        RELAX_TRY(linear(pl.arith, Hid, b.fc2, X, X, nullptr, 0.f, rows, 0));        // x += mlp
         if (taps) RELAX_TRY(vit_tap(h, *taps, i, X, N, NTOK, s));
     }
-    if (taps) return RELAX_OK;
-    RELAX_TRY(launch_layernorm(h, X, v.norm_g, v.norm_b, Y, rows, dim, kLnEps, s));
+    if (!pl.final_norm) return RELAX_OK;
+    RELAX_TRY(launch_layernorm(h, X, v.norm_g, v.norm_b, Final, rows, dim, kLnEps, s));
     if (tokens) {
         const int64_t t = (int64_t)N * NPATCH * (dim / 4);
-        hipLaunchKernelGGL(vit_drop_cls, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, Y, tokens, dim / 4, t, NTOK);
+        hipLaunchKernelGGL(vit_drop_cls, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, Final, tokens, dim / 4, t, NTOK);
     }
-    if (pooled) hipLaunchKernelGGL(vit_token_stats, dim3(dim / 64, N), dim3(256), 0, s, Y, pooled, dim, NTOK, 1, NPATCH);
+    if (pooled) hipLaunchKernelGGL(vit_token_stats, dim3(dim / 64, N), dim3(256), 0, s, Final, pooled, dim, NTOK, 1, NPATCH);
     RELAX_HIP_CHECK(h, hipGetLastError());
     return RELAX_OK;
 }

@@ -1,6 +1,6 @@
 // Stand-alone program (its own main) for AddressSanitizer + UBSan: csrc/host_logic.cpp's conv_hoelder and read_bn on the shapes of
 // tests/test_conv_hoelder_cpu.py and on malformed BatchNorm dicts, and the options table's set / get with an empty key, a 1 KiB key and every
-// key of the table.  Every input and output sits in a heap block of exactly its size, so a read or write past an end is reported.  Built and run by tests/test_conv_hoelder_cpu.py; exit status 0 and "host_logic_san: OK" if all holds.
+// key of the table, and vit_plan on the grid of its CPU test.  Every input and output sits in a heap block of exactly its size, so a read or write past an end is reported.  Built and run by tests/test_conv_hoelder_cpu.py; exit status 0 and "host_logic_san: OK" if all holds.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -122,11 +122,31 @@ static void option_cases() {
     CHECK(o.split_k == 2 && o.precision == 2 && o.h2_form == 2 && o.variant == 2 && o.variant_n64 == 2 && o.group_m == 2 && o.debug_poison == 1);
 }
 
+// vit_plan on the grid of tests/test_vit_plan_cpu.py (options x widths x patch sizes x token counts x requests): the routes in range, the
+// slots in order
+static void vit_plan_cases() {
+    const int depth = 12, requests[6][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 1, 1, 0}, {0, 0, 0, 1}, {0, 0, 0, depth}};
+    for (int precision = 0; precision <= 3; ++precision)
+        for (int sw = 0; sw < 4; ++sw)
+            for (const int dim : {192, 256, 384, 768})
+                for (const int patch : {8, 16})
+                    for (const int ntok : {2, 61, 197, 198, 785, 4097})
+                        for (const auto& r : requests) {
+                            const VitPlan p = vit_plan(VitOptions{precision, sw & 1, sw >> 1}, VitModel{dim, depth, dim / 64, patch, 3 * patch * patch},
+                                                       VitRequest{ntok, ntok - 1, r[0], r[1], r[2], r[3]});
+                            const VitArena& a = p.arena;
+                            CHECK(p.arith >= kVitF32 && p.arith <= kVitH2 && p.attention >= kVitAttention && p.attention <= kVitAttentionStreamH2);
+                            CHECK(a.patches == 0 && a.embedded > 0 && a.residual > a.embedded && a.operand > a.residual && a.qkv > a.operand);
+                            CHECK(a.final >= a.operand && a.hidden > a.qkv && a.hidden > a.final && a.floats > a.hidden);
+                        }
+}
+
 int main() {
     const int shapes[4][2] = {{1, 32}, {3, 64}, {64, 224}, {5, 4608}};
     for (const auto& sh : shapes) hoelder_cases(sh[0], sh[1]);
     read_bn_cases();
     option_cases();
+    vit_plan_cases();
     if (failures) return 1;
     std::printf("host_logic_san: OK\n");
     return 0;

@@ -16,6 +16,8 @@ import ctypes as C
 import os
 import subprocess
 
+from tests import vit_plan_cases
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WRAPS = (2 ** 31, 2 ** 32)
 # nothing here launches more than bench.py does at its default workload: 2048 fragments per backbone ("model": images), 2048 * 197 =
@@ -49,10 +51,9 @@ def host_library(directory):
 
 def vit_layout(lib, dim, patch):
     """The ViT's per-image sizes from the host library's own exports: the geometry (relax_host_vit_geometry) and the arena totals of the
-    two layouts (relax_host_vit_arena_floats).  The totals are not itemised, so the parts are written as the layout states them - fp32:
-    patches + embedded patches + (2 + 3 + 4) x ntok x dim, the 3 being qkv and the 4 the fc1 output; plane layout: 1.5 x patches, embedded
-    patches, (1 + 1.5 + 3 + 1 + 6) x ntok x dim, qkv as 3 and the fc1 output as 6 (bf16x6 planes; the f16x2 planes use 4 of the 6) - and
-    checked against the exported totals: a layout change moves a case or fails here."""
+    two layouts (relax_host_vit_arena_floats), itemised by the slots of host::vit_plan (relax_host_vit_plan: the fp32 layout under
+    gemm_precision 0, the plane layout under 2).  The plan's totals are checked against the exported totals: a layout change moves a case
+    or fails here."""
     geo = (C.c_int * 5)()
     err = C.create_string_buffer(256)
     if lib.relax_host_vit_geometry(patch, geo, err, 256) != 0:
@@ -60,16 +61,17 @@ def vit_layout(lib, dim, patch):
     _, _, npatch, ntok, patch_k = list(geo)
     totals = (C.c_int64 * 2)()
     lib.relax_host_vit_arena_floats(dim, ntok, npatch, patch_k, totals)
-    td = ntok * dim
-    fp32_parts = npatch * patch_k + npatch * dim + td * (2 + 3 + 4)
-    plane_parts = npatch * patch_k * 3 // 2 + npatch * dim + td * 5 + td * 3 // 2 + td * 6
-    if [fp32_parts, plane_parts] != list(totals):
-        raise AssertionError(f"the ViT arena layout moved: {list(totals)} floats per image, the parts restated here give {[fp32_parts, plane_parts]}")
+    fp32, planes = (vit_plan_cases.plan(lib, precision=p, dim=dim, patch=patch, patch_k=patch_k, ntok=ntok, npatch=npatch) for p in (0, 2))
+    if [fp32["floats"], planes["floats"]] != list(totals):
+        raise AssertionError(f"the ViT arena layout moved: {list(totals)} floats per image, the plan's slots end at {[fp32['floats'], planes['floats']]}")
+    fp32, planes = vit_plan_cases.slot_sizes(fp32), vit_plan_cases.slot_sizes(planes)
+    if fp32["qkv"] != planes["qkv"]:
+        raise AssertionError(f"qkv takes {fp32['qkv']} floats per image under fp32 and {planes['qkv']} in the plane layout")
     return {"ntok": ntok, "dim": dim, "arena_fp32": totals[0] * 4, "arena_planes": totals[1] * 4,
-            "qkv": td * 3 * 4,                 # fp32 values, or two fp16 planes of as many values
-            "hidden": td * 4 * 4,              # the fc1 output / fc2 input, fp32 or f16x2 planes
-            "hidden_x6": td * 6 * 4,           # the same as three bf16 planes of 4 x dim values = the layout's 6 x ntok x dim floats
-            "qkv_row": dim * 3 * 4, "hidden_row": dim * 4 * 4}
+            "qkv": fp32["qkv"] * 4,              # fp32 values, or two fp16 planes of as many values
+            "hidden": fp32["hidden"] * 4,        # the fc1 output / fc2 input, fp32 or f16x2 planes
+            "hidden_x6": planes["hidden"] * 4,   # the same as three bf16 planes of 4 x dim values = the layout's 6 x ntok x dim floats
+            "qkv_row": fp32["qkv"] // ntok * 4, "hidden_row": fp32["hidden"] // ntok * 4}
 
 
 def cases(vit):
