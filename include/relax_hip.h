@@ -477,6 +477,19 @@ int relax_resnet50_set_canvas(relax_handle* h, int Hc, int Wc);
 /* the canvas the next forward runs at (either pointer may be NULL) */
 int relax_resnet50_get_canvas(relax_handle* h, int* Hc, int* Wc);
 
+/* ResNet-50 on EVERY canvas size, opt-in.  flags = 0: the two entries above, with their rule and their messages.  RELAX_RN_CANVAS_ANY: Hc and
+ * Wc are any integers in [64, 1024]; every stage follows torch's floor rule floor((n + 2 p - k) / s) + 1, so maps may be odd (65 x 67:
+ * 33 x 34, 17 x 17, 9 x 9, 5 x 5, 3 x 3).  On such a canvas the stem runs its partial-tile form (image rows at any byte alignment), the max-pool
+ * its any-map form (the 3 x 3 window clipped at all four edges, per-image maxima on any map), and every bottleneck the first launch form whose
+ * kernel takes its maps.  On a canvas the default rule accepts the flag changes nothing: the same launches, the same bits.  Any other flag bit
+ * is refused by name; a value outside [64, 1024] is refused naming the value and the canvas ("resnet50: canvas height 63 is not in [64, 1024]
+ * (canvas 63 x 64)").  A refused call leaves the outputs / the previous canvas untouched.  relax_resnet50_get_canvas reports the canvas as
+ * before; relax_load_resnet50 puts 224 x 224 and the default rule back.  Host-only, as the entries above: the forward goes through
+ * relax_resnet50_features / relax_resnet50_clip_features at the handle's canvas. */
+#define RELAX_RN_CANVAS_ANY 1
+int relax_resnet50_canvas_geometry_ex(int Hc, int Wc, int flags, int* tap_hw, int64_t* arena_bytes_per_image);
+int relax_resnet50_set_canvas_ex(relax_handle* h, int Hc, int Wc, int flags);
+
 /* VGG-16 on N fragments (uint8 [N,224,224,3] BGR; images are processed in chunks of at most 32).  Every tap is read POST-ReLU:
  * torchvision's ReLU(inplace=True) behind each hooked module rectifies the hooked tensor before the reference copies it.
  *   layer_stack : fp32 [N,4224] = get_deep_feature('vgg16',..,'layer_stack') + process_video_feature(..,'layer_stack'):

@@ -63,6 +63,8 @@ PROTOTYPES = {
     "relax_resnet50_canvas_geometry": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "relax_resnet50_set_canvas": (C.c_int, [c_vp, C.c_int, C.c_int]),
     "relax_resnet50_get_canvas": (C.c_int, [c_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "relax_resnet50_canvas_geometry_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "relax_resnet50_set_canvas_ex": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_int]),
     "relax_vgg16_features": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, C.POINTER(c_vp), c_vp]),
     "relax_vit_features": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
     "relax_vit_features_ex": (C.c_int, [c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp]),

@@ -282,7 +282,7 @@ const char* relax_last_error(const relax_handle* h) {
 int relax_reserve(relax_handle* h, int max_images) {
     if (!h) return RELAX_ERR_INVALID;
     RELAX_REQUIRE(h, max_images > 0, "relax_reserve: max_images must be > 0");
-    size_t need = resnet_arena_bytes(max_images, h->rn.canvas_h, h->rn.canvas_w);   // (at the canvas set now: 224 x 224 unless relax_resnet50_set_canvas)
+    size_t need = resnet_arena_bytes(max_images, h->rn.canvas_h, h->rn.canvas_w, h->rn.canvas_flags);   // (at the canvas set now: 224 x 224 unless relax_resnet50_set_canvas)
     if (h->vit.loaded) {
         size_t v = vit_arena_bytes(h->vit, max_images);
         if (v > need) need = v;

@@ -443,6 +443,200 @@ __global__ __launch_bounds__(512) void conv1_x6_canvas(const uint8_t* __restrict
 #endif
 }
 
+// ---- the same stem on EVERY canvas (RELAX_RN_CANVAS_ANY: Hc, Wc any integers; host_logic.h, rn_stem_plan) ---------------------------------------
+// What conv1_x6_canvas assumes and this form does not:
+//   * the output map is OH = (Hc - 1) / 2 + 1 by OW = (Wc - 1) / 2 + 1 (torch's floor rule; Hc >> 1 on even sizes only) and need not be whole tiles:
+//     ceil(OH / 16) x ceil(OW / 16) tiles per image, the K loop runs on the whole tile (pixels right of / below the map contract zeros or the
+//     neighbouring rows' pixels: finite, never stored) and only the pixels inside the map are written;
+//   * an image row is Wc * 3 bytes at ANY alignment (65 x 67: 13 065 bytes per image, the images of a batch start at every address mod 4).  A patch
+//     row's window is still the 116 bytes from byte 6 x0 - 12 of the image row (a multiple of 3: byte k of it is channel k % 3); it is read as the 30
+//     ALIGNED dwords that cover it from the address rounded down, and the deposit shifts by that address's two low bits.  A dword that would reach
+//     outside the batch's bytes [0, N Hc Wc 3) - in front of the first image or behind the last row of the last one - is put together from the
+//     bytes that lie inside instead: no read leaves the allocation.  Bytes of a dword that belong to the neighbouring row or image are
+//     deposited as the zeros of the padding, by their position in the row;
+//   * the fused 16-pixel group sums only where a group never crosses a row end (OW a multiple of 16; the launcher refuses `gap` otherwise and the
+//     forward takes the mean from the raw output).
+// The K loop, the split and the order of the products are conv1_mma's: a pixel has the bits conv1_x6_canvas gives it where both forms apply.
+constexpr int C1A_WIN = 4 * C1C_ROW_DW;                    // 116 window bytes per patch row
+constexpr int C1A_ROW_DW = C1C_ROW_DW + 1;                 // 30 aligned dwords cover them at every misalignment (116 + 3 bytes)
+[[maybe_unused]] constexpr int C1A_LOADS = (C1C_PROWS * C1A_ROW_DW + 511) / 512;   // 3 dwords per thread and tile
+static_assert(C1A_WIN - 1 + 3 < C1C_PROW, "every deposited byte lands inside its patch row");
+
+template <bool H2>
+__global__ __launch_bounds__(512) void conv1_x6_any(const uint8_t* __restrict__ frags, const char* __restrict__ w_sp3, float* __restrict__ out,
+                                                    float* __restrict__ gap, int n_tiles, const float* __restrict__ w_inv, int Hc, int Wc, int64_t total_bytes) {
+#if __HIP_DEVICE_COMPILE__
+    constexpr int CH = H2 ? kH2ChunkBytes : kChunkBytes;
+    constexpr int UPR = C1_CHUNKS * CH / 16;
+    constexpr int WROW = C1_CHUNKS * CH + 16;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* wl = smem;
+    float* patch0 = reinterpret_cast<float*>(smem + C1_W_BYTES);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, half = lane >> 5;
+    const int OH = (Hc - 1) / 2 + 1, OW = (Wc - 1) / 2 + 1;
+    const int tiles_x = (OW + C1C_T - 1) / C1C_T, tiles_img = ((OH + C1C_T - 1) / C1C_T) * tiles_x;
+    const int row_bytes = Wc * 3;
+    const uint64_t base_addr = reinterpret_cast<uint64_t>(frags);
+
+    for (int u = tid; u < 64 * UPR; u += 512) {
+        const int n = u / UPR, q = u - n * UPR;
+        *reinterpret_cast<sp3_u32x4*>(wl + n * WROW + q * 16) = *reinterpret_cast<const sp3_u32x4*>(w_sp3 + ((int64_t)n * UPR + q) * 16);
+    }
+    for (int i = tid; i < 2 * C1C_PATCH_FLOATS; i += 512) patch0[i] = 0.f;
+    float* lut = patch0 + 2 * C1C_PATCH_FLOATS;
+    for (int i = tid; i < 3 * 256; i += 512) {
+        const int c = i >> 8;
+        const float u = (float)(i & 255) / 255.0f;                                                      // as rn_preprocess
+        lut[i] = c == 2 ? (u - 0.485f) / 0.229f : c == 1 ? (u - 0.456f) / 0.224f : (u - 0.406f) / 0.225f;
+    }
+    __syncthreads();
+
+    unsigned raw[C1A_LOADS];
+    // tile t: image, first output row / column, first input row, first byte of the window in an image row (negative left of the image)
+    auto tile_geom = [&](int t, int& img, int& y0, int& x0, int& iy0, int& win0) {
+        img = t / tiles_img;
+        const int rem = t - img * tiles_img;
+        const int ty = rem / tiles_x;
+        y0 = ty * C1C_T;
+        x0 = (rem - ty * tiles_x) * C1C_T;
+        iy0 = 2 * y0 - 3;
+        win0 = 6 * x0 - 12;
+    };
+    // byte offset (in the batch) of the window of input row iy, and the two low bits of its address: the aligned dwords start that many bytes before it
+    auto window = [&](int img, int iy, int win0, int64_t& g, int& a) {
+        g = ((int64_t)img * Hc + iy) * row_bytes + win0;
+        a = (int)((base_addr + (uint64_t)g) & 3u);
+    };
+    auto request = [&](int t) {
+        int img, y0, x0, iy0, win0;
+        tile_geom(t, img, y0, x0, iy0, win0);
+#pragma unroll
+        for (int i = 0; i < C1A_LOADS; ++i) {
+            const int e = tid + 512 * i;
+            const int row = e / C1A_ROW_DW, d = e - row * C1A_ROW_DW;
+            const int iy = iy0 + row;
+            unsigned v = 0u;
+            if (row < C1C_PROWS && (unsigned)iy < (unsigned)Hc) {
+                int64_t g;
+                int a;
+                window(img, iy, win0, g, a);
+                const int64_t off = g - a + 4 * d;                  // (frags + off is dword-aligned)
+                if (off >= 0 && off + 4 <= total_bytes) {
+                    v = *reinterpret_cast<const unsigned*>(frags + off);
+                } else {                                            // the ends of the batch: the bytes that exist
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (off + b >= 0 && off + b < total_bytes) v |= (unsigned)frags[off + b] << (8 * b);
+                }
+            }
+            raw[i] = v;
+        }
+    };
+    auto deposit = [&](int t, float* patch) {
+        int img, y0, x0, iy0, win0;
+        tile_geom(t, img, y0, x0, iy0, win0);
+#pragma unroll
+        for (int i = 0; i < C1A_LOADS; ++i) {
+            const int e = tid + 512 * i;
+            const int row = e / C1A_ROW_DW, d = e - row * C1A_ROW_DW;
+            if (row >= C1C_PROWS) continue;
+            const int iy = iy0 + row;
+            const bool row_ok = (unsigned)iy < (unsigned)Hc;
+            int64_t g;
+            int a = 0;
+            if (row_ok) window(img, iy, win0, g, a);               // (a row above / below the image: zeros at shift 0, every window byte once)
+            float* prow = patch + row * C1C_PROW;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int k = 4 * d + b - a;                        // byte of the window
+                if (k < 0 || k >= C1A_WIN) continue;
+                const int c = k % 3;
+                const int rb = win0 + k;                            // byte of the image row
+                const bool ok = row_ok && rb >= 0 && rb < row_bytes;
+                prow[k + 3 - 2 * c] = ok ? lut[c * 256 + ((raw[i] >> (8 * b)) & 255u)] : 0.f;   // (conv1_canvas_put4's column)
+            }
+        }
+    };
+
+    int cur = 0;
+    if ((int)blockIdx.x < n_tiles) {
+        request(blockIdx.x);
+        deposit(blockIdx.x, patch0);
+    }
+    __syncthreads();
+    for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        int img, y0, x0, iy0, win0;
+        tile_geom(t, img, y0, x0, iy0, win0);
+        const float* patch = patch0 + cur * C1C_PATCH_FLOATS;
+        const int next = t + gridDim.x;
+        if (next < n_tiles) request(next);                 // in flight under the MFMAs below
+
+        const int yl = 2 * wave + (r >> 4), xl = r & 15;
+        const float* arow = patch + (2 * yl) * C1C_PROW + C1C_COL0 + 6 * xl + 8 * half;
+        c1_floatx16 acc[2], accs[2];
+        conv1_mma<H2, C1C_PROW>(arow, wl, r, half, acc, accs);
+        if constexpr (H2) {   // the scales are powers of two: exact
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) acc[cb] = (acc[cb] + accs[cb]) * (w_inv[cb * 32 + r] * (1.f / kC1PatchScale));
+        }
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const int y = y0 + 2 * wave + g;
+            if (y >= OH) continue;                             // (wave-uniform) a row below the map
+            const int64_t pixg = ((int64_t)img * OH + y) * OW + x0;
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int col = (i & 3) + 8 * (i >> 2) + 4 * half;
+                    if (x0 + col < OW) out[(pixg + col) * 64 + cb * 32 + r] = acc[cb][8 * g + i];
+                }
+                if (gap) {   // (OW a multiple of 16: the tile's row is whole, inside the map, and one aligned group of the image's pixels)
+                    float s = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) s += acc[cb][8 * g + i];
+                    s += __shfl_xor(s, 32);
+                    if (half == 0) gap[(pixg >> 4) * 64 + cb * 32 + r] = s;
+                }
+            }
+        }
+        if (next < n_tiles) deposit(next, patch0 + (cur ^ 1) * C1C_PATCH_FLOATS);   // the other buffer: nobody reads it during this tile
+        __syncthreads();                                   // next patch complete, every wave done with this one
+        cur ^= 1;
+    }
+#endif
+}
+
+int launch_conv1_x6_any(relax_handle* h, const uint8_t* frags, const void* w_sp3, float* out, float* gap_groups, int N, int Hc, int Wc, hipStream_t s,
+                        const float* w_inv) {
+    RELAX_REQUIRE(h, frags && w_sp3 && out && N > 0 && Hc > 0 && Wc > 0 && Hc <= 4096 && Wc <= 4096, "conv1_x6_any: bad arguments (canvas %d x %d)", Hc, Wc);
+    const int OH = (Hc - 1) / 2 + 1, OW = (Wc - 1) / 2 + 1;
+    RELAX_REQUIRE(h, !gap_groups || OW % 16 == 0, "conv1_x6_any: the fused spatial mean needs output rows of whole 16-pixel groups (%d x %d)", OH, OW);
+    const int64_t tiles = (int64_t)N * ((OH + C1C_T - 1) / C1C_T) * ((OW + C1C_T - 1) / C1C_T);
+    RELAX_REQUIRE(h, tiles < 0x7fffffff, "conv1_x6_any: %d images of %d x %d are too many tiles", N, Hc, Wc);
+    static std::atomic<bool> lds_allowed_any[kMaxDevices];
+    RELAX_TRY(allow_dynamic_lds(h, {reinterpret_cast<const void*>(&conv1_x6_any<false>), reinterpret_cast<const void*>(&conv1_x6_any<true>)}, C1C_LDS,
+                                lds_allowed_any));
+    const int n_tiles = (int)tiles;
+    const int64_t total_bytes = (int64_t)N * Hc * Wc * 3;
+    const double flops = 2.0 * N * (double)OH * OW * 64.0 * 147.0;
+    const double bytes = (double)total_bytes + (double)N * OH * OW * 64 * 4;
+    int span;
+    RELAX_TRY(prof_begin(h, s, w_inv ? 5 : 2, flops, &span, bytes));
+    const dim3 grid(n_tiles < 256 ? n_tiles : 256);
+    if (w_inv)
+        hipLaunchKernelGGL(conv1_x6_any<true>, grid, dim3(512), C1C_LDS, s, frags, static_cast<const char*>(w_sp3), out, gap_groups, n_tiles, w_inv, Hc, Wc,
+                           total_bytes);
+    else
+        hipLaunchKernelGGL(conv1_x6_any<false>, grid, dim3(512), C1C_LDS, s, frags, static_cast<const char*>(w_sp3), out, gap_groups, n_tiles,
+                           static_cast<const float*>(nullptr), Hc, Wc, total_bytes);
+    if (hipGetLastError() != hipSuccess) { prof_abort(h, span); set_error(h, "conv1_x6_any: launch failed"); return RELAX_ERR_HIP; }
+    RELAX_TRY(prof_end(h, s, span));
+    return RELAX_OK;
+}
+
 // fp32 staging rows [64][224]: the packed conv1 rows in this kernel's K layout
 static int conv1_staged(relax_handle* h, const float* w_packed, int kpad, ScopedDev& tmp, const char* what) {
     if (!tmp.alloc(h, 64 * C1_K, what)) return RELAX_ERR_NOMEM;

@@ -233,13 +233,22 @@ const RnBlockGeom* rn_geometry() {
     return t.g;
 }
 
-bool rn_canvas_geometry(int Hc, int Wc, RnCanvasGeometry* g, std::string& err) {
+bool rn_canvas_geometry(int Hc, int Wc, RnCanvasGeometry* g, std::string& err) { return rn_canvas_geometry(Hc, Wc, 0, g, err); }
+
+bool rn_canvas_geometry(int Hc, int Wc, int flags, RnCanvasGeometry* g, std::string& err) {
+    const std::string canvas = " (canvas " + std::to_string(Hc) + " x " + std::to_string(Wc) + ")";
+    if (flags & ~kRnCanvasAny) {
+        err = "resnet50: canvas flags " + std::to_string(flags) + " have unknown bits " + std::to_string(flags & ~kRnCanvasAny) +
+              " (RELAX_RN_CANVAS_ANY = " + std::to_string(kRnCanvasAny) + " is the only flag)" + canvas;
+        return false;
+    }
     for (int axis = 0; axis < 2; ++axis) {
         const int v = axis == 0 ? Hc : Wc;
-        if (v >= kRnCanvasMin && v <= kRnCanvasMax && v % kRnCanvasStep == 0) continue;
-        err = std::string("resnet50: canvas ") + (axis == 0 ? "height " : "width ") + std::to_string(v) + " is not a multiple of " +
-              std::to_string(kRnCanvasStep) + " in [" + std::to_string(kRnCanvasMin) + ", " + std::to_string(kRnCanvasMax) + "] (canvas " +
-              std::to_string(Hc) + " x " + std::to_string(Wc) + ")";
+        const bool in_range = v >= kRnCanvasMin && v <= kRnCanvasMax;
+        if (in_range && ((flags & kRnCanvasAny) || v % kRnCanvasStep == 0)) continue;
+        const std::string what = std::string("resnet50: canvas ") + (axis == 0 ? "height " : "width ") + std::to_string(v);
+        const std::string range = "[" + std::to_string(kRnCanvasMin) + ", " + std::to_string(kRnCanvasMax) + "]";
+        err = (flags & kRnCanvasAny) ? what + " is not in " + range + canvas : what + " is not a multiple of " + std::to_string(kRnCanvasStep) + " in " + range + canvas;
         return false;
     }
     RnCanvasGeometry r{};
@@ -250,13 +259,14 @@ bool rn_canvas_geometry(int Hc, int Wc, RnCanvasGeometry* g, std::string& err) {
     static const int tap_c[kRnTaps] = {64, 256, 256, 256, 512, 512, 512, 512, 1024, 1024, 1024, 1024, 2048, 2048, 2048};
     H = (H + 2 - 3) / 2 + 1; W = (W + 2 - 3) / 2 + 1;
     const int64_t hw1 = (int64_t)H * W;      // layer1's maps
-    r.block_max = (hw1 * (64 / 4) / 256 + 63) / 64 * 64;
+    r.block_max = ((hw1 * (64 / 4) + 255) / 256 + 63) / 64 * 64;
     for (int b = 0; b < kRnBlocks; ++b) {
         H = (H + 2 - 3) / blocks[b].stride + 1; W = (W + 2 - 3) / blocks[b].stride + 1;
         if (blocks[b].tap >= 0) { r.tap_hw[blocks[b].tap][0] = H; r.tap_hw[blocks[b].tap][1] = W; }
     }
     r.x0 = (int64_t)Hc * Wc * 4;
     r.big = (int64_t)r.tap_hw[0][0] * r.tap_hw[0][1] * 64;
+    if (hw1 * 256 > r.big) r.big = hw1 * 256;   // (odd stem maps: the max-pool rounds up, layer1's 256-channel output is the larger tensor)
     r.t1 = hw1 * 128;
     r.t2 = hw1 * 64;
     r.gap_ws = 16 * 2048;
@@ -281,7 +291,9 @@ bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* pla
 bool rn_plan(const RnOptions& o, const RnRequest& rq, const RnCanvas& cv, int max_slots, RnPlan* plan, std::string& err) {
     const RnBlockGeom* g = rn_geometry();
     RnCanvasGeometry geo;
-    if (!rn_canvas_geometry(cv.Hc, cv.Wc, &geo, err)) return false;
+    if (!rn_canvas_geometry(cv.Hc, cv.Wc, cv.flags, &geo, err)) return false;
+    RnStemPlan stem;
+    if (!rn_stem_plan(cv, &stem, err)) return false;
     const int H1 = geo.tap_hw[1][0], W1 = geo.tap_hw[1][1];   // layer1's maps: the max-pool's output
     RnPlan p{};
     // f16x2 for layer3 / layer4 ("gemm_precision" 3 with "rn_h2"): per-image tables {maximum, scale, 1 / scale}, one slot per tensor
@@ -289,7 +301,8 @@ bool rn_plan(const RnOptions& o, const RnRequest& rq, const RnCanvas& cv, int ma
     // "rn_h2_early": the 3x3 convolutions of layer1 / layer2 on f16x2 as well (gemm_x6.hip, H2 form).  Their input (conv1's output)
     // is written as fp16 planes with the image's Hoelder scale  l1max(conv1) max|block input| + max|bias|; the block input's maximum
     // is measured by its producer: the max-pool (block maxima, reduced per image) or the previous block's conv3 epilogue.
-    bool use_early = use_h2 && o.rn_h2_early && rn_maps_pool_maxima(H1, W1, g[0].cin);
+    // (the any-map max-pool posts per-image maxima on every map)
+    bool use_early = use_h2 && o.rn_h2_early && (stem.pool_form == kRnPoolAny || rn_maps_pool_maxima(H1, W1, g[0].cin));
     for (int b = 0; b < kRnFirstH2Block && use_early; ++b) use_early = rn_early_h2(g[b].width, g[b].width);
     // "rn_fuse": layer1[0] back to back too, with the downsample convolution folded into its conv3 - the block input then travels as fp32 rows
     // (4 B per value instead of 6: conv1 splits them in its K loop, the fused launch reads each pixel's row as conv3's second source)
@@ -380,6 +393,23 @@ bool rn_plan(const RnOptions& o, const RnRequest& rq, const RnCanvas& cv, int ma
     if (next_slot > max_slots) {
         err = "resnet50: " + std::to_string(next_slot) + " per-image scale slots used, " + std::to_string(max_slots) + " reserved";
         return false;
+    }
+    *plan = p;
+    return true;
+}
+
+bool rn_stem_plan(const RnCanvas& cv, RnStemPlan* plan, std::string& err) {
+    RnCanvasGeometry geo;
+    if (!rn_canvas_geometry(cv.Hc, cv.Wc, cv.flags, &geo, err)) return false;
+    RnStemPlan p{};
+    if (rn_canvas_default_rule(cv.Hc, cv.Wc) && !((cv.flags & kRnCanvasAny) && cv.force_any)) {
+        p.stem_form = cv.Hc == kRnCanvasDefault && cv.Wc == kRnCanvasDefault ? kRnStem224 : kRnStemTiles;
+        p.pool_form = kRnPoolEven;
+        p.stem_fused_mean = 1;
+    } else {
+        p.stem_form = kRnStemAny;
+        p.pool_form = kRnPoolAny;
+        p.stem_fused_mean = rn_maps_stem_fused_mean(geo.tap_hw[0][0], geo.tap_hw[0][1]);
     }
     *plan = p;
     return true;
@@ -1262,13 +1292,27 @@ int relax_host_flow_chunk_pairs(int H, int W, int64_t ws_gb, int flow_max_pairs,
     return relax::host::flow_chunk_pairs(H, W, ws_gb, flow_max_pairs, T);
 }
 // the 16 bottlenecks: block, layer, index, cin, width, cout, stride, has_down, tap (16 * 9 ints)
-// the same on an [Hc, Wc] canvas; a refused canvas: -1 and rn_canvas_geometry's message
-int relax_host_rn_plan_canvas(const int* opts, const int* req, int Hc, int Wc, int max_slots, int* out, char* err, int err_len) {
+// the canvas entries under canvas flags (kRnCanvasAny; 0: the default rule and its messages)
+int relax_host_rn_canvas_geometry_ex(int Hc, int Wc, int flags, int* tap_hw, int64_t* sizes, char* err, int err_len) {
+    relax::host::RnCanvasGeometry g;
+    std::string e;
+    if (!relax::host::rn_canvas_geometry(Hc, Wc, flags, &g, e)) {
+        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return -1;
+    }
+    if (tap_hw) std::memcpy(tap_hw, g.tap_hw, sizeof(g.tap_hw));
+    if (sizes) {
+        const int64_t v[8] = {g.x0, g.big, g.t1, g.t2, g.gap_ws, g.block_max, g.floats_f32, g.floats_x6};
+        std::memcpy(sizes, v, sizeof(v));
+    }
+    return 0;
+}
+int relax_host_rn_plan_canvas_ex(const int* opts, const int* req, int Hc, int Wc, int flags, int max_slots, int* out, char* err, int err_len) {
     using namespace relax::host;
     const RnOptions o{opts[0], opts[1], opts[2], opts[3], opts[4], opts[5]};
     const RnRequest rq{req[0], req[1], req[2], req[3], (unsigned)req[4]};
     RnCanvas cv;
-    cv.Hc = Hc; cv.Wc = Wc;
+    cv.Hc = Hc; cv.Wc = Wc; cv.flags = flags;
     RnPlan p;
     std::string e;
     if (!rn_plan(o, rq, cv, max_slots, &p, e)) {
@@ -1278,19 +1322,26 @@ int relax_host_rn_plan_canvas(const int* opts, const int* req, int Hc, int Wc, i
     std::memcpy(out, &p, sizeof(p));
     return 0;
 }
+// the same on an [Hc, Wc] canvas; a refused canvas: -1 and rn_canvas_geometry's message
+int relax_host_rn_plan_canvas(const int* opts, const int* req, int Hc, int Wc, int max_slots, int* out, char* err, int err_len) {
+    return relax_host_rn_plan_canvas_ex(opts, req, Hc, Wc, 0, max_slots, out, err, err_len);
+}
 // canvas geometry: tap_hw [15][2]; sizes = x0, big, t1, t2, gap_ws, block_max, floats_f32, floats_x6 (8 values).  0, or -1 and the message
 int relax_host_rn_canvas_geometry(int Hc, int Wc, int* tap_hw, int64_t* sizes, char* err, int err_len) {
-    relax::host::RnCanvasGeometry g;
+    return relax_host_rn_canvas_geometry_ex(Hc, Wc, 0, tap_hw, sizes, err, err_len);
+}
+// the launches in front of the blocks: out = stem_form, pool_form, stem_fused_mean
+int relax_host_rn_stem_plan_ex(int Hc, int Wc, int flags, int* out, char* err, int err_len) {
+    using namespace relax::host;
+    RnCanvas cv;
+    cv.Hc = Hc; cv.Wc = Wc; cv.flags = flags;
+    RnStemPlan p;
     std::string e;
-    if (!relax::host::rn_canvas_geometry(Hc, Wc, &g, e)) {
+    if (!rn_stem_plan(cv, &p, e)) {
         if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
         return -1;
     }
-    if (tap_hw) std::memcpy(tap_hw, g.tap_hw, sizeof(g.tap_hw));
-    if (sizes) {
-        const int64_t v[8] = {g.x0, g.big, g.t1, g.t2, g.gap_ws, g.block_max, g.floats_f32, g.floats_x6};
-        std::memcpy(sizes, v, sizeof(v));
-    }
+    std::memcpy(out, &p, sizeof(p));
     return 0;
 }
 void relax_host_rn_geometry(int* out) { std::memcpy(out, relax::host::rn_geometry(), sizeof(relax::host::RnBlockGeom) * relax::host::kRnBlocks); }

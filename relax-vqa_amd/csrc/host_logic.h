@@ -365,7 +365,10 @@ bool rn_plan(const RnOptions& o, const RnRequest& rq, int max_slots, RnPlan* pla
 // stage map is even down to layer4 and the stem's output is whole 256-pixel tiles per image: Hc and Wc multiples of 32 in [64, 1024].
 constexpr int kRnTaps = 15;
 constexpr int kRnCanvasDefault = 224, kRnCanvasStep = 32, kRnCanvasMin = 64, kRnCanvasMax = 1024;
-struct RnCanvas { int Hc = kRnCanvasDefault, Wc = kRnCanvasDefault; };
+constexpr int kRnCanvasAny = 1;   // RELAX_RN_CANVAS_ANY: Hc and Wc any integers in [kRnCanvasMin, kRnCanvasMax] (odd maps, partial stem tiles)
+// force_any: under kRnCanvasAny, run the any-size stem and max-pool also where the default rule takes the canvas (tools/resnet_anysize_bench.py times the
+// two forms on one canvas with it; nothing else sets it)
+struct RnCanvas { int Hc = kRnCanvasDefault, Wc = kRnCanvasDefault, flags = 0, force_any = 0; };
 // Map sizes and the per-image floats of the forward's arena (resnet50.hip carves it in this order; every count is a multiple of 4).
 struct RnCanvasGeometry {
     int tap_hw[kRnTaps][2];       // {h, w} of every tap: the stem's raw output, then the tapped blocks (224 x 224: 112, 56 x 3, 28 x 4, 14 x 4, 7 x 3)
@@ -378,6 +381,14 @@ struct RnCanvasGeometry {
 };
 // false and a message that names the offending value (height before width) for anything but an accepted canvas
 bool rn_canvas_geometry(int Hc, int Wc, RnCanvasGeometry* g, std::string& err);
+// the same under `flags`: 0 is the rule above with its messages; kRnCanvasAny takes every Hc, Wc in [64, 1024] - torch's floor rule per stage, so
+// maps may be odd (then `big` is the larger of the stem's output and a layer1 block's, which the halving no longer makes equal); any other bit is
+// refused by name
+bool rn_canvas_geometry(int Hc, int Wc, int flags, RnCanvasGeometry* g, std::string& err);
+// whether the default rule takes the canvas (Hc and Wc multiples of 32 in [64, 1024])
+inline bool rn_canvas_default_rule(int Hc, int Wc) {
+    return Hc >= kRnCanvasMin && Hc <= kRnCanvasMax && Hc % kRnCanvasStep == 0 && Wc >= kRnCanvasMin && Wc <= kRnCanvasMax && Wc % kRnCanvasStep == 0;
+}
 constexpr int kRnAvgFloats = 2048, kRnImgSlots = 64;   // per image: the avgpool vector; the per-image tables {maximum, scale, 1 / scale} of the f16x2 launches
 
 // What a launch form asks of the MAPS of the block it runs on, restated from the kernels' own preconditions: a form is planned for a block only
@@ -392,6 +403,17 @@ inline bool rn_maps_sample2(int Ho, int Wo) { return Ho % 2 == 0 && Wo % 2 == 0;
 inline bool rn_maps_pool_maxima(int Hp, int Wp, int C) { return ((int64_t)Hp * Wp * (C / 4)) % 256 == 0; }
 // The schedule on an accepted canvas (the caller has run rn_canvas_geometry).  At 224 x 224 it is rn_plan's above, int for int.
 bool rn_plan(const RnOptions& o, const RnRequest& rq, const RnCanvas& cv, int max_slots, RnPlan* plan, std::string& err);
+// The launches in front of the blocks (RnPlan keeps its layout: these facts live here).  A canvas the default rule takes runs the forms it always
+// ran, whatever the flags; the any-size forms run only on the canvases that rule refuses.
+enum RnStemForm { kRnStem224 = 0, kRnStemTiles, kRnStemAny };   // conv1_x6 / conv1_x6_canvas (whole 16 x 16 tiles) / conv1_x6_any (partial tiles, rows at any alignment)
+enum RnPoolForm { kRnPoolEven = 0, kRnPoolAny };                // bn_relu_maxpool_nhwc (even maps, block maxima) / bn_relu_maxpool_any (any map, a ragged last block per image)
+struct RnStemPlan {
+    int stem_form, pool_form;
+    int stem_fused_mean;         // tap 0's 16-pixel group sums formed in the stem's epilogue (else the mean is taken from the raw output)
+};
+// the any-size stem fuses the mean where 16 consecutive pixels never cross a row end: output rows of whole 16-pixel groups
+inline bool rn_maps_stem_fused_mean(int Ho, int Wo) { return Ho > 0 && Wo % 16 == 0; }
+bool rn_stem_plan(const RnCanvas& cv, RnStemPlan* plan, std::string& err);
 
 // ---- DINO ViT geometry (224x224 input, 64-d heads) and the streaming attention kernel's plan (vit.hip, attention_stream.hip) ----------
 struct VitGeometry { int patch, side, npatch, ntok, patch_k; };   // patch 16: 14 per side, 196 patches, 197 tokens, K = 768; patch 8: 28, 784, 785, 192

@@ -377,6 +377,72 @@ int launch_bn_relu_maxpool_sp3(relax_handle* h, const float* x, const float* sca
     return RELAX_OK;
 }
 
+// ---- the same max-pool on ANY map (ResNet-50 under RELAX_RN_CANVAS_ANY) -----------------------------------------------------------------
+// torch's floor rule: Ho = (H - 1) / 2 + 1 (odd H: the last window starts on the last row), the 3 x 3 window clipped at all four edges (a clipped
+// tap is -inf to a maximum: skipped).  A workgroup stays inside one image - blocks_per_image = ceil(Ho Wo C/4 / 256) with a ragged last block, whose
+// idle threads store nothing and carry 0 into the maximum (the outputs are >= 0) - and posts its largest output with one plain store, as the even
+// form does; image_max_of_blocks reduces the blocks_per_image words of an image: no atomics, no order dependence.  (One atomicMax per block on the
+// image's word was measured first: 2304 blocks of an image contending for one address cost the 288 x 512 launch 335 us against 186.)
+template <bool SP3>
+__global__ __launch_bounds__(256) void bn_relu_maxpool_any(const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
+                                                           void* __restrict__ yv, int H, int W, int C, int blocks_per_image, unsigned* __restrict__ block_max) {
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, C4 = C / 4;
+    const int n = blockIdx.x / blocks_per_image;
+    const int i = (blockIdx.x - n * blocks_per_image) * 256 + threadIdx.x;   // (Ho Wo C4 <= 256 * 256 * 16)
+    const bool live = i < Ho * Wo * C4;
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) {
+        const int c4 = i % C4, pix = i / C4;
+        const int ox = pix % Wo, oy = pix / Wo;
+        const float4 sc = reinterpret_cast<const float4*>(scale)[c4];
+        const float4 sh = reinterpret_cast<const float4*>(shift)[c4];
+        m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+            const int iy = oy * 2 - 1 + dy;
+            if ((unsigned)iy >= (unsigned)H) continue;
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const int ix = ox * 2 - 1 + dx;
+                if ((unsigned)ix >= (unsigned)W) continue;
+                const float4 v = reinterpret_cast<const float4*>(x + (((int64_t)n * H + iy) * W + ix) * C)[c4];
+                m.x = fmaxf(m.x, fmaxf(v.x * sc.x + sh.x, 0.f));
+                m.y = fmaxf(m.y, fmaxf(v.y * sc.y + sh.y, 0.f));
+                m.z = fmaxf(m.z, fmaxf(v.z * sc.z + sh.z, 0.f));
+                m.w = fmaxf(m.w, fmaxf(v.w * sc.w + sh.w, 0.f));
+            }
+        }
+        const int64_t opix = ((int64_t)n * Ho + oy) * Wo + ox;   // (the window's centre (2 oy, 2 ox) is always inside the map: m is finite)
+        if (SP3) store_sp3_x4(static_cast<char*>(yv) + opix * C * 6, 4 * c4, (sp3_f32x4){m.x, m.y, m.z, m.w});
+        else reinterpret_cast<float4*>(static_cast<float*>(yv) + opix * C)[c4] = m;
+    }
+    if (block_max) {   // (kernel argument: every thread of the block reaches the barrier)
+        __shared__ unsigned wmax[4];
+        float mx = fmaxf(fmaxf(m.x, m.y), fmaxf(m.z, m.w));
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = __float_as_uint(mx);
+        __syncthreads();
+        if (threadIdx.x == 0) block_max[blockIdx.x] = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));   // (block n * blocks_per_image + its index in the image)
+    }
+}
+
+int launch_bn_relu_maxpool_any(relax_handle* h, const float* x, const float* scale, const float* shift, float* y, void* y_sp3, int Nimg, int H, int W,
+                               int C, hipStream_t s, unsigned* amax_out, unsigned* block_ws) {
+    RELAX_REQUIRE(h, Nimg > 0 && H > 0 && W > 0 && C > 0 && C % (y_sp3 ? 16 : 4) == 0 && (y != nullptr) != (y_sp3 != nullptr), "bn_relu_maxpool_any: bad shape");
+    const int64_t per_image = (int64_t)((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * (C / 4);
+    const int64_t blocks_per_image = (per_image + 255) / 256;
+    RELAX_REQUIRE(h, per_image < (1 << 30) && blocks_per_image * Nimg < 0x7fffffff, "bn_relu_maxpool_any: %d maps of %d x %d x %d are too many", Nimg, H, W, C);
+    RELAX_REQUIRE(h, !amax_out || block_ws, "bn_relu_maxpool_any: per-image maxima need the block workspace");
+    const dim3 grid((unsigned)(blocks_per_image * Nimg));
+    unsigned* bm = amax_out ? block_ws : nullptr;
+    if (y_sp3) hipLaunchKernelGGL(bn_relu_maxpool_any<true>, grid, dim3(256), 0, s, x, scale, shift, y_sp3, H, W, C, (int)blocks_per_image, bm);
+    else hipLaunchKernelGGL(bn_relu_maxpool_any<false>, grid, dim3(256), 0, s, x, scale, shift, static_cast<void*>(y), H, W, C, (int)blocks_per_image, bm);
+    if (amax_out) hipLaunchKernelGGL(image_max_of_blocks, dim3(Nimg), dim3(64), 0, s, block_ws, (int)blocks_per_image, amax_out);
+    RELAX_HIP_CHECK(h, hipGetLastError());
+    return RELAX_OK;
+}
+
 // ---- global average pool, deterministic two-stage ---------------------------------------------------------------
 // stage 1: grid (C/64, Nimg, S); a workgroup owns 64 channels of one image and 1/S of the pixels;
 //          16 lanes x float4 cover the channels (256 B coalesced), 16 lane-groups stride the pixels;

@@ -209,6 +209,7 @@ struct ResNet50W {
     std::vector<Bottleneck> blocks;  // 16
     DeviceOwner mem;
     int canvas_h = 224, canvas_w = 224;   // the canvas the forward reads its images at (relax_resnet50_set_canvas; a load puts 224 x 224 back)
+    int canvas_flags = 0;                 // the rule it was accepted under (relax_resnet50_set_canvas_ex: RELAX_RN_CANVAS_ANY; a load puts 0 back)
 };
 
 struct LinearW {
@@ -427,6 +428,10 @@ int make_conv1_x6_weights(relax_handle* h, const float* w_packed, int kpad, void
 int launch_conv1_x6(relax_handle* h, const uint8_t* frags, const void* w_sp3, float* out, float* gap_groups, int N, int Hc, int Wc, hipStream_t s,
                     const float* w_inv = nullptr);   // frags [N,Hc,Wc,3]; w_inv: `w_sp3` holds fp16 planes and the f16x2 form runs
 int make_conv1_h2_weights(relax_handle* h, const float* w_packed, int kpad, void** w_h2_out, float** w_inv_out, DeviceOwner& mem);
+// the same stem on any canvas: out [N,(Hc-1)/2+1,(Wc-1)/2+1,64], partial 16 x 16 tiles, image rows at any byte alignment; gap_groups only where
+// the output rows are whole 16-pixel groups (host_logic.h: rn_maps_stem_fused_mean)
+int launch_conv1_x6_any(relax_handle* h, const uint8_t* frags, const void* w_sp3, float* out, float* gap_groups, int N, int Hc, int Wc, hipStream_t s,
+                        const float* w_inv = nullptr);
 inline int launch_gemm_x6(relax_handle* h, const void* A_sp3, const void* W_sp3, const float* bias, const float* residual,
                           float* out, void* out_sp3, int M, int N, int K, int act, hipStream_t s) {
     ConvDescX6 d{};
@@ -485,6 +490,10 @@ int launch_bn_relu_maxpool_f32(relax_handle* h, const float* x, const float* sca
                                hipStream_t s, unsigned* amax_out, unsigned* block_ws);   // fp32 rows out + the per-image maxima
 int launch_bn_relu_maxpool_sp3(relax_handle* h, const float* x, const float* scale, const float* shift, void* y_sp3,
                                int Nimg, int H, int W, int C, hipStream_t s, unsigned* amax_out = nullptr, unsigned* block_ws = nullptr);
+// the same max-pool on any map: out [(H-1)/2+1][(W-1)/2+1], the window clipped at all four edges.  y: fp32 rows; y_sp3: bf16 planes (one of the two);
+// amax_out [Nimg]: the per-image maximum of the outputs, posted on any map (block_ws: Nimg * ceil(Ho Wo C/4 / 256) words of scratch)
+int launch_bn_relu_maxpool_any(relax_handle* h, const float* x, const float* scale, const float* shift, float* y, void* y_sp3, int Nimg, int H, int W,
+                               int C, hipStream_t s, unsigned* amax_out, unsigned* block_ws);
 int launch_gap_groups_finish(relax_handle* h, const float* groups, float* out, int Nimg, int HW, int C, int64_t out_stride,
                              hipStream_t s);
 int launch_gap_groups_finish_rows(relax_handle* h, const float* groups, float* out, int Nimg, int HW, int C, int64_t out_stride, int group,
@@ -503,7 +512,7 @@ void free_head(relax_handle* h);
 void free_head_train(relax_handle* h);
 void free_vgg(relax_handle* h);
 size_t vgg_arena_bytes(int n_images);
-size_t resnet_arena_bytes(int n_images, int Hc = 224, int Wc = 224);   // 0 for a canvas the forward does not take
+size_t resnet_arena_bytes(int n_images, int Hc = 224, int Wc = 224, int flags = 0);   // 0 for a canvas the forward does not take under `flags` (RELAX_RN_CANVAS_ANY)
 size_t vit_arena_bytes(const VitW& v, int n_images);                          // at the loaded geometry (224 x 224: relax_reserve)
 size_t vit_arena_bytes(const VitW& v, int n_images, int ntok, int npatch);    // at a call's geometry
 

@@ -10,6 +10,7 @@
 // eval-mode BatchNorm folded in (scale into the weights, shift as bias); bn1 stays separate because
 // the conv1 tap is taken before it.
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 #include "relax_internal.h"
@@ -135,11 +136,18 @@ void free_resnet(relax_handle* h) {
 static constexpr size_t kAvg = host::kRnAvgFloats;
 static constexpr size_t kImgSlots = host::kRnImgSlots;   // per-image tables of the f16x2 blocks: slot t = {maximum, scale, 1 / scale} x images
 
-size_t resnet_arena_bytes(int n, int Hc, int Wc) {
+size_t resnet_arena_bytes(int n, int Hc, int Wc, int flags) {
     host::RnCanvasGeometry g;
     std::string err;
-    if (!host::rn_canvas_geometry(Hc, Wc, &g, err)) return 0;
+    if (!host::rn_canvas_geometry(Hc, Wc, flags, &g, err)) return 0;
     return sizeof(float) * (size_t)(g.floats_f32 > g.floats_x6 ? g.floats_f32 : g.floats_x6) * (size_t)n;
+}
+
+// RELAX_RN_FORCE_ANY_FORMS=1 in the environment (read once): a canvas set under RELAX_RN_CANVAS_ANY runs the any-size stem and max-pool even where the
+// default rule takes it.  For tools/resnet_anysize_bench.py, which times the two forms of each on one canvas; not an option of the library.
+static bool force_any_forms() {
+    static const bool on = [] { const char* v = std::getenv("RELAX_RN_FORCE_ANY_FORMS"); return v && std::atoi(v) != 0; }();
+    return on;
 }
 
 // output side of a convolution along one axis
@@ -311,25 +319,32 @@ int relax_load_resnet50(relax_handle* h, const float* const* tensors, const char
 }
 
 int relax_resnet50_canvas_geometry(int Hc, int Wc, int* tap_hw, int64_t* arena_bytes_per_image) {
+    return relax_resnet50_canvas_geometry_ex(Hc, Wc, 0, tap_hw, arena_bytes_per_image);
+}
+
+int relax_resnet50_canvas_geometry_ex(int Hc, int Wc, int flags, int* tap_hw, int64_t* arena_bytes_per_image) {
     host::RnCanvasGeometry g;
     std::string err;
-    if (!host::rn_canvas_geometry(Hc, Wc, &g, err)) {
+    if (!host::rn_canvas_geometry(Hc, Wc, flags, &g, err)) {
         set_error(nullptr, "%s", err.c_str());   // (no handle: relax_last_error(NULL), this thread's)
         return RELAX_ERR_INVALID;
     }
     if (tap_hw) std::memcpy(tap_hw, g.tap_hw, sizeof(g.tap_hw));
-    if (arena_bytes_per_image) *arena_bytes_per_image = (int64_t)resnet_arena_bytes(1, Hc, Wc);
+    if (arena_bytes_per_image) *arena_bytes_per_image = (int64_t)resnet_arena_bytes(1, Hc, Wc, flags);
     return RELAX_OK;
 }
 
 // validation and two integers: no launch, no allocation, no synchronisation (the arena grows in the forward)
-int relax_resnet50_set_canvas(relax_handle* h, int Hc, int Wc) {
+int relax_resnet50_set_canvas(relax_handle* h, int Hc, int Wc) { return relax_resnet50_set_canvas_ex(h, Hc, Wc, 0); }
+
+int relax_resnet50_set_canvas_ex(relax_handle* h, int Hc, int Wc, int flags) {
     if (!h) return RELAX_ERR_INVALID;
     host::RnCanvasGeometry g;
     std::string err;
-    RELAX_REQUIRE(h, host::rn_canvas_geometry(Hc, Wc, &g, err), "%s", err.c_str());
+    RELAX_REQUIRE(h, host::rn_canvas_geometry(Hc, Wc, flags, &g, err), "%s", err.c_str());
     h->rn.canvas_h = Hc;
     h->rn.canvas_w = Wc;
+    h->rn.canvas_flags = flags;
     return RELAX_OK;
 }
 
@@ -346,16 +361,20 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
                           float* const* taps_nchw, hipStream_t s) {
     // the canvas is read here, once: a captured graph keeps the canvas it was captured with
     const int Hc = h->rn.canvas_h, Wc = h->rn.canvas_w;
+    host::RnCanvas cv;
+    cv.Hc = Hc; cv.Wc = Wc; cv.flags = h->rn.canvas_flags;
+    cv.force_any = (cv.flags & host::kRnCanvasAny) && force_any_forms();
     host::RnCanvasGeometry geo;
+    host::RnStemPlan stem;   // which stem and max-pool kernels take this canvas: the any-size forms only where the default rule refuses it
     {
         std::string geo_err;
-        RELAX_REQUIRE(h, host::rn_canvas_geometry(Hc, Wc, &geo, geo_err), "%s", geo_err.c_str());
+        RELAX_REQUIRE(h, host::rn_canvas_geometry(Hc, Wc, cv.flags, &geo, geo_err) && host::rn_stem_plan(cv, &stem, geo_err), "%s", geo_err.c_str());
     }
     const size_t kX0 = (size_t)geo.x0, kBig = (size_t)geo.big, kT1 = (size_t)geo.t1, kT2 = (size_t)geo.t2, kGapWs = (size_t)geo.gap_ws;
     const int H0 = geo.tap_hw[0][0], W0 = geo.tap_hw[0][1];       // the stem's output (112 x 112)
     const int H1 = geo.tap_hw[1][0], W1 = geo.tap_hw[1][1];       // the max-pool's (56 x 56)
     const int HWlast = geo.tap_hw[RELAX_RN50_NUM_TAPS - 1][0] * geo.tap_hw[RELAX_RN50_NUM_TAPS - 1][1];   // layer4's map (49 positions)
-    RELAX_TRY(ensure_buf(h, h->arena, resnet_arena_bytes(N, Hc, Wc)));
+    RELAX_TRY(ensure_buf(h, h->arena, resnet_arena_bytes(N, Hc, Wc, cv.flags)));
     float* base = static_cast<float*>(h->arena.p);
     const size_t n = (size_t)N;
     float* X0 = base;
@@ -399,8 +418,6 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
         for (int t = 0; taps_nchw && t < RELAX_RN50_NUM_TAPS; ++t) rq.taps |= taps_nchw[t] ? 1u << t : 0u;
         host::RnPlan plan;
         std::string plan_err;
-        host::RnCanvas cv;
-        cv.Hc = Hc; cv.Wc = Wc;
         RELAX_REQUIRE(h, rn.blocks.size() == (size_t)host::kRnBlocks && host::rn_plan(opt, rq, cv, (int)kImgSlots, &plan, plan_err), "%s",
                       plan_err.empty() ? "resnet50: not the 16 bottlenecks of the schedule" : plan_err.c_str());
         // bf16x6.  conv1 7x7/2 (raw) straight from the uint8 fragments (conv1_x6.hip: preprocess, im2col, split and contraction in one
@@ -408,9 +425,15 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
         // travels as split planes written by its producer
         float* gap0 = T2 + kT2 * n;   // = the fp32 carving's gapws: free until the blocks carve the arena anew below
         RELAX_REQUIRE(h, !plan.conv1_h2 || rn.conv1.w_h2, "resnet50: the stem's fp16-plane weights are missing");
-        RELAX_TRY(launch_conv1_x6(h, frags, plan.conv1_h2 ? rn.conv1.w_h2 : rn.conv1.w_sp3, bufA, layer_stack ? gap0 : nullptr, N, Hc, Wc, s,
-                                  plan.conv1_h2 ? rn.conv1.w_inv : nullptr));
-        if (layer_stack) RELAX_TRY(launch_gap_groups_finish(h, gap0, layer_stack, n_ls, H0 * W0, 64, RELAX_RN50_LAYER_STACK_DIM, s));
+        const bool stem_mean = layer_stack && stem.stem_fused_mean;
+        if (stem.stem_form == host::kRnStemAny)
+            RELAX_TRY(launch_conv1_x6_any(h, frags, plan.conv1_h2 ? rn.conv1.w_h2 : rn.conv1.w_sp3, bufA, stem_mean ? gap0 : nullptr, N, Hc, Wc, s,
+                                          plan.conv1_h2 ? rn.conv1.w_inv : nullptr));
+        else
+            RELAX_TRY(launch_conv1_x6(h, frags, plan.conv1_h2 ? rn.conv1.w_h2 : rn.conv1.w_sp3, bufA, stem_mean ? gap0 : nullptr, N, Hc, Wc, s,
+                                      plan.conv1_h2 ? rn.conv1.w_inv : nullptr));
+        if (stem_mean) RELAX_TRY(launch_gap_groups_finish(h, gap0, layer_stack, n_ls, H0 * W0, 64, RELAX_RN50_LAYER_STACK_DIM, s));
+        else if (layer_stack) RELAX_TRY(launch_gap_ws(h, bufA, layer_stack, n_ls, H0 * W0, 64, RELAX_RN50_LAYER_STACK_DIM, gap0, s));   // (the raw output's mean, as the later taps')
         if (taps_nchw && taps_nchw[0]) RELAX_TRY(launch_nhwc_to_nchw(h, bufA, taps_nchw[0], N, H0 * W0, 64, s));
         float* f32a = bufB;                                   // block outputs as fp32, where something needs them (ping-pong with f32b)
         float* f32b = bufD;
@@ -442,7 +465,10 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
         };
         if (plan.n_slots) RELAX_HIP_CHECK(h, fill_async(imgtab, 0, sizeof(float) * 3 * kImgSlots * n, s));
         unsigned* blockmax = reinterpret_cast<unsigned*>(imgtab + 3 * kImgSlots * n);
-        if (plan.pool_f32)
+        if (stem.pool_form == host::kRnPoolAny)   // (block maxima with a ragged last block per image: geo.block_max words per image hold them)
+            RELAX_TRY(launch_bn_relu_maxpool_any(h, bufA, rn.bn1_scale, rn.bn1_shift, plan.pool_f32 ? bufD : nullptr, plan.pool_f32 ? nullptr : spa, N, H0, W0, 64, s,
+                                                 plan.s_stem >= 0 ? slot_amax(plan.s_stem) : nullptr, blockmax));
+        else if (plan.pool_f32)
             RELAX_TRY(launch_bn_relu_maxpool_f32(h, bufA, rn.bn1_scale, rn.bn1_shift, bufD, N, H0, W0, 64, s, slot_amax(plan.s_stem), blockmax));
         else
             RELAX_TRY(launch_bn_relu_maxpool_sp3(h, bufA, rn.bn1_scale, rn.bn1_shift, spa, N, H0, W0, 64, s,
@@ -588,7 +614,10 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
     // conv1 7x7/2 (raw), algorithmic FLOPs use the real 3 input channels
     RELAX_TRY(run_conv(h, rn.conv1, X0, N, Hc, Wc, nullptr, bufA, 0, s, 2.0 * N * (double)H0 * W0 * 64.0 * 147.0));
     RELAX_TRY(emit_tap(0, bufA));
-    RELAX_TRY(launch_bn_relu_maxpool(h, bufA, rn.bn1_scale, rn.bn1_shift, bufB, N, H0, W0, 64, s));
+    if (stem.pool_form == host::kRnPoolAny)
+        RELAX_TRY(launch_bn_relu_maxpool_any(h, bufA, rn.bn1_scale, rn.bn1_shift, bufB, nullptr, N, H0, W0, 64, s, nullptr, nullptr));
+    else
+        RELAX_TRY(launch_bn_relu_maxpool(h, bufA, rn.bn1_scale, rn.bn1_shift, bufB, N, H0, W0, 64, s));
     float* cur = bufB;
     float* other = bufA;
     int H = H1, W = W1;

@@ -34,6 +34,7 @@ LAYER_STACK_DIM = 13120
 RN50_POOL_DIM = 2051
 TOP_N = 196
 TARGET = 224
+RN_CANVAS_ANY = 1            # RELAX_RN_CANVAS_ANY (include/relax_hip.h): ResNet-50 canvases of any size in [64, 1024]
 VGG16_LAYER_STACK_DIM = 4224
 VGG16_POOL_DIM = 4099
 VGG16_FEATURE_INDEX = [0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28]   # features[i] of the 13 convolutions (tap order)
@@ -799,13 +800,18 @@ class RelaxEngine:
         return ls, pl
 
     # ---- ResNet-50 on any canvas ---------------------------------------------------------------
-    def resnet50_canvas_geometry(self, Hc, Wc):
+    def resnet50_canvas_geometry(self, Hc, Wc, any_size=False):
         """-> ([(h, w)] * 15: the map of every tap on an [Hc, Wc] canvas, arena bytes per image).  Accepted: Hc and Wc multiples of 32 in
         [64, 1024] (every stage map even down to layer4, the stem's output whole 256-pixel tiles); anything else is a ValueError that names
-        the offending value.  Host arithmetic: no model needs to be loaded."""
+        the offending value.  any_size=True (RELAX_RN_CANVAS_ANY): every Hc, Wc in [64, 1024], the maps by torch's floor rule (65 x 67: 33 x 34,
+        17 x 17, 9 x 9, 5 x 5, 3 x 3).  Host arithmetic: no model needs to be loaded."""
         taps = (C.c_int * 30)()
         arena = C.c_int64(0)
-        if self.lib.relax_resnet50_canvas_geometry(int(Hc), int(Wc), taps, C.byref(arena)) != 0:
+        if any_size:
+            rc = self.lib.relax_resnet50_canvas_geometry_ex(int(Hc), int(Wc), RN_CANVAS_ANY, taps, C.byref(arena))
+        else:
+            rc = self.lib.relax_resnet50_canvas_geometry(int(Hc), int(Wc), taps, C.byref(arena))
+        if rc != 0:
             raise ValueError(self.lib.relax_last_error(None).decode())
         return [(taps[2 * t], taps[2 * t + 1]) for t in range(15)], int(arena.value)
 
@@ -815,6 +821,12 @@ class RelaxEngine:
         self._check(self.lib.relax_resnet50_get_canvas(self.h, C.byref(hc), C.byref(wc)), "relax_resnet50_get_canvas")
         return hc.value, wc.value
 
+    def _rn_set_canvas(self, Hc, Wc, any_size):
+        if any_size:
+            self._check(self.lib.relax_resnet50_set_canvas_ex(self.h, Hc, Wc, RN_CANVAS_ANY), "relax_resnet50_set_canvas_ex")
+        else:
+            self._check(self.lib.relax_resnet50_set_canvas(self.h, Hc, Wc), "relax_resnet50_set_canvas")
+
     def _rn_canvas_images(self, images):
         images = self._dev_u8(images)
         if images.dim() == 3:
@@ -823,16 +835,18 @@ class RelaxEngine:
             raise ValueError(f"images must be [N,Hc,Wc,3], got {tuple(images.shape)}")
         return images
 
-    def resnet50_features_canvas(self, images, layer_stack=True, pool=True, taps=None):
+    def resnet50_features_canvas(self, images, layer_stack=True, pool=True, taps=None, any_size=False):
         """images uint8 [N,Hc,Wc,3] BGR on any accepted canvas (resnet50_canvas_geometry) -> what resnet50_features returns: (layer_stack fp32
         [N,13120] | None, pool fp32 [N,2051] | None[, taps]), the exported taps [N,C,h_t,w_t] of that canvas.  torchvision's ResNet-50 takes
         any size; both rows are spatial means and keep their widths.  At 224 x 224 this is resnet50_features, launch for launch.  The canvas is
-        set on the handle for this call and 224 x 224 put back when it returns or raises, so every other method keeps finding the default."""
+        set on the handle for this call and 224 x 224 (with the default rule) put back when it returns or raises, so every other method keeps
+        finding the default.  any_size=True: every canvas in [64, 1024] (resnet50_canvas_geometry); on a canvas the default rule takes, the
+        same launches and bits as without it."""
         images = self._rn_canvas_images(images)
         N, Hc, Wc = (int(v) for v in images.shape[:3])
-        shapes = self.resnet50_canvas_geometry(Hc, Wc)[0]       # (a refused canvas: ValueError naming the value, the handle untouched)
+        shapes = self.resnet50_canvas_geometry(Hc, Wc, any_size)[0]       # (a refused canvas: ValueError naming the value, the handle untouched)
         try:
-            self._check(self.lib.relax_resnet50_set_canvas(self.h, Hc, Wc), "relax_resnet50_set_canvas")
+            self._rn_set_canvas(Hc, Wc, any_size)
             dev = self.device
             ls = torch.empty((N, LAYER_STACK_DIM), dtype=torch.float32, device=dev) if layer_stack else None
             pl = torch.empty((N, RN50_POOL_DIM), dtype=torch.float32, device=dev) if pool else None
@@ -850,7 +864,7 @@ class RelaxEngine:
             self.lib.relax_resnet50_set_canvas(self.h, TARGET, TARGET)
         return (ls, pl, tap_out) if taps is not None else (ls, pl)
 
-    def resnet50_clip_features_canvas(self, images, n_layer_stack):
+    def resnet50_clip_features_canvas(self, images, n_layer_stack, any_size=False):
         """resnet50_clip_features on any accepted canvas: images uint8 [N,Hc,Wc,3], the first n_layer_stack -> layer stack fp32
         [n_layer_stack,13120], the others -> pool fp32 [N - n_layer_stack,2051]; ONE forward.  224 x 224 is put back as in
         resnet50_features_canvas."""
@@ -859,9 +873,9 @@ class RelaxEngine:
         n_ls = int(n_layer_stack)
         if not 0 <= n_ls <= N:
             raise ValueError(f"n_layer_stack={n_ls} outside [0, {N}]")
-        self.resnet50_canvas_geometry(Hc, Wc)
+        self.resnet50_canvas_geometry(Hc, Wc, any_size)
         try:
-            self._check(self.lib.relax_resnet50_set_canvas(self.h, Hc, Wc), "relax_resnet50_set_canvas")
+            self._rn_set_canvas(Hc, Wc, any_size)
             ls = torch.empty((n_ls, LAYER_STACK_DIM), dtype=torch.float32, device=self.device)
             pl = torch.empty((N - n_ls, RN50_POOL_DIM), dtype=torch.float32, device=self.device)
             rc = self.lib.relax_resnet50_clip_features(self.h, _ptr(images), N, n_ls, _ptr(ls) if n_ls else None, _ptr(pl) if N > n_ls else None,
@@ -1074,30 +1088,31 @@ class RelaxEngine:
         _, pooled = self.vit_features(torch.cat([fr["ori_frag"], fr["diff_frag"]], dim=0), tokens=False, pooled=True)
         return torch.cat([pooled[:T], pooled[T:]], dim=1)
 
-    def fragment_resnet_vectors(self, frames, patch_size=16, target_size=TARGET, top_n=None):
+    def fragment_resnet_vectors(self, frames, patch_size=16, target_size=TARGET, top_n=None, any_size=False):
         """frames uint8 [T,2,H,W,3] -> fp32 [T, 13120 + 2051]: the ResNet-50 layer stack of the original fragment | the pool of the
         frame-difference fragment, both cut by fragment_pairs at patch_size on a target_size x target_size canvas and run through ResNet-50 at
         that canvas in ONE forward - the row of extract_clip's 'resnet' block, which is this at target_size 224.  target_size: a multiple of
         patch_size (fragment_pairs) and of 32 (resnet50_canvas_geometry) up to 448; e.g. 232 at patch 8 is a fragment canvas but not a
-        ResNet-50 one and is refused naming the value, before anything is cut."""
-        self.resnet50_canvas_geometry(target_size, target_size)
+        ResNet-50 one and is refused naming the value, before anything is cut - unless any_size=True, under which every fragment canvas in
+        [64, 448] is a ResNet-50 one too."""
+        self.resnet50_canvas_geometry(target_size, target_size, any_size)
         fr = self.fragment_pairs(frames, top_n=top_n, patch_size=patch_size, target_size=target_size)
-        return self._fragment_resnet_row(fr)
+        return self._fragment_resnet_row(fr, any_size)
 
-    def _fragment_resnet_row(self, fr):
+    def _fragment_resnet_row(self, fr, any_size=False):
         T = fr["ori_frag"].shape[0]
-        ls, pool = self.resnet50_clip_features_canvas(torch.cat([fr["ori_frag"], fr["diff_frag"]], dim=0), T)
+        ls, pool = self.resnet50_clip_features_canvas(torch.cat([fr["ori_frag"], fr["diff_frag"]], dim=0), T, any_size=any_size)
         return torch.cat([ls, pool], dim=1)
 
-    def fragment_canvas_vectors(self, frames, target_size, patch_size=16, top_n=None):
+    def fragment_canvas_vectors(self, frames, target_size, patch_size=16, top_n=None, any_size=False):
         """frames uint8 [T,2,H,W,3] -> fp32 [T, 15171 + 6*dim]: fragment_resnet_vectors | fragment_vit_vectors of the same fragments (ONE
         fragment_pairs call) - extract_clip's 'resnet' | 'vit' row on a canvas of the caller's choosing (a multiple of 32 and of patch_size, up
-        to 448)."""
-        self.resnet50_canvas_geometry(target_size, target_size)
+        to 448; any_size=True: a multiple of patch_size in [64, 448], e.g. 232 at patch 8)."""
+        self.resnet50_canvas_geometry(target_size, target_size, any_size)
         fr = self.fragment_pairs(frames, top_n=top_n, patch_size=patch_size, target_size=target_size)
         T = fr["ori_frag"].shape[0]
         _, pooled = self.vit_features(torch.cat([fr["ori_frag"], fr["diff_frag"]], dim=0), tokens=False, pooled=True)
-        return torch.cat([self._fragment_resnet_row(fr), pooled[:T], pooled[T:]], dim=1)
+        return torch.cat([self._fragment_resnet_row(fr, any_size), pooled[:T], pooled[T:]], dim=1)
 
     def fragment_vit_layer_stack(self, frames, n=4, cls=False, patch_size=16, target_size=TARGET, top_n=None):
         """frames uint8 [T,2,H,W,3] -> fp32 [T, 2*n*3*dim] (+ 2*n*dim columns with cls=True): fragment_vit_vectors with the last n blocks'
@@ -1195,18 +1210,39 @@ class RelaxEngine:
             lan = self.resize_frames_to(frames, size, bilinear=False, lanczos=True)[1]
         return self.vit_features(lan, tokens=tokens, pooled=pooled, attention=attention)
 
-    def whole_frame_resnet_canvas(self, frames, size, layer_stack=True, pool=True):
+    def whole_frame_resnet_canvas(self, frames, size, layer_stack=True, pool=True, any_size=False):
         """frames uint8 [N,H,W,3] BGR -> resnet50_features_canvas of the frames BILINEAR-resized to the canvas `size` (an int: the shorter side,
         as transforms.Resize(size); or an (h, w) pair) on the GPU, Pillow-exact: the reference's whole-frame ResNet input (transforms.Resize,
         src/extractor/visualise_resnet.py:40-50) without squashing the frame to a square - for 16:9 frames (288, 512) keeps the aspect
         ratio on an accepted canvas.  A size whose result is not an accepted canvas (e.g. the int 288 on 1080 x 1920 -> 288 x 512 is, (270,
-        480) is not) is refused naming the value, before anything is resized.  size=(224, 224) is whole_frame_features' ResNet half."""
+        480) is not) is refused naming the value, before anything is resized - unless any_size=True, under which every size in [64, 1024]
+        is a canvas (1080 x 1920 -> (270, 480)).  size=(224, 224) is whole_frame_features' ResNet half."""
         if len(frames.shape) != 4 or frames.shape[3] != 3:
             raise ValueError(f"frames must be uint8 [N,H,W,3], got {tuple(frames.shape)}")
         oh, ow = self._resize_target(int(frames.shape[1]), int(frames.shape[2]), size)
-        self.resnet50_canvas_geometry(oh, ow)
+        self.resnet50_canvas_geometry(oh, ow, any_size)
         bil = self.resize_frames_to(frames, (oh, ow), bilinear=True, lanczos=False)[0]
-        return self.resnet50_features_canvas(bil, layer_stack=layer_stack, pool=pool)
+        return self.resnet50_features_canvas(bil, layer_stack=layer_stack, pool=pool, any_size=any_size)
+
+    def whole_frame_canvas_vectors(self, frames, size):
+        """frames uint8 [N,H,W,3] BGR -> fp32 [N, 13120 + 2051 + 3*dim]: both backbones on the SAME canvas `size` (an int: the shorter side; or an
+        (h, w) pair; anything in [64, 1024] both ways) - whole_frame_resnet_canvas(any_size=True)'s layer stack | pool beside
+        whole_frame_vit_canvas' pooled row, from ONE resize call that reads each frame once for both filters (ResNet-50 sees the BILINEAR canvas, the
+        ViT the LANCZOS one, as the reference's whole-frame inputs).  E.g. 1080 x 1920 -> (270, 480); a 540 x 960 frame at its own size is not
+        resized at all."""
+        if self.vit_dim is None:
+            raise RuntimeError("load_vit first")
+        if len(frames.shape) != 4 or frames.shape[3] != 3:
+            raise ValueError(f"frames must be uint8 [N,H,W,3], got {tuple(frames.shape)}")
+        oh, ow = self._resize_target(int(frames.shape[1]), int(frames.shape[2]), size)
+        self.resnet50_canvas_geometry(oh, ow, True)              # (refused before anything is resized)
+        if (oh, ow) == (int(frames.shape[1]), int(frames.shape[2])):
+            bil = lan = self._dev_u8(frames)
+        else:
+            bil, lan = self.resize_frames_to(frames, (oh, ow), bilinear=True, lanczos=True)
+        ls, pool = self.resnet50_features_canvas(bil, any_size=True)
+        _, pooled = self.vit_features(lan, tokens=False, pooled=True)
+        return torch.cat([ls, pool, pooled], dim=1)
 
     # ---- fragment-free ablation rows (src/main_residual.py, src/main_layer.py) ---------------------------------
     RESIDUAL_NAMES = ("frame_diff", "optical_flow")
