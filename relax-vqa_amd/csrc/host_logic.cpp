@@ -214,6 +214,99 @@ void vgg16_fc1_to_nhwc(const float* w, int rows, int C, int HW, float* out) {
     }
 }
 
+// ---- VGG-16 schedule ---------------------------------------------------------------------------------------------------------------------
+const int kVggConvSide[kVggConvs] = {224, 224, 112, 112, 56, 56, 56, 28, 28, 28, 14, 14, 14};
+const int kVggPoolAfter[kVggConvs] = {0, 1, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 1};
+
+VggArena vgg_arena() {
+    const int64_t map = (int64_t)224 * 224 * 64;   // the largest activation (conv1_x output) as fp32
+    const int64_t planes = map * 3 / 2;            // ... as split planes (6 B per value; fp16 planes and fp32 rows take 4)
+    const int64_t groups = map / 16;               // group sums of the fused mean (largest: 16-row groups at 224^2 x 64 = 4-row groups at 56^2 x 256)
+    const int64_t fc = 4096;
+    VggArena a{};
+    a.a32 = 0;
+    a.planes0 = a.a32 + map;
+    a.planes1 = a.planes0 + planes;
+    a.groups = a.planes1 + planes;
+    a.fc1 = a.groups + groups;
+    a.fc2 = a.fc1 + fc;
+    a.slots = a.fc2 + fc;
+    a.floats = a.slots + 3 * kVggSlots;
+    return a;
+}
+
+bool vgg_plan(const VggOptions& o, const VggRequest& rq, int max_slots, VggPlan* plan, std::string& err) {
+    const bool h2 = o.precision == 3, x6 = o.precision >= 2;
+    VggPlan p{};
+    p.arena = vgg_arena();
+    p.classifier = rq.want_pool || (rq.taps >> 13 & 3u) != 0;
+    p.n_rows = p.classifier ? kVggSteps : kVggSteps - 2;
+    int next_slot = 0, rows = 0;
+    int cur = kVggBufPlanes0, oth = kVggBufPlanes1;   // the next contraction's input (planes of the arithmetic, or fp32 rows) and the other plane buffer
+    int s_in = -1, s_max = -1;                        // f16x2: the slot with the current tensor's scale, and the one with its measured maximum
+    auto step = [&](int route, int layer, int side, int cin, int cout) -> VggLayerPlan& {
+        VggLayerPlan& q = p.row[rows++];
+        q.route = route; q.layer = layer; q.side = side; q.cin = cin; q.cout = cout;
+        q.in = cur; q.out32 = kVggBufNone; q.out_planes = kVggBufNone;
+        q.want_export = !vgg_is_pool(route) && (rq.taps >> layer & 1u);
+        q.no_split = route == kVggConvH3 || route == kVggConvX6H2 || route == kVggConvX6;   // the bits do not depend on which outputs are requested
+        q.s_in = vgg_is_pool(route) ? -1 : s_in;   // (a pool reads the fp32 map)
+        q.s_in_max = s_max; q.s_out = h2 ? next_slot++ : -1;
+        return q;
+    };
+    // the one ladder: gemm_h3 takes Cout % 256 == 0, the four-wave f16x2 tiles of gemm_x6 the rest
+    auto contraction = [&](int cout) { return h2 ? (cout % 256 == 0 ? kVggConvH3 : kVggConvX6H2) : x6 ? kVggConvX6 : kVggConvF32; };
+    for (int i = 0; i < kVggConvs; ++i) {
+        const int side = kVggConvSide[i], hw = side * side, cout = kVggConvCout[i];
+        const bool pool_next = kVggPoolAfter[i] != 0;
+        VggLayerPlan& q = step(i == 0 ? kVggConv11 : contraction(cout), i, side, kVggConvCin[i], cout);
+        q.want_mean = rq.want_layer_stack != 0;
+        q.measure_max = h2;
+        if (i == 0) {   // conv1_1 writes where the next convolution reads (its own input is the fragments); its scale is a constant of the weights
+            q.in = kVggBufNone; q.s_in_max = -1;
+            q.out32 = x6 ? (q.want_export ? kVggBufA32 : kVggBufNone) : cur;
+            q.out_planes = x6 ? cur : kVggBufNone;
+            q.gap_group = q.want_mean ? 16 : 0;
+        } else {
+            // under planes the fp32 copy exists iff a pool follows or the tap is exported; fp32 rows go to the other plane buffer
+            q.out32 = x6 ? ((pool_next || q.want_export) ? kVggBufA32 : kVggBufNone) : oth;
+            q.out_planes = (x6 && !pool_next) ? oth : kVggBufNone;
+            if (x6 && q.want_mean) q.gap_group = q.route == kVggConvH3 ? 4 : hw % 16 == 0 ? 16 : 4;
+        }
+        s_in = s_max = q.s_out;
+        if (!pool_next) {
+            if (i > 0) std::swap(cur, oth);
+            continue;
+        }
+        // the pool reads the fp32 map and writes into the buffer its producer's input came from (consumed by now): no swap.  f16x2: a new scale slot
+        // from the measured maximum of the map, which bounds the pool's outputs too - the maximum slot stays the producer's
+        const int src = q.out32;
+        VggLayerPlan& m = step(h2 ? kVggPoolH2 : x6 ? kVggPoolSp3 : kVggPoolF32, i, side, cout, cout);
+        m.in = src;
+        (x6 ? m.out_planes : m.out32) = cur;
+        s_in = m.s_out;
+    }
+    // classifier: pool5 (NHWC flatten) -> fc1 + ReLU -> fc2 + ReLU, planned whether or not it runs (n_rows ends in front of it)
+    for (int i = 0; i < 2; ++i) {
+        const bool last = i == 1;
+        VggLayerPlan& q = step(contraction(4096), 13 + i, 1, i == 0 ? 512 * 49 : 4096, 4096);
+        if (last && !x6) q.in = kVggBufFc1;
+        const bool need32 = last || q.want_export || !x6;
+        q.out32 = need32 ? (last ? kVggBufFc2 : kVggBufFc1) : kVggBufNone;
+        q.out_planes = (x6 && !last) ? oth : kVggBufNone;
+        q.measure_max = h2 && q.out_planes != kVggBufNone;
+        s_in = s_max = q.s_out;
+        if (q.out_planes != kVggBufNone) std::swap(cur, oth);
+    }
+    p.n_slots = next_slot;
+    if (next_slot > max_slots) {
+        err = "vgg16: " + std::to_string(next_slot) + " per-image scale slots used, " + std::to_string(max_slots) + " reserved";
+        return false;
+    }
+    *plan = p;
+    return true;
+}
+
 // ---- ResNet-50 schedule ------------------------------------------------------------------------------------------------------------------
 const RnBlockGeom* rn_geometry() {
     struct Table { RnBlockGeom g[kRnBlocks]; };
@@ -1232,6 +1325,29 @@ int relax_host_vgg16_check_keys(const float* const* tensors, const char* const* 
     return -1;
 }
 void relax_host_vgg16_fc1_to_nhwc(const float* w, int rows, int c, int hw, float* out) { relax::host::vgg16_fc1_to_nhwc(w, rows, c, hw, out); }
+// VGG-16 schedule as plain integers.  opts: precision; req: N, want_layer_stack, want_pool, tap mask.  out: [n_slots, classifier, n_rows] + per step
+// the 16 VggLayerPlan fields in declaration order + per convolution [map side, pool behind it] (3 + 20 * 16 + 13 * 2 ints); arena: the eight
+// VggArena offsets + vgg_arena_bytes(N).  0, or -1 with a message and both arrays untouched when the plan needs more than max_slots slots.
+int relax_host_vgg_plan(const int* opts, const int* req, int max_slots, int* out, int64_t* arena, char* err, int err_len) {
+    using namespace relax::host;
+    static_assert(sizeof(VggLayerPlan) == 16 * sizeof(int) && sizeof(VggArena) == 8 * sizeof(int64_t), "VggLayerPlan is 16 ints, VggArena 8 offsets");
+    VggPlan p;
+    std::string e;
+    if (!vgg_plan(VggOptions{opts[0]}, VggRequest{req[0], req[1], req[2], (unsigned)req[3]}, max_slots, &p, e)) {
+        if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return -1;
+    }
+    out[0] = p.n_slots; out[1] = p.classifier; out[2] = p.n_rows;
+    std::memcpy(out + 3, p.row, sizeof(p.row));
+    int* geo = out + 3 + kVggSteps * 16;
+    for (int i = 0; i < kVggConvs; ++i) {
+        geo[2 * i] = kVggConvSide[i];
+        geo[2 * i + 1] = kVggPoolAfter[i];
+    }
+    std::memcpy(arena, &p.arena, sizeof(p.arena));
+    arena[8] = vgg_arena_bytes(req[0]);
+    return 0;
+}
 
 // ResNet-50 schedule as plain integers.  opts: the six RnOptions in order; req: N, n_ls, pool_from, want_pool, tap mask.
 // out: [conv1_h2, pool_f32, s_stem, n_slots] + per block the 23 RnBlockPlan fields in declaration order (4 + 16 * 23 ints).

@@ -266,11 +266,64 @@ constexpr int kVggConvs = 13;
 extern const int kVggFeatureIndex[kVggConvs];
 extern const int kVggConvCout[kVggConvs];
 extern const int kVggConvCin[kVggConvs];
+extern const int kVggConvSide[kVggConvs];     // side of the square map a convolution reads and writes (3x3, pad 1): 224 down to 14
+extern const int kVggPoolAfter[kVggConvs];    // 1: features[index + 2] is the 2x2 / stride-2 max-pool (behind conv1_2, 2_2, 3_3, 4_3, 5_3)
 // Every weight / bias the VGG-16 loader reads is present with its torchvision size: true, or false and a message naming the key.
 bool vgg16_check_keys(const StateDict& sd, std::string& err);
 // classifier.0.weight [rows][C*HW] in torchvision's NCHW flatten order (column c*HW + p) -> the same rows in NHWC order
 // (column p*C + c), so fc1 is a plain GEMM over the pool5 rows as the NHWC driver stores them.  out must hold rows * C * HW floats.
 void vgg16_fc1_to_nhwc(const float* w, int rows, int C, int HW, float* out);
+
+// The forward of one chunk of images, decided before anything launches (vgg16.hip executes it): the route of every step, the buffer every tensor
+// lies in, the fp32 copies, the fused-mean group sizes and the per-image scale slots.  Host arithmetic only.
+constexpr int kVggChunk = 32;     // images per pass through the network (the 224^2 x 64 maps are 12.8 MB per image in fp32)
+constexpr int kVggSlots = 24;     // per-image tables {maximum, scale, 1 / scale} the arena reserves (the f16x2 schedule uses 20)
+constexpr int kVggTaps = 15;      // the 13 convolutions, fc1, fc2
+constexpr int kVggSteps = kVggConvs + 5 + 2;   // 13 convolutions, 5 max-pools, fc1, fc2
+struct VggOptions { int precision; };          // "gemm_precision": 3 f16x2, 2 bf16x6, 0 / 1 fp32 rows into the exact-fp32 (bf16x3) kernel
+// N <= kVggChunk images; bit t of taps: tap t is exported
+struct VggRequest { int N, want_layer_stack, want_pool; unsigned taps; };
+enum VggRoute {
+    kVggConv11 = 0,    // vgg_conv1_1: the streaming kernel that reads the uint8 fragments
+    kVggConvH3,        // gemm_h3, convolution form (f16x2 onto Cout % 256 == 0: conv3_x .. conv5_x and the classifier as 1x1 convolutions over 1x1 images)
+    kVggConvX6H2,      // gemm_x6 on fp16 planes (f16x2 onto 64 / 128 channels)
+    kVggConvX6,        // gemm_x6 on split planes (bf16x6)
+    kVggConvF32,       // the exact-fp32 (bf16x3) kernel on fp32 rows
+    kVggPoolH2,        // vgg_maxpool2x2 writing fp16 planes with the image's scale,
+    kVggPoolSp3,       // ... split planes,
+    kVggPoolF32        // ... fp32 rows
+};
+inline bool vgg_is_pool(int route) { return route >= kVggPoolH2; }
+enum VggBuffer { kVggBufNone = 0, kVggBufA32, kVggBufPlanes0, kVggBufPlanes1, kVggBufFc1, kVggBufFc2 };
+// One step, in launch order.  s_*: slots of the per-image tables, -1 = unused; a slot's scale is written by the step whose s_out it is (from the
+// maximum in s_in_max, measured by an earlier step), its maximum by that step's epilogue where measure_max is set.
+struct VggLayerPlan {
+    int route;
+    int layer;                   // the tap index of a convolution (0 .. 12) or classifier layer (13, 14); a pool: that of the convolution in front of it
+    int side, cin, cout;         // the input map is side x side x cin (a classifier layer: 1 x 1 x K; a pool writes side / 2)
+    int in;                      // VggBuffer the step reads (conv1_1: none, it reads the fragments)
+    int out32;                   // ... its output as fp32 rows goes to: what a pool, an export, a launch_gap mean or the pool vector reads - and, under
+                                 // the fp32 route, the next step (then it is a plane buffer holding rows)
+    int out_planes;              // ... its output as planes of the arithmetic goes to (the next contraction's input)
+    int want_mean;               // the tap's spatial mean goes into the layer stack ...
+    int gap_group;               // ... finished from sums over groups of 16 / 4 rows formed in the epilogue; 0: launch_gap over the fp32 copy
+    int want_export, no_split;
+    int s_in, s_out, s_in_max;   // scale of the input planes; scale of the output (Hoelder's bound over the maximum in s_in_max; a pool: that maximum itself)
+    int measure_max;             // the epilogue measures the per-image maximum of the output into slot s_out
+};
+// per-image float offsets of the arena's parts in carving order, and their total
+struct VggArena { int64_t a32, planes0, planes1, groups, fc1, fc2, slots, floats; };
+VggArena vgg_arena();
+inline int64_t vgg_arena_bytes(int n) { return (int64_t)sizeof(float) * vgg_arena().floats * (n < kVggChunk ? n : kVggChunk); }   // the workspace of a call on n images
+struct VggPlan {
+    int n_slots;                 // slots of the schedule with its classifier (their numbers do not depend on the request)
+    int classifier;              // 0: neither the pool vector nor fc1 / fc2 is asked for, the forward ends behind pool5
+    int n_rows;                  // kVggSteps, or kVggSteps - 2 without the classifier
+    VggLayerPlan row[kVggSteps];
+    VggArena arena;
+};
+// false and a message if the schedule needs more than max_slots per-image tables
+bool vgg_plan(const VggOptions& o, const VggRequest& rq, int max_slots, VggPlan* plan, std::string& err);
 
 // ---- scales of the two-plane fp16 format (csrc/h2.h): powers of two from RIGOROUS bounds, so no value can leave the fp16 range --------
 // The power of two that puts `amax` into [2^14, 2^15) (so twice the bound still fits below 65504); 1 for zero / non-finite.

@@ -443,6 +443,41 @@ inline int launch_gemm_x6(relax_handle* h, const void* A_sp3, const void* W_sp3,
 
 // f16x2 contraction kernel (gemm_h2.hip)
 int launch_gemm_h2(relax_handle* h, const GemmDescH2& d, hipStream_t s);
+
+// Descriptors of one loaded convolution (ConvW) over Nimg maps of H x W, for the backbones (resnet50.hip, vgg16.hip): geometry, weights and
+// bias; the caller adds the outputs and whatever else its launch takes.
+inline int conv_out(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }   // output side along one axis
+// the exact-fp32 (bf16x3) kernel on fp32 rows
+inline ConvDesc conv_f32(const ConvW& c, const float* in, int Nimg, int H, int W, const float* residual, float* out, int act, double flops = 0) {
+    ConvDesc d{};
+    d.in = in; d.Nimg = Nimg; d.H = H; d.W = W; d.Cin = c.Cin;
+    d.Ho = conv_out(H, c.KH, c.stride, c.pad);
+    d.Wo = conv_out(W, c.KW, c.stride, c.pad);
+    d.KH = c.KH; d.KW = c.KW; d.stride = c.stride; d.pad = c.pad;
+    d.w = c.w; d.Cout = c.Cout; d.Kpad = c.Kpad;
+    d.bias = c.bias; d.residual = residual; d.out = out; d.act = act; d.flops = flops;
+    return d;
+}
+// gemm_x6 with the bf16x6 weights (a launch on fp16 planes replaces w and sets in_h2, colscale, img_in_inv)
+inline ConvDescX6 conv_x6(const ConvW& c, const void* in_sp3, int Nimg, int H, int W, int act = 1) {
+    ConvDescX6 d{};
+    d.in = in_sp3; d.Nimg = Nimg; d.H = H; d.W = W; d.Cin = c.Cin;
+    d.Ho = conv_out(H, c.KH, c.stride, c.pad); d.Wo = conv_out(W, c.KW, c.stride, c.pad);
+    d.KH = c.KH; d.KW = c.KW; d.stride = c.stride; d.pad = c.pad;
+    d.w = c.w_sp3; d.Cout = c.Cout; d.bias = c.bias; d.act = act;
+    return d;
+}
+// gemm_h3, convolution form with per-image scales: fills geometry and weights into `g` (whose outputs the caller has set); the caller adds the
+// slots of the per-image tables
+inline GemmDescH2 conv_h2(const ConvW& c, const void* in_h2, int Nimg, int H, int W, int act, GemmDescH2 g = GemmDescH2{}) {
+    g.a = in_h2; g.w = c.w_h2; g.colscale = c.w_inv; g.bias = c.bias; g.act = act;
+    g.pixels = 1; g.Nimg = Nimg; g.H = H; g.W = W; g.Cin = c.Cin;
+    g.Ho = conv_out(H, c.KH, c.stride, c.pad); g.Wo = conv_out(W, c.KW, c.stride, c.pad);
+    g.KH = c.KH; g.KW = c.KW; g.stride = c.stride; g.pad = c.pad;
+    g.M = Nimg * g.Ho * g.Wo; g.N = c.Cout; g.K = c.KH * c.KW * c.Cin;
+    g.rows_per_img = g.Ho * g.Wo;
+    return g;
+}
 int launch_to_h2(relax_handle* h, const float* x, int64_t ld, void* y, int64_t rows, int K, float scale, const float* row_scale, hipStream_t s,
                  int rows_per_scale = 1);
 int launch_h2_image_scales(relax_handle* h, const unsigned* amax_a, float la, const unsigned* amax_b, float lb, const unsigned* amax_r,

@@ -150,19 +150,6 @@ static bool force_any_forms() {
     return on;
 }
 
-// output side of a convolution along one axis
-static int conv_out(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }
-
-// geometry, bf16x6 weights and bias of one folded convolution over N maps of H x W
-static ConvDescX6 conv_x6(const ConvW& c, const void* in_sp3, int Nimg, int H, int W, int act = 1) {
-    ConvDescX6 d{};
-    d.in = in_sp3; d.Nimg = Nimg; d.H = H; d.W = W; d.Cin = c.Cin;
-    d.Ho = conv_out(H, c.KH, c.stride, c.pad); d.Wo = conv_out(W, c.KW, c.stride, c.pad);
-    d.KH = c.KH; d.KW = c.KW; d.stride = c.stride; d.pad = c.pad;
-    d.w = c.w_sp3; d.Cout = c.Cout; d.bias = c.bias; d.act = act;
-    return d;
-}
-
 // the loader built what the plan's form of this block reads (both go by the predicates of host_logic.h)
 static bool has_weights(const Bottleneck& k, const host::RnBlockPlan& q) {
     if (q.c1_h2 && !k.c1.w_h2) return false;
@@ -177,14 +164,7 @@ static bool has_weights(const Bottleneck& k, const host::RnBlockPlan& q) {
 
 static int run_conv(relax_handle* h, const ConvW& c, const float* in, int Nimg, int H, int W, const float* residual,
                     float* out, int act, hipStream_t s, double flops = 0) {
-    ConvDesc d{};
-    d.in = in; d.Nimg = Nimg; d.H = H; d.W = W; d.Cin = c.Cin;
-    d.Ho = conv_out(H, c.KH, c.stride, c.pad);
-    d.Wo = conv_out(W, c.KW, c.stride, c.pad);
-    d.KH = c.KH; d.KW = c.KW; d.stride = c.stride; d.pad = c.pad;
-    d.w = c.w; d.Cout = c.Cout; d.Kpad = c.Kpad;
-    d.bias = c.bias; d.residual = residual; d.out = out; d.act = act; d.flops = flops;
-    return launch_conv(h, d, s);
+    return launch_conv(h, conv_f32(c, in, Nimg, H, W, residual, out, act, flops), s);
 }
 
 // ---- derived weights --------------------------------------------------------------------------------------
@@ -454,12 +434,8 @@ static int resnet_forward(relax_handle* h, const uint8_t* frags, int N, int n_ls
                                           slot_inv(t), N, s);
         };
         auto conv_h2 = [&](const ConvW& c, const void* in, int Hin, int Win, int slot_in, GemmDescH2 g, int slot_out, int act) {
-            g.a = in; g.w = c.w_h2; g.colscale = c.w_inv; g.bias = c.bias; g.act = act;
-            g.pixels = 1; g.Nimg = N; g.H = Hin; g.W = Win; g.Cin = c.Cin;
-            g.Ho = conv_out(Hin, c.KH, c.stride, c.pad); g.Wo = conv_out(Win, c.KW, c.stride, c.pad);
-            g.KH = c.KH; g.KW = c.KW; g.stride = c.stride; g.pad = c.pad;
-            g.M = N * g.Ho * g.Wo; g.N = c.Cout; g.K = c.KH * c.KW * c.Cin;
-            g.rows_per_img = g.Ho * g.Wo; g.img_in_inv = slot_inv(slot_in);
+            g = relax::conv_h2(c, in, N, Hin, Win, act, g);
+            g.img_in_inv = slot_inv(slot_in);
             if (g.out_h2) { g.img_out_scale = slot_scale(slot_out); g.amax_out = slot_amax(slot_out); }
             return launch_gemm_h2(h, g, s);
         };

@@ -17,7 +17,7 @@
 //                       max-pool output takes the measured maximum of the convolution in front of it (the pool does not raise it).
 //   "gemm_precision" 2  bf16x6 everywhere (split planes written by the producer's epilogue).
 //   "gemm_precision" 0  the exact-fp32 kernel on fp32 rows (1: bf16x3, opt-in).
-// Images go through in chunks of at most kVggChunk (the 224^2 x 64 maps are 12.8 MB per image in fp32).
+// Images go through in chunks of at most host::kVggChunk (the 224^2 x 64 maps are 12.8 MB per image in fp32).
 #include <cmath>
 
 #include "relax_internal.h"
@@ -27,22 +27,8 @@
 
 namespace relax {
 
-static constexpr int kVggChunk = 32;            // images per pass through the network (workspace: vgg_arena_bytes(kVggChunk), ~1.7 GB)
-static constexpr int kVggSlots = 24;            // per-image tables {maximum, scale, 1 / scale}: 13 convolutions + 5 pools + fc1 + fc2 = 20 used
-static const int kVggHW[host::kVggConvs] = {224, 224, 112, 112, 56, 56, 56, 28, 28, 28, 14, 14, 14};
-static const bool kVggPoolAfter[host::kVggConvs] = {false, true, false, true, false, false, true, false, false, true, false, false, true};
-
-// floats per image of the arena
-static constexpr size_t kMap = (size_t)224 * 224 * 64;          // the largest activation (conv1_x output)
-static constexpr size_t kPlanes = kMap * 3 / 2;                 // ... as split planes (6 B per value; fp16 planes and fp32 take 4)
-static constexpr size_t kGroups = (size_t)224 * 224 / 16 * 64;  // group sums of the fused spatial mean (largest: 16-row groups at 224^2, = 4-row at 56^2 x 256)
-static constexpr size_t kFc = 4096;
-static constexpr size_t kVggFloatsPerImage = kMap + 2 * kPlanes + kGroups + 2 * kFc + 3 * kVggSlots;
-
-size_t vgg_arena_bytes(int n) {
-    const size_t c = (size_t)(n < kVggChunk ? n : kVggChunk);
-    return sizeof(float) * kVggFloatsPerImage * c;
-}
+// the arena of a call (host_logic.cpp's vgg_arena: ~1.7 GB for a whole chunk)
+size_t vgg_arena_bytes(int n) { return (size_t)host::vgg_arena_bytes(n); }
 
 // ---- kernels ---------------------------------------------------------------------------------------
 
@@ -240,171 +226,112 @@ static int load_vgg(relax_handle* h, const host::StateDict& sd) {
 }
 
 // ---- forward ---------------------------------------------------------------------------------------
-// One chunk of N <= kVggChunk images.  Rows of the outputs: layer_stack [N][4224], pool [N][4099], taps as in relax_vgg16_features,
-// each already offset to the chunk's first image.
+// Where a step's tensors lie and which table rows it reads and writes: the plan's buffer and slot numbers as pointers of this chunk
+struct VggIo {
+    const void* in;
+    float* out32;
+    void* planes;
+    float* gap;                  // group sums of the fused mean, or null
+    const float* in_inv;         // f16x2: 1 / scale of the input planes, scale of the output planes, the output's measured maximum
+    const float* out_scale;
+    unsigned* out_max;
+};
+
+// One contraction step (a convolution over N maps, or a classifier layer) on the kernel of its route
+static int vgg_contract(relax_handle* h, const host::VggLayerPlan& q, const ConvW& c, int N, const VggIo& io, hipStream_t s) {
+    int Nimg = N, H = q.side, W = q.side;
+    // a classifier layer is a plain GEMM over N rows - but on gemm_h3 a 1x1 convolution over N images of 1x1 pixels, whose scales are per image
+    if (q.side == 1 && q.route != host::kVggConvH3) { Nimg = 1; W = N; }
+    switch (q.route) {
+        case host::kVggConvH3: {
+            GemmDescH2 g = conv_h2(c, io.in, Nimg, H, W, 1);
+            g.img_in_inv = io.in_inv;
+            g.out = io.out32; g.out_h2 = io.planes; g.img_out_scale = io.planes ? io.out_scale : nullptr; g.amax_out = io.out_max;
+            g.gap_groups = io.gap; g.no_split = q.no_split;
+            return launch_gemm_h2(h, g, s);
+        }
+        case host::kVggConvX6H2:
+        case host::kVggConvX6: {
+            ConvDescX6 d = conv_x6(c, io.in, Nimg, H, W, 1);
+            d.out = io.out32; d.gap_groups = io.gap; d.no_split = q.no_split;
+            if (q.route == host::kVggConvX6H2) {
+                d.in_h2 = 1; d.w = c.w_h2; d.colscale = c.w_inv; d.img_in_inv = io.in_inv;
+                d.out_h2 = io.planes; d.img_out_scale = io.planes ? io.out_scale : nullptr; d.amax_out = io.out_max;
+            } else {
+                d.out_sp3 = io.planes;
+            }
+            return launch_conv_x6(h, d, s);
+        }
+        default:   // kVggConvF32
+            return launch_conv(h, conv_f32(c, static_cast<const float*>(io.in), Nimg, H, W, nullptr, io.out32, 1), s);
+    }
+}
+
+// One chunk of N <= host::kVggChunk images: host::vgg_plan (CPU-tested) decides every step, here are the pointers and the launches.  Rows of the
+// outputs: layer_stack [N][4224], pool [N][4099], taps as in relax_vgg16_features, each already offset to the chunk's first image.
 static int vgg_chunk(relax_handle* h, const uint8_t* frags, int N, float* layer_stack, float* pool, float* const* taps, int64_t tap_off, hipStream_t s) {
     const VggW& v = h->vgg;
-    const int mode = h->gemm.precision;       // 3 f16x2, 2 bf16x6, 0 / 1 fp32 rows into the exact-fp32 (bf16x3) kernel
-    const bool h2 = mode == 3, x6 = mode >= 2;
+    host::VggRequest rq{N, layer_stack != nullptr, pool != nullptr, 0u};
+    for (int t = 0; taps && t < host::kVggTaps; ++t) rq.taps |= taps[t] ? 1u << t : 0u;
+    host::VggPlan plan;
+    std::string plan_err;
+    RELAX_REQUIRE(h, host::vgg_plan(host::VggOptions{h->gemm.precision}, rq, host::kVggSlots, &plan, plan_err), "%s", plan_err.c_str());
     const size_t n = (size_t)N;
     float* base = static_cast<float*>(h->arena.p);
-    float* A32 = base;                                         // fp32 map in front of a max-pool, or of an export
-    char* cur = reinterpret_cast<char*>(A32 + kMap * n);       // the next contraction's input (planes of the mode, or fp32 rows)
-    char* oth = reinterpret_cast<char*>(A32 + (kMap + kPlanes) * n);
-    float* groups = A32 + (kMap + 2 * kPlanes) * n;
-    float* fc1 = groups + kGroups * n;
-    float* fc2 = fc1 + kFc * n;
-    float* tab = fc2 + kFc * n;
-    int next_slot = 0;
-    auto new_slot = [&](int* slot) -> int {   // checked before anything writes the table
-        RELAX_REQUIRE(h, next_slot < kVggSlots, "vgg16: per-image scale slot %d requested, %d reserved", next_slot, kVggSlots);
-        *slot = next_slot++;
-        return RELAX_OK;
-    };
-    auto slot_amax = [&](int t) { return reinterpret_cast<unsigned*>(tab + (size_t)(3 * t) * n); };
-    auto slot_scale = [&](int t) { return tab + (size_t)(3 * t + 1) * n; };
-    auto slot_inv = [&](int t) { return tab + (size_t)(3 * t + 2) * n; };
-    RELAX_HIP_CHECK(h, fill_async(tab, 0, sizeof(float) * 3 * kVggSlots * n, s));
+    const host::VggArena& a = plan.arena;
+    void* const buf[] = {nullptr, base + a.a32 * n, base + a.planes0 * n, base + a.planes1 * n, base + a.fc1 * n, base + a.fc2 * n};   // by host::VggBuffer
+    float* groups = base + a.groups * n;
+    float* tab = base + a.slots * n;       // slot t = {maximum, scale, 1 / scale} x images
+    auto slot_max = [&](int t) { return t < 0 ? nullptr : reinterpret_cast<unsigned*>(tab + (size_t)(3 * t) * n); };
+    auto slot_scale = [&](int t) { return t < 0 ? nullptr : tab + (size_t)(3 * t + 1) * n; };
+    auto slot_inv = [&](int t) { return t < 0 ? nullptr : tab + (size_t)(3 * t + 2) * n; };
+    RELAX_HIP_CHECK(h, fill_async(tab, 0, sizeof(float) * 3 * host::kVggSlots * n, s));
 
     int off = 0;   // layer-stack column of the current tap
-    auto tap_out = [&](int i, const float* f32, int HW, int C, int group) -> int {   // the mean (group > 0: from the fused group sums) and the export
-        if (layer_stack) {
-            if (group > 0) RELAX_TRY(launch_gap_groups_finish_rows(h, groups, layer_stack + off, N, HW, C, RELAX_VGG16_LAYER_STACK_DIM, group, s));
-            else RELAX_TRY(launch_gap(h, f32, layer_stack + off, N, HW, C, RELAX_VGG16_LAYER_STACK_DIM, s));
-        }
-        if (taps && taps[i]) RELAX_TRY(launch_nhwc_to_nchw(h, f32, taps[i] + tap_off * C * HW, N, HW, C, s));
-        off += C;
-        return RELAX_OK;
-    };
-
-    // conv1_1
-    const bool export0 = taps && taps[0];
-    int s_in = -1;                 // slot of the current input tensor (f16x2: its scale; its maximum is amax_in)
-    unsigned* amax_in = nullptr;
-    if (h2) {
-        RELAX_TRY(new_slot(&s_in));
-        amax_in = slot_amax(s_in);
-    }
-    {
-        float* o32 = x6 ? (export0 ? A32 : nullptr) : reinterpret_cast<float*>(cur);
-        hipLaunchKernelGGL(vgg_conv1_1, dim3(224 * 224 / kC11Pix, N), dim3(256), 0, s, frags, v.conv[0].w, v.conv[0].bias, o32,
-                           h2 ? cur : nullptr, v.conv1_scale, (x6 && !h2) ? cur : nullptr, layer_stack ? groups : nullptr, amax_in,
-                           h2 ? slot_scale(s_in) : nullptr, h2 ? slot_inv(s_in) : nullptr);
-        RELAX_HIP_CHECK(h, hipGetLastError());
-        RELAX_TRY(tap_out(0, o32, 224 * 224, 64, 16));
-    }
-    for (int i = 1; i < host::kVggConvs; ++i) {
-        const ConvW& c = v.conv[i];
-        const int H = kVggHW[i], HW = H * H, C = c.Cout;
-        const bool pool_next = kVggPoolAfter[i];
-        const bool want_export = taps && taps[i];
-        float* o32 = x6 ? ((pool_next || want_export) ? A32 : nullptr) : reinterpret_cast<float*>(oth);
-        void* oplanes = (x6 && !pool_next) ? oth : nullptr;
-        float* gap = (x6 && layer_stack) ? groups : nullptr;
-        int group = 0;
-        int s_out = -1;
-        if (h2) {   // the output's scale from Hoelder on the measured input maximum, fixed before the launch; its own maximum is measured
-            RELAX_TRY(new_slot(&s_out));
-            RELAX_TRY(launch_h2_image_scales(h, amax_in, c.l1max, nullptr, 0.f, nullptr, c.bmax, slot_scale(s_out), slot_inv(s_out), N, s));
-        }
-        if (h2 && C % 256 == 0) {   // gemm_h3, convolution form (conv3_x .. conv5_x)
-            GemmDescH2 g{};
-            g.a = cur; g.w = c.w_h2; g.colscale = c.w_inv; g.bias = c.bias; g.act = 1;
-            g.pixels = 1; g.Nimg = N; g.H = H; g.W = H; g.Cin = c.Cin; g.Ho = H; g.Wo = H;
-            g.KH = 3; g.KW = 3; g.stride = 1; g.pad = 1;
-            g.M = N * HW; g.N = C; g.K = c.Kpad;
-            g.rows_per_img = HW; g.img_in_inv = slot_inv(s_in);
-            g.out = o32; g.out_h2 = oplanes; g.img_out_scale = oplanes ? slot_scale(s_out) : nullptr; g.amax_out = slot_amax(s_out);
-            g.gap_groups = gap;
-            g.no_split = true;    // the pool vector's bits do not depend on whether the layer stack is requested
-            RELAX_TRY(launch_gemm_h2(h, g, s));
-            group = 4;
-        } else if (x6) {            // gemm_x6: f16x2 on the four-wave tiles (64 / 128 channels) or bf16x6
-            ConvDescX6 d{};
-            d.in = cur; d.Nimg = N; d.H = H; d.W = H; d.Cin = c.Cin; d.Ho = H; d.Wo = H;
-            d.KH = 3; d.KW = 3; d.stride = 1; d.pad = 1;
-            d.Cout = C; d.bias = c.bias; d.act = 1;
-            d.out = o32; d.gap_groups = gap; d.no_split = true;
-            if (h2) {
-                d.in_h2 = 1; d.w = c.w_h2; d.colscale = c.w_inv; d.img_in_inv = slot_inv(s_in);
-                d.out_h2 = oplanes; d.img_out_scale = oplanes ? slot_scale(s_out) : nullptr; d.amax_out = slot_amax(s_out);
-            } else {
-                d.w = c.w_sp3; d.out_sp3 = oplanes;
-            }
-            RELAX_TRY(launch_conv_x6(h, d, s));
-            group = HW % 16 == 0 ? 16 : 4;
-        } else {
-            ConvDesc d{};
-            d.in = reinterpret_cast<const float*>(cur); d.Nimg = N; d.H = H; d.W = H; d.Cin = c.Cin; d.Ho = H; d.Wo = H;
-            d.KH = 3; d.KW = 3; d.stride = 1; d.pad = 1;
-            d.w = c.w; d.Cout = C; d.Kpad = c.Kpad; d.bias = c.bias; d.out = o32; d.act = 1;
-            RELAX_TRY(launch_conv(h, d, s));
-        }
-        RELAX_TRY(tap_out(i, o32, HW, C, gap ? group : 0));
-        if (h2) { s_in = s_out; amax_in = slot_amax(s_out); }
-        if (pool_next) {
-            // 2x2 max-pool of the fp32 map into `cur` (its input has been consumed): fp16 planes with the scale of the measured maximum of
-            // the map (the pool's outputs are a subset of its values, so the same maximum bounds them), split planes, or fp32 rows
-            const int Ho = H / 2;
-            const int64_t threads = (int64_t)N * Ho * Ho * C / 8;
+    for (int r = 0; r < plan.n_rows; ++r) {
+        const host::VggLayerPlan& q = plan.row[r];
+        const bool pooling = host::vgg_is_pool(q.route), fc = q.layer >= host::kVggConvs;
+        const ConvW& c = fc ? v.fc[q.layer - host::kVggConvs] : v.conv[q.layer];
+        const int H = q.side, HW = H * H, C = q.cout;
+        const VggIo io{buf[q.in], static_cast<float*>(buf[q.out32]), buf[q.out_planes], q.gap_group ? groups : nullptr,
+                       slot_inv(q.s_in), slot_scale(q.s_out), q.measure_max ? slot_max(q.s_out) : nullptr};
+        // f16x2: the output's scale is fixed before the launch, from Hoelder's bound on the measured maximum of the producer's input - a pool's
+        // from the measured maximum of the map it reads, which its outputs cannot pass
+        if (q.s_out >= 0 && q.s_in_max >= 0)
+            RELAX_TRY(launch_h2_image_scales(h, slot_max(q.s_in_max), pooling ? 1.f : c.l1max, nullptr, 0.f, nullptr, pooling ? 0.f : c.bmax,
+                                             slot_scale(q.s_out), slot_inv(q.s_out), N, s));
+        if (pooling) {
+            const int64_t threads = (int64_t)N * (H / 2) * (H / 2) * C / 8;
             const dim3 grid((unsigned)((threads + 255) / 256));
-            if (h2) {
-                int s_p = -1;
-                RELAX_TRY(new_slot(&s_p));
-                RELAX_TRY(launch_h2_image_scales(h, amax_in, 1.f, nullptr, 0.f, nullptr, 0.f, slot_scale(s_p), slot_inv(s_p), N, s));
-                hipLaunchKernelGGL(vgg_maxpool2x2<1>, grid, dim3(256), 0, s, o32, cur, slot_scale(s_p), N, H, H, C);
-                s_in = s_p;   // (amax_in stays: the maximum of the map)
-            } else if (x6) {
-                hipLaunchKernelGGL(vgg_maxpool2x2<2>, grid, dim3(256), 0, s, o32, cur, nullptr, N, H, H, C);
-            } else {
-                hipLaunchKernelGGL(vgg_maxpool2x2<0>, grid, dim3(256), 0, s, o32, cur, nullptr, N, H, H, C);
-            }
+            const float* x = static_cast<const float*>(io.in);
+            if (q.route == host::kVggPoolH2) hipLaunchKernelGGL(vgg_maxpool2x2<1>, grid, dim3(256), 0, s, x, io.planes, io.out_scale, N, H, H, C);
+            else if (q.route == host::kVggPoolSp3) hipLaunchKernelGGL(vgg_maxpool2x2<2>, grid, dim3(256), 0, s, x, io.planes, nullptr, N, H, H, C);
+            else hipLaunchKernelGGL(vgg_maxpool2x2<0>, grid, dim3(256), 0, s, x, io.out32, nullptr, N, H, H, C);
+            RELAX_HIP_CHECK(h, hipGetLastError());
+            continue;
+        }
+        if (q.route == host::kVggConv11) {   // its planes are fp16 with the static scale where the plan gives it a slot, else split planes
+            const bool h2 = q.s_out >= 0;
+            hipLaunchKernelGGL(vgg_conv1_1, dim3(224 * 224 / kC11Pix, N), dim3(256), 0, s, frags, c.w, c.bias, io.out32,
+                               h2 ? static_cast<char*>(io.planes) : nullptr, v.conv1_scale, h2 ? nullptr : static_cast<char*>(io.planes), io.gap,
+                               io.out_max, slot_scale(q.s_out), slot_inv(q.s_out));
             RELAX_HIP_CHECK(h, hipGetLastError());
         } else {
-            char* t = cur; cur = oth; oth = t;
+            RELAX_TRY(vgg_contract(h, q, c, N, io, s));
         }
-    }
-    // classifier: pool5 (NHWC flatten, `cur`) -> fc1 + ReLU -> fc2 + ReLU (Dropout: identity in eval)
-    const bool want_fc1 = taps && taps[13], want_fc2 = taps && taps[14];
-    if (!pool && !want_fc1 && !want_fc2) return RELAX_OK;
-    for (int i = 0; i < 2; ++i) {
-        const ConvW& c = v.fc[i];
-        const bool last = i == 1;
-        float* o32 = i == 0 ? fc1 : fc2;
-        const bool need32 = last || want_fc1 || !x6;
-        void* oplanes = (x6 && !last) ? oth : nullptr;
-        if (h2) {   // a 1x1 convolution over N images of 1x1 pixels: the per-image scales of the convolution form
-            int s_out = -1;
-            RELAX_TRY(new_slot(&s_out));
-            RELAX_TRY(launch_h2_image_scales(h, amax_in, c.l1max, nullptr, 0.f, nullptr, c.bmax, slot_scale(s_out), slot_inv(s_out), N, s));
-            GemmDescH2 g{};
-            g.a = cur; g.w = c.w_h2; g.colscale = c.w_inv; g.bias = c.bias; g.act = 1;
-            g.pixels = 1; g.Nimg = N; g.H = 1; g.W = 1; g.Cin = c.Cin; g.Ho = 1; g.Wo = 1;
-            g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0;
-            g.M = N; g.N = 4096; g.K = c.Cin;
-            g.rows_per_img = 1; g.img_in_inv = slot_inv(s_in);
-            g.out = need32 ? o32 : nullptr; g.out_h2 = oplanes; g.img_out_scale = oplanes ? slot_scale(s_out) : nullptr;
-            g.amax_out = oplanes ? slot_amax(s_out) : nullptr;
-            g.no_split = true;
-            RELAX_TRY(launch_gemm_h2(h, g, s));
-            s_in = s_out;
-            amax_in = slot_amax(s_out);
-        } else if (x6) {
-            ConvDescX6 d{};
-            d.in = cur; d.Nimg = 1; d.H = 1; d.W = N; d.Cin = c.Cin; d.Ho = 1; d.Wo = N;
-            d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0;
-            d.w = c.w_sp3; d.Cout = 4096; d.bias = c.bias; d.act = 1;
-            d.out = need32 ? o32 : nullptr; d.out_sp3 = oplanes; d.no_split = true;
-            RELAX_TRY(launch_conv_x6(h, d, s));
-        } else {
-            const float* a = i == 0 ? reinterpret_cast<const float*>(cur) : fc1;
-            RELAX_TRY(launch_gemm(h, a, c.w, c.bias, nullptr, o32, N, 4096, c.Cin, 1, s));
+        if (fc) {
+            if (q.want_export)
+                RELAX_HIP_CHECK(h, hipMemcpyAsync(taps[q.layer] + tap_off * C, io.out32, sizeof(float) * C * n, hipMemcpyDeviceToDevice, s));
+            continue;
         }
-        if (taps && taps[13 + i])
-            RELAX_HIP_CHECK(h, hipMemcpyAsync(taps[13 + i] + tap_off * 4096, o32, sizeof(float) * 4096 * n, hipMemcpyDeviceToDevice, s));
-        if (oplanes) { char* t = cur; cur = oth; oth = t; }
+        if (q.want_mean) {   // from the fused group sums, or over the fp32 copy
+            if (q.gap_group > 0) RELAX_TRY(launch_gap_groups_finish_rows(h, groups, layer_stack + off, N, HW, C, RELAX_VGG16_LAYER_STACK_DIM, q.gap_group, s));
+            else RELAX_TRY(launch_gap(h, io.out32, layer_stack + off, N, HW, C, RELAX_VGG16_LAYER_STACK_DIM, s));
+        }
+        if (q.want_export) RELAX_TRY(launch_nhwc_to_nchw(h, io.out32, taps[q.layer] + tap_off * C * HW, N, HW, C, s));
+        off += C;
     }
-    if (pool) RELAX_TRY(launch_pool_stats(h, fc2, 4096, pool, RELAX_VGG16_POOL_DIM, N, 4096, s));
+    if (pool) RELAX_TRY(launch_pool_stats(h, static_cast<float*>(buf[host::kVggBufFc2]), 4096, pool, RELAX_VGG16_POOL_DIM, N, 4096, s));
     return RELAX_OK;
 }
 
@@ -434,8 +361,8 @@ int relax_vgg16_features(relax_handle* h, const uint8_t* frags, int N, float* la
     RELAX_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     RELAX_TRY(ensure_buf(h, h->arena, vgg_arena_bytes(N)));
-    for (int i0 = 0; i0 < N; i0 += kVggChunk) {
-        const int c = N - i0 < kVggChunk ? N - i0 : kVggChunk;
+    for (int i0 = 0; i0 < N; i0 += host::kVggChunk) {
+        const int c = N - i0 < host::kVggChunk ? N - i0 : host::kVggChunk;
         RELAX_TRY(vgg_chunk(h, frags + (int64_t)i0 * 224 * 224 * 3, c, layer_stack ? layer_stack + (int64_t)i0 * RELAX_VGG16_LAYER_STACK_DIM : nullptr,
                             pool ? pool + (int64_t)i0 * RELAX_VGG16_POOL_DIM : nullptr, taps_nchw, i0, s));
     }

@@ -1,6 +1,6 @@
 // Stand-alone program (its own main) for AddressSanitizer + UBSan: csrc/host_logic.cpp's conv_hoelder and read_bn on the shapes of
 // tests/test_conv_hoelder_cpu.py and on malformed BatchNorm dicts, and the options table's set / get with an empty key, a 1 KiB key and every
-// key of the table, and vit_plan on the grid of its CPU test.  Every input and output sits in a heap block of exactly its size, so a read or write past an end is reported.  Built and run by tests/test_conv_hoelder_cpu.py; exit status 0 and "host_logic_san: OK" if all holds.
+// key of the table, and vit_plan and vgg_plan on the grids of their CPU tests.  Every input and output sits in a heap block of exactly its size, so a read or write past an end is reported.  Built and run by tests/test_conv_hoelder_cpu.py; exit status 0 and "host_logic_san: OK" if all holds.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -141,12 +141,49 @@ static void vit_plan_cases() {
                         }
 }
 
+// vgg_plan on the grid of tests/test_vgg16_plan_cpu.py (every precision x requests x tap masks x N), accepted at its own slot count and refused
+// one short of it: the rows in range, the slots below n_slots, the plan untouched by a refusal.  Every plan sits in a heap block of its size.
+static void vgg_plan_cases() {
+    const unsigned masks[6] = {0u, 0x7FFFu, 1u << 0, 1u << 3, 1u << 13, 1u << 14};
+    for (int precision = 0; precision <= 3; ++precision)
+        for (int want = 0; want < 4; ++want)
+            for (const unsigned taps : masks)
+                for (const int n : {1, kVggChunk}) {
+                    if (want == 0 && taps == 0u) continue;
+                    const VggRequest rq{n, want & 1, want >> 1, taps};
+                    std::vector<VggPlan> heap(1);
+                    VggPlan& p = heap[0];
+                    std::string err;
+                    CHECK(vgg_plan(VggOptions{precision}, rq, kVggSlots, &p, err) && err.empty());
+                    CHECK(p.n_slots == (precision == 3 ? 20 : 0) && p.n_rows == (p.classifier ? kVggSteps : kVggSteps - 2));
+                    CHECK(p.classifier == (rq.want_pool || (taps >> 13 & 3u)));
+                    CHECK(p.arena.a32 == 0 && p.arena.floats == 13054024 && vgg_arena_bytes(n) == 4 * p.arena.floats * n);
+                    for (int r = 0; r < p.n_rows; ++r) {
+                        const VggLayerPlan& q = p.row[r];
+                        CHECK(q.route >= kVggConv11 && q.route <= kVggPoolF32 && q.layer >= 0 && q.layer < kVggTaps);
+                        CHECK(q.in >= kVggBufNone && q.in <= kVggBufFc2 && q.out32 >= kVggBufNone && q.out32 <= kVggBufFc2);
+                        CHECK(q.out_planes == kVggBufNone || q.out_planes == kVggBufPlanes0 || q.out_planes == kVggBufPlanes1);
+                        CHECK(q.s_in < p.n_slots && q.s_out < p.n_slots && q.s_in_max < p.n_slots && q.s_in >= -1 && q.s_out >= -1 && q.s_in_max >= -1);
+                        CHECK(q.gap_group == 0 || q.gap_group == 4 || q.gap_group == 16);
+                    }
+                    std::vector<VggPlan> heap2(1);
+                    std::memset(static_cast<void*>(&heap2[0]), 0x5A, sizeof(VggPlan));
+                    const VggPlan before = heap2[0];
+                    err.clear();
+                    CHECK(!vgg_plan(VggOptions{precision}, rq, p.n_slots - 1, &heap2[0], err));
+                    CHECK(err == "vgg16: " + std::to_string(p.n_slots) + " per-image scale slots used, " + std::to_string(p.n_slots - 1) + " reserved");
+                    CHECK(std::memcmp(&before, &heap2[0], sizeof(VggPlan)) == 0);
+                    CHECK(vgg_plan(VggOptions{precision}, rq, p.n_slots, &heap2[0], err));
+                }
+}
+
 int main() {
     const int shapes[4][2] = {{1, 32}, {3, 64}, {64, 224}, {5, 4608}};
     for (const auto& sh : shapes) hoelder_cases(sh[0], sh[1]);
     read_bn_cases();
     option_cases();
     vit_plan_cases();
+    vgg_plan_cases();
     if (failures) return 1;
     std::printf("host_logic_san: OK\n");
     return 0;
