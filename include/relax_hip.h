@@ -750,6 +750,12 @@ int relax_op_bn_relu_maxpool_amax(relax_handle* h, const float* x, const float* 
 /* spatial mean: x [Nimg,HW,C] -> out[n*out_stride + c] */
 int relax_op_gap(relax_handle* h, const float* x, float* out, int Nimg, int HW, int C, int64_t out_stride,
                  relax_stream stream);
+/* The tail of the pool vectors as an op (a test entry point; the forwards reach the same kernel after the avgpool / fc2): row i of v
+ * (DEVICE fp32, n rows of dim floats, v_stride >= dim floats apart) -> out[i*out_stride + 0 .. dim-1] = the row, bit for bit, then its
+ * mean, max and population std at dim, dim + 1, dim + 2 (out_stride >= dim + 3; nothing else of `out` is written).  dim is 2048
+ * (ResNet-50's pool vector) or 4096 (VGG-16's); any other dim is refused, the message names it.  Enqueued on `stream`. */
+int relax_op_pool_stats(relax_handle* h, const float* v, int64_t v_stride, float* out, int64_t out_stride, int n, int dim,
+                        relax_stream stream);
 
 /* x [Nimg, tokens, dim] -> out [Nimg, 3*dim] = per-channel mean | max | population std over tokens
  * (process_video_feature, vit branch: src/main_residual_fragment.py:128-136; src/main_fragment_pool.py:124-133) */

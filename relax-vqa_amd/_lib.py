@@ -113,6 +113,7 @@ PROTOTYPES = {
     "relax_op_bn_relu_maxpool": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_op_bn_relu_maxpool_amax": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_op_gap": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int64, c_vp]),
+    "relax_op_pool_stats": (C.c_int, [c_vp, c_vp, C.c_int64, c_vp, C.c_int64, C.c_int, C.c_int, c_vp]),
     "relax_op_token_stats": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_op_vit_norm_token_stats": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_float, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp]),
     "relax_copy_bytes": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, c_vp]),

@@ -667,4 +667,15 @@ int relax_op_gap(relax_handle* h, const float* x, float* out, int Nimg, int HW, 
     return launch_gap(h, x, out, Nimg, HW, C, out_stride, static_cast<hipStream_t>(stream));
 }
 
+int relax_op_pool_stats(relax_handle* h, const float* v, int64_t v_stride, float* out, int64_t out_stride, int n, int dim,
+                        relax_stream stream) {
+    if (!h) return RELAX_ERR_INVALID;
+    RELAX_REQUIRE(h, v && out, "relax_op_pool_stats: NULL operand");
+    RELAX_REQUIRE(h, dim == 2048 || dim == 4096, "relax_op_pool_stats: dim %d is neither 2048 nor 4096", dim);
+    RELAX_REQUIRE(h, n > 0 && v_stride >= dim && out_stride >= (int64_t)dim + 3, "relax_op_pool_stats: bad shape n=%d v_stride=%lld out_stride=%lld",
+                  n, (long long)v_stride, (long long)out_stride);
+    RELAX_HIP_CHECK(h, hipSetDevice(h->device));
+    return launch_pool_stats(h, v, v_stride, out, out_stride, n, dim, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -1535,10 +1535,32 @@ class RelaxEngine:
                                                       Cc, _stream()), "relax_op_bn_relu_maxpool")
         return y
 
-    def op_gap(self, x):
+    def op_gap(self, x, out=None):
+        """x fp32 [Nimg,HW,C] -> the spatial means [Nimg,C]; out: a contiguous fp32 [Nimg, stride >= C] tensor whose rows receive them in
+        their first C columns (the rest of each row is left as it is)"""
         Nimg, HW, Cc = x.shape
-        out = torch.empty((Nimg, Cc), dtype=torch.float32, device=self.device)
-        self._check(self.lib.relax_op_gap(self.h, _ptr(x), _ptr(out), Nimg, HW, Cc, Cc, _stream()), "relax_op_gap")
+        if out is None:
+            out = torch.empty((Nimg, Cc), dtype=torch.float32, device=self.device)
+        elif (out.dim() != 2 or out.shape[0] != Nimg or out.shape[1] < Cc or out.dtype != torch.float32 or not out.is_contiguous()
+              or out.device != self.device):
+            raise ValueError(f"op_gap: out must be contiguous fp32 [{Nimg}, >= {Cc}] on {self.device}")
+        self._check(self.lib.relax_op_gap(self.h, _ptr(x), _ptr(out), Nimg, HW, Cc, out.shape[1], _stream()), "relax_op_gap")
+        return out
+
+    def op_pool_stats(self, v, dim, out=None):
+        """The tail of the pool vectors (relax_op_pool_stats): v contiguous fp32 [n, v_stride >= dim] -> out [n, out_stride >= dim + 3] with
+        out[:, :dim] = v[:, :dim], then mean, max and population std of those dim values; dim 2048 or 4096.  Columns past dim + 2 of a
+        given `out` are left as they are."""
+        if v.dim() != 2 or v.dtype != torch.float32 or not v.is_contiguous() or v.device != self.device or v.shape[1] < dim:
+            raise ValueError(f"op_pool_stats: v must be contiguous fp32 [n, >= {dim}] on {self.device}")
+        n = v.shape[0]
+        if out is None:
+            out = torch.empty((n, dim + 3), dtype=torch.float32, device=self.device)
+        elif (out.dim() != 2 or out.shape[0] != n or out.shape[1] < dim + 3 or out.dtype != torch.float32 or not out.is_contiguous()
+              or out.device != self.device):
+            raise ValueError(f"op_pool_stats: out must be contiguous fp32 [{n}, >= {dim + 3}] on {self.device}")
+        self._check(self.lib.relax_op_pool_stats(self.h, _ptr(v), v.shape[1], _ptr(out), out.shape[1], n, dim, _stream()),
+                    "relax_op_pool_stats")
         return out
 
     def op_token_stats(self, x):

@@ -649,6 +649,14 @@ def call_op_gap(eng, t):
     return (eng.op_gap(t["x"]),)
 
 
+def make_pool_vectors(seed):
+    return {"v": _f32(seed, 58, 2, 2048)}
+
+
+def call_op_pool_stats(eng, t):
+    return (eng.op_pool_stats(t["v"], 2048),)
+
+
 def make_tokens(seed):
     return {"x": _f32(seed, 55, 2, 50, 384), "g": _f32(seed, 56, 384), "b": _f32(seed, 57, 384)}
 
@@ -835,6 +843,7 @@ CASES = {
     "relax_op_bn_relu_maxpool": _e(make_maxpool, call_op_maxpool),
     "relax_op_bn_relu_maxpool_amax": _e(make_maxpool, call_op_maxpool_amax),
     "relax_op_gap": _e(make_gap, call_op_gap),
+    "relax_op_pool_stats": _e(make_pool_vectors, call_op_pool_stats),
     "relax_op_token_stats": _e(make_tokens, call_op_token_stats),
     "relax_op_vit_norm_token_stats": _e(make_tokens, call_op_vit_norm_token_stats),
     "relax_copy_bytes": _e(make_bytes, call_copy_bytes),
